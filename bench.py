@@ -7,15 +7,19 @@ a-trous dispatches + 3 blits) over a G-buffer already resident in HBM.  Sponza i
 (SURVEY.md section 8d): the workload is the procedural `sponza_proc` atrium (257 536 triangles, 103 primitives)
 with the camera dolly of section 8(d); data = synthetic.
 
-    python bench.py --gpus 1 --steps 32 --warmup 4
+    python bench.py --gpus 1 --steps 32 --warmup 4 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints ONE JSON line.  `value` = unique rays traced by all ranks / wall time of the K timed frames
-(max over ranks).  Extra objects: `roofline` (the a-trous kernel against the 8 TB/s HBM peak, timed live with HIP
-events on the launch stream), `cpu_baseline` (the CPU oracle -- a restatement, NOT lavapipe -- on the host cores
-over a bounded sample), `traversal` (Mrays/s of the ray-tracing kernel alone), `passes` (per-pass ms under the
-reference's pass names).
+(max over ranks); `ms_per_step` = that wall time / K.  A plain run sets up, warms up (W frames, then untimed frames
+for --warmup-seconds), times exactly K frames (--min-seconds repeats the block and reports the median one), writes the
+last timed frame's images with --dump-outputs and prints the line.  --full times blocks of K frames for >= 1 s and reports
+the median one, as the benchmark always did, and adds what else the benchmark measures and checks: `roofline` (the
+a-trous kernel against the 8 TB/s HBM peak, timed live with HIP events on the launch stream), `cpu_baseline` (the
+CPU oracle -- a restatement, NOT lavapipe -- on the host cores over a bounded sample), `traversal` (Mrays/s of the
+ray-tracing kernel alone), `passes` (per-pass ms under the reference's pass names), the N = 1 extra configurations,
+and at N > 1 the check of the ranks' tiles against one full-frame context and the launcher's c_abi probe.
 """
 import argparse
 import json
@@ -58,8 +62,9 @@ def parse():
                    help="N > 1: after this verified frame the grid is cut again at equal cost -- a uniform map scaled by the ranks' measured "
                         "frame times (tiling.refine_cost_map; VHR_BENCH_REPLAN_TIMES=t0,t1,... overrides them) -- and the SVGF history follows its pixels "
                         "(HybridFrameLoop.replan); the remaining verified frames check the NEW rectangles against the single context")
-    p.add_argument("--verify-frames", type=int, default=3,
-                   help="N > 1 only: before timing, check that the gathered strips equal a single full-frame context bit for bit")
+    p.add_argument("--verify-frames", type=int, default=None,
+                   help="N > 1 only: before timing, check that the gathered strips equal a single full-frame context bit for bit "
+                        "(default: 3 with --full or --replan-frame, else 0)")
     p.add_argument("--backend", default=os.environ.get("VHR_BENCH_BACKEND", "nccl"), choices=["nccl", "gloo"],
                    help="gloo + --share-device lets several ranks run on ONE GPU (functional check of the strip path only)")
     p.add_argument("--exchange-raytraced", action="store_true",
@@ -72,9 +77,19 @@ def parse():
     p.add_argument("--frames-in-flight", type=int, default=1, choices=[1, 2, 3],
                    help="frames in flight of the timed region (vhr_set_option frames_in_flight; 1 = the single-stream contract). "
                         "At N = 1 the line carries the 2-frames-in-flight figures as extra fields either way")
-    p.add_argument("--min-seconds", type=float, default=1.0,
-                   help="the timed block of --steps frames is repeated until this much time has been measured; value = the median block")
-    p.add_argument("--no-extras", action="store_true", help="skip the extra blocks (mirror-ray frame, frames in flight) of the N = 1 line")
+    p.add_argument("--min-seconds", type=float, default=None,
+                   help="the timed block of --steps frames is repeated until this much time has been measured; value = the median block "
+                        "(default: 0 = one block, exactly --steps timed frames; 1.0 with --full, whose roofline samples the a-trous launches of the timed region)")
+    p.add_argument("--warmup-seconds", type=float, default=None,
+                   help="N = 1: after the --warmup frames (at least one), untimed blocks of 8 frames go on until this much time has passed, so that the "
+                        "timed frames start on a GPU at its steady clock; the path's state is then put back to where the --warmup frames left it "
+                        "(default: 1.0; 0 with --full, whose median over >= --min-seconds of blocks leaves the cold first blocks out)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure and check everything beyond the headline: kernel and pass times, rooflines, traversal counters, the N = 1 "
+                        "extra configurations, the CPU baseline, and at N > 1 the tile check and the launcher's c_abi probe")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed frames, write the images the last timed frame produced as DIR/<name>.npy (float32, at most 64 MB in all)")
+    p.add_argument("--no-extras", action="store_true", help="with --full: skip the extra blocks (mirror-ray frame, frames in flight) of the N = 1 line")
     p.add_argument("--grid", default="auto", help="N > 1: the screen decomposition -- auto = the planner's grid of screen tiles (2x4 at N = 8: the busiest "
                    "rank computes +19 %% instead of a row strip's +44 %%), strips = row strips, or ROWSxCOLS")
     p.add_argument("--comm", default="auto", choices=["auto", "torch", "c_abi"],
@@ -92,6 +107,12 @@ def parse():
                    help="launcher only: skip the second, time-bounded child that repeats a short run through the library's own RCCL calls (--comm c_abi)")
     p.add_argument("--launch-timeout", type=float, default=1500.0, help="launcher only: seconds the ranks may take before the launcher ends them")
     args = p.parse_args()
+    if args.verify_frames is None:
+        args.verify_frames = 3 if (args.full or args.replan_frame is not None) else 0
+    if args.min_seconds is None:
+        args.min_seconds = 1.0 if args.full else 0.0
+    if args.warmup_seconds is None:
+        args.warmup_seconds = 0.0 if args.full else 1.0
     if args.share_device and args.backend == "nccl":
         args.backend = "gloo"            # RCCL refuses two ranks on one device: ranks that share a GPU talk over gloo
     return args
@@ -171,8 +192,8 @@ def launch_ranks(args, argv):
         return rc or 1
     # The measured route is torch.distributed (backend nccl == RCCL).  The library's own RCCL calls (vhr_comm_*, csrc/comm.cpp) get a
     # second, short, time-bounded run of their own so that a fault in a route that has never met a second device cannot cost the
-    # measurement above: its outcome is reported as `c_abi_route`, never as `value`.
-    if (rc == 0 and "error" not in line and not args.no_c_abi_probe and args.comm == "auto" and args.backend == "nccl" and not args.share_device):
+    # measurement above: its outcome is reported as `c_abi_route`, never as `value`.  (--full only: a plain run measures the headline alone)
+    if (args.full and rc == 0 and "error" not in line and not args.no_c_abi_probe and args.comm == "auto" and args.backend == "nccl" and not args.share_device):
         probe = command(["--comm", "c_abi", "--no-extras", "--no-cpu-baseline", "--min-seconds", "0.3"])
         prc, pout, pto = run(probe, 240.0)
         pl = json_line(pout)
@@ -372,6 +393,55 @@ def time_blocks(loop, barrier, first_frame, steps, min_seconds, max_blocks=400, 
             return times, f
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6          # all files of --dump-outputs together, .npy headers included
+NPY_HEADER_BYTES = 256                   # room left per file for its header (np.save writes 128 bytes for these shapes)
+
+
+def last_step_outputs(args, loop, world, rank):
+    """What a caller of the timed path receives after its last frame, as float32 arrays {name: array}: the denoised shadow / AO image,
+    the raw visibility it was denoised from and, with mirror bounces, the reflections.  At N > 1, rank 0's: the frame gathered there
+    (or, without a gather, its own tile).  Call right after the timed region, before any other frame runs."""
+    import torch
+    from vulkanhybridrenderer_amd import lib
+
+    def f32(a):
+        return np.ascontiguousarray(a).view(np.float16).astype(np.float32)
+    if world > 1:
+        if rank != 0:
+            return {}
+        gathered = loop.gathered_frame()
+        if gathered is not None:
+            return {"denoised": gathered.cpu().numpy().astype(np.float32)}
+        x0, x1, y0, y1 = loop.owned_rect()
+        return {"denoised_rank0_tile": f32(loop.ctx.download(lib.DENOISED)[y0:y1, x0:x1])}
+    torch.cuda.synchronize()
+    loop.ctx.synchronize()
+    out = {"denoised": f32(loop.ctx.download(lib.DENOISED)), "raytraced": f32(loop.ctx.download(lib.RAYTRACED))}
+    if _bounces(args):
+        out["reflections"] = f32(loop.ctx.download(lib.REFLECTIONS))
+    return out
+
+
+def dump_outputs(directory, outputs, budget=DUMP_BUDGET_BYTES):
+    """DIR/<name>.npy for every array.  Above `budget` bytes in all (files, headers included), every image keeps the same fixed, seeded sample of its pixels (rows of
+    [pixels, channels], in pixel order), sized so that the files fit; `sampled_pixels` then holds the flat pixel indices as float64."""
+    os.makedirs(directory, exist_ok=True)
+    total = sum(a.nbytes for a in outputs.values())
+    room = budget - NPY_HEADER_BYTES * (len(outputs) + 1)
+    written = dict(outputs)
+    if total > room:
+        pixels = {a.shape[0] * a.shape[1] for a in outputs.values()}
+        assert len(pixels) == 1, "the images of one frame share their size"
+        pixels = pixels.pop()
+        keep = room // (total // pixels + 8)                                     # 8: the float64 index of each kept pixel
+        idx = np.sort(np.random.default_rng(12345).choice(pixels, size=keep, replace=False))
+        written = {name: a.reshape(pixels, -1)[idx] for name, a in outputs.items()}
+        written["sampled_pixels"] = idx.astype(np.float64)
+    for name, a in written.items():
+        np.save(os.path.join(directory, f"{name}.npy"), a)
+    return {name: list(a.shape) for name, a in written.items()}
+
+
 def main():
     args = parse()
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # dmabuf IPC: what RCCL's peer-to-peer setup needs on this driver (already exported on the GPU boxes)
@@ -498,7 +568,14 @@ def main():
         loop.frame(i)
     f += args.warmup
     barrier()
-    # Only the roofline kernel (a-trous) carries event pairs inside the timed region, and only every 11th / 13th of its launches
+    if args.warmup_seconds > 0 and world == 1 and f > 0:
+        # untimed frames until the clocks have settled; their count depends on time, so the path's cross-frame state is put back to where
+        # the --warmup frames left it (vhr_hybrid_save_state / _load_state): the timed frames get the same inputs and history on every run
+        snapshot = loop.save_state()
+        time_blocks(loop, barrier, f, 8, args.warmup_seconds, max_blocks=1 << 30)
+        barrier()
+        f = loop.load_state(snapshot)
+    # With --full, only the roofline kernel (a-trous) carries event pairs inside the timed region, and only every 11th / 13th of its launches
     # (a dispatch with an event pair costs ~6 us that the next kernel waits for: all five launches of a frame timed = +30 us on
     # a 0.5 ms frame, every 6th still +5 us; the stride is coprime with the launches per frame, so the sample walks through the
     # step sizes evenly: ~600 samples per second of timed region).  The other kernels are timed in a short extra loop afterwards
@@ -509,26 +586,33 @@ def main():
     async_dead = (world == 1 and args.frames_in_flight == 1 and option_overrides.get("svgf_async_unread", 1) != 0
                   and not option_overrides.get("svgf_elide_unread", 0) and loop.denoise and loop.atrous_steps == 5)
     ATROUS_TIMING_STRIDE = 13 if async_dead else 11       # coprime with the 4 (5) launches per frame on the context's stream: every step size sampled evenly
-    ctx.set_option("kernel_timing_stride", ATROUS_TIMING_STRIDE)
-    ctx.set_kernel_timing(["svgf_atrous"])
-    for k in ("raygen", "svgf_temporal", "svgf_atrous", "svgf_atrous_async", "blit", "reflection"):
-        ctx.kernel_time(k, reset=True)
-    # ---- the timed region: blocks of exactly --steps frames, repeated until --min-seconds have been measured (a single 20-frame
-    # block lasts 14 ms); every block is bracketed by barrier + synchronize, the MEDIAN block is reported ----
+    if args.full:                                         # (a plain run carries no event pair in its timed frames)
+        ctx.set_option("kernel_timing_stride", ATROUS_TIMING_STRIDE)
+        ctx.set_kernel_timing(["svgf_atrous"])
+        for k in ("raygen", "svgf_temporal", "svgf_atrous", "svgf_atrous_async", "blit", "reflection"):
+            ctx.kernel_time(k, reset=True)
+    # ---- the timed region: one block of exactly --steps frames, repeated until --min-seconds have been measured (1 s with --full; a
+    # single 20-frame block lasts 14 ms); every block is bracketed by barrier + synchronize, the MEDIAN block is reported ----
     first_timed = f
     def slowest_rank(dt):
         t = torch.tensor([dt], dtype=torch.float64, device="cpu" if args.backend == "gloo" else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
     block_s, f = time_blocks(loop, barrier, f, args.steps, args.min_seconds, slowest=slowest_rank if world > 1 else None)
-    ctx.gather_performance_statistics()
-    atrous_timed = ctx.kernel_time("svgf_atrous")
-    ctx.set_option("kernel_timing_stride", 1)
-    ctx.set_kernel_timing(["raygen", "svgf_temporal", "svgf_atrous_async", "blit", "reflection"])
-    for i in range(f, f + min(args.steps, 8)):
-        loop.frame(i)
-    f += min(args.steps, 8)
-    barrier()
+    dumped = None
+    if args.dump_outputs:                          # the last timed frame's images, before any other frame overwrites them
+        outputs = last_step_outputs(args, loop, world, rank)
+        if outputs:
+            dumped = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, outputs), "frame_index": f - 1}
+    if args.full:
+        ctx.gather_performance_statistics()
+        atrous_timed = ctx.kernel_time("svgf_atrous")
+        ctx.set_option("kernel_timing_stride", 1)
+        ctx.set_kernel_timing(["raygen", "svgf_temporal", "svgf_atrous_async", "blit", "reflection"])
+        for i in range(f, f + min(args.steps, 8)):
+            loop.frame(i)
+        f += min(args.steps, 8)
+        barrier()
 
     rays_per_block = [sum(loop.rays_in_frame(i) for i in range(first_timed + b * args.steps, first_timed + (b + 1) * args.steps)) for b in range(len(block_s))]
     cpu_dev = "cpu" if (world > 1 and args.backend == "gloo") else "cuda"
@@ -541,54 +625,55 @@ def main():
     mid = int(np.argsort(t_blocks)[len(t_blocks) // 2])         # the median block
     dt_max, total_rays = float(t_blocks[mid]), float(r_blocks[mid])
 
-    kt = {k: ctx.kernel_time(k) for k in ("raygen", "svgf_temporal", "svgf_atrous_async", "blit", "reflection")}
-    async_dead = async_dead and kt["svgf_atrous_async"][1] > 0
-    kt["svgf_atrous"] = atrous_timed
-    ctx.set_kernel_timing(False)
-    # traversal work counters (one extra, untimed frame with the in-kernel statistics enabled)
-    ctx.set_ray_statistics(True)
-    loop.frame(f)
-    f += 1
-    barrier()
-    ray_stats, trav_stats = ctx.ray_statistics(), ctx.traversal_statistics()
-    ctx.set_ray_statistics(False)
-    refl_block = None
-    if _bounces(args) and world == 1:
-        refl_block = reflection_block(ctx, loop, f, barrier)
-        f += 9
-    y0, y1 = loop.owned_rows()
-    # pixels an a-trous launch computes, averaged over the 5 launches of a frame: strips / tiles shrink the overlap per iteration
-    # (tiling.atrous_output_extent: 28, 24, 16, 0, 0 of E = 30); at N = 1 this is W x H
-    from vulkanhybridrenderer_amd import tiling
+    if args.full:                                  # kernel, pass and traversal figures: frames of their own after the timed region
+        kt = {k: ctx.kernel_time(k) for k in ("raygen", "svgf_temporal", "svgf_atrous_async", "blit", "reflection")}
+        async_dead = async_dead and kt["svgf_atrous_async"][1] > 0
+        kt["svgf_atrous"] = atrous_timed
+        ctx.set_kernel_timing(False)
+        # traversal work counters (one extra, untimed frame with the in-kernel statistics enabled)
+        ctx.set_ray_statistics(True)
+        loop.frame(f)
+        f += 1
+        barrier()
+        ray_stats, trav_stats = ctx.ray_statistics(), ctx.traversal_statistics()
+        ctx.set_ray_statistics(False)
+        refl_block = None
+        if _bounces(args) and world == 1:
+            refl_block = reflection_block(ctx, loop, f, barrier)
+            f += 9
+        y0, y1 = loop.owned_rows()
+        # pixels an a-trous launch computes, averaged over the 5 launches of a frame: strips / tiles shrink the overlap per iteration
+        # (tiling.atrous_output_extent: 28, 24, 16, 0, 0 of E = 30); at N = 1 this is W x H
+        from vulkanhybridrenderer_amd import tiling
 
-    def computed_pixels(extend):
-        cx0, cx1, cy0, cy1 = loop.plan.computed_rect(extend)
-        return (cx1 - cx0) * (cy1 - cy0)
-    exts = [tiling.atrous_output_extent(loop.plan.overlap, 1 << i) if world > 1 else 0 for i in range(loop.atrous_steps)]
-    pixels_svgf = sum(computed_pixels(e) for e in exts) / len(exts)
-    atrous_us = kt["svgf_atrous"][0] / max(1, kt["svgf_atrous"][1]) * 1e3
-    atrous_bytes = int(ATROUS_BYTES_PER_PIXEL * pixels_svgf)
-    pixels_temporal, pixels_owned = computed_pixels(None), computed_pixels(0)
-    achieved = atrous_bytes / (atrous_us * 1e-6) / 1e9 if atrous_us > 0 else 0.0
-    raygen_ms = kt["raygen"][0] / max(1, kt["raygen"][1])
-    passes = {}
-    for name in ("Raytrace Pass", "SVGF Denoise Pass"):
-        ema, last = ctx.pass_time_ms(name)
-        passes[name] = round(last, 4)
-    # distribution of the per-pass GPU times (the reference's timestamp pairs, render_graph.cpp:167-199) over 12 more frames,
-    # gathered frame by frame outside the timed region: median and p95
-    samples = {name: [] for name in passes}
-    for i in range(f, f + 12):
-        loop.frame(i)
-        ctx.gather_performance_statistics()
-        for name in samples:
-            samples[name].append(ctx.pass_time_ms(name)[1])
-    f += 12
-    barrier()
-    passes_median = {k: round(float(np.median(v)), 4) for k, v in samples.items()}
-    passes_p95 = {k: round(float(np.percentile(v, 95)), 4) for k, v in samples.items()}
-    rays_one_frame = loop.rays_in_frame(first_timed)
-    bvh = ctx.bvh_statistics()
+        def computed_pixels(extend):
+            cx0, cx1, cy0, cy1 = loop.plan.computed_rect(extend)
+            return (cx1 - cx0) * (cy1 - cy0)
+        exts = [tiling.atrous_output_extent(loop.plan.overlap, 1 << i) if world > 1 else 0 for i in range(loop.atrous_steps)]
+        pixels_svgf = sum(computed_pixels(e) for e in exts) / len(exts)
+        atrous_us = kt["svgf_atrous"][0] / max(1, kt["svgf_atrous"][1]) * 1e3
+        atrous_bytes = int(ATROUS_BYTES_PER_PIXEL * pixels_svgf)
+        pixels_temporal, pixels_owned = computed_pixels(None), computed_pixels(0)
+        achieved = atrous_bytes / (atrous_us * 1e-6) / 1e9 if atrous_us > 0 else 0.0
+        raygen_ms = kt["raygen"][0] / max(1, kt["raygen"][1])
+        passes = {}
+        for name in ("Raytrace Pass", "SVGF Denoise Pass"):
+            ema, last = ctx.pass_time_ms(name)
+            passes[name] = round(last, 4)
+        # distribution of the per-pass GPU times (the reference's timestamp pairs, render_graph.cpp:167-199) over 12 more frames,
+        # gathered frame by frame outside the timed region: median and p95
+        samples = {name: [] for name in passes}
+        for i in range(f, f + 12):
+            loop.frame(i)
+            ctx.gather_performance_statistics()
+            for name in samples:
+                samples[name].append(ctx.pass_time_ms(name)[1])
+        f += 12
+        barrier()
+        passes_median = {k: round(float(np.median(v)), 4) for k, v in samples.items()}
+        passes_p95 = {k: round(float(np.percentile(v, 95)), 4) for k, v in samples.items()}
+        rays_one_frame = loop.rays_in_frame(first_timed)
+        bvh = ctx.bvh_statistics()
     degraded = list(loop.degraded)
     gather_on, gather_error, plan, tp, rpp, rrpp = loop.gather, loop.gather_error, loop.plan, loop.tp, loop.rays_per_pixel, loop.reference_rays_per_pixel
     trace_overlap = getattr(loop, "trace_overlap", False)
@@ -598,7 +683,7 @@ def main():
     # ---- extra blocks of the N = 1 line (each its own context, after the timed region): what raygen.rgen's pass costs with its
     # always-on mirror ray, and the same workload with two frames in flight ----
     extras = {}
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         def one(options=None, host_k0=None, refl_out=None, **kw):
             lp = HybridFrameLoop(scene, W, H, n_frames, **common, **kw)
             for key, val in {**option_overrides, **(options or {})}.items():
@@ -655,22 +740,7 @@ def main():
         extras[f"value_frames_in_flight_{other}"] = mr
 
     if rank == 0:
-        node_bytes = 32 if option_overrides.get("compact_nodes", 1) else 48
-        trav_gbs = (trav_stats["node_visits"] * node_bytes + trav_stats["triangle_tests"] * 48) / max(raygen_ms, 1e-9) / 1e6
         transport = "RCCL (nccl)" if args.backend == "nccl" else "gloo (host memory)"
-        from vulkanhybridrenderer_amd import lib as _lib
-        fingerprint = _lib.source_fingerprint()
-        pmc, pmc_note = load_pmc(args, fingerprint)
-        valu = (pmc or {}).get("svgf_atrous_valu_insts_per_launch")
-        traffic = (pmc or {}).get("svgf_atrous_mean_traffic_bytes_per_launch")
-        traffic = int(traffic) if traffic else None
-        # MI355X_MICROARCH.md "Wave scheduling": a wave64 VALU instruction issues over 2 cycles of its SIMD-32
-        valu_floor_us = valu * 2.0 / (SIMDS * CLOCK_HZ) * 1e6 if valu else None
-        temporal_us = kt["svgf_temporal"][0] / max(1, kt["svgf_temporal"][1]) * 1e3
-        temporal_bytes = int(TEMPORAL_BYTES_PER_PIXEL * pixels_temporal)
-        svgf_pass_us = passes_median.get("SVGF Denoise Pass", 0.0) * 1e3
-        # (the pass's time stamps cover what the context's stream executes: with the dead dispatch on the side stream, four a-trous launches)
-        svgf_pass_bytes = int(temporal_bytes + (loop_atrous_steps - (1 if async_dead else 0)) * atrous_bytes + 3 * 16 * pixels_owned)
         out = {
             "metric": "Mrays/s (unique rays) + ms/frame, Sponza 1080p RT shadows+AO+SVGF",
             "value": round(total_rays / dt_max / 1e6, 2),
@@ -701,7 +771,7 @@ def main():
                 "exchanges_note": comm_note,
                 "frames_in_flight": args.frames_in_flight,
                 "schedule": ("reference schedule, every dispatch executed; the fifth a-trous dispatch (output never read, hybrid_render_path.cpp:299-328) is issued on the "
-                             "context's side stream beside the next frame's ray tracing (svgf_async_unread, images bit-identical; ms_per_step_all_dispatches_in_order = without)")
+                             "context's side stream beside the next frame's ray tracing (svgf_async_unread, images bit-identical; with --full, ms_per_step_all_dispatches_in_order = without)")
                             if async_dead else "reference schedule, every dispatch in recorded order on one stream",
                 # every ray of every frame is traced; only the order the launch's workgroups START in comes from the past (their lifetimes two launches ago)
                 "ray_tracing_block_order": ("row-major" if option_overrides.get("raygen_cost_order", 1) == 0 else
@@ -723,81 +793,101 @@ def main():
                         "raygen.rgen's always-on mirror ray is off unless --reflections (composition discards it in this mode): "
                         "ms_per_step_with_mirror_ray is the frame with it",
             },
-            "roofline": {
-                "kernel": "svgf_atrous_tile_kernel<step, 4 rows per tile at 1080p (8 at 4K)> (svgf_atrous_filter.comp: LDS comb tiles, weights in the exponent)",
-                "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                # the PMC-derived fields (traffic, valu, traversal.address_unit) come from profiles/pmc_<workload>.json and are quoted only when that
-                # file was collected on the library loaded here (vhr_source_fingerprint) for this very workload; else null and the reason
-                "pmc_file": None if pmc is None else f"profiles/pmc_{workload_key(args)}.json", "pmc_note": pmc_note, "library_fingerprint": fingerprint,
-                "traffic_source": "tools/pmc_workload.sh (rocprofv3 --pmc FETCH_SIZE x the correction calibrated in the same run + WRITE_SIZE; includes Infinity-Cache hits; mean over the five "
-                                  "launches of a frame.  Three of them also do the work of the pass's three blits -- iteration 0 stores the history copy (+8 B/px) and "
-                                  "copies the normals (+16 B/px), iteration 3 stores the Denoised image (+8 B/px): +13 MB on this average and +1.5 / +0.5 us on those "
-                                  "launches, which the 24 B/px of `achieved` do not count)",
-                # the same mean without the bytes of the three blits those launches carry (32 B/px per frame over five launches, N = 1 only)
-                "traffic_less_fused_blit_bytes": (None if traffic is None or world > 1 else int(traffic - 32 * pixels_owned / 5)),
-                "avg_launch_us": round(atrous_us, 2), "launches": int(kt["svgf_atrous"][1]),
-                "launches_note": (f"HIP event pairs on every {ATROUS_TIMING_STRIDE}th a-trous launch of the timed region on the context's stream "
-                                  f"({(4 if async_dead else 5) * args.steps * len(t_blocks)} launches, {'steps 1, 2, 4, 8' if async_dead else 'all five step sizes'} sampled evenly); "
-                                  "profiles/*kernel_stats* hold rocprofv3's average over all launches, one row per step size"),
-                # the reference's dead fifth dispatch (step 16; nothing reads its output): issued on the side stream, where it fills what the next
-                # frame's ray-tracing kernel leaves free -- its launch lasts as long as it shares the chip, which says nothing about the kernel
-                # with the mirror ray on, its launch runs beside the SVGF pass (option reflection_async, default): the a-trous launches then share the
-                # chip with a kernel of another pass and `achieved` says what they get of it, not what the kernel does alone (the run without
-                # --reflections is the kernel's own number)
-                "shares_the_chip_with": ("reflection_queue_kernel (the mirror ray's launch on its own stream, reflection_async)"
-                                         if _bounces(args) and world == 1 and option_overrides.get("reflection_async", 1) and args.frames_in_flight == 1 else None),
-                "side_stream_launch": None if not async_dead else {
-                    "what": "svgf_atrous_filter.comp step 16, the dispatch hybrid_render_path.cpp:299-328 never reads (option svgf_async_unread): same kernel, "
-                            "same bytes, beside raygen_queue_kernel of the next frame; not on the frame's critical path and not part of `achieved`",
-                    "avg_launch_us": round(kt["svgf_atrous_async"][0] / max(1, kt["svgf_atrous_async"][1]) * 1e3, 1), "launches": int(kt["svgf_atrous_async"][1])},
-                "algorithmic_bytes_per_launch": int(atrous_bytes),
-                # what actually bounds the kernel: issue of its vector instructions (PMC: lanes 96-97 % active, traffic 1.2-1.3 x algorithmic)
-                "valu": None if not valu else {
-                    "insts_per_launch": valu, "floor_us": round(valu_floor_us, 2), "frac": round(valu_floor_us / atrous_us, 4) if atrous_us > 0 else None,
-                    "source": "tools/pmc_workload.sh (rocprofv3 --pmc SQ_INSTS_VALU, wave-level instructions per launch); floor = insts x 2 cycles / (1024 SIMDs x 2.4 GHz), "
-                              "a wave64 instruction on a SIMD-32 (MI355X_MICROARCH.md).  The knock-out builds (profiles/r3_atrous_knockouts.txt) price the kernel's mix higher: a packed "
-                              "fp32 instruction 4 cycles, a transcendental 8"},
-            },
-            # the rest of the denoiser against the same HBM peak (VERDICT r2 #2d): svgf.comp alone, and the whole SVGF pass with the
-            # reference's schedule (1 temporal + 5 a-trous + 3 blits = 220 B/px) over the pass's median GPU time
-            "roofline_temporal": {"kernel": "svgf_temporal_kernel (svgf.comp)", "bound": "hbm", "algorithmic_bytes_per_launch": temporal_bytes,
-                                  "avg_launch_us": round(temporal_us, 2), "achieved": round(temporal_bytes / max(temporal_us, 1e-9) / 1e3, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                  "frac": round(temporal_bytes / max(temporal_us, 1e-9) / 1e3 / HBM_PEAK_GBS, 4)},
-            "roofline_svgf_pass": {"pass": "SVGF Denoise Pass (hybrid_render_path.cpp:245-331)" + (": the commands on the context's stream (1 temporal + 4 a-trous + 3 blits; the fifth, dead "
-                                           "a-trous dispatch runs on the side stream and is outside the pass's time stamps and these bytes)" if async_dead else ""),
-                                   "bound": "hbm", "algorithmic_bytes_per_frame": svgf_pass_bytes,
-                                   "median_us": round(svgf_pass_us, 1), "achieved": round(svgf_pass_bytes / max(svgf_pass_us, 1e-9) / 1e3, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                   "frac": round(svgf_pass_bytes / max(svgf_pass_us, 1e-9) / 1e3 / HBM_PEAK_GBS, 4)},
-            "traversal": {
-                "kernel": "raygen_queue_kernel (raygen.rgen's shadow + AO rays + miss.rmiss); the mirror ray runs in reflection_kernel (kernels_us.reflection)",
-                "avg_launch_ms": round(raygen_ms, 4),
-                "mrays_per_s": round(rays_one_frame * (1 + args.ao_spp) / max(1, rpp) / max(raygen_ms, 1e-9) / 1e3, 1),
-                "bvh_nodes": int(bvh["nodes"]), "bvh_bytes": int(bvh["node_bytes"] + bvh["triangle_bytes"]), "bvh_max_depth": int(bvh["max_depth"]),
-                "active_lane_utilisation": round(trav_stats["active_lane_utilisation"], 3),
-                "node_visits_per_ray": round(trav_stats["node_visits"] / max(1, ray_stats["covered_pixels"] * (1 + args.ao_spp)), 2),
-                "triangle_tests_per_ray": round(trav_stats["triangle_tests"] / max(1, ray_stats["covered_pixels"] * (1 + args.ao_spp)), 2),
-                # bytes the walk asks for: a 32-byte half-precision node per visit (48-byte nodes with compact_nodes 0), a 48-byte record per triangle test
-                "effective_traversal_gbs": round(trav_gbs, 1),
-                # against the level the cache-resident tree is read from (L2 ~34.5 TB/s), not HBM
-                "l2_frac": round(trav_gbs / L2_PEAK_GBS, 4),
-                "stack_overflows": int(ray_stats["stack_overflows"]),
-                "address_unit": address_unit_block(pmc, raygen_ms),
-                "note": "counters cover the any-hit (shadow + AO) queue kernel; utilisation = (node visits + triangle tests) / (64 x wave-level trips of those loops)",
-            },
-            # K0: the reference builds its BLAS / TLAS on the device once per scene (resource_manager.cpp:650,692,792); so does this
-            # (binned SAH, csrc/kernels_bvh.hip), once per scene, outside the frame.  upload = scene arrays + the tree fetched back for the host's self-checks
-            "k0_build_ms": round(build_ms, 1), "k0_upload_ms": round(upload_ms, 1), "k0_builder": k0_builder, "bvh_frame": bvh_frame, "bvh_presplit": {"percent": args.bvh_presplit, "level": presplit_level} if args.bvh_presplit else None,
-            "kernels_us": {"svgf_temporal": round(kt["svgf_temporal"][0] / max(1, kt["svgf_temporal"][1]) * 1e3, 2),
-                           "svgf_atrous": round(atrous_us, 2),
-                           "blit": round(kt["blit"][0] / max(1, kt["blit"][1]) * 1e3, 2) if kt["blit"][1] else None,      # None: all three blits are stores of a-trous launches
-                           "reflection": round(kt["reflection"][0] / max(1, kt["reflection"][1]) * 1e3, 2) if kt["reflection"][1] else None},
-            "passes_ms": passes, "passes_ms_median": passes_median, "passes_ms_p95": passes_p95,
         }
-        if refl_block is not None:
-            out["traversal_reflection"] = refl_block
-        out.update(extras)
-        if not args.no_cpu_baseline:
+        if dumped is not None:
+            out["dump_outputs"] = dumped
+        if args.full:
+            node_bytes = 32 if option_overrides.get("compact_nodes", 1) else 48
+            trav_gbs = (trav_stats["node_visits"] * node_bytes + trav_stats["triangle_tests"] * 48) / max(raygen_ms, 1e-9) / 1e6
+            from vulkanhybridrenderer_amd import lib as _lib
+            fingerprint = _lib.source_fingerprint()
+            pmc, pmc_note = load_pmc(args, fingerprint)
+            valu = (pmc or {}).get("svgf_atrous_valu_insts_per_launch")
+            traffic = (pmc or {}).get("svgf_atrous_mean_traffic_bytes_per_launch")
+            traffic = int(traffic) if traffic else None
+            # CDNA wave scheduling: a wave64 VALU instruction issues over 2 cycles of its SIMD-32
+            valu_floor_us = valu * 2.0 / (SIMDS * CLOCK_HZ) * 1e6 if valu else None
+            temporal_us = kt["svgf_temporal"][0] / max(1, kt["svgf_temporal"][1]) * 1e3
+            temporal_bytes = int(TEMPORAL_BYTES_PER_PIXEL * pixels_temporal)
+            svgf_pass_us = passes_median.get("SVGF Denoise Pass", 0.0) * 1e3
+            # (the pass's time stamps cover what the context's stream executes: with the dead dispatch on the side stream, four a-trous launches)
+            svgf_pass_bytes = int(temporal_bytes + (loop_atrous_steps - (1 if async_dead else 0)) * atrous_bytes + 3 * 16 * pixels_owned)
+            out.update({
+                "roofline": {
+                    "kernel": "svgf_atrous_tile_kernel<step, 4 rows per tile at 1080p (8 at 4K)> (svgf_atrous_filter.comp: LDS comb tiles, weights in the exponent)",
+                    "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                    # the PMC-derived fields (traffic, valu, traversal.address_unit) come from profiles/pmc_<workload>.json and are quoted only when that
+                    # file was collected on the library loaded here (vhr_source_fingerprint) for this very workload; else null and the reason
+                    "pmc_file": None if pmc is None else f"profiles/pmc_{workload_key(args)}.json", "pmc_note": pmc_note, "library_fingerprint": fingerprint,
+                    "traffic_source": "tools/pmc_workload.sh (rocprofv3 --pmc FETCH_SIZE x the correction calibrated in the same run + WRITE_SIZE; includes Infinity-Cache hits; mean over the five "
+                                      "launches of a frame.  Three of them also do the work of the pass's three blits -- iteration 0 stores the history copy (+8 B/px) and "
+                                      "copies the normals (+16 B/px), iteration 3 stores the Denoised image (+8 B/px): +13 MB on this average and +1.5 / +0.5 us on those "
+                                      "launches, which the 24 B/px of `achieved` do not count)",
+                    # the same mean without the bytes of the three blits those launches carry (32 B/px per frame over five launches, N = 1 only)
+                    "traffic_less_fused_blit_bytes": (None if traffic is None or world > 1 else int(traffic - 32 * pixels_owned / 5)),
+                    "avg_launch_us": round(atrous_us, 2), "launches": int(kt["svgf_atrous"][1]),
+                    "launches_note": (f"HIP event pairs on every {ATROUS_TIMING_STRIDE}th a-trous launch of the timed region on the context's stream "
+                                      f"({(4 if async_dead else 5) * args.steps * len(t_blocks)} launches, {'steps 1, 2, 4, 8' if async_dead else 'all five step sizes'} sampled evenly); "
+                                      "profiles/*kernel_stats* hold rocprofv3's average over all launches, one row per step size"),
+                    # the reference's dead fifth dispatch (step 16; nothing reads its output): issued on the side stream, where it fills what the next
+                    # frame's ray-tracing kernel leaves free -- its launch lasts as long as it shares the chip, which says nothing about the kernel
+                    # with the mirror ray on, its launch runs beside the SVGF pass (option reflection_async, default): the a-trous launches then share the
+                    # chip with a kernel of another pass and `achieved` says what they get of it, not what the kernel does alone (the run without
+                    # --reflections is the kernel's own number)
+                    "shares_the_chip_with": ("reflection_queue_kernel (the mirror ray's launch on its own stream, reflection_async)"
+                                             if _bounces(args) and world == 1 and option_overrides.get("reflection_async", 1) and args.frames_in_flight == 1 else None),
+                    "side_stream_launch": None if not async_dead else {
+                        "what": "svgf_atrous_filter.comp step 16, the dispatch hybrid_render_path.cpp:299-328 never reads (option svgf_async_unread): same kernel, "
+                                "same bytes, beside raygen_queue_kernel of the next frame; not on the frame's critical path and not part of `achieved`",
+                        "avg_launch_us": round(kt["svgf_atrous_async"][0] / max(1, kt["svgf_atrous_async"][1]) * 1e3, 1), "launches": int(kt["svgf_atrous_async"][1])},
+                    "algorithmic_bytes_per_launch": int(atrous_bytes),
+                    # what actually bounds the kernel: issue of its vector instructions (PMC: lanes 96-97 % active, traffic 1.2-1.3 x algorithmic)
+                    "valu": None if not valu else {
+                        "insts_per_launch": valu, "floor_us": round(valu_floor_us, 2), "frac": round(valu_floor_us / atrous_us, 4) if atrous_us > 0 else None,
+                        "source": "tools/pmc_workload.sh (rocprofv3 --pmc SQ_INSTS_VALU, wave-level instructions per launch); floor = insts x 2 cycles / (1024 SIMDs x 2.4 GHz), "
+                                  "a wave64 instruction on a SIMD-32 (CDNA wave scheduling).  The knock-out builds (profiles/r3_atrous_knockouts.txt) price the kernel's mix higher: a packed "
+                                  "fp32 instruction 4 cycles, a transcendental 8"},
+                },
+                # the rest of the denoiser against the same HBM peak: svgf.comp alone, and the whole SVGF pass with the
+                # reference's schedule (1 temporal + 5 a-trous + 3 blits = 220 B/px) over the pass's median GPU time
+                "roofline_temporal": {"kernel": "svgf_temporal_kernel (svgf.comp)", "bound": "hbm", "algorithmic_bytes_per_launch": temporal_bytes,
+                                      "avg_launch_us": round(temporal_us, 2), "achieved": round(temporal_bytes / max(temporal_us, 1e-9) / 1e3, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                      "frac": round(temporal_bytes / max(temporal_us, 1e-9) / 1e3 / HBM_PEAK_GBS, 4)},
+                "roofline_svgf_pass": {"pass": "SVGF Denoise Pass (hybrid_render_path.cpp:245-331)" + (": the commands on the context's stream (1 temporal + 4 a-trous + 3 blits; the fifth, dead "
+                                               "a-trous dispatch runs on the side stream and is outside the pass's time stamps and these bytes)" if async_dead else ""),
+                                       "bound": "hbm", "algorithmic_bytes_per_frame": svgf_pass_bytes,
+                                       "median_us": round(svgf_pass_us, 1), "achieved": round(svgf_pass_bytes / max(svgf_pass_us, 1e-9) / 1e3, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                       "frac": round(svgf_pass_bytes / max(svgf_pass_us, 1e-9) / 1e3 / HBM_PEAK_GBS, 4)},
+                "traversal": {
+                    "kernel": "raygen_queue_kernel (raygen.rgen's shadow + AO rays + miss.rmiss); the mirror ray runs in reflection_kernel (kernels_us.reflection)",
+                    "avg_launch_ms": round(raygen_ms, 4),
+                    "mrays_per_s": round(rays_one_frame * (1 + args.ao_spp) / max(1, rpp) / max(raygen_ms, 1e-9) / 1e3, 1),
+                    "bvh_nodes": int(bvh["nodes"]), "bvh_bytes": int(bvh["node_bytes"] + bvh["triangle_bytes"]), "bvh_max_depth": int(bvh["max_depth"]),
+                    "active_lane_utilisation": round(trav_stats["active_lane_utilisation"], 3),
+                    "node_visits_per_ray": round(trav_stats["node_visits"] / max(1, ray_stats["covered_pixels"] * (1 + args.ao_spp)), 2),
+                    "triangle_tests_per_ray": round(trav_stats["triangle_tests"] / max(1, ray_stats["covered_pixels"] * (1 + args.ao_spp)), 2),
+                    # bytes the walk asks for: a 32-byte half-precision node per visit (48-byte nodes with compact_nodes 0), a 48-byte record per triangle test
+                    "effective_traversal_gbs": round(trav_gbs, 1),
+                    # against the level the cache-resident tree is read from (L2 ~34.5 TB/s), not HBM
+                    "l2_frac": round(trav_gbs / L2_PEAK_GBS, 4),
+                    "stack_overflows": int(ray_stats["stack_overflows"]),
+                    "address_unit": address_unit_block(pmc, raygen_ms),
+                    "note": "counters cover the any-hit (shadow + AO) queue kernel; utilisation = (node visits + triangle tests) / (64 x wave-level trips of those loops)",
+                },
+                # K0: the reference builds its BLAS / TLAS on the device once per scene (resource_manager.cpp:650,692,792); so does this
+                # (binned SAH, csrc/kernels_bvh.hip), once per scene, outside the frame.  upload = scene arrays + the tree fetched back for the host's self-checks
+                "k0_build_ms": round(build_ms, 1), "k0_upload_ms": round(upload_ms, 1), "k0_builder": k0_builder, "bvh_frame": bvh_frame, "bvh_presplit": {"percent": args.bvh_presplit, "level": presplit_level} if args.bvh_presplit else None,
+                "kernels_us": {"svgf_temporal": round(kt["svgf_temporal"][0] / max(1, kt["svgf_temporal"][1]) * 1e3, 2),
+                               "svgf_atrous": round(atrous_us, 2),
+                               "blit": round(kt["blit"][0] / max(1, kt["blit"][1]) * 1e3, 2) if kt["blit"][1] else None,      # None: all three blits are stores of a-trous launches
+                               "reflection": round(kt["reflection"][0] / max(1, kt["reflection"][1]) * 1e3, 2) if kt["reflection"][1] else None},
+                "passes_ms": passes, "passes_ms_median": passes_median, "passes_ms_p95": passes_p95,
+            })
+            if refl_block is not None:
+                out["traversal_reflection"] = refl_block
+            out.update(extras)
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(scene, W, H, tp, args.cpu_frames, rpp)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -1,6 +1,6 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r6_pmc_k1; rm -rf $O; mkdir -p $O
-B="--steps 8 --warmup 2 --no-cpu-baseline --no-extras --min-seconds 0"
+B="--steps 8 --warmup 2 --full --no-cpu-baseline --no-extras --min-seconds 0 --warmup-seconds 0"
 for v in 1 0; do
   rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d $O/pre$v -- python3 $R/bench.py $B --option raygen_precompute=$v > $O/pre$v.log 2>&1 || { echo fail $v; tail -3 $O/pre$v.log; }
 done

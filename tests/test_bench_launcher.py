@@ -129,3 +129,63 @@ def test_help_text_formats():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and "--bvh-frame" in out.stdout and "--gpus" in out.stdout, out.stderr[-500:]
+
+
+def test_dump_outputs_keeps_whole_images_within_the_budget_and_a_fixed_sample_beyond(tmp_path):
+    """bench.dump_outputs: float32 images under the budget are written whole; above it every image keeps the same seeded sample of
+    pixels (the same from call to call), `sampled_pixels` says which, and the files together stay within the budget."""
+    import bench
+    import numpy as np
+    rng = np.random.default_rng(1)
+    outs = {"denoised": rng.random((40, 60, 4), dtype=np.float32), "raytraced": rng.random((40, 60, 2), dtype=np.float32)}
+    shapes = bench.dump_outputs(str(tmp_path / "whole"), outs)
+    assert shapes == {"denoised": [40, 60, 4], "raytraced": [40, 60, 2]}
+    for name, a in outs.items():
+        got = np.load(tmp_path / "whole" / f"{name}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, a)
+    budget = 12000
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), outs, budget=budget)
+    idx = np.load(tmp_path / "s1" / "sampled_pixels.npy")
+    assert idx.dtype == np.float64 and np.array_equal(idx, np.load(tmp_path / "s2" / "sampled_pixels.npy"))
+    assert np.all(np.diff(idx) > 0) and idx[-1] < 40 * 60
+    for name, a in outs.items():
+        got = np.load(tmp_path / "s1" / f"{name}.npy")
+        assert np.array_equal(got, a.reshape(40 * 60, -1)[idx.astype(np.int64)])
+        assert np.array_equal(got, np.load(tmp_path / "s2" / f"{name}.npy"))
+    assert sum(f.stat().st_size for f in (tmp_path / "s1").iterdir()) <= budget
+    assert sum(f.stat().st_size for f in (tmp_path / "whole").iterdir()) <= bench.DUMP_BUDGET_BYTES
+
+
+def test_help_names_the_plain_and_full_options():
+    r = subprocess.run([sys.executable, BENCH, "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout, r.stderr[-500:]
+
+
+def test_the_tile_check_runs_with_full_or_when_asked():
+    """N > 1: a plain run checks no tiles against a single full-frame context; --full checks 3 frames, --replan-frame needs the check and
+    gets it, and an explicit --verify-frames is taken as given."""
+    import bench
+    for argv, want in ((["--gpus", "2"], 0), (["--gpus", "2", "--full"], 3), (["--gpus", "2", "--replan-frame", "1"], 3),
+                       (["--gpus", "2", "--verify-frames", "5"], 5), (["--gpus", "2", "--full", "--verify-frames", "0"], 0)):
+        old = sys.argv
+        sys.argv = ["bench.py"] + argv
+        try:
+            assert bench.parse().verify_frames == want, argv
+        finally:
+            sys.argv = old
+
+
+def test_plain_runs_time_one_block_and_full_runs_a_second_of_blocks():
+    """A plain run times exactly --steps frames (one block) after an untimed second of warm-up; --full times blocks for >= 1 s and reports the
+    median one without that warm-up (the a-trous roofline samples the launches of the timed region); explicit values are taken as given."""
+    import bench
+    for argv, want in (([], (0.0, 1.0)), (["--full"], (1.0, 0.0)), (["--min-seconds", "0.3"], (0.3, 1.0)),
+                       (["--full", "--min-seconds", "0", "--warmup-seconds", "0"], (0.0, 0.0)), (["--warmup-seconds", "2"], (0.0, 2.0))):
+        old = sys.argv
+        sys.argv = ["bench.py", "--gpus", "1"] + argv
+        try:
+            a = bench.parse()
+            assert (a.min_seconds, a.warmup_seconds) == want, argv
+        finally:
+            sys.argv = old

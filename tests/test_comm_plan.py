@@ -277,17 +277,17 @@ def test_bench_refuses_more_gpus_than_the_box_has(n):
 @pytest.mark.gpu
 def test_bench_through_the_c_abi_at_world_two(tmp_path):
     """bench.py --gpus 2 WITHOUT torchrun (the launcher starts the ranks): the measured route is torch.distributed over RCCL, and the
-    launcher's second, time-bounded run reports the library's own RCCL calls (vhr_comm_*) as `c_abi_route`.  Then --comm c_abi as the
-    measured route.  Needs two devices: skipped on the one-GPU boxes of rounds 1-4."""
+    launcher's second, time-bounded run reports the library's own RCCL calls (vhr_comm_*) as `c_abi_route` (both, and the tile check, with
+    --full).  Then --comm c_abi as the measured route.  Skips itself with fewer than two GPUs."""
     import torch
     if torch.cuda.device_count() < 2:
         pytest.skip("needs two GPUs")
-    r, line = _bench(["--gpus", "2", "--steps", "4", "--warmup", "2", "--min-seconds", "0.1", "--no-cpu-baseline"])
+    r, line = _bench(["--gpus", "2", "--steps", "4", "--warmup", "2", "--min-seconds", "0.1", "--full", "--no-cpu-baseline"])
     assert r.returncode == 0, r.stderr[-3000:]
     assert line["n_gpus"] == 2 and line["ranks"] == 2 and line["config"]["multi_gpu_on_hardware"] is True
     assert line["config"]["strips_vs_single_context"] == "bit-identical"
     assert "c_abi_route" in line
-    r, line = _bench(["--gpus", "2", "--steps", "4", "--warmup", "2", "--min-seconds", "0.1", "--comm", "c_abi", "--no-cpu-baseline"])
+    r, line = _bench(["--gpus", "2", "--steps", "4", "--warmup", "2", "--min-seconds", "0.1", "--comm", "c_abi", "--full", "--no-cpu-baseline"])
     assert r.returncode == 0, r.stderr[-3000:]
     assert line["config"]["strips_vs_single_context"] == "bit-identical"
     assert "vhr_comm" in line["config"]["exchanges_through"]
@@ -331,3 +331,25 @@ def test_cost_balanced_cuts(vhr, world, grid):
     for r in range(world):                                # nothing to weigh: the equal-pixel plan
         assert tiling.make_tile_plan(W, H, world, r, 3, 5, 5, grid=grid, cost=np.zeros_like(cost), cost_cell=cell) == equal[r]
         _same_plan(lib.tile_plan(W, H, world, r, gr, gc, 3, 5, 5, cost=np.zeros_like(cost), cost_cell=cell), equal[r])
+
+
+@pytest.mark.gpu
+def test_dumped_outputs_are_the_same_from_run_to_run(tmp_path):
+    """Two plain runs with the same arguments: exactly --steps timed frames in one block, ms_per_step in the line, and the last timed
+    frame's images written as float32 .npy -- equal bit for bit between the runs."""
+    import numpy as np
+    lines = []
+    for d in ("a", "b"):
+        r, line = _bench(["--gpus", "1", "--scene", "tiny", "--width", "320", "--height", "200", "--steps", "5", "--warmup", "2",
+                          "--dump-outputs", str(tmp_path / d)])
+        assert r.returncode == 0 and line and "error" not in line, (r.stdout[-2000:], r.stderr[-3000:])
+        lines.append(line)
+    for line in lines:
+        assert line["steps"] == 5 and line["timed_blocks"]["blocks"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert "roofline" not in line and "cpu_baseline" not in line
+        assert sorted(line["dump_outputs"]["arrays"]) == ["denoised", "raytraced"]
+        assert line["dump_outputs"]["frame_index"] == 2 + 5 - 1         # --warmup frames 0-1, the timed frames 2-6: the last timed one
+    for name, shape in (("denoised", (200, 320, 4)), ("raytraced", (200, 320, 2))):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == shape and np.array_equal(a, b, equal_nan=True)
+    assert np.any(np.load(tmp_path / "a" / "denoised.npy") != 0)

@@ -11,7 +11,7 @@ OUT=$R/gpurun_out/pmc/$KEY
 rm -rf $OUT; mkdir -p $OUT
 rm -f $R/gpurun_out/pmc/pmc_$KEY.json      # a failed pass must not leave an earlier run's file for `cp gpurun_out/pmc/pmc_*.json profiles/`
 cd /tmp && export TMPDIR=/tmp
-B="--steps 8 --warmup 2 --no-cpu-baseline --no-extras --min-seconds 0 $*"
+B="--steps 8 --warmup 2 --full --no-cpu-baseline --no-extras --min-seconds 0 --warmup-seconds 0 $*"
 echo "[$KEY] FETCH_SIZE calibration"; rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/cal_fetch -- python3 $R/tools/calibrate_fetch.py > $OUT/cal_fetch.log 2>&1 || { echo "calibration failed"; tail -3 $OUT/cal_fetch.log; exit 1; }
 echo "[$KEY] FETCH_SIZE"; rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/bench_fetch -- python3 $R/bench.py $B > $OUT/bench_fetch.log 2>&1 || { echo "fetch pass failed"; tail -3 $OUT/bench_fetch.log; exit 1; }
 echo "[$KEY] WRITE_SIZE"; rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/bench_write -- python3 $R/bench.py $B > $OUT/bench_write.log 2>&1 || { echo "write pass failed"; exit 1; }
