@@ -557,7 +557,8 @@ int vhr_option_info(int32_t index, const char **name, int32_t *default_value, in
  * hipEventRecord, whose barrier packet costs ~4 us of stream time per record)
  * kind: 0 = raygen (K1: shadow + AO rays; with raygen_variant 0 also the mirror ray), 1 = svgf.comp (K3),
  * 2 = svgf_atrous_filter.comp (K4) on the context's stream, 3 = blits (K5), 4 = the mirror-ray kernel (K1's reflection ray + K2),
- * 5 / 6 / 7 = ssao.comp / ssao_blur.comp / ssr.comp, 8 = K4 dispatches issued on the side stream ("svgf_async_unread").
+ * 5 / 6 / 7 = ssao.comp / ssao_blur.comp / ssr.comp, 8 = K4 dispatches issued on the side stream ("svgf_async_unread"),
+ * 9 = vhr_ray_query (its two launches, each counted: the walk and decision (vi)'s binary64 redo).
  * kind_mask has bit (1 << kind) set for every kind to time (0 = off).  vhr_get_kernel_time synchronises, folds
  * the recorded pairs into (total milliseconds, launch count) and optionally resets the totals. */
 int vhr_set_kernel_timing(vhr_context *ctx, int32_t kind_mask);
@@ -637,6 +638,34 @@ int vhr_get_bvh_fingerprint(vhr_context *ctx, uint64_t *out);
  * of the order of the triangles inside a leaf.  The host's and the device's build of a scene agree on it ("bvh_builder" 0 / 1: the same
  * algorithm, the same tree; the reference's BLAS / TLAS are the driver's, resource_manager.cpp:593-801). */
 int vhr_get_bvh_tree_fingerprint(vhr_context *ctx, uint64_t *out);
+
+/* ---- Batched ray queries on the scene's BVH (rayQueryEXT with an opaque TLAS, cull mask 0xFF) ----
+ * Traces `count` caller-made rays against the geometry of the last vhr_update_geometry.  The flags of rayQueryInitializeEXT this
+ * stands for are gl_RayFlagsTerminateOnFirstHitEXT (VHR_RAY_QUERY_TERMINATE_ON_FIRST_HIT) or none; the mask is 0xFF.
+ *   - All geometry is opaque and two-sided; a triangle is hit iff tmin < t < tmax (decision (vi): fp32 Moeller-Trumbore, a candidate whose
+ *     solution contradicts itself decided again in binary64 -- the same test, bit for bit, as every walker of the library and the oracle).
+ *   - Without the flag: results = vhr_ray_hit[count], the hit of smallest t, ties broken by the smaller flat triangle index (primitive-major
+ *     order of vhr_update_geometry); a miss is geometry_index = primitive_index = 0xFFFFFFFF, t = u = v = 0.  With it: results =
+ *     uint8_t[count], 1 = some triangle is hit (which one ends the walk depends on the tree; the boolean does not).
+ *   - Degenerate rays are not rejected: a zero or NaN direction or tmin >= tmax misses, an infinite tmax is an unbounded ray.
+ *   - Device path (no VHR_RAY_QUERY_HOST_MEMORY): `rays` and `results` are device pointers.  The work is enqueued on the stream
+ *     vhr_get_current_stream reports at the time of the call (after a vhr_update_geometry made earlier on it) and the call returns
+ *     without synchronising; `results` is complete when that stream is.  It may be called between frames or inside a pass callback.
+ *     VHR_RAY_QUERY_HOST_MEMORY: host pointers, staged through device memory of the context's; the call returns with results in place.
+ *   - No side effects: no frame state is read or written (statistics, cost-order lifetimes, images), so the frames around a query are
+ *     bit-identical to frames without one.  Queries in flight on different streams share nothing (the query's counters and its list of
+ *     rays to decide again exist once per stream); a query reads `rays` and writes `results` in its stream's order only.
+ *   - VHR_ERROR_INVALID_ARGUMENT (message in vhr_last_error) for a NULL pointer with count > 0, an unknown flag bit, `rays` not 16-byte
+ *     aligned or `results` not 4-byte aligned -- checked first, on every context.  Then VHR_ERROR_NO_DEVICE on a host-only context.
+ *     count == 0 returns VHR_OK and launches nothing; a context without geometry makes every ray miss. */
+int vhr_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, uint32_t flags, void *results);
+/* The last vhr_ray_query (waits for the device): out[0] = rays, out[1] = rays with a hit, out[2] = rays decided again in binary64 by the
+ * second launch, out[3] = waves whose traversal stack overflowed (must be 0).  All 0 before the first query. */
+int vhr_get_ray_query_statistics(vhr_context *ctx, uint64_t out[4]);
+/* The layouts this library was built with, for bindings: out[0] = sizeof(vhr_ray), out[1] = offsetof(vhr_ray, tmin), out[2] =
+ * offsetof(vhr_ray, direction), out[3] = offsetof(vhr_ray, tmax), out[4] = sizeof(vhr_ray_hit), out[5] = offsetof(vhr_ray_hit,
+ * geometry_index), out[6] = offsetof(vhr_ray_hit, primitive_index), out[7] = offsetof(vhr_ray_hit, reserved).  Returns 8. */
+int vhr_ray_query_struct_layout(uint32_t out[8]);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,7 @@
 #ifndef VHR_TYPES_H
 #define VHR_TYPES_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -103,6 +104,28 @@ typedef struct vhr_trace_params {
     float    tmax;            /* 10000.0 */
 } vhr_trace_params;
 
+/* One ray of vhr_ray_query (include/vhr_amd.h): the arguments of rayQueryInitializeEXT after the TLAS, the cull mask and the flags.
+ * 32 bytes; an array of them must start at a 16-byte boundary (the kernel reads a ray as two 16-byte loads). */
+typedef struct vhr_ray {
+    float origin[3];
+    float tmin;
+    float direction[3];
+    float tmax;
+} vhr_ray;
+
+/* The committed closest hit of one ray (vhr_ray_query without VHR_RAY_QUERY_TERMINATE_ON_FIRST_HIT).  24 bytes. */
+typedef struct vhr_ray_hit {
+    float t, u, v;                 /* rayQueryGetIntersectionTEXT and the barycentrics (u, v); 0 on a miss */
+    uint32_t geometry_index;       /* rayQueryGetIntersectionGeometryIndexEXT = the primitive (vhr_update_geometry order); 0xFFFFFFFF = miss */
+    uint32_t primitive_index;      /* rayQueryGetIntersectionPrimitiveIndexEXT = the triangle within that primitive; 0xFFFFFFFF on a miss */
+    uint32_t reserved;             /* 0 */
+} vhr_ray_hit;
+
+enum {
+    VHR_RAY_QUERY_TERMINATE_ON_FIRST_HIT = 1,   /* gl_RayFlagsTerminateOnFirstHitEXT: results = uint8_t[count], 1 = occluded, 0 = not */
+    VHR_RAY_QUERY_HOST_MEMORY = 2               /* rays and results are host memory: staged, and the call returns with the results in place */
+};
+
 /* VkFormat values (passed through unchanged from reference-side code) */
 enum {
     VHR_FORMAT_UNDEFINED           = 0,
@@ -178,6 +201,9 @@ static_assert(sizeof(vhr_per_frame_data) == 584, "PerFrameData");
 static_assert(sizeof(vhr_svgf_push_constants) == 24, "SVGFPushConstants");
 static_assert(sizeof(vhr_ssr_push_constants) == 16 && sizeof(vhr_ssao_push_constants) == 4, "SSRPushConstants / SSAOPushConstants");
 static_assert(sizeof(vhr_trace_params) == 32, "vhr_trace_params");
+static_assert(sizeof(vhr_ray) == 32 && offsetof(vhr_ray, tmin) == 12 && offsetof(vhr_ray, direction) == 16 && offsetof(vhr_ray, tmax) == 28, "vhr_ray");
+static_assert(sizeof(vhr_ray_hit) == 24 && offsetof(vhr_ray_hit, geometry_index) == 12 && offsetof(vhr_ray_hit, primitive_index) == 16 &&
+              offsetof(vhr_ray_hit, reserved) == 20, "vhr_ray_hit");
 #else
 _Static_assert(sizeof(vhr_vertex) == 56, "Vertex");
 _Static_assert(sizeof(vhr_material) == 44, "Material");
@@ -187,6 +213,9 @@ _Static_assert(sizeof(vhr_per_frame_data) == 584, "PerFrameData");
 _Static_assert(sizeof(vhr_svgf_push_constants) == 24, "SVGFPushConstants");
 _Static_assert(sizeof(vhr_ssr_push_constants) == 16 && sizeof(vhr_ssao_push_constants) == 4, "SSRPushConstants / SSAOPushConstants");
 _Static_assert(sizeof(vhr_trace_params) == 32, "vhr_trace_params");
+_Static_assert(sizeof(vhr_ray) == 32 && offsetof(vhr_ray, tmin) == 12 && offsetof(vhr_ray, direction) == 16 && offsetof(vhr_ray, tmax) == 28, "vhr_ray");
+_Static_assert(sizeof(vhr_ray_hit) == 24 && offsetof(vhr_ray_hit, geometry_index) == 12 && offsetof(vhr_ray_hit, primitive_index) == 16 &&
+               offsetof(vhr_ray_hit, reserved) == 20, "vhr_ray_hit");
 #endif
 
 #endif /* VHR_TYPES_H */

@@ -1,0 +1,131 @@
+"""vhr_ray_query throughput on sponza_proc at 1080p (one GPU process), against the any-hit launch of K1 in the same run.
+
+  (a) the rayquery render path's shadow rays (rayquery_render_path/default.frag:36-45) from every covered pixel of frame 1's stand-in
+      G-buffer, in pixel order: in_pos, tmin 0.1, -light.direction, tmax 10000 -- closest hit and any hit;
+  (b) the same rays shuffled;
+  (c) as many uniformly random rays: origins in the scene's box, isotropic directions, tmin 0, tmax inf.
+
+Each batch is already on the device (torch tensors, Context.ray_query_device) and is queried --reps times after --warmup; a rate is rays
+over the mean time of a query, from HIP events around each call (wall) and from the library's kernel timing kind "ray_query" (the two
+launches' own begin / end timestamps).  K1: kernel kind "raygen" of a HybridFrameLoop over --frames frames of the same camera path (no
+mirror ray, SVGF on), once with the shadow ray alone and once as bench.py runs it (shadow + 2 AO rays per covered pixel).  One JSON line
+per measurement, the library's source fingerprint in each.
+
+  python tools/ray_query_rate.py [--reps 20] [--warmup 3] [--frames 20] [--out profiles/ray_query_rate.jsonl]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from vulkanhybridrenderer_amd import lib, ray_queries, scenes  # noqa: E402
+from vulkanhybridrenderer_amd.harness import HybridFrameLoop  # noqa: E402
+
+
+def time_queries(ctx, torch, rays_d, n, out_d, any_hit, reps, warmup):
+    for _ in range(warmup):
+        ctx.ray_query_device(rays_d.data_ptr(), n, out_d.data_ptr(), any_hit=any_hit)
+    torch.cuda.synchronize()
+    ctx.kernel_time("ray_query", reset=True)
+    ctx.set_kernel_timing(["ray_query"])
+    start = [torch.cuda.Event(enable_timing=True) for _ in range(reps)]
+    stop = [torch.cuda.Event(enable_timing=True) for _ in range(reps)]
+    for i in range(reps):
+        start[i].record()
+        ctx.ray_query_device(rays_d.data_ptr(), n, out_d.data_ptr(), any_hit=any_hit)
+        stop[i].record()
+    torch.cuda.synchronize()
+    ctx.set_kernel_timing(False)
+    wall_ms = float(np.mean([a.elapsed_time(b) for a, b in zip(start, stop)]))
+    kernel_ms, launches = ctx.kernel_time("ray_query", reset=True)
+    stats = ctx.ray_query_statistics()
+    return dict(wall_ms=wall_ms, kernel_ms=kernel_ms / reps, launches_per_query=launches / reps,
+                grays_per_s_wall=n / (wall_ms * 1e-3) / 1e9, grays_per_s_kernel=n / (kernel_ms / reps * 1e-3) / 1e9,
+                hits=stats[1], binary64_rays=stats[2], stack_overflows=stats[3])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--frames", type=int, default=20)
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    W, H = args.width, args.height
+    scene = scenes.sponza_proc()
+    fp = lib.load().vhr_source_fingerprint().decode()
+    lines = []
+
+    def emit(rec):
+        rec = dict(rec, scene="sponza_proc", width=W, height=H, fingerprint=fp)
+        print(json.dumps(rec), flush=True)
+        lines.append(rec)
+
+    def k1(loop, what):
+        ctx = loop.ctx
+        for i in range(3):
+            loop.frame(i)
+        ctx.synchronize()
+        ctx.kernel_time("raygen", reset=True)
+        ctx.set_kernel_timing(["raygen"])
+        for i in range(args.frames):
+            loop.frame(i)
+        ctx.synchronize()
+        ctx.set_kernel_timing(False)
+        ms, launches = ctx.kernel_time("raygen", reset=True)
+        covered = float(np.mean([loop.covered_pixels[loop.frame_slot(i)] for i in range(args.frames)]))
+        rays = covered * loop.rays_per_pixel
+        rec = dict(measure=what, ms=ms / max(1, launches), launches=launches, rays=rays, ns_per_ray=ms / max(1, launches) * 1e6 / rays)
+        emit(rec)
+        return rec
+
+    # K1 with its shadow ray alone (the like-for-like ray: origin on the surface, towards the light, tmax 10000), then K1 as bench.py runs
+    # it, whose loop also provides the stand-in G-buffer (torch's stream, no mirror ray)
+    loop = HybridFrameLoop(scene, W, H, args.frames, shadow=True, ao_spp=0, reflections=0, denoise=True)
+    try:
+        k1_shadow = k1(loop, "K1 any-hit launch, shadow ray only (ao_spp 0)")
+    finally:
+        loop.close()
+    loop = HybridFrameLoop(scene, W, H, args.frames, shadow=True, ao_spp=2, reflections=0, denoise=True)
+    try:
+        ctx = loop.ctx
+        k1_bench = k1(loop, "K1 any-hit launch, shadow + 2 AO rays per covered pixel (bench.py)")
+        depth = loop.gbuffers[1][2].cpu().numpy()
+        shadow, _ = ray_queries.rayquery_shadow_rays(loop.pfds[1], depth)
+        n = len(shadow)
+        rng = np.random.default_rng(args.seed)
+        lo, hi = ray_queries.scene_bounds(scene)
+        batches = [("(a) rayquery shadow rays, pixel order", shadow),
+                   ("(b) rayquery shadow rays, shuffled", shadow[rng.permutation(n)]),
+                   ("(c) uniformly random rays", ray_queries.random_rays(rng, n, lo, hi, margin=0.0))]
+        out_hit = torch.empty((n, 6), dtype=torch.int32, device="cuda")
+        out_any = torch.empty(n, dtype=torch.uint8, device="cuda")
+        for what, rays in batches:
+            rays_d = torch.from_numpy(np.ascontiguousarray(rays)).cuda()
+            for any_hit in (True, False):
+                r = time_queries(ctx, torch, rays_d, n, out_any if any_hit else out_hit, any_hit, args.reps, args.warmup)
+                r = dict(measure=what, mode="any hit" if any_hit else "closest hit", rays=n, **r)
+                r["ns_per_ray_kernel"] = r["kernel_ms"] * 1e6 / n
+                r["vs_k1_per_ray"] = r["ns_per_ray_kernel"] / k1_bench["ns_per_ray"]
+                r["vs_k1_shadow_per_ray"] = r["ns_per_ray_kernel"] / k1_shadow["ns_per_ray"]
+                emit(r)
+    finally:
+        loop.close()
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            for rec in lines:
+                f.write(json.dumps(rec) + "\n")
+
+
+if __name__ == "__main__":
+    main()

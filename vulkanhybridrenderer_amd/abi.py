@@ -51,6 +51,12 @@ svgf_push_constants_dtype = np.dtype([("integrated_shadow_and_ao", "<i4", 2),
 trace_params_dtype = np.dtype([("shadow_enable", "<u4"), ("ao_spp", "<u4"), ("ao_tmax", "<f4"),
                                ("reflections", "<u4"), ("cone_cos_max", "<f4"), ("normal_bias", "<f4"),
                                ("tmin", "<f4"), ("tmax", "<f4")])
+# vhr_ray_query (include/vhr_types.h: vhr_ray, vhr_ray_hit)
+ray_dtype = np.dtype([("origin", "<f4", 3), ("tmin", "<f4"), ("direction", "<f4", 3), ("tmax", "<f4")])
+ray_hit_dtype = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("geometry_index", "<u4"), ("primitive_index", "<u4"),
+                          ("reserved", "<u4")])
+RAY_QUERY_TERMINATE_ON_FIRST_HIT, RAY_QUERY_HOST_MEMORY = 1, 2
+RAY_MISS = 0xFFFFFFFF              # vhr_ray_hit.geometry_index / primitive_index of a miss
 
 assert vertex_dtype.itemsize == 56
 assert material_dtype.itemsize == 44
@@ -59,6 +65,7 @@ assert directional_light_dtype.itemsize == 112
 assert per_frame_dtype.itemsize == 584
 assert svgf_push_constants_dtype.itemsize == 24
 assert trace_params_dtype.itemsize == 32
+assert ray_dtype.itemsize == 32 and ray_hit_dtype.itemsize == 24
 
 
 def default_trace_params(shadow=True, ao_spp=2, reflections=True):

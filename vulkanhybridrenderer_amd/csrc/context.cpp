@@ -283,6 +283,8 @@ void vhr_destroy(vhr_context *ctx) {
     hipFree(ctx->d_textures);
     free_scene(ctx);
     hipFree(ctx->d_ray_stats);
+    for (auto &q : ctx->rq_scratch) { hipFree(q.counters); hipFree(q.list); }
+    hipFree(ctx->d_rq_staging);
     hipFree(ctx->d_tile_counter);
     for (vhr_context::CostOrder *co : { &ctx->cost_order_raygen, &ctx->cost_order_reflection, &ctx->cost_order_raytraced })
         for (int i = 0; i < 2; ++i) { hipFree(co->cost[i]); hipFree(co->order[i]); }
@@ -743,6 +745,59 @@ int vhr_get_drain_statistics(vhr_context *ctx, uint64_t out[4]) {
     const RayStats &r = ctx->h_ray_stats;
     out[0] = r.cut_entries; out[1] = r.drain_le4; out[2] = r.drain_le8; out[3] = r.drain_le16;
     return VHR_OK;
+}
+
+int vhr_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, uint32_t flags, void *results) {
+    if (!ctx) return VHR_ERROR_INVALID_ARGUMENT;
+    // the arguments first (the same answer on every context), then the device
+    if (flags & ~uint32_t(VHR_RAY_QUERY_TERMINATE_ON_FIRST_HIT | VHR_RAY_QUERY_HOST_MEMORY))
+        return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_ray_query: unknown flag bits " + std::to_string(flags));
+    if (count > 0 && (!rays || !results)) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_ray_query: rays and results must not be NULL when count > 0");
+    if (count > 0 && reinterpret_cast<uintptr_t>(rays) % 16u) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_ray_query: rays must be 16-byte aligned");
+    if (count > 0 && reinterpret_cast<uintptr_t>(results) % 4u) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_ray_query: results must be 4-byte aligned");
+    if (ctx->host_only) return ctx->fail(VHR_ERROR_NO_DEVICE, "vhr_ray_query: host-only context: no device work");
+    if (count == 0) return VHR_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool any_hit = (flags & VHR_RAY_QUERY_TERMINATE_ON_FIRST_HIT) != 0;
+    const uint64_t ray_bytes = uint64_t(count) * sizeof(vhr_ray), result_bytes = uint64_t(count) * (any_hit ? 1u : sizeof(vhr_ray_hit));
+    ctx->rq_rays = count;
+    if (!(flags & VHR_RAY_QUERY_HOST_MEMORY)) return vhr::launch_ray_query(ctx, rays, count, any_hit, results);
+    // host memory: staged through the context's own buffer (rays, then the results at the next 256-byte boundary)
+    const uint64_t result_offset = (ray_bytes + 255u) & ~uint64_t(255u), staging = result_offset + result_bytes;
+    if (ctx->rq_staging_bytes < staging) {
+        (void)hipFree(ctx->d_rq_staging);
+        ctx->d_rq_staging = nullptr;
+        ctx->rq_staging_bytes = 0;
+        HIP_TRY(ctx, hipMalloc(&ctx->d_rq_staging, staging));
+        ctx->rq_staging_bytes = staging;
+    }
+    char *const d = static_cast<char *>(ctx->d_rq_staging);
+    HIP_TRY(ctx, hipMemcpyAsync(d, rays, ray_bytes, hipMemcpyHostToDevice, ctx->stream));
+    const int rc = vhr::launch_ray_query(ctx, reinterpret_cast<const vhr_ray *>(d), count, any_hit, d + result_offset);
+    if (rc != VHR_OK) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(results, d + result_offset, result_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return VHR_OK;
+}
+
+int vhr_get_ray_query_statistics(vhr_context *ctx, uint64_t out[4]) {
+    if (!ctx || !out) return VHR_ERROR_INVALID_ARGUMENT;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (ctx->host_only || ctx->rq_rays == 0 || !ctx->rq_last_counters) return VHR_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipDeviceSynchronize());         // the stream of the last query may be the caller's: wait for the device, then read
+    RayQueryCounters c;
+    HIP_TRY(ctx, hipMemcpy(&c, ctx->rq_last_counters, sizeof(c), hipMemcpyDeviceToHost));
+    out[0] = ctx->rq_rays; out[1] = c.hits; out[2] = c.redo_count; out[3] = c.overflows;
+    return VHR_OK;
+}
+
+int vhr_ray_query_struct_layout(uint32_t out[8]) {
+    if (!out) return VHR_ERROR_INVALID_ARGUMENT;
+    out[0] = sizeof(vhr_ray); out[1] = offsetof(vhr_ray, tmin); out[2] = offsetof(vhr_ray, direction); out[3] = offsetof(vhr_ray, tmax);
+    out[4] = sizeof(vhr_ray_hit); out[5] = offsetof(vhr_ray_hit, geometry_index); out[6] = offsetof(vhr_ray_hit, primitive_index);
+    out[7] = offsetof(vhr_ray_hit, reserved);
+    return 8;
 }
 
 int vhr_calibration_stream_read(vhr_context *ctx, int32_t storage_image, uint32_t bytes_per_lane) {

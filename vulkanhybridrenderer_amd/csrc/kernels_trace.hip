@@ -1545,7 +1545,9 @@ __global__ __launch_bounds__(kTraceBlock) void reflection_kernel(const RaygenArg
 // decision vi), early exit of the node loop, LDS stack + scratch spill.  Leaves: every triangle, Moeller-Trumbore against the
 // full [tmin, tmax] interval, closest = min t then smaller flat index; with `any_hit` (wave-uniform) the first accepted
 // triangle ends the ray (gl_RayFlagsTerminateOnFirstHitEXT -- the boolean does not depend on the order).  ALPHA: every
-// candidate first runs shadow_anyhit.rahit (alpha_ignored).
+// candidate first runs shadow_anyhit.rahit (alpha_ignored).  PER_RAY (the batched ray query, ray_query_kernel): every ray brings
+// its own interval -- fetch(r, pix, origin, direction, tmin, tmax), the ray's tmax seeds the cull -- and commit(pix, triangle, u, v, t)
+// is also told the hit's t; `tmin` / `tmax` are then unused.
 // ---------------------------------------------------------------------------------------------
 constexpr uint32_t kNoHit = 0xffffffffu;
 
@@ -1554,7 +1556,7 @@ constexpr uint32_t kNoHit = 0xffffffffu;
 struct WalkCounters { uint32_t nodes = 0, leaves = 0, triangles = 0, wave_trips = 0, refills = 0; };
 
 struct NoFlag { __device__ __forceinline__ void operator()(uint32_t) const {} };
-template <bool SPILL, bool ALPHA, bool DEFER, bool STATS = false, typename Fetch, typename Commit, typename Flag = NoFlag>
+template <bool SPILL, bool ALPHA, bool DEFER, bool STATS = false, bool PER_RAY = false, typename Fetch, typename Commit, typename Flag = NoFlag>
 __device__ __forceinline__ void wave_queue_walk(const DeviceScene &sc, int *stack, const uint32_t stack_levels, const uint32_t lane,
                                                 const uint32_t total, const uint32_t refill_threshold, const uint32_t early_exit,
                                                 const float tmin, const float tmax, const bool any_hit, uint32_t &overflow,
@@ -1572,6 +1574,7 @@ __device__ __forceinline__ void wave_queue_walk(const DeviceScene &sc, int *stac
     volatile int spill[SPILL ? kSpillStack : 1];
     float tmin_v = tmin;
     asm volatile("" : "+v"(tmin_v));
+    float ray_tmin = tmin, ray_tmax = tmax;               // the interval of the lane's ray (PER_RAY: its own, else the launch's)
     for (;;) {
         const unsigned long long idle = __ballot(!has);
         const uint32_t n_idle = uint32_t(__popcll(idle));
@@ -1580,16 +1583,17 @@ __device__ __forceinline__ void wave_queue_walk(const DeviceScene &sc, int *stac
             next += n_idle;
             if (STATS && lane == 0) ++wc->refills;
             if (!has && r < total) {
-                fetch(r, pix, ro, rd);
+                if constexpr (PER_RAY) { fetch(r, pix, ro, rd, ray_tmin, ray_tmax); tmin_v = ray_tmin; }
+                else fetch(r, pix, ro, rd);
                 f3 bo, bd;
                 box_ray(sc, ro, rd, bo, bd);                  // "bvh_frame": the slab tests' ray (ro, rd stay the triangle tests')
                 rinv = f3{ cull_reciprocal(bd.x), cull_reciprocal(bd.y), cull_reciprocal(bd.z) };
                 noi = f3{ -(bo.x * rinv.x), -(bo.y * rinv.y), -(bo.z * rinv.z) };
                 ainv = f3{ fabsf(rinv.x), fabsf(rinv.y), fabsf(rinv.z) };
-                tbest = tmax; best_tri = kNoHit; best_flat = 0; best_u = 0.0f; best_v = 0.0f;
+                tbest = ray_tmax; best_tri = kNoHit; best_flat = 0; best_u = 0.0f; best_v = 0.0f;
                 cur = 0; sp = 0;
                 // the ray against the tile's cut: the (t, flat index) order of the commit makes the result independent of the order the subtrees are walked in
-                if (cut_n) cut_to_stack(cut, cut_n, stack, stack_levels, rinv, noi, tmin_v, tmax, cur, sp, emask);
+                if (cut_n) cut_to_stack(cut, cut_n, stack, stack_levels, rinv, noi, tmin_v, ray_tmax, cur, sp, emask);
                 has = true;
             }
         }
@@ -1635,14 +1639,14 @@ __device__ __forceinline__ void wave_queue_walk(const DeviceScene &sc, int *stac
                 float t, uu, ww;
                 if (STATS) ++my_tris;
                 const f3 v0 = f3{ ta.x, ta.y, ta.z }, e1 = f3{ ta.w, tb.x, tb.y }, e2 = f3{ tb.z, tb.w, tc.x };
-                if (mt_candidate(ro, rd, v0, e1, e2, tmin, tmax, t, uu, ww)) {
+                if (mt_candidate(ro, rd, v0, e1, e2, ray_tmin, ray_tmax, t, uu, ww)) {
                     // decision (vi): a candidate that contradicts itself is decided again in binary64.  DEFER (the mirror ray's kernels, where about one ray of a
                     // 1080p frame has one): not here, where the walk's registers are all alive -- the ray's pixel is flagged and computed again by the per-pixel
                     // code when the tile is shaded (redo_pixel_reflection); the walk goes on as if the candidate had missed.  !DEFER (the raytraced path,
                     // whose shadow rays leave the hit point itself: 6 % of its rays have one): inline.
                     if (!solution_consistent(ro, rd, v0, e1, e2, t, uu, ww)) {
                         if (DEFER) { flag(pix); continue; }
-                        if (!mt_binary64(ro, rd, v0, e1, e2, tmin, tmax, t, uu, ww)) continue;
+                        if (!mt_binary64(ro, rd, v0, e1, e2, ray_tmin, ray_tmax, t, uu, ww)) continue;
                     }
                     if (ALPHA && alpha_ignored(sc, first + i, uu, ww)) continue;
                     const uint32_t flat = __float_as_uint(tc.w);
@@ -1671,7 +1675,8 @@ __device__ __forceinline__ void wave_queue_walk(const DeviceScene &sc, int *stac
         }
         if (has && cur == kStackSentinel) {
             has = false;
-            commit(pix, best_tri, best_u, best_v);
+            if constexpr (PER_RAY) commit(pix, best_tri, best_u, best_v, tbest);
+            else commit(pix, best_tri, best_u, best_v);
         }
         if (STATS) {
             wc->nodes += my_nodes; wc->triangles += my_tris;
@@ -2838,6 +2843,162 @@ int launch_ray_triangle_pairs(vhr_context *ctx, const float *pairs, uint32_t n, 
     }
     (void)hipFree(d_pairs); (void)hipFree(d_tuv); (void)hipFree(d_hit);
     return rc;
+}
+
+// ---------------------------------------------------------------------------------------------
+// vhr_ray_query: batched rayQueryEXT on the scene's BVH (the reference's RayqueryRenderPath, rayquery_render_path/default.frag:36-45,
+// asks the same of the TLAS from a fragment shader).  Launch 1 (ray_query_kernel): every wave owns kQueryWaveRays consecutive rays of
+// the batch and runs wave_queue_walk over them (PER_RAY: each ray's own [tmin, tmax]; no tile, so no shared descent).  Decision (vi)
+// stays out of the loop as in the mirror-ray kernel (DEFER): a ray with a self-contradicting candidate is walked on as if it had
+// missed and its index is appended to a list at its commit.  Launch 2 (ray_query_redo_kernel) walks every listed ray again with
+// traverse<>, which decides in binary64 in place, and overwrites its result; it strides over the list, whose length only the
+// device knows.  Neither launch reads or writes anything of a frame.
+// ---------------------------------------------------------------------------------------------
+#ifndef VHR_QUERY_WAVE_RAYS
+#define VHR_QUERY_WAVE_RAYS 256      // rays per wave of ray_query_kernel (a scratch build may change it)
+#endif
+constexpr uint32_t kQueryWaveRays = VHR_QUERY_WAVE_RAYS;
+
+struct RayQueryArgs {
+    DeviceScene scene;
+    const float4 *rays;                   // 2 x float4 per ray: (origin, tmin), (direction, tmax)
+    void *results;                        // vhr_ray_hit[count] or uint8_t[count] (any_hit)
+    uint32_t *redo_list;                  // capacity count
+    RayQueryCounters *counters;
+    uint32_t count, any_hit;
+};
+static_assert(sizeof(vhr_ray) == 2 * sizeof(float4), "vhr_ray is two float4");
+
+__device__ __forceinline__ void ray_query_store(const RayQueryArgs &a, const uint32_t ray, const bool any_hit, const bool hit, const float t,
+                                                const float u, const float v, const uint32_t prim, const uint32_t tri) {
+    if (any_hit) { static_cast<uint8_t *>(a.results)[ray] = hit ? 1u : 0u; return; }
+    uint32_t *const r = static_cast<uint32_t *>(a.results) + size_t(ray) * 6u;      // vhr_ray_hit (results is 4-byte aligned)
+    r[0] = hit ? __float_as_uint(t) : 0u; r[1] = hit ? __float_as_uint(u) : 0u; r[2] = hit ? __float_as_uint(v) : 0u;
+    r[3] = hit ? prim : kNoHit; r[4] = hit ? tri : kNoHit; r[5] = 0u;
+}
+
+template <bool SPILL>
+__global__ __launch_bounds__(kQueueBlock * 2) void ray_query_kernel(const RayQueryArgs a, const uint32_t stack_levels, const uint32_t refill_threshold,
+                                                                    const uint32_t early_exit, const Stamps st) {
+    vhr_stamp(st);
+    extern __shared__ int s_dyn[];                        // per wave: (stack_levels + 3) x 64 ints, see raygen_queue_kernel
+    const uint32_t lane = threadIdx.x & 63u, wave = uint32_t(__builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)));
+    const uint64_t first = (uint64_t(blockIdx.x) * 2u + wave) * kQueryWaveRays;
+    if (first >= a.count) return;
+    const uint32_t base = uint32_t(first), total = uint32_t(min(uint64_t(kQueryWaveRays), uint64_t(a.count) - first));
+    const bool any_hit = a.any_hit != 0u;
+    if (a.scene.node_count == 0) {                        // no geometry: every ray misses
+        for (uint32_t r = lane; r < total; r += 64u) ray_query_store(a, base + r, any_hit, false, 0.0f, 0.0f, 0.0f, 0u, 0u);
+        return;
+    }
+    int *stack = s_dyn + wave * (stack_levels + 3u) * kQueueBlock + lane;
+    stack[0] = kStackSentinel;
+    uint32_t overflow = 0, hits = 0;
+    bool flagged = false;                                 // decision (vi) asked for binary64 on the lane's current ray
+    wave_queue_walk<SPILL, false, true, false, true>(
+        a.scene, stack, stack_levels, lane, total, refill_threshold, early_exit, 0.0f, 0.0f, any_hit, overflow, nullptr, 0u,
+        [&](uint32_t r, uint32_t &ray, f3 &ro, f3 &rd, float &tmin, float &tmax) {
+            ray = base + r;
+            const float4 p = a.rays[size_t(ray) * 2u], q = a.rays[size_t(ray) * 2u + 1u];
+            ro = f3{ p.x, p.y, p.z }; tmin = p.w;
+            rd = f3{ q.x, q.y, q.z }; tmax = q.w;
+        },
+        [&](uint32_t ray, uint32_t tri, float u, float v, float t) {
+            const bool hit = tri != kNoHit;
+            hits += hit ? 1u : 0u;
+            ray_query_store(a, ray, any_hit, hit, t, u, v, hit ? a.scene.tris[tri].prim : 0u, hit ? a.scene.tris[tri].tri : 0u);
+            if (flagged) {                                // (rare: a plain vector atomic per listed ray)
+                a.redo_list[atomicAdd(&a.counters->redo_count, 1u)] = ray;
+                flagged = false;
+            }
+        }, nullptr,
+        [&](uint32_t) { flagged = true; });
+    for (int off = 32; off > 0; off >>= 1) hits += uint32_t(__shfl_xor(int(hits), off));
+    const bool wave_overflow = __any(overflow != 0u);
+    if (lane == 0) {
+        if (hits) atomicAdd(&a.counters->hits, (unsigned long long)hits);
+        if (wave_overflow) atomicAdd(&a.counters->overflows, 1u);
+    }
+}
+
+// Decision (vi), second half, for the rays launch 1 listed: the per-pixel walker with the binary64 redo inside its leaf test.
+__global__ __launch_bounds__(kTraceBlock) void ray_query_redo_kernel(const RayQueryArgs a, const Stamps st) {
+    vhr_stamp(st);
+    __shared__ int s_stack[kTraceStack * kTraceBlock];
+    const uint32_t n = a.counters->redo_count;            // written by launch 1
+    const bool any_hit = a.any_hit != 0u;
+    uint32_t overflow = 0;
+    int delta = 0;                                        // change of the hit count
+    for (uint32_t i = blockIdx.x * kTraceBlock + threadIdx.x; i < n; i += gridDim.x * kTraceBlock) {
+        const uint32_t ray = a.redo_list[i];
+        const float4 p = a.rays[size_t(ray) * 2u], q = a.rays[size_t(ray) * 2u + 1u];
+        const f3 o = f3{ p.x, p.y, p.z }, d = f3{ q.x, q.y, q.z };
+        Hit best;
+        best.t = best.u = best.v = 0.0f; best.tri_index = 0; best.flat = 0;
+        bool hit, was;
+        if (any_hit) {
+            was = static_cast<const uint8_t *>(a.results)[ray] != 0u;
+            hit = traverse<true>(a.scene, o, d, p.w, q.w, s_stack + threadIdx.x, best, overflow);
+        } else {
+            was = static_cast<const uint32_t *>(a.results)[size_t(ray) * 6u + 3u] != kNoHit;
+            hit = traverse<false>(a.scene, o, d, p.w, q.w, s_stack + threadIdx.x, best, overflow);
+        }
+        ray_query_store(a, ray, any_hit, hit, best.t, best.u, best.v, hit && !any_hit ? a.scene.tris[best.tri_index].prim : 0u,
+                        hit && !any_hit ? a.scene.tris[best.tri_index].tri : 0u);
+        delta += int(hit) - int(was);
+    }
+    if (delta) atomicAdd(&a.counters->hits, (unsigned long long)(long long)delta);
+    if (overflow) atomicAdd(&a.counters->overflows, 1u);
+}
+
+int launch_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, bool any_hit, void *results) {
+    if (count == 0) return VHR_OK;
+    RayQueryScratch *q = nullptr;                  // this stream's counters and list
+    for (RayQueryScratch &e : ctx->rq_scratch) if (e.stream == ctx->stream) q = &e;
+    if (!q) {
+        ctx->rq_scratch.push_back(RayQueryScratch{ ctx->stream, nullptr, nullptr, 0 });
+        q = &ctx->rq_scratch.back();
+        if (hipMalloc(reinterpret_cast<void **>(&q->counters), sizeof(RayQueryCounters)) != hipSuccess) {
+            q->counters = nullptr;
+            ctx->rq_scratch.pop_back();
+            return ctx->fail(VHR_ERROR_DEVICE, "vhr_ray_query: device allocation failed");
+        }
+    }
+    if (q->capacity < count) {
+        (void)hipFree(q->list);                     // (synchronises: a query still in flight is done with it)
+        q->list = nullptr;
+        q->capacity = 0;
+        if (hipMalloc(reinterpret_cast<void **>(&q->list), size_t(count) * sizeof(uint32_t)) != hipSuccess)
+            return ctx->fail(VHR_ERROR_DEVICE, "vhr_ray_query: device allocation failed");
+        q->capacity = count;
+    }
+    ctx->rq_last_counters = q->counters;
+    RayQueryArgs a;
+    a.scene = ctx->device_scene();
+    a.rays = reinterpret_cast<const float4 *>(rays);
+    a.results = results;
+    a.redo_list = q->list;
+    a.counters = q->counters;
+    a.count = count;
+    a.any_hit = any_hit ? 1u : 0u;
+    if (hipMemsetAsync(q->counters, 0, sizeof(RayQueryCounters), ctx->stream) != hipSuccess)
+        return ctx->fail(VHR_ERROR_DEVICE, "vhr_ray_query: hipMemsetAsync failed");
+    const uint32_t levels = std::max<uint32_t>(1u, std::min<uint32_t>(ctx->bvh_depth + 1u, uint32_t(std::max(1, ctx->options[kOptLdsStackLevels]))));
+    const uint32_t threshold = uint32_t(std::max(1, std::min(64, ctx->options[kOptRefillThreshold])));
+    const uint32_t early_exit = uint32_t(std::max(0, std::min(15, ctx->options[kOptEarlyExit])));
+    const size_t lds = size_t(levels + 3) * kQueueBlock * sizeof(int) * 2;
+    const bool spill = levels < ctx->bvh_depth + 1u;
+    const dim3 grid(uint32_t((uint64_t(count) + 2u * kQueryWaveRays - 1u) / (2u * kQueryWaveRays)));
+    ctx->time_begin(kKernelRayQuery);
+    if (spill) launch(ctx, ray_query_kernel<true>, grid, dim3(kQueueBlock * 2), lds, a, levels, threshold, early_exit);
+    else launch(ctx, ray_query_kernel<false>, grid, dim3(kQueueBlock * 2), lds, a, levels, threshold, early_exit);
+    if (a.scene.node_count != 0) {
+        const uint32_t redo_blocks = std::min<uint32_t>((count + kTraceBlock - 1u) / kTraceBlock, uint32_t(ctx->cu_count) * 4u);
+        launch(ctx, ray_query_redo_kernel, dim3(redo_blocks), dim3(kTraceBlock), 0, a);
+    }
+    ctx->time_end(kKernelRayQuery);
+    if (hipGetLastError() != hipSuccess) return ctx->fail(VHR_ERROR_DEVICE, "vhr_ray_query: kernel launch failed");
+    return VHR_OK;
 }
 
 }  // namespace vhr

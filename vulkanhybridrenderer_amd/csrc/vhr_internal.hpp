@@ -254,6 +254,13 @@ struct SvgfCmd {
     const void *src_base; void *dst_base;                          // Copy: the images' base pointers (hazard checks)
 };
 
+// vhr_ray_query's counters (csrc/kernels_trace.hip): rays the binary64 launch walked again (= entries of the redo list), waves whose stack
+// overflowed, rays with a hit.  A buffer of the query's own: no frame reads or writes it.
+struct RayQueryCounters { uint32_t redo_count, overflows; unsigned long long hits; };
+// ... and the list of rays decision (vi) hands to the binary64 launch; one set per stream queries were enqueued on, so that queries in flight
+// on different streams (between frames on the caller's, inside a pass on the frame's front stream) share nothing
+struct RayQueryScratch { hipStream_t stream; RayQueryCounters *counters; uint32_t *list; uint64_t capacity; };
+
 struct RayStats {
     unsigned long long unique_rays, covered_pixels, stack_overflows, node_visits, leaf_visits, triangle_tests, wave_iterations, second_bounce_rays;
     unsigned long long cycles_total, cycles_setup, cycles_refill, cycles_nodes, cycles_leaves, refills, waves, drain_iterations;   // per-wave s_memtime sums
@@ -312,7 +319,7 @@ inline constexpr OptionInfo kOptionInfo[kOptCount] = {
 };
 
 // optional per-kernel timing with HIP events on the context stream (vhr_set_kernel_timing)
-enum KernelKind { kKernelRaygen = 0, kKernelTemporal = 1, kKernelAtrous = 2, kKernelCopy = 3, kKernelReflection = 4, kKernelSsao = 5, kKernelSsaoBlur = 6, kKernelSsr = 7, kKernelAtrousAsync = 8, kKernelKinds = 9 };
+enum KernelKind { kKernelRaygen = 0, kKernelTemporal = 1, kKernelAtrous = 2, kKernelCopy = 3, kKernelReflection = 4, kKernelSsao = 5, kKernelSsaoBlur = 6, kKernelSsr = 7, kKernelAtrousAsync = 8, kKernelRayQuery = 9, kKernelKinds = 10 };
 struct KernelTimer {
     std::vector<hipEvent_t> events;     // begin/end pairs
     size_t used = 0;                    // events recorded since the last drain
@@ -441,6 +448,13 @@ struct vhr_context {
     vhr::RayStats h_ray_stats = {};
     vhr::RayStats h_refl_stats = {};      // the mirror-ray launch's counters (d_ray_stats[1])
     uint64_t raytraced_pixels = 0;      // != 0: the last TraceRays was the raytraced render path's (primary rays launched)
+    // vhr_ray_query: its own scratch, which no frame touches -- counters and redo list per stream, and (VHR_RAY_QUERY_HOST_MEMORY, which waits
+    // for its stream before it returns) the device copies of the caller's rays and results; the buffers grow to the largest query so far
+    std::vector<vhr::RayQueryScratch> rq_scratch;
+    const vhr::RayQueryCounters *rq_last_counters = nullptr;   // the last query's (vhr_get_ray_query_statistics)
+    void *d_rq_staging = nullptr;
+    uint64_t rq_staging_bytes = 0;
+    uint64_t rq_rays = 0;               // rays of the last query (0: none yet)
 
     int options[vhr::kOptCount];       // vhr_set_option; defaults from vhr::kOptionInfo (the constructor)
     vhr_context() { for (int i = 0; i < vhr::kOptCount; ++i) options[i] = vhr::kOptionInfo[i].def; }
@@ -539,5 +553,7 @@ void launch_stamp(vhr_context *ctx);            // a one-thread kernel that take
 int flush_recorded(vhr_context *ctx);          // issue the commands a compute pass recorded (no-op when there are none)
 int launch_calibration_read(vhr_context *ctx, const Image &img, uint32_t bytes_per_lane, uint32_t *sink);
 int launch_ray_triangle_pairs(vhr_context *ctx, const float *pairs, uint32_t n, uint32_t *hit, float *tuv);
+// vhr_ray_query's device path: `rays` (count x vhr_ray) and `results` (vhr_ray_hit or uint8_t per ray) are device memory; enqueued on ctx->stream
+int launch_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, bool any_hit, void *results);
 
 }  // namespace vhr

@@ -37,7 +37,7 @@ EXPORTS = [
     "vhr_get_kernel_time", "vhr_set_option", "vhr_get_option", "vhr_option_count", "vhr_option_info", "vhr_get_traversal_statistics", "vhr_source_fingerprint", "vhr_debug_wave_lifetimes", "vhr_get_reflection_statistics", "vhr_get_binary64_statistics", "vhr_debug_ray_triangle", "vhr_get_traversal_cycles", "vhr_get_drain_statistics", "vhr_get_build_times", "vhr_atrous_overlap", "vhr_atrous_output_extent", "vhr_strip_plan_make",
     "vhr_strip_plan_exchanges", "vhr_tile_grid_choose", "vhr_tile_plan_make", "vhr_tile_plan_make_weighted", "vhr_get_tile_cost_map", "vhr_tile_plan_exchanges", "vhr_tile_plan_replan", "vhr_comm_replan", "vhr_comm_get_unique_id", "vhr_comm_use_library", "vhr_comm_library", "vhr_comm_create", "vhr_comm_create_tiled", "vhr_comm_destroy", "vhr_comm_last_error", "vhr_comm_exchange_raytraced",
     "vhr_comm_start_frame_exchanges", "vhr_comm_finish_frame_exchanges",
-    "vhr_calibration_stream_read",
+    "vhr_calibration_stream_read", "vhr_ray_query", "vhr_get_ray_query_statistics", "vhr_ray_query_struct_layout",
 ]
 
 
@@ -278,6 +278,9 @@ def load():
     L.vhr_comm_finish_frame_exchanges.argtypes = [vp]
     L.vhr_comm_replan.argtypes = [vp, C.POINTER(TilePlanC), i32, i32, i32]
     L.vhr_calibration_stream_read.argtypes = [vp, i32, u32]
+    L.vhr_ray_query.argtypes = [vp, vp, u32, u32, vp]
+    L.vhr_get_ray_query_statistics.argtypes = [vp, C.POINTER(u64)]
+    L.vhr_ray_query_struct_layout.argtypes = [C.POINTER(u32)]
     L.vhr_set_kernel_timing.argtypes = [vp, i32]
     L.vhr_get_kernel_time.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(u64), i32]
     _lib = L
@@ -688,7 +691,51 @@ class Context:
         self.check(self.L.vhr_get_bvh_statistics(self.handle, out), "bvh_statistics")
         return dict(nodes=out[0], triangles=out[1], max_depth=out[2], node_bytes=out[3], triangle_bytes=out[4])
 
-    KERNEL_KINDS = {"raygen": 0, "svgf_temporal": 1, "svgf_atrous": 2, "blit": 3, "reflection": 4, "ssao": 5, "ssao_blur": 6, "ssr": 7, "svgf_atrous_async": 8}
+    KERNEL_KINDS = {"raygen": 0, "svgf_temporal": 1, "svgf_atrous": 2, "blit": 3, "reflection": 4, "ssao": 5, "ssao_blur": 6, "ssr": 7, "svgf_atrous_async": 8,
+                    "ray_query": 9}
+
+    @staticmethod
+    def _rays_array(rays):
+        """(n, 8) float32 (origin, tmin, direction, tmax) or abi.ray_dtype -> a C-contiguous, 16-byte-aligned ray_dtype array."""
+        a = np.asarray(rays)
+        if a.dtype == abi.ray_dtype:
+            if a.ndim != 1:
+                raise ValueError(f"ray_query: a ray_dtype array must be 1-D, got shape {a.shape}")
+        elif a.dtype == np.float32:
+            if a.ndim != 2 or a.shape[1] != 8:
+                raise ValueError(f"ray_query: float32 rays must have shape (n, 8), got {a.shape}")
+            a = np.ascontiguousarray(a).view(abi.ray_dtype).reshape(-1)
+        else:
+            raise TypeError(f"ray_query: rays must be float32 (n, 8) or abi.ray_dtype, got {a.dtype}")
+        if not a.flags.c_contiguous or a.ctypes.data % 16:       # vhr_ray_query wants 16-byte-aligned rays: copy into an aligned buffer
+            raw = np.empty(len(a) * abi.ray_dtype.itemsize + 16, np.uint8)
+            start = -raw.ctypes.data % 16
+            aligned = raw[start:start + len(a) * abi.ray_dtype.itemsize].view(abi.ray_dtype)
+            aligned[:] = a
+            a = aligned
+        return a
+
+    def ray_query(self, rays, any_hit=False):
+        """vhr_ray_query on host arrays: rays (n, 8) float32 or abi.ray_dtype.  Returns abi.ray_hit_dtype[n] (closest hit; a miss has
+        geometry_index = primitive_index = abi.RAY_MISS) or, with any_hit, bool[n] (occluded)."""
+        r = self._rays_array(rays)
+        n = len(r)
+        out = np.zeros(n, np.uint8) if any_hit else np.zeros(n, abi.ray_hit_dtype)
+        flags = abi.RAY_QUERY_HOST_MEMORY | (abi.RAY_QUERY_TERMINATE_ON_FIRST_HIT if any_hit else 0)
+        self.check(self.L.vhr_ray_query(self.handle, r.ctypes.data if n else None, n, flags, out.ctypes.data if n else None), "ray_query")
+        return out.astype(bool) if any_hit else out
+
+    def ray_query_device(self, rays_ptr, count, results_ptr, any_hit=False):
+        """vhr_ray_query on device memory (e.g. torch tensors' data_ptr()): `count` vhr_ray records at rays_ptr (16-byte aligned), results
+        (vhr_ray_hit, or one uint8 per ray with any_hit) at results_ptr.  Enqueued on current_stream(); returns without synchronising."""
+        flags = abi.RAY_QUERY_TERMINATE_ON_FIRST_HIT if any_hit else 0
+        self.check(self.L.vhr_ray_query(self.handle, rays_ptr or None, int(count), flags, results_ptr or None), "ray_query_device")
+
+    def ray_query_statistics(self):
+        """The last ray query: [rays, rays with a hit, rays decided again in binary64, waves whose stack overflowed (must be 0)]."""
+        out = (C.c_uint64 * 4)()
+        self.check(self.L.vhr_get_ray_query_statistics(self.handle, out), "ray_query_statistics")
+        return [int(x) for x in out]
 
     def current_stream(self):
         """hipStream_t (as an int) the library is enqueueing on right now: inside a pass callback, the stream that pass is ordered on."""
