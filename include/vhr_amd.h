@@ -271,6 +271,19 @@ int  vhr_raytraced_rebuild(vhr_raytraced_render_path *path, int32_t use_anyhit_s
 const char *vhr_raytraced_last_error(vhr_raytraced_render_path *path);
 
 /* ---------------------------------------------------------------------------------------------
+ * RayqueryRenderPath (src/render_paths/rayquery_render_path.{h,cpp}) re-hosted on the API above (csrc/rayquery_render_path.cpp): one
+ * external graphics pass, "Forward Pass", with the outputs RENDER_OUTPUT (binding 0) and "Depth" (D32_SFLOAT, binding 1, clear depth 0)
+ * (:12-18).  The path owns nothing and has no settings.  Its raster body is the integrator's (forward_pass, may be NULL);
+ * vhr_standin_rayquery_forward is the library's stand-in for it.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct vhr_rayquery_render_path vhr_rayquery_render_path;
+int  vhr_rayquery_create(vhr_context *ctx, vhr_external_pass_callback forward_pass, void *forward_user, vhr_rayquery_render_path **out);
+void vhr_rayquery_destroy(vhr_rayquery_render_path *path);
+int  vhr_rayquery_build(vhr_rayquery_render_path *path);       /* RenderPath::Build (render_path.cpp:14-20), at the context's display extent */
+int  vhr_rayquery_rebuild(vhr_rayquery_render_path *path);     /* RenderPath::Rebuild (render_path.cpp:21-27) */
+const char *vhr_rayquery_last_error(vhr_rayquery_render_path *path);
+
+/* ---------------------------------------------------------------------------------------------
  * Harness / test access (no reference counterpart: the reference inspects images through its ImGui
  * debug-texture viewer, renderer.cpp:215-224)
  * ------------------------------------------------------------------------------------------- */
@@ -334,6 +347,31 @@ int vhr_standin_composition(vhr_context *ctx, uint32_t resource_idx, const vhr_c
  * (raytraced_render_path/composition.vert:5-8, composition.frag:11-13): the named image sampled at the texel centres and
  * written as swapchain texels (B8G8R8A8_SRGB, presentation orientation) into a storage image of 4-byte texels. */
 int vhr_standin_raytraced_composition(vhr_context *ctx, const char *raytraced_output_image, int32_t output_storage_image);
+
+/* Stand-in for the rayquery render path's "Forward Pass" (rayquery_render_path.cpp:11-54, rayquery_render_path/default.vert:19-28,
+ * default.frag:16-49), called from that pass's callback.  A ray caster on the path's own BVH, not a rasteriser: per pixel the closest
+ * hit of the camera ray through the near-plane point of the pixel centre (the G-buffer stand-in's ray; the raster pass discards nothing,
+ * so no alpha test), then default.frag -- one terminate-on-first-hit query from in_pos (tmin 0.1) along -light.direction (tmax 10000),
+ * every triangle opaque, and 0.2 * albedo + max(dot(N, L), 0) * albedo * light.color * in_shadow, alpha 1, without light.intensity.
+ * Uses the per-frame data of resource_idx and computes the whole display (strips and screen tiles are out of scope).  Writes:
+ *   output_storage_image  a pool storage image of 4-byte texels: swapchain texels (B8G8R8A8_SRGB, bytes b g r a), in the presentation
+ *                         orientation vhr_standin_composition writes (row 0 = top); a miss is (0, 0, 0, 0)
+ *   depth_image           the transient "Depth" (D32_SFLOAT): reverse-Z clip.z / clip.w in the G-buffer stand-in's orientation, 0 for a miss
+ *   three optional probes in device memory (NULL = not written), one entry per pixel in Depth's row order:
+ *     primary_hits        the committed primary hit (geometry_index 0xFFFFFFFF where nothing is hit; t in the ray's parameterisation,
+ *                         1 = the near plane), 4-byte aligned
+ *     positions           4 floats: in_pos and w = 1 where covered, (0, 0, 0, 0) where not, 4-byte aligned
+ *     shadowed            1 = the inline query found an occluder (0 for a miss)
+ * With vhr_set_ray_statistics on, vhr_get_ray_statistics reports one primary ray per pixel + one query per covered pixel, and the
+ * stack overflows.  "variant_rayquery" picks the kernel (vhr_set_option); kernel timing kind 10. */
+typedef struct vhr_rayquery_forward_desc {
+    int32_t output_storage_image;
+    const char *depth_image;
+    vhr_ray_hit *primary_hits;
+    float *positions;
+    uint8_t *shadowed;
+} vhr_rayquery_forward_desc;
+int vhr_standin_rayquery_forward(vhr_context *ctx, uint32_t resource_idx, const vhr_rayquery_forward_desc *desc);
 
 /* Multi-GPU row strips: this context owns rows [row_begin, row_end) of the
  * display.  Ray tracing runs on the owned rows; the SVGF kernels on the owned rows extended by `overlap`
@@ -467,6 +505,8 @@ int vhr_get_ray_statistics(vhr_context *ctx, uint64_t out[4]);
  *   "reflection_variant" the mirror ray + reflection_hit.rchit: reflection_kernel / reflection_queue_kernel (closest-hit queue per 16x8 tile,
  *                        shading with the whole wave; one or two bounces)
  *   "raytraced_variant"  the raytraced render path's pass: raytraced_kernel / raytraced_queue_kernel
+ *   "variant_rayquery"   the rayquery render path's forward pass (vhr_standin_rayquery_forward): rayquery_forward_kernel /
+ *                        rayquery_forward_queue_kernel (primary ray + inline query per 16x8 tile and wave)
  *   "atrous_variant"     svgf_atrous_filter.comp: svgf_atrous_kernel (direct cached loads, product-form weights) / svgf_atrous_tile_kernel
  *                        (LDS comb tiles, weights in the exponent)
  *  The queue kernels:
@@ -558,7 +598,7 @@ int vhr_option_info(int32_t index, const char **name, int32_t *default_value, in
  * kind: 0 = raygen (K1: shadow + AO rays; with raygen_variant 0 also the mirror ray), 1 = svgf.comp (K3),
  * 2 = svgf_atrous_filter.comp (K4) on the context's stream, 3 = blits (K5), 4 = the mirror-ray kernel (K1's reflection ray + K2),
  * 5 / 6 / 7 = ssao.comp / ssao_blur.comp / ssr.comp, 8 = K4 dispatches issued on the side stream ("svgf_async_unread"),
- * 9 = vhr_ray_query (its two launches, each counted: the walk and decision (vi)'s binary64 redo).
+ * 9 = vhr_ray_query (its two launches, each counted: the walk and decision (vi)'s binary64 redo), 10 = vhr_standin_rayquery_forward.
  * kind_mask has bit (1 << kind) set for every kind to time (0 = off).  vhr_get_kernel_time synchronises, folds
  * the recorded pairs into (total milliseconds, launch count) and optionally resets the totals. */
 int vhr_set_kernel_timing(vhr_context *ctx, int32_t kind_mask);

@@ -1,0 +1,391 @@
+"""The rayquery render path (rayquery_render_path.cpp:11-54, default.vert:19-28, default.frag:16-49): the host graph on a host-only
+context, and on the GPU the "Forward Pass" stand-in (vhr_standin_rayquery_forward) -- the work-queue kernel against the literal one bit
+for bit, depth against the G-buffer stand-in, the inline queries against the oracle and vhr_ray_query, colour against a float64 numpy
+restatement of default.frag, per-frame data by resource index, an empty scene, and a resize."""
+import numpy as np
+import pytest
+
+from tests import f2_scene
+from vulkanhybridrenderer_amd import abi, camera, lib, scenes
+
+MISS = abi.RAY_MISS
+FORWARD = "Forward Pass"
+
+
+# --------------------------------------------------------------------------------------------- CPU
+def test_host_graph(vhr):
+    """rayquery_render_path.cpp on a host-only context: one pass, "Depth" at the display extent, no pool images, Rebuild, destroy."""
+    ctx = lib.Context(1280, 720, host_only=True)
+    try:
+        p = lib.RayqueryRenderPath(ctx)
+        p.build()
+        assert ctx.execution_order() == [FORWARD]
+        assert ctx.contains_image(lib.DEPTH) and ctx.image_format(lib.DEPTH) == abi.FORMAT_D32_SFLOAT
+        info = ctx.transient_info(lib.DEPTH)
+        assert (info.width, info.height, info.bytes_per_pixel) == (1280, 720, 4)
+        p.rebuild()
+        assert ctx.execution_order() == [FORWARD]
+        p.destroy()
+        assert ctx.upload_new_storage_image(8, 8, abi.FORMAT_B8G8R8A8_UNORM) == 0      # the path owns no pool images (:56)
+        p2 = lib.RayqueryRenderPath(ctx, forward_pass=lambda c: None)
+        p2.build()
+        assert ctx.execution_order() == [FORWARD]
+        p2.destroy()
+    finally:
+        ctx.close()
+
+
+def test_host_resize_then_build_takes_the_new_extent(vhr):
+    ctx = lib.Context(640, 360, host_only=True)
+    try:
+        p = lib.RayqueryRenderPath(ctx)
+        p.build()
+        ctx.resize(333, 177)
+        p.build()
+        info = ctx.transient_info(lib.DEPTH)
+        assert (info.width, info.height) == (333, 177)
+        assert ctx.execution_order() == [FORWARD]
+        p.destroy()
+    finally:
+        ctx.close()
+
+
+def test_host_only_standin_and_bindings(vhr):
+    """The option, the kernel timing kind, and no device work on a host-only context."""
+    assert lib.option_table()["variant_rayquery"] == (1, 0, 1)
+    assert lib.Context.KERNEL_KINDS["rayquery_forward"] == 10
+    ctx = lib.Context(64, 48, host_only=True)
+    try:
+        p = lib.RayqueryRenderPath(ctx)
+        p.build()
+        with pytest.raises(lib.VhrError, match="host-only"):
+            ctx.standin_rayquery_forward(0)
+        p.destroy()
+    finally:
+        ctx.close()
+
+
+# --------------------------------------------------------------------------------------------- GPU
+class _Forward:
+    """A context with the path built and the stand-in as its pass body, writing all three probes into torch tensors."""
+
+    def __init__(self, sc, W, H):
+        import torch
+        self.torch = torch
+        self.W, self.H = W, H
+        self.ctx = lib.Context(W, H)
+        self.ctx.upload_scene(sc)
+        self.ctx.set_ray_statistics(True)
+        self.resource_idx = 0
+        self._alloc()
+        self.path = lib.RayqueryRenderPath(self.ctx, forward_pass=self._body)
+        self.path.build()
+
+    def _alloc(self):
+        n = self.W * self.H
+        self.present = self.ctx.upload_new_storage_image(self.W, self.H, abi.FORMAT_B8G8R8A8_SRGB)
+        self.hits = self.torch.zeros((n, 6), dtype=self.torch.int32, device="cuda")
+        self.pos = self.torch.zeros((n, 4), dtype=self.torch.float32, device="cuda")
+        self.sh = self.torch.zeros(n, dtype=self.torch.uint8, device="cuda")
+        self.torch.cuda.synchronize()
+
+    def _body(self, c):
+        c.standin_rayquery_forward(self.present, self.resource_idx, primary_hits_ptr=self.hits.data_ptr(), positions_ptr=self.pos.data_ptr(),
+                                   shadowed_ptr=self.sh.data_ptr())
+
+    def resize(self, W, H):
+        self.ctx.resize(W, H)
+        self.W, self.H = W, H
+        self._alloc()
+        self.path.build()
+
+    def run(self, pfd, variant=1, resource_idx=0, pfds=None):
+        self.ctx.set_option("variant_rayquery", variant)
+        self.resource_idx = resource_idx
+        for i, p in enumerate(pfds or [pfd]):
+            self.ctx.update_per_frame_ubo(i, p)
+        self.ctx.execute(0, 0)
+        self.ctx.synchronize()
+        H, W = self.H, self.W
+        hits = np.ascontiguousarray(self.hits.cpu().numpy()).view(np.uint32).view(abi.ray_hit_dtype).reshape(H, W)
+        return dict(out=self.ctx.download(self.present), depth=self.ctx.download(lib.DEPTH), hits=hits,
+                    pos=self.pos.cpu().numpy().reshape(H, W, 4), sh=self.sh.cpu().numpy().reshape(H, W), stats=self.ctx.ray_statistics())
+
+    def close(self):
+        self.path.destroy()
+        self.ctx.close()
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint8)
+
+
+def _assert_same(a, b, what):
+    for k in ("out", "depth", "hits", "pos", "sh"):
+        assert np.array_equal(_bits(a[k]), _bits(b[k])), f"{what}: {k} differs"
+    assert a["stats"] == b["stats"], what
+
+
+def _check_counts(r, W, H):
+    covered = int((r["hits"]["geometry_index"] != MISS).sum())
+    assert r["stats"]["stack_overflows"] == 0
+    assert r["stats"]["covered_pixels"] == covered                      # one query per covered pixel
+    assert r["stats"]["unique_rays"] == W * H + covered
+    assert np.array_equal(r["pos"][..., 3] == 1.0, r["hits"]["geometry_index"] != MISS)
+    return covered
+
+
+def _scene(name):
+    return {"f4": f2_scene.scene_f4, "sponza": scenes.sponza_proc, "tiny": scenes.tiny_scene}[name]()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("scene_name,W,H", [("f4", 160, 96), ("f4", 333, 177), ("sponza", 1920, 1080)])
+def test_gpu_queue_kernel_equals_literal_kernel(scene_name, W, H):
+    """variant_rayquery 1 (work queue, default) and 0 (one pixel per thread): output, depth and all three probes bit for bit, with deep
+    and shallow LDS stacks (the second spills to scratch), at an extent that is not a multiple of the 16x8 tile."""
+    sc = _scene(scene_name)
+    pfd = camera.dolly_frames(sc, W, H, 2)[1]
+    f = _Forward(sc, W, H)
+    try:
+        base = f.run(pfd, variant=0)
+        covered = _check_counts(base, W, H)
+        assert 0.2 * W * H < covered <= W * H
+        assert 0 < int(base["sh"].sum()) < covered                     # some pixels shadowed, some lit
+        for levels in (8, 2):
+            f.ctx.set_option("lds_stack_levels", levels)
+            got = f.run(pfd, variant=1)
+            _check_counts(got, W, H)
+            _assert_same(got, base, f"{scene_name} {W}x{H}, queue kernel with {levels} LDS levels")
+        f.ctx.set_option("lds_stack_levels", 8)
+    finally:
+        f.close()
+
+
+def _gbuffer_depth(sc, W, H, pfd):
+    ctx = lib.Context(W, H)
+    ctx.upload_scene(sc)
+    path = lib.HybridRenderPath(ctx, gbuffer_pass=lambda c: c.standin_gbuffer(0))
+    path.build()
+    try:
+        ctx.update_per_frame_ubo(0, pfd)
+        ctx.execute(0, 0)
+        ctx.synchronize()
+        return ctx.download(lib.DEPTH)
+    finally:
+        path.destroy()
+        ctx.close()
+
+
+@pytest.mark.gpu
+def test_gpu_depth_against_the_gbuffer_standin():
+    """Same camera ray, same first hit: without alpha-masked or transparent materials the depth is the G-buffer stand-in's bit for bit.
+    On scene_f4 the raster pass discards nothing while the G-buffer steps through the fence's masked texels: nearer (reverse Z: greater)
+    or equal everywhere, strictly nearer somewhere."""
+    for name, W, H in (("tiny", 200, 120), ("sponza", 480, 270)):
+        sc = _scene(name)
+        pfd = camera.dolly_frames(sc, W, H, 2)[1]
+        f = _Forward(sc, W, H)
+        try:
+            fw = f.run(pfd)["depth"]
+        finally:
+            f.close()
+        gb = _gbuffer_depth(sc, W, H, pfd)
+        assert (fw != 0).mean() > 0.3
+        assert np.array_equal(fw.view(np.uint32), gb.view(np.uint32)), f"{name}: {(fw != gb).sum()} depths differ"
+    sc = f2_scene.scene_f4()
+    W, H = 160, 96
+    pfd = camera.dolly_frames(sc, W, H, 2)[1]
+    f = _Forward(sc, W, H)
+    try:
+        fw = f.run(pfd)["depth"]
+    finally:
+        f.close()
+    gb = _gbuffer_depth(sc, W, H, pfd)
+    assert (fw >= gb).all() and (fw > gb).any()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("scene_name,W,H,step", [("f4", 160, 96, 3), ("sponza", 480, 270, 17)])
+def test_gpu_queries_equal_the_oracle_and_vhr_ray_query(oracle, scene_name, W, H, step):
+    """The inline query of every covered pixel (in_pos, tmin 0.1, -light.direction, tmax 10000, terminate on first hit) equals
+    vhr_ray_query's any-hit answer for the same ray, and the oracle's occluded() on a grid of pixels."""
+    sc = _scene(scene_name)
+    pfd = camera.dolly_frames(sc, W, H, 2)[1]
+    f = _Forward(sc, W, H)
+    try:
+        r = f.run(pfd)
+        cov = r["pos"][..., 3] == 1.0
+        L = -np.asarray(pfd["directional_light"]["direction"][:3], np.float32)
+        rays = np.zeros((int(cov.sum()), 8), np.float32)
+        rays[:, 0:3] = r["pos"][cov][:, :3]
+        rays[:, 3], rays[:, 4:7], rays[:, 7] = 0.1, L, 10000.0
+        occ = f.ctx.ray_query(rays, any_hit=True)
+        assert np.array_equal(occ, r["sh"][cov] == 1), f"{int((occ != (r['sh'][cov] == 1)).sum())} queries differ from vhr_ray_query"
+        assert (r["sh"][~cov] == 0).all()
+        osc = oracle.Scene(sc)
+        checked = 0
+        for y in range(0, H, step):
+            for x in range(0, W, step):
+                if cov[y, x]:
+                    assert osc.occluded(r["pos"][y, x, :3], L, 0.1, 1e4) == bool(r["sh"][y, x]), (x, y)
+                    checked += 1
+        assert checked > 100
+    finally:
+        f.close()
+
+
+# ---- default.frag in float64 --------------------------------------------------------------------------
+def _srgb_decode_lut():
+    c = np.arange(256) / 255.0
+    return np.where(c <= 0.04045, c / 12.92, ((c + 0.055) / 1.055) ** 2.4).astype(np.float32).astype(np.float64)
+
+
+def _wrap(i, n, mode):
+    if mode == abi.ADDRESS_CLAMP_TO_EDGE:
+        return np.clip(i, 0, n - 1)
+    if mode == abi.ADDRESS_MIRRORED_REPEAT:
+        m = np.mod(i, 2 * n)
+        return np.where(m < n, m, 2 * n - 1 - m)
+    return np.mod(i, n)
+
+
+def _sample(tex, u, v):
+    """texture() with the texture's own sampler (filter, address modes) at LOD 0, float64, on an sRGB or UNORM RGBA8 image."""
+    img = np.asarray(tex["rgba8"])
+    h, w = img.shape[:2]
+    texel = img.astype(np.float64) / 255.0
+    if tex["format"] == abi.FORMAT_R8G8B8A8_SRGB:
+        texel[..., :3] = _srgb_decode_lut()[img[..., :3]]
+    x, y = u * w, v * h
+    if tex["mag"] == abi.FILTER_NEAREST:
+        return texel[_wrap(np.floor(y).astype(np.int64), h, tex["address_v"]), _wrap(np.floor(x).astype(np.int64), w, tex["address_u"])]
+    x, y = x - 0.5, y - 0.5
+    x0, y0 = np.floor(x), np.floor(y)
+    fx, fy = (x - x0)[:, None], (y - y0)[:, None]
+    xi, yi = x0.astype(np.int64), y0.astype(np.int64)
+    xa, xb = _wrap(xi, w, tex["address_u"]), _wrap(xi + 1, w, tex["address_u"])
+    ya, yb = _wrap(yi, h, tex["address_v"]), _wrap(yi + 1, h, tex["address_v"])
+    return (texel[ya, xa] * (1 - fx) + texel[ya, xb] * fx) * (1 - fy) + (texel[yb, xa] * (1 - fx) + texel[yb, xb] * fx) * fy
+
+
+def _restate(sc, pfd, r):
+    """default.frag:16-48 + the sRGB attachment store from the probes: B8G8R8A8 texels in the presentation orientation."""
+    H, W = r["depth"].shape
+    hits = r["hits"].reshape(-1)
+    cov = hits["geometry_index"] != MISS
+    prim = hits["geometry_index"][cov].astype(np.int64)
+    tri = hits["primitive_index"][cov].astype(np.int64)
+    u, v = hits["u"][cov].astype(np.float64), hits["v"][cov].astype(np.float64)
+    P = sc.primitives
+    io, vo = P["index_offset"][prim].astype(np.int64), P["vertex_offset"][prim].astype(np.int64)
+    b = np.stack([1.0 - u - v, u, v], 1)
+    verts = [sc.vertices[vo + sc.indices[io + 3 * tri + k].astype(np.int64)] for k in range(3)]
+    lerp = lambda field: sum(np.asarray(verts[k][field], np.float64) * b[:, k:k + 1] for k in range(3))    # noqa: E731
+    normal, tangent, uv = lerp("normal"), lerp("tangent"), lerp("uv0")
+    mat = P["material"][prim]
+    albedo = np.asarray(mat["base_color"], np.float64)[:, :3].copy()
+    for t in np.unique(mat["base_color_texture"]):
+        if t >= 0:
+            m = mat["base_color_texture"] == t
+            albedo[m] = _sample(sc.textures[t], uv[m, 0], uv[m, 1])[:, :3]
+    N = normal.copy()
+    for t in np.unique(mat["normal_map"]):
+        if t >= 0:
+            m = mat["normal_map"] == t
+            tsn = _sample(sc.textures[t], uv[m, 0], uv[m, 1])[:, :3] * 2.0 - 1.0
+            tsn /= np.linalg.norm(tsn, axis=1, keepdims=True)
+            T, n = tangent[m, :3], normal[m]
+            bit = np.cross(tsn, T) * tangent[m, 3:4]
+            tg = T - n * (T * n).sum(1, keepdims=True)
+            tg /= np.linalg.norm(tg, axis=1, keepdims=True)
+            N[m] = tg * tsn[:, 0:1] + bit * tsn[:, 1:2] + n * tsn[:, 2:3]
+    light = pfd["directional_light"]
+    L = -np.asarray(light["direction"], np.float64)[:3]
+    lc = np.asarray(light["color"], np.float64)[:3]
+    lit = 1.0 - r["sh"].reshape(-1)[cov].astype(np.float64)
+    col = 0.2 * albedo + np.maximum(N @ L, 0.0)[:, None] * albedo * lc * lit[:, None]
+    with np.errstate(invalid="ignore"):
+        enc = np.where(col <= 0.0031308, 12.92 * col, 1.055 * np.power(np.maximum(col, 0.0), 1 / 2.4) - 0.055)
+        q = np.where(col > 0.0, np.where(col >= 1.0, 255.0, np.floor(enc * 255.0 + 0.5)), 0.0)
+    out = np.zeros((H * W, 4), np.uint8)
+    out[cov] = np.concatenate([q[:, ::-1], np.full((len(q), 1), 255.0)], 1).astype(np.uint8)
+    return out.reshape(H, W, 4)[::-1], cov.reshape(H, W)[::-1]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("scene_name,W,H", [("f4", 160, 96), ("sponza", 1920, 1080)])
+def test_gpu_colour_against_a_float64_restatement(scene_name, W, H):
+    """Texels against default.frag restated in float64 from the probes (textures with their own samplers, sRGB decode and encode):
+    misses exactly (0, 0, 0, 0), alpha 255, every channel within 1 LSB on >= 99.9 % of the covered pixels."""
+    sc = _scene(scene_name)
+    pfd = camera.dolly_frames(sc, W, H, 2)[1]
+    f = _Forward(sc, W, H)
+    try:
+        r = f.run(pfd)
+    finally:
+        f.close()
+    want, cov = _restate(sc, pfd, r)
+    got = r["out"]
+    assert (got[~cov] == 0).all()
+    assert (got[cov][:, 3] == 255).all()
+    d = np.abs(got[cov].astype(int) - want[cov].astype(int)).max(1)
+    assert (d <= 1).mean() >= 0.999, f"{int((d > 1).sum())} of {int(cov.sum())} pixels off by more than 1 LSB (max {d.max()})"
+    assert len(np.unique(got[cov].reshape(-1, 4), axis=0)) > 20        # (a picture, not a constant)
+
+
+@pytest.mark.gpu
+def test_gpu_per_frame_data_follows_resource_idx():
+    """Two frames with different lights in slots 0 and 1: the stand-in reads the slot it is given."""
+    sc = f2_scene.scene_f4()
+    W, H = 160, 96
+    a = camera.dolly_frames(sc, W, H, 2)[1]
+    b = a.copy()
+    d = np.array([-0.5, -0.7, 0.3])
+    b["directional_light"]["direction"][:3] = d / np.linalg.norm(d)
+    b["directional_light"]["color"][:3] = (0.6, 0.8, 1.0)
+    f = _Forward(sc, W, H)
+    try:
+        ra = f.run(None, resource_idx=0, pfds=[a, b])
+        rb = f.run(None, resource_idx=1, pfds=[a, b])
+        only_b = f.run(None, resource_idx=0, pfds=[b])
+    finally:
+        f.close()
+    assert not np.array_equal(ra["out"], rb["out"]) and not np.array_equal(ra["sh"], rb["sh"])
+    _assert_same(rb, only_b, "slot 1 against the same frame in slot 0")
+
+
+@pytest.mark.gpu
+def test_gpu_empty_scene_is_all_clear():
+    sc = scenes.tiny_scene()
+    sc.primitives = sc.primitives[:0]
+    W, H = 70, 45
+    f = _Forward(sc, W, H)
+    try:
+        for variant in (1, 0):
+            r = f.run(camera.dolly_frames(sc, W, H, 2)[1], variant=variant)
+            assert not r["out"].any() and not r["depth"].any() and not r["pos"].any() and not r["sh"].any()
+            assert (r["hits"]["geometry_index"] == MISS).all() and (r["hits"]["primitive_index"] == MISS).all()
+            assert r["stats"]["covered_pixels"] == 0 and r["stats"]["unique_rays"] == W * H
+    finally:
+        f.close()
+
+
+@pytest.mark.gpu
+def test_gpu_resize_then_build_equals_a_fresh_context():
+    sc = f2_scene.scene_f4()
+    f = _Forward(sc, 160, 96)
+    try:
+        f.run(camera.dolly_frames(sc, 160, 96, 2)[1])
+        f.resize(333, 177)
+        pfd = camera.dolly_frames(sc, 333, 177, 2)[1]
+        got = f.run(pfd)
+    finally:
+        f.close()
+    fresh = _Forward(sc, 333, 177)
+    try:
+        want = fresh.run(pfd)
+    finally:
+        fresh.close()
+    assert got["out"].shape == (177, 333, 4)
+    _assert_same(got, want, "after vhr_resize + build")

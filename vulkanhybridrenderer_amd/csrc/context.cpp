@@ -1060,4 +1060,17 @@ int vhr_standin_gbuffer_with_albedo(vhr_context *ctx, uint32_t resource_idx, con
     return launch_standin_gbuffer(ctx, ctx->per_frame[resource_idx], n->second, m->second, d->second, albedo);
 }
 
+int vhr_standin_rayquery_forward(vhr_context *ctx, uint32_t resource_idx, const vhr_rayquery_forward_desc *d) {
+    if (!ctx || !d || !d->depth_image || resource_idx >= 3)
+        return ctx ? ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "standin_rayquery_forward: bad argument") : VHR_ERROR_INVALID_ARGUMENT;
+    if (ctx->host_only) return ctx->fail(VHR_ERROR_NO_DEVICE, "host-only context: no device work");
+    auto it = ctx->images.find(d->depth_image);
+    if (it == ctx->images.end()) return ctx->fail(VHR_ERROR_NOT_FOUND, "standin_rayquery_forward: unknown transient image");
+    if (d->output_storage_image < 0 || uint32_t(d->output_storage_image) >= vhr_context::kMaxGlobalResources || !ctx->storage_images[d->output_storage_image].used)
+        return ctx->fail(VHR_ERROR_NOT_FOUND, "standin_rayquery_forward: output storage image is not allocated");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return launch_rayquery_forward(ctx, ctx->per_frame[resource_idx], ctx->storage_images[d->output_storage_image], it->second, d->primary_hits,
+                                   d->positions, d->shadowed);
+}
+
 }  // extern "C"

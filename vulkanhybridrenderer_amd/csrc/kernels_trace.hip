@@ -2811,6 +2811,286 @@ int launch_raytraced_composition(vhr_context *ctx, const Image &in, Image &out) 
 }
 
 // ---------------------------------------------------------------------------------------------
+// Stand-in for the rayquery render path's "Forward Pass" (rayquery_render_path.cpp:11-54, default.vert:19-28, default.frag:16-49):
+// the visible surface of every pixel by a primary ray (gbuffer_kernel's camera ray: from the camera through the near-plane point of
+// the pixel centre, tmin 1 in that parameterisation, no alpha layers -- the raster pass discards nothing), then the fragment stage:
+// one terminate-on-first-hit query from in_pos towards the light (tmin 0.1, tmax 10000, every triangle opaque) and the shading of
+// default.frag.  Writes swapchain texels (B8G8R8A8_SRGB, presentation orientation: row 0 = top, like composition_kernel), the
+// reverse-Z depth in the G-buffer's orientation (clip.z / clip.w, like gbuffer_kernel) and, where asked for, three probes per pixel in
+// Depth's row order: the committed primary hit (vhr_ray_hit), in_pos with w = 1 (0 for a miss) and the query's answer.  A miss writes
+// (0, 0, 0, 0) and depth 0 (the clears of :16-17).
+// ---------------------------------------------------------------------------------------------
+struct RayqueryForwardArgs {
+    DeviceScene scene;
+    vhr_per_frame_data pfd;
+    float projview[16];      // camera_proj * camera_view (the depth, as gbuffer_kernel computes it)
+    uchar4 *out;             // RENDER_OUTPUT: B8G8R8A8_SRGB texels
+    float *depth;            // "Depth", D32_SFLOAT
+    uint32_t *hits;          // probes, nullptr = not asked for: vhr_ray_hit (6 words) per pixel
+    float *positions;        // 4 floats per pixel
+    uint8_t *shadowed;       // 1 = the inline query found an occluder
+    uint32_t width, height;
+    RayStats *stats;         // nullptr = off; covered_pixels counts the primary hits (= queries)
+};
+
+// the camera ray of a pixel (gbuffer_kernel): origin the camera, direction to the pixel centre's point on the near plane (reverse Z: depth 1)
+__device__ __forceinline__ f3 rayquery_primary_dir(const vhr_per_frame_data &pfd, f3 cam, uint32_t x, uint32_t y, uint32_t W, uint32_t H) {
+    const float u = (float(x) + 0.5f) / float(W), v = (float(y) + 0.5f) / float(H);
+    return get_world_space_position(pfd, 1.0f, u, v) - cam;
+}
+
+// default.frag:16-48 once the inline query's answer is known
+__device__ f3 rayquery_forward_shade(const DeviceScene &sc, const vhr_per_frame_data &pfd, const Hit &h, bool shadowed) {
+    const BvhTri &bt = sc.tris[h.tri_index];
+    const vhr_primitive &prim = sc.primitives[bt.prim];                                  // :16
+    const TriAttributes at = interpolate(sc, prim, bt.tri, h.u, h.v);                     // in_normal: object space, not renormalised (vert:23)
+    f3 albedo;
+    if (prim.material.base_color_texture == -1) {                                        // :17-23
+        albedo = f3{ prim.material.base_color[0], prim.material.base_color[1], prim.material.base_color[2] };
+    } else {
+        const f4 t = sample_texture(sc, prim.material.base_color_texture, at.uvx, at.uvy);
+        albedo = f3{ t.x, t.y, t.z };
+    }
+    const f3 normal = at.normal;
+    f3 N = normal;                                                                       // :25-31
+    if (prim.material.normal_map >= 0) {
+        const f4 tg = interpolate_tangent(sc, prim, bt.tri, h.u, h.v);
+        const f3 T = f3{ tg.x, tg.y, tg.z };
+        const f4 tx = sample_texture(sc, prim.material.normal_map, at.uvx, at.uvy);
+        const f3 tsn = normalize3(f3{ tx.x * 2.0f - 1.0f, tx.y * 2.0f - 1.0f, tx.z * 2.0f - 1.0f });
+        const f3 bitangent = cross3(tsn, T) * tg.w;                                      // sic
+        const f3 tangent = normalize3(T - normal * dot3(T, normal));
+        N = (tangent * tsn.x + bitangent * tsn.y) + normal * tsn.z;
+    }
+    const f3 light_dir = -f3{ pfd.directional_light.direction[0], pfd.directional_light.direction[1], pfd.directional_light.direction[2] };
+    const f3 lc = f3{ pfd.directional_light.color[0], pfd.directional_light.color[1], pfd.directional_light.color[2] };
+    const float in_shadow = shadowed ? 0.0f : 1.0f;                                      // :41-44
+    const f3 ambient = albedo * 0.2f;                                                    // :46
+    return ambient + mul3(mul3(albedo * fmaxf(dot3(N, light_dir), 0.0f), lc), f3{ in_shadow, in_shadow, in_shadow });   // :47 (no light.intensity)
+}
+
+// the pixel's outputs: texel (flipped presentation row), depth and the probes (Depth's rows); `hit` false = the clears
+__device__ __forceinline__ void rayquery_forward_store(const RayqueryForwardArgs &a, const uint32_t x, const uint32_t y, const bool hit, const Hit &h,
+                                                       const f3 cam, const f3 dir, const f3 position, const bool shadowed) {
+    const uint32_t W = a.width, H = a.height;
+    const size_t i = size_t(y) * W + x;
+    uchar4 texel = make_uchar4(0, 0, 0, 0);
+    float depth = 0.0f;
+    if (hit) {
+        const f3 c = rayquery_forward_shade(a.scene, a.pfd, h, shadowed);
+        texel = make_uchar4(srgb8(c.z), srgb8(c.y), srgb8(c.x), 255);                      // out_color = vec4(.., 1.0) through the sRGB attachment
+        const f3 P = cam + dir * h.t;
+        const f4 clip = mat4_mul(a.projview, f4{ P.x, P.y, P.z, 1.0f });
+        depth = clip.z / clip.w;
+    }
+    a.out[size_t(H - 1 - y) * W + x] = texel;
+    a.depth[i] = depth;
+    if (a.hits) {
+        uint32_t *const r = a.hits + i * 6u;
+        r[0] = hit ? __float_as_uint(h.t) : 0u; r[1] = hit ? __float_as_uint(h.u) : 0u; r[2] = hit ? __float_as_uint(h.v) : 0u;
+        r[3] = hit ? a.scene.tris[h.tri_index].prim : kNoHit; r[4] = hit ? a.scene.tris[h.tri_index].tri : kNoHit; r[5] = 0u;
+    }
+    if (a.positions) {
+        float *const p = a.positions + i * 4u;
+        p[0] = hit ? position.x : 0.0f; p[1] = hit ? position.y : 0.0f; p[2] = hit ? position.z : 0.0f; p[3] = hit ? 1.0f : 0.0f;
+    }
+    if (a.shadowed) a.shadowed[i] = hit && shadowed ? 1u : 0u;
+}
+
+// Literal form (`variant_rayquery` 0): one pixel per thread, the two rays one after the other through traverse<> -- the cross-check.
+__global__ __launch_bounds__(kTraceBlock) void rayquery_forward_kernel(const RayqueryForwardArgs a, const Stamps st) {
+    vhr_stamp(st);
+    __shared__ int s_rq_stack[kTraceStack * kTraceBlock];
+    int *stack = s_rq_stack + threadIdx.x;
+    uint32_t x, y;
+    pixel_of_thread(x, y, 0);
+    bool hit = false;
+    uint32_t overflow = 0;
+    if (x < a.width && y < a.height) {
+        const f3 cam = f3{ a.pfd.camera_view_inverse[12], a.pfd.camera_view_inverse[13], a.pfd.camera_view_inverse[14] };
+        const f3 dir = rayquery_primary_dir(a.pfd, cam, x, y, a.width, a.height);
+        Hit h;
+        h.t = h.u = h.v = 0.0f; h.tri_index = 0; h.flat = 0;
+        hit = traverse<false>(a.scene, cam, dir, 1.0f, 3.0e38f, stack, h, overflow);
+        f3 position = f3{ 0.0f, 0.0f, 0.0f };
+        bool shadowed = false;
+        if (hit) {
+            f3 unused_normal;
+            hit_position_normal(a.scene, h, position, unused_normal);                    // in_pos (vert:22, interpolated)
+            const f3 light_dir = -f3{ a.pfd.directional_light.direction[0], a.pfd.directional_light.direction[1], a.pfd.directional_light.direction[2] };
+            Hit sh;
+            shadowed = traverse<true>(a.scene, position, light_dir, 0.1f, 10000.0f, stack, sh, overflow);   // frag:36-44
+        }
+        rayquery_forward_store(a, x, y, hit, h, cam, dir, position, shadowed);
+    }
+    if (a.stats) {
+        const unsigned long long cov = __ballot(hit), ovf = __ballot(overflow != 0);
+        if ((threadIdx.x & 63u) == 0) {
+            if (cov) atomicAdd(&a.stats->covered_pixels, (unsigned long long)__popcll(cov));
+            if (ovf) atomicAdd(&a.stats->stack_overflows, (unsigned long long)__popcll(ovf));
+        }
+    }
+}
+
+// Work-queue form (default, `variant_rayquery` 1), raytraced_queue_kernel's schedule: a wave owns a 16x8-pixel tile and runs
+// wave_queue_walk twice -- the primary rays (closest hit, each ray's t committed for the depth), then the inline query of every
+// covered pixel (any hit) from the tile's shared descent around the hit points -- with the ray setup, in_pos and default.frag done by
+// the whole wave in between and after.  Decision (vi) is decided inline in binary64 like the raytraced path's queue kernel (its shadow
+// rays leave the surface itself): the same test as traverse<>, so the same rays give rayquery_forward_kernel's outputs bit for bit.
+template <bool SPILL>
+__global__ __launch_bounds__(kQueueBlock * 2) __attribute__((amdgpu_waves_per_eu(5, 6))) void rayquery_forward_queue_kernel(
+    const RayqueryForwardArgs a, const uint32_t stack_levels, const uint32_t refill_threshold, const uint32_t tiles_x, const uint32_t tiles_total,
+    const uint32_t early_exit, const Stamps st) {
+    vhr_stamp(st);
+    extern __shared__ int s_dyn[];                        // per wave: (stack_levels + 3) x 64 ints
+    // rows 0-2: primary direction -> rows 0-3 primary hit record (triangle, u, v, t); rows 4-6: in_pos; row 7: the query's answer
+    __shared__ float s_ray_all[2][8][kReflRays];
+    __shared__ uint8_t s_list_all[2][kReflRays];
+    __shared__ float4 s_cut_all[2][kCutMax][2];           // the tile's shared descent (build_tile_cut), once per walk
+    const uint32_t lane = threadIdx.x & 63u, wave = uint32_t(__builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)));
+    const uint32_t tile = blockIdx.x * 2u + wave;
+    if (tile >= tiles_total) return;                      // waves of a block share nothing and never synchronise
+    float (&s_ray)[8][kReflRays] = s_ray_all[wave];
+    uint8_t (&s_list)[kReflRays] = s_list_all[wave];
+    int *stack = s_dyn + wave * (stack_levels + 3u) * kQueueBlock + lane;
+    stack[0] = kStackSentinel;
+    const uint32_t W = a.width, H = a.height;
+    const uint32_t tile_y = tile / tiles_x, tile_x = tile - tile_y * tiles_x;
+    const f3 cam = f3{ a.pfd.camera_view_inverse[12], a.pfd.camera_view_inverse[13], a.pfd.camera_view_inverse[14] };
+    const f3 light_dir = -f3{ a.pfd.directional_light.direction[0], a.pfd.directional_light.direction[1], a.pfd.directional_light.direction[2] };
+
+    // ---- primary rays, whole wave ----
+    unsigned long long in_mask[2];
+    uint32_t total = 0;
+#pragma unroll
+    for (uint32_t sub = 0; sub < 2; ++sub) {
+        const uint32_t x = tile_x * 16u + sub * 8u + (lane & 7u), y = tile_y * 8u + (lane >> 3);
+        const bool in_range = x < W && y < H;
+        const uint32_t p = sub * 64u + lane;
+        if (in_range) {
+            const f3 dir = rayquery_primary_dir(a.pfd, cam, x, y, W, H);
+            s_ray[0][p] = dir.x; s_ray[1][p] = dir.y; s_ray[2][p] = dir.z;
+        }
+        const unsigned long long m = __ballot(in_range);
+        in_mask[sub] = m;
+        if (in_range) s_list[total + lane_rank(m)] = uint8_t(p);
+        total += uint32_t(__popcll(m));
+    }
+    wave_lds_sync();
+    const bool traced = a.scene.node_count != 0;
+    uint32_t overflow = 0;
+    // ---- walk 1: closest hit of the primary rays; the commit keeps t (PER_RAY) for the depth ----
+    uint32_t cut_n = traced && total ? build_tile_cut_uniform(a.scene, cam, cam, s_cut_all[wave], lane) : 0u;
+    wave_queue_walk<SPILL, false, false, false, true>(
+        a.scene, stack, stack_levels, lane, traced ? total : 0u, refill_threshold, early_exit, 0.0f, 0.0f, false, overflow, s_cut_all[wave], cut_n,
+        [&](uint32_t r, uint32_t &pix, f3 &ro, f3 &rd, float &tmin, float &tmax) {
+            pix = s_list[r];
+            ro = cam;
+            rd = f3{ s_ray[0][pix], s_ray[1][pix], s_ray[2][pix] };
+            tmin = 1.0f; tmax = 3.0e38f;
+        },
+        [&](uint32_t pix, uint32_t tri, float u, float v, float t) {
+            s_ray[0][pix] = __uint_as_float(tri); s_ray[1][pix] = u; s_ray[2][pix] = v; s_ray[3][pix] = t;
+        });
+    wave_lds_sync();
+    // ---- in_pos of every covered pixel, whole wave (vert:22) ----
+    uint32_t nhit = 0;
+    f3 omin = f3{ 3.0e38f, 3.0e38f, 3.0e38f }, omax = f3{ -3.0e38f, -3.0e38f, -3.0e38f };   // bounds of the queries' origins
+#pragma unroll
+    for (uint32_t sub = 0; sub < 2; ++sub) {
+        const uint32_t p = sub * 64u + lane;
+        const bool inside = traced && ((in_mask[sub] >> lane) & 1ull);
+        const uint32_t tri = inside ? __float_as_uint(s_ray[0][p]) : kNoHit;
+        const bool hit = tri != kNoHit;
+        if (hit) {
+            Hit h;
+            h.t = 0.0f; h.u = s_ray[1][p]; h.v = s_ray[2][p]; h.tri_index = tri; h.flat = 0;
+            f3 position, unused_normal;
+            hit_position_normal(a.scene, h, position, unused_normal);
+            s_ray[4][p] = position.x; s_ray[5][p] = position.y; s_ray[6][p] = position.z;
+            omin = f3{ fminf(omin.x, position.x), fminf(omin.y, position.y), fminf(omin.z, position.z) };
+            omax = f3{ fmaxf(omax.x, position.x), fmaxf(omax.y, position.y), fmaxf(omax.z, position.z) };
+        }
+        const unsigned long long m = __ballot(hit);
+        if (hit) s_list[nhit + lane_rank(m)] = uint8_t(p);
+        nhit += uint32_t(__popcll(m));
+    }
+    wave_lds_sync();
+    // ---- walk 2: the inline queries (frag:36-44), any hit; the answer (an occluder's triangle or kNoHit) lands in row 7 ----
+    cut_n = nhit ? build_tile_cut_uniform(a.scene, omin, omax, s_cut_all[wave], lane) : 0u;
+    wave_queue_walk<SPILL, false, false>(
+        a.scene, stack, stack_levels, lane, nhit, refill_threshold, early_exit, 0.1f, 10000.0f, true, overflow, s_cut_all[wave], cut_n,
+        [&](uint32_t r, uint32_t &pix, f3 &ro, f3 &rd) {
+            pix = s_list[r];
+            ro = f3{ s_ray[4][pix], s_ray[5][pix], s_ray[6][pix] };
+            rd = light_dir;
+        },
+        [&](uint32_t pix, uint32_t tri, float, float) { s_ray[7][pix] = __uint_as_float(tri); });
+    wave_lds_sync();
+    // ---- default.frag and the stores, whole wave ----
+#pragma unroll
+    for (uint32_t sub = 0; sub < 2; ++sub) {
+        if (!((in_mask[sub] >> lane) & 1ull)) continue;
+        const uint32_t x = tile_x * 16u + sub * 8u + (lane & 7u), y = tile_y * 8u + (lane >> 3);
+        const uint32_t p = sub * 64u + lane;
+        const uint32_t tri = traced ? __float_as_uint(s_ray[0][p]) : kNoHit;
+        const bool hit = tri != kNoHit;
+        Hit h;
+        h.t = hit ? s_ray[3][p] : 0.0f; h.u = hit ? s_ray[1][p] : 0.0f; h.v = hit ? s_ray[2][p] : 0.0f; h.tri_index = hit ? tri : 0u; h.flat = 0;
+        const f3 position = hit ? f3{ s_ray[4][p], s_ray[5][p], s_ray[6][p] } : f3{ 0.0f, 0.0f, 0.0f };
+        const bool shadowed = hit && __float_as_uint(s_ray[7][p]) != kNoHit;
+        rayquery_forward_store(a, x, y, hit, h, cam, rayquery_primary_dir(a.pfd, cam, x, y, W, H), position, shadowed);
+    }
+    if (a.stats && lane == 0) {
+        if (nhit) atomicAdd(&a.stats->covered_pixels, (unsigned long long)nhit);
+        if (overflow) atomicAdd(&a.stats->stack_overflows, 1ull);
+    }
+}
+
+int launch_rayquery_forward(vhr_context *ctx, const vhr_per_frame_data &pfd, Image &out, Image &depth, void *hits, float *positions, uint8_t *shadowed) {
+    if (out.width != depth.width || out.height != depth.height) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "standin_rayquery_forward: image extents differ");
+    if (out.bpp != 4) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "standin_rayquery_forward: the output storage image must have 4-byte texels (B8G8R8A8_SRGB)");
+    if (depth.format != VHR_FORMAT_D32_SFLOAT) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "standin_rayquery_forward: \"Depth\" must be D32_SFLOAT (rayquery_render_path.cpp:17)");
+    if (reinterpret_cast<uintptr_t>(hits) % 4u || reinterpret_cast<uintptr_t>(positions) % 4u)
+        return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "standin_rayquery_forward: primary_hits and positions must be 4-byte aligned");
+    RayqueryForwardArgs a;
+    a.scene = ctx->device_scene();
+    a.pfd = pfd;
+    host_mat4_mul(pfd.camera_proj, pfd.camera_view, a.projview);
+    a.out = static_cast<uchar4 *>(out.ptr);
+    a.depth = static_cast<float *>(depth.ptr);
+    a.hits = static_cast<uint32_t *>(hits);
+    a.positions = positions;
+    a.shadowed = shadowed;
+    a.width = depth.width;
+    a.height = depth.height;
+    a.stats = ctx->ray_stats_enabled ? ctx->d_ray_stats : nullptr;
+    if (a.width == 0 || a.height == 0) return VHR_OK;
+    if (a.stats && hipMemsetAsync(ctx->d_ray_stats, 0, sizeof(RayStats), ctx->stream) != hipSuccess)
+        return ctx->fail(VHR_ERROR_DEVICE, "hipMemsetAsync(ray stats) failed");
+    ctx->time_begin(kKernelRayqueryForward);
+    if (ctx->options[kOptRayqueryVariant] != 0) {
+        const uint32_t levels = std::max<uint32_t>(1u, std::min<uint32_t>(ctx->bvh_depth + 1u, uint32_t(std::max(1, ctx->options[kOptLdsStackLevels]))));
+        const uint32_t threshold = uint32_t(std::max(1, std::min(64, ctx->options[kOptRefillThreshold])));
+        const uint32_t early_exit = uint32_t(std::max(0, std::min(15, ctx->options[kOptEarlyExit])));
+        const uint32_t tiles_x = (a.width + 15) / 16, tiles_total = tiles_x * ((a.height + 7) / 8);
+        const size_t lds = size_t(levels + 3) * kQueueBlock * sizeof(int) * 2;
+        if (levels < ctx->bvh_depth + 1u)
+            launch(ctx, rayquery_forward_queue_kernel<true>, dim3((tiles_total + 1) / 2), dim3(kQueueBlock * 2), lds, a, levels, threshold, tiles_x, tiles_total, early_exit);
+        else
+            launch(ctx, rayquery_forward_queue_kernel<false>, dim3((tiles_total + 1) / 2), dim3(kQueueBlock * 2), lds, a, levels, threshold, tiles_x, tiles_total, early_exit);
+    } else {
+        launch(ctx, rayquery_forward_kernel, dim3((a.width + 15) / 16, (a.height + 15) / 16), dim3(kTraceBlock), 0, a);
+    }
+    ctx->time_end(kKernelRayqueryForward);
+    if (hipGetLastError() != hipSuccess) return ctx->fail(VHR_ERROR_DEVICE, "rayquery forward kernel launch failed");
+    if (a.stats && hipMemcpyAsync(&ctx->h_ray_stats, ctx->d_ray_stats, sizeof(RayStats), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+        return ctx->fail(VHR_ERROR_DEVICE, "hipMemcpyAsync(ray stats) failed");
+    ctx->raytraced_pixels = uint64_t(a.width) * a.height;      // ray statistics: one primary ray per pixel + one query per primary hit
+    return VHR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // vhr_debug_ray_triangle: decision (vi) as the walkers' triangle test computes it, on explicit (ray, triangle) pairs -- what tests/ hold against the oracle's
 // orc_ray_triangle and against exact arithmetic (tests/golden/kat_decision_vi.json), without a scene or a tree in between.  17 floats per pair:
 // o, d, v0, e1, e2, tmin, tmax; out: hit (0 / 1) and (t, u, v).  One pair per thread.

@@ -1,6 +1,7 @@
 // The two render paths re-hosted on the vhr:: facade (include/vhr_render_graph.hpp): what an integrator instantiates.
 //   vhr::HybridRenderPath     <- src/render_paths/hybrid_render_path.{h,cpp}      (the hot path: Raytrace Pass + SVGF Denoise Pass)
 //   vhr::RaytracedRenderPath  <- src/render_paths/raytraced_render_path.{h,cpp}   
+//   vhr::RayqueryRenderPath   <- src/render_paths/rayquery_render_path.{h,cpp}    (one raster pass whose fragment stage traces an inline query)
 // Settings the reference changes through ImGui radio buttons (then Rebuild()) are plain public members here.
 #pragma once
 
@@ -60,6 +61,17 @@ public:
 
     // "Alpha test for shadows" (raytraced_render_path.h:15; the UI sets it at raytraced_render_path.cpp:80-93)
     int use_anyhit_shader = 0;
+};
+
+class RayqueryRenderPath : public RenderPath {
+public:
+    using RenderPath::RenderPath;
+    void RegisterPath(DeviceContext &context, RenderGraph &render_graph, ResourceManager &resource_manager) override;
+    void DeregisterPath(DeviceContext &context, RenderGraph &render_graph, ResourceManager &resource_manager) override;
+    void ImGuiDrawSettings() {}                        // rayquery_render_path.cpp:58: the path has no settings
+
+    // the path's only pass is a raster pass (its fragment stage traces the inline query) and stays with the integrator
+    ExternalPassCallback forward_pass;
 };
 
 }  // namespace vhr

@@ -303,7 +303,9 @@ struct RayStats {
     X(kOptShrinkOverlap, "strip_shrink_overlap", 0, 0, 1)       /* later a-trous iterations compute only the margin still needed */     \
     /* instrumentation */                                                                                                               \
     X(kOptPassTimestamps, "pass_timestamps", 1, 0, 3)           /* 0 off, 1 in-kernel stamps, 2 + a stamp in front of external passes, 3 event pairs */ \
-    X(kOptKernelTimingStride, "kernel_timing_stride", 1, 1, 1000000)   /* every n-th launch of a timed kind carries an event pair */
+    X(kOptKernelTimingStride, "kernel_timing_stride", 1, 1, 1000000)   /* every n-th launch of a timed kind carries an event pair */ \
+    /* added after the table above (its entries keep their indices, and the name sorts after every older one) */                        \
+    X(kOptRayqueryVariant, "variant_rayquery", 1, 0, 1)         /* the rayquery path's forward pass: rayquery_forward_kernel / rayquery_forward_queue_kernel */
 
 enum Option {
 #define X(e, n, d, lo, hi) e,
@@ -319,7 +321,8 @@ inline constexpr OptionInfo kOptionInfo[kOptCount] = {
 };
 
 // optional per-kernel timing with HIP events on the context stream (vhr_set_kernel_timing)
-enum KernelKind { kKernelRaygen = 0, kKernelTemporal = 1, kKernelAtrous = 2, kKernelCopy = 3, kKernelReflection = 4, kKernelSsao = 5, kKernelSsaoBlur = 6, kKernelSsr = 7, kKernelAtrousAsync = 8, kKernelRayQuery = 9, kKernelKinds = 10 };
+enum KernelKind { kKernelRaygen = 0, kKernelTemporal = 1, kKernelAtrous = 2, kKernelCopy = 3, kKernelReflection = 4, kKernelSsao = 5, kKernelSsaoBlur = 6, kKernelSsr = 7, kKernelAtrousAsync = 8, kKernelRayQuery = 9,
+                  kKernelRayqueryForward = 10, kKernelKinds = 11 };
 struct KernelTimer {
     std::vector<hipEvent_t> events;     // begin/end pairs
     size_t used = 0;                    // events recorded since the last drain
@@ -534,6 +537,8 @@ int launch_raygen(vhr_context *ctx, const vhr_per_frame_data &pfd, uint32_t widt
 int launch_raytraced(vhr_context *ctx, const vhr_per_frame_data &pfd, uint32_t width, uint32_t height, Image &out, bool alpha_test);
 int launch_raytraced_composition(vhr_context *ctx, const Image &in, Image &out);
 int launch_standin_gbuffer(vhr_context *ctx, const vhr_per_frame_data &pfd, Image &normals, Image &motion, Image &depth, Image *albedo);
+// the rayquery render path's "Forward Pass" stand-in (vhr_standin_rayquery_forward); hits / positions / shadowed: device memory or nullptr
+int launch_rayquery_forward(vhr_context *ctx, const vhr_per_frame_data &pfd, Image &out, Image &depth, void *hits, float *positions, uint8_t *shadowed);
 int launch_composition(vhr_context *ctx, const vhr_per_frame_data &pfd, const vhr_composition_desc &d, const Image &albedo, const Image &normals,
                        const Image &motion, const Image &depth, const Image &shadow_ao, const Image *reflections, const Image *ssao, const Image *shadow_map, Image &out);
 int launch_standin_shadow_map(vhr_context *ctx, const vhr_per_frame_data &pfd, Image &shadow_map);

@@ -32,7 +32,8 @@ EXPORTS = [
     "vhr_get_transient_image", "vhr_get_storage_image", "vhr_upload_transient_image", "vhr_download_transient_image",
     "vhr_upload_storage_image", "vhr_download_storage_image", "vhr_standin_gbuffer", "vhr_standin_gbuffer_with_albedo", "vhr_standin_composition", "vhr_standin_shadow_map", "vhr_set_strip", "vhr_set_tile",
     "vhr_standin_raytraced_composition", "vhr_raytraced_create", "vhr_raytraced_destroy", "vhr_raytraced_build", "vhr_raytraced_rebuild",
-    "vhr_raytraced_last_error",
+    "vhr_raytraced_last_error", "vhr_standin_rayquery_forward", "vhr_rayquery_create", "vhr_rayquery_destroy", "vhr_rayquery_build",
+    "vhr_rayquery_rebuild", "vhr_rayquery_last_error",
     "vhr_set_ray_statistics", "vhr_get_ray_statistics", "vhr_get_bvh_statistics", "vhr_get_current_stream", "vhr_get_bvh_builder", "vhr_get_bvh_presplit_level", "vhr_get_bvh_frame", "vhr_get_bvh_form_checks", "vhr_get_bvh_fingerprint", "vhr_get_bvh_tree_fingerprint", "vhr_set_kernel_timing",
     "vhr_get_kernel_time", "vhr_set_option", "vhr_get_option", "vhr_option_count", "vhr_option_info", "vhr_get_traversal_statistics", "vhr_source_fingerprint", "vhr_debug_wave_lifetimes", "vhr_get_reflection_statistics", "vhr_get_binary64_statistics", "vhr_debug_ray_triangle", "vhr_get_traversal_cycles", "vhr_get_drain_statistics", "vhr_get_build_times", "vhr_atrous_overlap", "vhr_atrous_output_extent", "vhr_strip_plan_make",
     "vhr_strip_plan_exchanges", "vhr_tile_grid_choose", "vhr_tile_plan_make", "vhr_tile_plan_make_weighted", "vhr_get_tile_cost_map", "vhr_tile_plan_exchanges", "vhr_tile_plan_replan", "vhr_comm_replan", "vhr_comm_get_unique_id", "vhr_comm_use_library", "vhr_comm_library", "vhr_comm_create", "vhr_comm_create_tiled", "vhr_comm_destroy", "vhr_comm_last_error", "vhr_comm_exchange_raytraced",
@@ -82,6 +83,12 @@ class CompositionDesc(C.Structure):
                 ("albedo_image", C.c_char_p), ("normals_image", C.c_char_p), ("motion_image", C.c_char_p), ("depth_image", C.c_char_p),
                 ("shadow_ao_image", C.c_char_p), ("reflections_image", C.c_char_p), ("output_storage_image", C.c_int32),
                 ("ssao_image", C.c_char_p), ("shadow_map_image", C.c_char_p)]
+
+
+class RayqueryForwardDesc(C.Structure):
+    """vhr_rayquery_forward_desc (include/vhr_amd.h); the three probes are device pointers (None = not written)."""
+    _fields_ = [("output_storage_image", C.c_int32), ("depth_image", C.c_char_p), ("primary_hits", C.c_void_p), ("positions", C.c_void_p),
+                ("shadowed", C.c_void_p)]
 
 
 class StripPlanC(C.Structure):
@@ -228,6 +235,14 @@ def load():
     L.vhr_raytraced_rebuild.argtypes = [vp, i32]
     L.vhr_raytraced_last_error.argtypes = [vp]
     L.vhr_raytraced_last_error.restype = C.c_char_p
+    L.vhr_standin_rayquery_forward.argtypes = [vp, u32, C.POINTER(RayqueryForwardDesc)]
+    L.vhr_rayquery_create.argtypes = [vp, EXTERNAL_CB, vp, C.POINTER(vp)]
+    L.vhr_rayquery_destroy.argtypes = [vp]
+    L.vhr_rayquery_destroy.restype = None
+    L.vhr_rayquery_build.argtypes = [vp]
+    L.vhr_rayquery_rebuild.argtypes = [vp]
+    L.vhr_rayquery_last_error.argtypes = [vp]
+    L.vhr_rayquery_last_error.restype = C.c_char_p
     L.vhr_set_strip.argtypes = [vp, u32, u32, u32, u32]
     L.vhr_set_tile.argtypes = [vp, u32, u32, u32, u32, u32, u32, u32]
     L.vhr_set_ray_statistics.argtypes = [vp, i32]
@@ -569,6 +584,13 @@ class Context:
         self.check(self.L.vhr_standin_raytraced_composition(self.handle, raytraced_output.encode(), output_storage_image),
                    "standin_raytraced_composition")
 
+    def standin_rayquery_forward(self, output_storage_image, resource_idx=0, depth=DEPTH, primary_hits_ptr=0, positions_ptr=0, shadowed_ptr=0):
+        """The rayquery path's "Forward Pass" stand-in (default.vert + default.frag with its inline shadow query): swapchain texels into
+        the pool storage image, reverse-Z depth into `depth`.  The probes are device pointers (e.g. torch tensors' data_ptr(); 0 = not
+        written), one entry per pixel in Depth's row order: abi.ray_hit_dtype, 4 float32 (in_pos, covered), uint8 (shadowed)."""
+        d = RayqueryForwardDesc(output_storage_image, depth.encode(), primary_hits_ptr or None, positions_ptr or None, shadowed_ptr or None)
+        self.check(self.L.vhr_standin_rayquery_forward(self.handle, resource_idx, C.byref(d)), "standin_rayquery_forward")
+
     def set_ray_statistics(self, enable):
         self.check(self.L.vhr_set_ray_statistics(self.handle, int(enable)), "set_ray_statistics")
 
@@ -692,7 +714,7 @@ class Context:
         return dict(nodes=out[0], triangles=out[1], max_depth=out[2], node_bytes=out[3], triangle_bytes=out[4])
 
     KERNEL_KINDS = {"raygen": 0, "svgf_temporal": 1, "svgf_atrous": 2, "blit": 3, "reflection": 4, "ssao": 5, "ssao_blur": 6, "ssr": 7, "svgf_atrous_async": 8,
-                    "ray_query": 9}
+                    "ray_query": 9, "rayquery_forward": 10}
 
     @staticmethod
     def _rays_array(rays):
@@ -881,6 +903,32 @@ class RaytracedRenderPath:
     def destroy(self):
         if self.handle:
             self.ctx.L.vhr_raytraced_destroy(self.handle)
+            self.handle = None
+
+
+class RayqueryRenderPath:
+    """vhr_rayquery_*: the C++ re-host of RayqueryRenderPath (csrc/rayquery_render_path.cpp): one external "Forward Pass" whose body
+    (`forward_pass(ctx)`, e.g. calling Context.standin_rayquery_forward) is the integrator's."""
+
+    def __init__(self, ctx, forward_pass=None):
+        self.ctx = ctx
+        self._f = EXTERNAL_CB(lambda user, c: ctx._guard(lambda: forward_pass(ctx))) if forward_pass else EXTERNAL_CB()
+        self.handle = C.c_void_p()
+        ctx.check(ctx.L.vhr_rayquery_create(ctx.handle, self._f, None, C.byref(self.handle)), "vhr_rayquery_create")
+
+    def _check(self, rc, what):
+        if rc < 0:
+            raise VhrError(f"{what}: {self.ctx.L.vhr_rayquery_last_error(self.handle).decode()}")
+
+    def build(self):
+        self._check(self.ctx.L.vhr_rayquery_build(self.handle), "RayqueryRenderPath::Build")
+
+    def rebuild(self):
+        self._check(self.ctx.L.vhr_rayquery_rebuild(self.handle), "RayqueryRenderPath::Rebuild")
+
+    def destroy(self):
+        if self.handle:
+            self.ctx.L.vhr_rayquery_destroy(self.handle)
             self.handle = None
 
 
