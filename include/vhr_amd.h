@@ -284,6 +284,22 @@ int  vhr_rayquery_rebuild(vhr_rayquery_render_path *path);     /* RenderPath::Re
 const char *vhr_rayquery_last_error(vhr_rayquery_render_path *path);
 
 /* ---------------------------------------------------------------------------------------------
+ * ForwardRasterRenderPath (src/render_paths/forward_raster_render_path.{h,cpp}) re-hosted on the API above
+ * (csrc/forward_raster_render_path.cpp): two external graphics passes.  "Depth Prepass" (:12-50) writes "ShadowMap" (4096 x 4096
+ * D32_SFLOAT, clear depth 0); "Forward Pass" (:52-96) samples it and writes RENDER_OUTPUT (binding 0) and "Depth" (D32_SFLOAT, binding 1,
+ * clear depth 0), both multisampled when enable_msaa (the default, forward_raster_render_path.h:14).  A multisampled RENDER_OUTPUT makes the
+ * graph create "Forward Pass_MSAA" (B8G8R8A8_SRGB, 8 samples) to resolve from (render_graph.cpp:929-945).  The bodies are the integrator's
+ * (either may be NULL); vhr_standin_shadow_map and vhr_standin_forward_raster are the library's stand-ins for them.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct vhr_forward_raster_render_path vhr_forward_raster_render_path;
+int  vhr_forward_raster_create(vhr_context *ctx, vhr_external_pass_callback depth_prepass, void *depth_user, vhr_external_pass_callback forward_pass,
+                               void *forward_user, int32_t enable_msaa, vhr_forward_raster_render_path **out);
+void vhr_forward_raster_destroy(vhr_forward_raster_render_path *path);
+int  vhr_forward_raster_build(vhr_forward_raster_render_path *path);    /* RenderPath::Build (render_path.cpp:14-20), at the context's display extent */
+int  vhr_forward_raster_rebuild(vhr_forward_raster_render_path *path, int32_t enable_msaa);   /* toggle + Rebuild (forward_raster_render_path.cpp:99-111) */
+const char *vhr_forward_raster_last_error(vhr_forward_raster_render_path *path);
+
+/* ---------------------------------------------------------------------------------------------
  * Harness / test access (no reference counterpart: the reference inspects images through its ImGui
  * debug-texture viewer, renderer.cpp:215-224)
  * ------------------------------------------------------------------------------------------- */
@@ -296,6 +312,10 @@ typedef struct vhr_image_info {
 int vhr_get_display_size(vhr_context *ctx, uint32_t *width, uint32_t *height);   /* context.swapchain.extent */
 int vhr_get_transient_image(vhr_context *ctx, const char *name, vhr_image_info *out);
 int vhr_get_storage_image(vhr_context *ctx, int32_t id, vhr_image_info *out);
+/* Samples per texel of a transient image: 1, or 8 for one declared multisampled (VK_SAMPLE_COUNT_8_BIT, render_graph.cpp:341).  An 8-sample
+ * image is pixel-major with a pixel's 8 samples consecutive in the standard sample order; its bytes_per_pixel (vhr_image_info) covers all
+ * 8 samples, so width * height * bytes_per_pixel is still the allocation and the byte count of an upload or download. */
+int vhr_get_transient_image_samples(vhr_context *ctx, const char *name, uint32_t *samples);
 /* synchronous copies (stream-ordered, then waited) */
 int vhr_upload_transient_image(vhr_context *ctx, const char *name, const void *host_data, uint64_t bytes);
 int vhr_download_transient_image(vhr_context *ctx, const char *name, void *host_data, uint64_t bytes);
@@ -372,6 +392,39 @@ typedef struct vhr_rayquery_forward_desc {
     uint8_t *shadowed;
 } vhr_rayquery_forward_desc;
 int vhr_standin_rayquery_forward(vhr_context *ctx, uint32_t resource_idx, const vhr_rayquery_forward_desc *desc);
+
+/* Stand-in for the forward raster path's "Forward Pass" (forward_raster_render_path.cpp:52-96, default.vert, forward_raster_render_path/
+ * default.frag), called from that pass's callback.  A ray caster on the path's own BVH, not a rasteriser.  S = 8 samples per pixel when
+ * "Depth" has 8 (enable_msaa), else 1 at the pixel centre.  The 8 positions are Vulkan's standard locations, in pixel units from the
+ * pixel's top-left corner, y down in framebuffer rows: (0.5625,0.3125) (0.4375,0.6875) (0.8125,0.5625) (0.3125,0.1875) (0.1875,0.8125)
+ * (0.0625,0.4375) (0.6875,0.9375) (0.9375,0.0625).  A sample's ray is the G-buffer stand-in's camera ray through the sample's point on the
+ * near plane (tmin 1).  Its visible triangle: the nearest hit (ties: the smaller flat index) among the triangles whose fragment at this
+ * pixel is not discarded; that decision (alpha_mask == 1 && albedo.a < alpha_cutoff, albedo = base_color without a texture) uses the
+ * triangle's attributes at the PIXEL CENTRE (the centre ray against the triangle's plane, extrapolated outside it), as the raster pipeline
+ * without sample shading does.  Each distinct visible triangle of a pixel is shaded once, at the pixel centre: albedo / pi +
+ * max(dot(N, L), 0) * albedo * light.color (shadow forced to 1, alpha 1).  Uses the per-frame data of resource_idx and computes the whole
+ * display (strips and screen tiles are out of scope).  Everything is in framebuffer rows (row 0 = the top of the presented image).  Writes:
+ *   output_storage_image  a pool storage image of 4-byte texels: the resolved swapchain texels (B8G8R8A8_SRGB, bytes b g r a).  With 8
+ *                         samples: per channel the fp32 mean, summed in sample order, of the samples' decoded values (colour from sRGB,
+ *                         alpha as UNORM), encoded like every sRGB store here -- Vulkan leaves the arithmetic of an sRGB resolve to the
+ *                         implementation, and this is the library's; with 1 sample: the sample itself.  Nothing hit: (0, 0, 0, 0)
+ *   depth_image           the transient "Depth" (D32_SFLOAT, 1 or 8 samples): reverse-Z clip.z / clip.w of each sample's own hit, 0 for a miss
+ *   msaa_image            the transient "Forward Pass_MSAA" (B8G8R8A8_SRGB, 8 samples): the shaded samples; required when "Depth" has 8
+ *                         samples and NULL otherwise (else VHR_ERROR_INVALID_ARGUMENT)
+ *   two optional probes in device memory (NULL = not written):
+ *     sample_hits         vhr_ray_hit per sample (t in the ray's parameterisation, 1 = the near plane; geometry_index 0xFFFFFFFF for a miss),
+ *                         pixel-major with a pixel's samples consecutive, 4-byte aligned
+ *     fragments           uint8_t per pixel: the number of fragments shaded (distinct visible triangles)
+ * With vhr_set_ray_statistics on, vhr_get_ray_statistics counts W x H x S primary rays.  "variant_standin_forward_raster" picks the kernel
+ * (vhr_set_option); kernel timing kind 11. */
+typedef struct vhr_forward_raster_desc {
+    int32_t output_storage_image;
+    const char *depth_image;
+    const char *msaa_image;
+    vhr_ray_hit *sample_hits;
+    uint8_t *fragments;
+} vhr_forward_raster_desc;
+int vhr_standin_forward_raster(vhr_context *ctx, uint32_t resource_idx, const vhr_forward_raster_desc *desc);
 
 /* Multi-GPU row strips: this context owns rows [row_begin, row_end) of the
  * display.  Ray tracing runs on the owned rows; the SVGF kernels on the owned rows extended by `overlap`
@@ -507,6 +560,8 @@ int vhr_get_ray_statistics(vhr_context *ctx, uint64_t out[4]);
  *   "raytraced_variant"  the raytraced render path's pass: raytraced_kernel / raytraced_queue_kernel
  *   "variant_rayquery"   the rayquery render path's forward pass (vhr_standin_rayquery_forward): rayquery_forward_kernel /
  *                        rayquery_forward_queue_kernel (primary ray + inline query per 16x8 tile and wave)
+ *   "variant_standin_forward_raster" the forward raster path's forward pass (vhr_standin_forward_raster): forward_raster_kernel /
+ *                        forward_raster_queue_kernel (the tile's S x 128 sample rays per 16x8 tile and wave, fragments shaded by the whole wave)
  *   "atrous_variant"     svgf_atrous_filter.comp: svgf_atrous_kernel (direct cached loads, product-form weights) / svgf_atrous_tile_kernel
  *                        (LDS comb tiles, weights in the exponent)
  *  The queue kernels:
@@ -598,7 +653,8 @@ int vhr_option_info(int32_t index, const char **name, int32_t *default_value, in
  * kind: 0 = raygen (K1: shadow + AO rays; with raygen_variant 0 also the mirror ray), 1 = svgf.comp (K3),
  * 2 = svgf_atrous_filter.comp (K4) on the context's stream, 3 = blits (K5), 4 = the mirror-ray kernel (K1's reflection ray + K2),
  * 5 / 6 / 7 = ssao.comp / ssao_blur.comp / ssr.comp, 8 = K4 dispatches issued on the side stream ("svgf_async_unread"),
- * 9 = vhr_ray_query (its two launches, each counted: the walk and decision (vi)'s binary64 redo), 10 = vhr_standin_rayquery_forward.
+ * 9 = vhr_ray_query (its two launches, each counted: the walk and decision (vi)'s binary64 redo), 10 = vhr_standin_rayquery_forward,
+ * 11 = vhr_standin_forward_raster.
  * kind_mask has bit (1 << kind) set for every kind to time (0 = off).  vhr_get_kernel_time synchronises, folds
  * the recorded pairs into (total milliseconds, launch count) and optionally resets the totals. */
 int vhr_set_kernel_timing(vhr_context *ctx, int32_t kind_mask);

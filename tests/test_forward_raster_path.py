@@ -1,0 +1,757 @@
+"""The forward raster render path (forward_raster_render_path.cpp:12-111, forward_raster_render_path/default.frag) with the render graph's
+multisampled transient images (render_graph.cpp:341, :921-945): the host graph on a host-only context, the sample pattern and the resolve
+arithmetic on the CPU, and on the GPU the "Forward Pass" stand-in (vhr_standin_forward_raster) -- the work-queue kernel against the literal
+one bit for bit, visibility against the oracle's tmin-stepped closest hits with the discard restated at the pixel centre, colour against a
+float64 restatement of default.frag, the resolve, orientation and coverage against an analytic quad, tile-border slivers, the alpha test at
+the pixel centre, S = 1 against the rayquery stand-in, the depth prepass against the oracle, resource index, an empty scene and a resize."""
+import numpy as np
+import pytest
+
+from tests import f2_scene
+from tests.test_rayquery_path import _sample, _srgb_decode_lut
+from vulkanhybridrenderer_amd import abi, camera, lib, scenes
+from vulkanhybridrenderer_amd.scenes import _Builder
+
+MISS = abi.RAY_MISS
+DEPTH_PREPASS, FORWARD = "Depth Prepass", "Forward Pass"
+MSAA = "Forward Pass_MSAA"
+SHADOW_MAP = "ShadowMap"
+# Vulkan's standard 8-sample locations: pixel units from the top-left corner, y down in framebuffer rows
+SAMPLES_X = np.array([0.5625, 0.4375, 0.8125, 0.3125, 0.1875, 0.0625, 0.6875, 0.9375], np.float32)
+SAMPLES_Y = np.array([0.3125, 0.6875, 0.5625, 0.1875, 0.8125, 0.4375, 0.9375, 0.0625], np.float32)
+
+
+def _offsets(S):
+    return (SAMPLES_X, SAMPLES_Y) if S == 8 else (np.array([0.5], np.float32), np.array([0.5], np.float32))
+
+
+# ---- the resolve, restated in numpy --------------------------------------------------------------------------------------
+def _srgb8(c):
+    """srgb8() of the library in float32: NaN -> 0, clamp, encode, round.  Also returns how close the value before rounding lies to a
+    rounding boundary (the device's powf and numpy's pow may differ in the last place)."""
+    c = np.asarray(c, np.float32)
+    with np.errstate(invalid="ignore"):
+        p = np.power(np.maximum(c, np.float32(0)).astype(np.float64), 1.0 / 2.4).astype(np.float32)
+        e = np.where(c <= np.float32(0.0031308), np.float32(12.92) * c, np.float32(1.055) * p - np.float32(0.055)).astype(np.float32)
+        pre = (e * np.float32(255.0)).astype(np.float32) + np.float32(0.5)
+        q = np.where(c > 0, np.where(c >= 1, 255, np.floor(pre)), 0).astype(np.uint8)
+        margin = np.where((c > 0) & (c < 1), np.abs(pre - np.round(pre)), 1.0)
+    return q, margin
+
+
+def resolve(msaa):
+    """(..., 8, 4) B8G8R8A8_SRGB samples -> (..., 4): per channel the float32 mean, summed in sample order, of the decoded samples (colour
+    from sRGB, alpha as UNORM), colour encoded with srgb8 and alpha as UNORM.  Returns (texels, margin of the colour encode)."""
+    lut = _srgb_decode_lut().astype(np.float32)
+    acc = np.zeros(msaa.shape[:-2] + (4,), np.float32)
+    for s in range(msaa.shape[-2]):
+        acc[..., :3] += lut[msaa[..., s, :3]]
+        acc[..., 3] += msaa[..., s, 3].astype(np.float32) / np.float32(255.0)
+    mean = acc * np.float32(0.125)
+    col, margin = _srgb8(mean[..., :3])
+    alpha = np.floor(np.clip(mean[..., 3], 0, 1) * np.float32(255.0) + np.float32(0.5)).astype(np.uint8)
+    return np.concatenate([col, alpha[..., None]], -1), margin.min(-1)
+
+
+# --------------------------------------------------------------------------------------------- CPU
+def test_host_graph(vhr):
+    """forward_raster_render_path.cpp on a host-only context: two passes, ShadowMap 4096^2, 8-sample Depth and _MSAA, Rebuild without MSAA."""
+    ctx = lib.Context(1280, 720, host_only=True)
+    try:
+        p = lib.ForwardRasterRenderPath(ctx)
+        p.build()
+        assert ctx.execution_order() == [DEPTH_PREPASS, FORWARD]
+        sm = ctx.transient_info(SHADOW_MAP)
+        assert (sm.width, sm.height, sm.format, sm.bytes_per_pixel) == (4096, 4096, abi.FORMAT_D32_SFLOAT, 4)
+        assert ctx.transient_samples(SHADOW_MAP) == 1
+        for name, fmt in ((lib.DEPTH, abi.FORMAT_D32_SFLOAT), (MSAA, abi.FORMAT_B8G8R8A8_SRGB)):
+            info = ctx.transient_info(name)
+            assert (info.width, info.height, info.format, info.bytes_per_pixel) == (1280, 720, fmt, 32), name
+            assert ctx.transient_samples(name) == 8, name
+        p.rebuild(enable_msaa=0)
+        assert ctx.execution_order() == [DEPTH_PREPASS, FORWARD]
+        assert ctx.transient_samples(lib.DEPTH) == 1 and ctx.transient_info(lib.DEPTH).bytes_per_pixel == 4
+        assert not ctx.contains_image(MSAA)
+        p.rebuild(enable_msaa=1)
+        assert ctx.transient_samples(lib.DEPTH) == 8 and ctx.contains_image(MSAA)
+        p.destroy()
+        p2 = lib.ForwardRasterRenderPath(ctx, depth_prepass=lambda c: None, forward_pass=lambda c: None, enable_msaa=0)
+        p2.build()
+        assert not ctx.contains_image(MSAA) and ctx.transient_samples(lib.DEPTH) == 1
+        p2.destroy()
+    finally:
+        ctx.close()
+
+
+def test_host_resize_then_build_takes_the_new_extent(vhr):
+    ctx = lib.Context(640, 360, host_only=True)
+    try:
+        p = lib.ForwardRasterRenderPath(ctx)
+        p.build()
+        ctx.resize(333, 177)
+        p.build()
+        for name in (lib.DEPTH, MSAA):
+            info = ctx.transient_info(name)
+            assert (info.width, info.height, info.bytes_per_pixel) == (333, 177, 32)
+        assert ctx.transient_info(SHADOW_MAP).width == 4096
+        p.destroy()
+    finally:
+        ctx.close()
+
+
+def test_existing_paths_keep_single_sample_images(vhr):
+    ctx = lib.Context(320, 180, host_only=True)
+    try:
+        p = lib.RayqueryRenderPath(ctx)
+        p.build()
+        assert ctx.transient_samples(lib.DEPTH) == 1 and ctx.transient_info(lib.DEPTH).bytes_per_pixel == 4
+        assert not ctx.contains_image(FORWARD + "_MSAA")
+        p.destroy()
+        h = lib.HybridRenderPath(ctx)
+        h.build()
+        for name in (lib.DEPTH, lib.NORMALS):
+            assert ctx.transient_samples(name) == 1, name
+        h.destroy()
+    finally:
+        ctx.close()
+
+
+def test_host_only_standin_option_and_kind(vhr):
+    """The option, the kernel timing kind, and no device work on a host-only context."""
+    assert lib.option_table()["variant_standin_forward_raster"] == (1, 0, 1)
+    assert sorted(lib.option_table())[-2:] == ["variant_rayquery", "variant_standin_forward_raster"]   # newer names sort last
+    assert lib.Context.KERNEL_KINDS["forward_raster"] == 11
+    ctx = lib.Context(64, 48, host_only=True)
+    try:
+        p = lib.ForwardRasterRenderPath(ctx)
+        p.build()
+        with pytest.raises(lib.VhrError, match="host-only"):
+            ctx.standin_forward_raster(0, msaa=MSAA)
+        with pytest.raises(lib.VhrError):
+            ctx.transient_samples("no such image")
+        p.destroy()
+    finally:
+        ctx.close()
+
+
+def test_desc_mismatch_is_refused(vhr):
+    """msaa_image is required with an 8-sample "Depth" and must be NULL with a 1-sample one: VHR_ERROR_INVALID_ARGUMENT (checked before
+    the host-only refusal)."""
+    ctx = lib.Context(64, 48, host_only=True)
+    try:
+        p = lib.ForwardRasterRenderPath(ctx)
+        p.build()
+        with pytest.raises(lib.VhrError, match="msaa_image is required"):
+            ctx.standin_forward_raster(0)
+        with pytest.raises(lib.VhrError, match="unknown msaa image"):
+            ctx.standin_forward_raster(0, msaa="no such image")
+        assert ctx.L.vhr_standin_forward_raster(ctx.handle, 0, lib.C.byref(lib.ForwardRasterDesc(0, b"Depth", None, None, None))) == -1   # INVALID_ARGUMENT
+        p.rebuild(enable_msaa=0)
+        with pytest.raises(lib.VhrError, match="must be NULL"):
+            ctx.standin_forward_raster(0, msaa=lib.DEPTH)
+        p.destroy()
+    finally:
+        ctx.close()
+
+
+def test_sample_pattern_is_vulkans_standard_8x():
+    """The table the kernels use (vhr_amd.h) against Vulkan's standard locations in 1/16 pixel units; each row and column used once."""
+    assert (SAMPLES_X * 16).tolist() == [9, 7, 13, 5, 3, 1, 11, 15]
+    assert (SAMPLES_Y * 16).tolist() == [5, 11, 9, 3, 13, 7, 15, 1]
+    assert sorted((SAMPLES_X * 16).tolist()) == sorted((SAMPLES_Y * 16).tolist()) == list(range(1, 16, 2))
+
+
+def test_resolve_arithmetic_kat():
+    """Eight equal samples resolve to themselves; alpha is round(255 k / 8) for k covered samples; a known mixed case."""
+    rng = np.random.default_rng(5)
+    t = rng.integers(0, 256, (64, 4)).astype(np.uint8)
+    t[:, 3] = 255
+    got, _ = resolve(np.repeat(t[:, None, :], 8, 1))
+    assert np.array_equal(got, t)
+    for k in range(9):
+        m = np.zeros((1, 8, 4), np.uint8)
+        m[0, :k] = (10, 20, 30, 255)
+        assert resolve(m)[0][0, 3] == int(np.floor(255 * k / 8 + 0.5))
+    half = np.zeros((1, 8, 4), np.uint8)
+    half[0, :4] = (255, 255, 255, 255)                  # 4 white samples, 4 cleared: linear 0.5 -> sRGB 188
+    assert resolve(half)[0][0].tolist() == [188, 188, 188, 128]
+
+
+def test_sample_rays_map_the_y_offsets():
+    """The restated ray parameterisation (used by the GPU tests) puts a sample with a small framebuffer y offset nearer the TOP of the
+    presented image, i.e. higher up in the G-buffer's upward v."""
+    W, H = 4, 4
+    u, v = _sample_uv(np.array([1]), np.array([1]), W, H, 8)
+    top = np.argmin(SAMPLES_Y)
+    assert v[0, top] == v[0].max() and v[0, np.argmax(SAMPLES_Y)] == v[0].min()
+
+
+def _sample_uv(x, fy, W, H, S):
+    """float32 (u, v) of the sample rays of framebuffer pixels (x, fy), as the kernels compute them: (n, S) each."""
+    sx, sy = _offsets(S)
+    x = np.asarray(x, np.float32)[:, None]
+    gy = (H - 1 - np.asarray(fy)).astype(np.float32)[:, None]
+    u = ((x + sx[None, :]) / np.float32(W)).astype(np.float32)
+    v = ((gy + (np.float32(1.0) - sy[None, :])) / np.float32(H)).astype(np.float32)
+    return u, v
+
+
+def _sample_dirs(pfd, x, fy, W, H, S):
+    """get_world_space_position(pfd, 1, u, v) - cam in float32 with the kernels' operation order: (n, S, 3) and the camera."""
+    u, v = _sample_uv(x, fy, W, H, S)
+    m = np.asarray(pfd["camera_viewproj_inverse"], np.float32).reshape(16)
+    cam = np.asarray(pfd["camera_view_inverse"], np.float32).reshape(16)[12:15]
+    f = np.float32
+    px, py, pz, pw = u * f(2) - f(1), v * f(2) - f(1), f(1), f(1)
+    r = [((m[i] * px + m[4 + i] * py) + m[8 + i] * pz) + m[12 + i] * pw for i in range(4)]
+    d = np.stack([(r[0] / r[3]) - cam[0], (r[1] / r[3]) - cam[1], (r[2] / r[3]) - cam[2]], -1).astype(np.float32)
+    return d, cam
+
+
+# --------------------------------------------------------------------------------------------- GPU
+class _Forward:
+    """A context with the path built, the shadow-map stand-in and the forward stand-in as its pass bodies, writing both probes."""
+
+    def __init__(self, sc, W, H, msaa=1):
+        import torch
+        self.torch = torch
+        self.W, self.H, self.S = W, H, 8 if msaa else 1
+        self.ctx = lib.Context(W, H)
+        self.ctx.upload_scene(sc)
+        self.ctx.set_ray_statistics(True)
+        self.resource_idx = 0
+        self._alloc()
+        self.path = lib.ForwardRasterRenderPath(self.ctx, depth_prepass=self._prepass, forward_pass=self._body, enable_msaa=msaa)
+        self.path.build()
+
+    def _alloc(self):
+        n = self.W * self.H
+        self.present = self.ctx.upload_new_storage_image(self.W, self.H, abi.FORMAT_B8G8R8A8_SRGB)
+        self.hits = self.torch.zeros((n * self.S, 6), dtype=self.torch.int32, device="cuda")
+        self.frags = self.torch.zeros(n, dtype=self.torch.uint8, device="cuda")
+        self.torch.cuda.synchronize()
+
+    def _prepass(self, c):
+        c.standin_shadow_map(self.resource_idx, SHADOW_MAP)
+
+    def _body(self, c):
+        c.standin_forward_raster(self.present, self.resource_idx, msaa=MSAA if self.S == 8 else None, sample_hits_ptr=self.hits.data_ptr(),
+                                 fragments_ptr=self.frags.data_ptr())
+
+    def resize(self, W, H):
+        self.ctx.resize(W, H)
+        self.W, self.H = W, H
+        self._alloc()
+        self.path.build()
+
+    def run(self, pfd, variant=1, resource_idx=0, pfds=None):
+        self.ctx.set_option("variant_standin_forward_raster", variant)
+        self.resource_idx = resource_idx
+        for i, p in enumerate(pfds or [pfd]):
+            self.ctx.update_per_frame_ubo(i, p)
+        self.ctx.execute(0, 0)
+        self.ctx.synchronize()
+        H, W, S = self.H, self.W, self.S
+        hits = np.ascontiguousarray(self.hits.cpu().numpy()).view(np.uint32).view(abi.ray_hit_dtype).reshape(H, W, S)
+        depth = self.ctx.download(lib.DEPTH).reshape(H, W, S)
+        r = dict(out=self.ctx.download(self.present), depth=depth, hits=hits, frags=self.frags.cpu().numpy().reshape(H, W),
+                 stats=self.ctx.ray_statistics())
+        r["msaa"] = self.ctx.download(MSAA) if S == 8 else r["out"].reshape(H, W, 1, 4)
+        return r
+
+    def close(self):
+        self.path.destroy()
+        self.ctx.close()
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint8)
+
+
+def _assert_same(a, b, what):
+    for k in ("out", "depth", "hits", "frags", "msaa"):
+        assert np.array_equal(_bits(a[k]), _bits(b[k])), f"{what}: {k} differs"
+    assert a["stats"] == b["stats"], what
+
+
+def _check_invariants(r, W, H, S):
+    hit = r["hits"]["geometry_index"] != MISS
+    assert r["stats"]["stack_overflows"] == 0
+    assert r["stats"]["unique_rays"] == W * H * S                         # S primary rays per pixel, nothing else
+    assert np.array_equal(r["depth"] != 0, hit)
+    assert np.array_equal(r["msaa"][..., 3] == 255, hit) and not r["msaa"][~hit].any()
+    keys = r["hits"]["geometry_index"].astype(np.uint64) << np.uint64(32) | r["hits"]["primitive_index"].astype(np.uint64)
+    distinct = np.array([[len(set(keys[y, x][hit[y, x]].tolist())) for x in range(W)] for y in range(H)])
+    assert np.array_equal(r["frags"], distinct)                           # one fragment per distinct visible triangle
+    if S == 8:
+        want, margin = resolve(r["msaa"])
+        assert np.array_equal(want[..., 3], np.floor(255 * hit.sum(-1) / 8 + 0.5).astype(np.uint8))
+        bad = (want != r["out"]).any(-1)
+        assert (margin[bad] < 1e-3).all(), f"{int(bad.sum())} resolved texels differ from the restated resolve"
+        assert bad.mean() <= 1e-4
+    else:
+        assert np.array_equal(r["out"], r["msaa"][:, :, 0])
+    return hit
+
+
+def _scene(name):
+    return {"f4": f2_scene.scene_f4, "f2": f2_scene.scene, "sponza": scenes.sponza_proc, "bistro": scenes.bistro_proc, "tiny": scenes.tiny_scene}[name]()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("scene_name,W,H", [("f4", 160, 96), ("f4", 333, 177), ("f2", 203, 121), ("sponza", 480, 270), ("bistro", 333, 177)])
+@pytest.mark.parametrize("msaa", [1, 0])
+def test_gpu_queue_kernel_equals_literal_kernel(scene_name, W, H, msaa):
+    """variant_standin_forward_raster 1 (work queue, default) and 0 (one pixel per thread): every output and both probes bit for bit, with deep and
+    shallow LDS stacks (the second spills to scratch), at extents that are not multiples of the 16x8 tile."""
+    sc = _scene(scene_name)
+    pfd = camera.dolly_frames(sc, W, H, 2)[1]
+    f = _Forward(sc, W, H, msaa)
+    try:
+        base = f.run(pfd, variant=0)
+        hit = _check_invariants(base, W, H, f.S)
+        assert 0.2 < hit.mean() <= 1.0
+        for levels in (8, 2):
+            f.ctx.set_option("lds_stack_levels", levels)
+            got = f.run(pfd, variant=1)
+            _assert_same(got, base, f"{scene_name} {W}x{H} msaa {msaa}, queue kernel with {levels} LDS levels")
+        f.ctx.set_option("lds_stack_levels", 8)
+    finally:
+        f.close()
+
+
+def _world_tris(sc):
+    """World-space vertex positions per primitive (float64)."""
+    out = []
+    for p in sc.primitives:
+        M = np.asarray(p["transform"], np.float64).reshape(4, 4).T
+        out.append(M)
+    return out
+
+
+def _centre_alpha(sc, mats, prim, tri, cam, cdir):
+    """default.frag's alpha at the pixel centre for (primitive, triangle), float64: the centre ray against the triangle's plane, the
+    barycentrics extrapolated; None when the primitive is not alpha-masked."""
+    P = sc.primitives[prim]
+    m = P["material"]
+    if m["alpha_mask"] != 1:
+        return None
+    if m["base_color_texture"] == -1:
+        return float(m["base_color"][3])
+    io, vo = int(P["index_offset"]), int(P["vertex_offset"])
+    vs = [sc.vertices[vo + int(sc.indices[io + 3 * tri + k])] for k in range(3)]
+    pw = [(mats[prim] @ np.append(np.asarray(v["pos"], np.float64), 1.0))[:3] for v in vs]
+    e1, e2 = pw[1] - pw[0], pw[2] - pw[0]
+    d = np.asarray(cdir, np.float64)
+    pvec = np.cross(d, e2)
+    det = e1 @ pvec
+    tvec = np.asarray(cam, np.float64) - pw[0]
+    u, v = (tvec @ pvec) / det, (d @ np.cross(tvec, e1)) / det
+    uv = sum(np.asarray(vs[k]["uv0"], np.float64) * b for k, b in enumerate((1 - u - v, u, v)))
+    return float(_sample(sc.textures[int(m["base_color_texture"])], np.array([uv[0]]), np.array([uv[1]]))[0, 3])
+
+
+def _oracle_visibility(oracle, sc, pfd, W, H, S, pixels, tol=1e-4):
+    """Per sample of the given pixels: the oracle's closest hit stepped past every candidate whose fragment is discarded at the pixel centre.
+    Returns {(x, fy): [(prim, tri, t) or None] * S} and the number of samples that met a centre alpha within `tol` of the cutoff."""
+    osc = oracle.Scene(sc)
+    mats = _world_tris(sc)
+    xs, ys = np.array([p[0] for p in pixels]), np.array([p[1] for p in pixels])
+    dirs, cam = _sample_dirs(pfd, xs, ys, W, H, S)
+    cdirs, _ = _sample_dirs(pfd, xs, ys, W, H, 1)
+    out, near = {}, 0
+    for i, (x, fy) in enumerate(pixels):
+        res = []
+        for s in range(S):
+            tmin = np.float32(1.0)
+            got = None
+            for _ in range(64):
+                h = osc.closest(cam, dirs[i, s], tmin, 3.0e38)
+                if h is None:
+                    break
+                t, _u, _v, prim, tri = h
+                a = _centre_alpha(sc, mats, prim, tri, cam, cdirs[i, 0])
+                if a is not None:
+                    cut = float(sc.primitives[prim]["material"]["alpha_cutoff"])
+                    near += abs(a - cut) <= tol
+                    if a < cut:
+                        tmin = t
+                        continue
+                got = (prim, tri, t)
+                break
+            res.append(got)
+        out[(x, fy)] = res
+    return out, near
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("scene_name,W,H,step", [("f4", 160, 96, 5), ("f4", 203, 121, 4), ("sponza", 240, 135, 11)])
+def test_gpu_visibility_against_the_oracle(oracle, scene_name, W, H, step):
+    """Per sample: the visible triangle and its t equal the oracle's tmin-stepped closest hit with the discard restated at the pixel
+    centre, except samples that met a centre alpha within 1e-4 of the cutoff (counted, <= 0.01 %); depth is clip.z / clip.w of that t."""
+    sc = _scene(scene_name)
+    pfd = camera.dolly_frames(sc, W, H, 2)[1]
+    f = _Forward(sc, W, H)
+    try:
+        r = f.run(pfd)
+    finally:
+        f.close()
+    pixels = [(x, y) for y in range(0, H, step) for x in range(0, W, step)]
+    want, near = _oracle_visibility(oracle, sc, pfd, W, H, 8, pixels)
+    mismatches = 0
+    for (x, y), res in want.items():
+        for s, w in enumerate(res):
+            g = r["hits"][y, x, s]
+            if w is None:
+                mismatches += g["geometry_index"] != MISS
+            else:
+                mismatches += not (g["geometry_index"] == w[0] and g["primitive_index"] == w[1] and g["t"] == w[2])
+    n = len(pixels) * 8
+    assert mismatches <= near and near <= max(1, n // 10000), (mismatches, near, n)
+    hit = r["hits"]["geometry_index"] != MISS
+    assert hit.mean() > 0.3
+
+
+def _restate_msaa(sc, pfd, r):
+    """default.frag at the pixel centre for every covered sample's triangle, float64, through the sRGB store: (H, W, S, 4)."""
+    H, W, S = r["hits"].shape
+    hits = r["hits"]
+    cov = hits["geometry_index"] != MISS
+    ys, xs, ss = np.nonzero(cov)
+    cdirs, cam = _sample_dirs(pfd, xs, ys, W, H, 1)
+    prim = hits["geometry_index"][cov].astype(np.int64)
+    tri = hits["primitive_index"][cov].astype(np.int64)
+    P = sc.primitives
+    io, vo = P["index_offset"][prim].astype(np.int64), P["vertex_offset"][prim].astype(np.int64)
+    verts = [sc.vertices[vo + sc.indices[io + 3 * tri + k].astype(np.int64)] for k in range(3)]
+    mats = np.stack([np.asarray(p["transform"], np.float64).reshape(4, 4).T for p in P])[prim]
+    pw = [np.einsum("nij,nj->ni", mats, np.concatenate([np.asarray(v["pos"], np.float64), np.ones((len(v), 1))], 1))[:, :3] for v in verts]
+    e1, e2 = pw[1] - pw[0], pw[2] - pw[0]
+    d = cdirs[:, 0].astype(np.float64)
+    pvec = np.cross(d, e2)
+    det = (e1 * pvec).sum(1)
+    tvec = cam.astype(np.float64) - pw[0]
+    u = (tvec * pvec).sum(1) / det
+    v = (d * np.cross(tvec, e1)).sum(1) / det
+    b = np.stack([1.0 - u - v, u, v], 1)
+    lerp = lambda field: sum(np.asarray(verts[k][field], np.float64) * b[:, k:k + 1] for k in range(3))    # noqa: E731
+    normal, tangent, uv = lerp("normal"), lerp("tangent"), lerp("uv0")
+    mat = P["material"][prim]
+    albedo = np.asarray(mat["base_color"], np.float64)[:, :3].copy()
+    for t in np.unique(mat["base_color_texture"]):
+        if t >= 0:
+            m = mat["base_color_texture"] == t
+            albedo[m] = _sample(sc.textures[t], uv[m, 0], uv[m, 1])[:, :3]
+    N = normal.copy()
+    for t in np.unique(mat["normal_map"]):
+        if t >= 0:
+            m = mat["normal_map"] == t
+            tsn = _sample(sc.textures[t], uv[m, 0], uv[m, 1])[:, :3] * 2.0 - 1.0
+            tsn /= np.linalg.norm(tsn, axis=1, keepdims=True)
+            T, n = tangent[m, :3], normal[m]
+            bit = np.cross(tsn, T) * tangent[m, 3:4]
+            tg = T - n * (T * n).sum(1, keepdims=True)
+            tg /= np.linalg.norm(tg, axis=1, keepdims=True)
+            N[m] = tg * tsn[:, 0:1] + bit * tsn[:, 1:2] + n * tsn[:, 2:3]
+    light = pfd["directional_light"]
+    L = -np.asarray(light["direction"], np.float64)[:3]
+    lc = np.asarray(light["color"], np.float64)[:3]
+    col = albedo / np.pi + np.maximum(N @ L, 0.0)[:, None] * albedo * lc
+    with np.errstate(invalid="ignore"):
+        enc = np.where(col <= 0.0031308, 12.92 * col, 1.055 * np.power(np.maximum(col, 0.0), 1 / 2.4) - 0.055)
+        q = np.where(col > 0.0, np.where(col >= 1.0, 255.0, np.floor(enc * 255.0 + 0.5)), 0.0)
+    out = np.zeros((H, W, S, 4), np.uint8)
+    out[cov] = np.concatenate([q[:, ::-1], np.full((len(q), 1), 255.0)], 1).astype(np.uint8)
+    return out, cov
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("scene_name,W,H", [("f4", 160, 96), ("bistro", 480, 270), ("sponza", 640, 360)])
+def test_gpu_colour_msaa_and_resolve(scene_name, W, H):
+    """_MSAA texels against default.frag restated in float64 at the pixel centre (1 LSB on >= 99.9 % of the covered samples), misses
+    exactly clear; the resolved output is the resolve of the downloaded _MSAA image, its alpha round(255 k / 8)."""
+    sc = _scene(scene_name)
+    pfd = camera.dolly_frames(sc, W, H, 2)[1]
+    f = _Forward(sc, W, H)
+    try:
+        r = f.run(pfd)
+    finally:
+        f.close()
+    _check_invariants(r, W, H, 8)
+    want, cov = _restate_msaa(sc, pfd, r)
+    got = r["msaa"]
+    assert (got[~cov] == 0).all() and (got[cov][:, 3] == 255).all()
+    d = np.abs(got[cov].astype(int) - want[cov].astype(int)).max(1)
+    assert (d <= 1).mean() >= 0.999, f"{int((d > 1).sum())} of {int(cov.sum())} samples off by more than 1 LSB (max {d.max()})"
+    partial = (cov.sum(-1) > 0) & (cov.sum(-1) < 8)
+    assert partial.any()                                                  # edges: antialiased texels exist
+    assert len(np.unique(r["out"][partial][:, 3])) > 2
+
+
+def _quad_scene(pfd, W, H, corners_fb, depth_scale=40.0, texture=None, uv=None, extra=()):
+    """A quad whose corners are the framebuffer points `corners_fb` (x right, y down), placed on the plane parallel to the near plane at
+    `depth_scale` times the near-plane distance from the camera; plus `extra` meshes.  Built in float64 from the frame's matrices."""
+    inv = np.asarray(pfd["camera_viewproj_inverse"], np.float64).reshape(4, 4).T
+    cam = np.asarray(pfd["camera_view_inverse"], np.float64).reshape(4, 4).T[:3, 3]
+
+    def world(X, Y, k):
+        u, v = X / W, (H - Y) / H
+        p = inv @ np.array([2 * u - 1, 2 * v - 1, 1.0, 1.0])
+        return cam + (p[:3] / p[3] - cam) * k
+    pos = np.array([world(X, Y, depth_scale) for X, Y in corners_fb])
+    b = _Builder()
+    nrm = np.tile(np.cross(pos[1] - pos[0], pos[3] - pos[0]), (4, 1))
+    quad = (pos, nrm, np.array(uv if uv is not None else [[0, 0], [1, 0], [1, 1], [0, 1]], float), np.array([[0, 1, 2], [0, 2, 3]], np.uint32))
+    b.add(quad, base_color=(0.9, 0.5, 0.2, 1.0), base_color_texture=-1 if texture is None else 0)
+    if texture is not None:
+        b.p[-1]["material"]["alpha_mask"] = 1
+        b.p[-1]["material"]["alpha_cutoff"] = 0.5
+    for mesh in extra:
+        b.add(mesh(world), base_color=(0.3, 0.6, 0.9, 1.0))
+    return b.finish("quad", dict(position=(0.0, 0.0, 0.0), yaw=0.0, pitch=0.0, yfov=0.9, znear=0.1, dolly=(0, 0, 0)),
+                    camera.directional_light((0.2, -0.9, -0.4)), [texture] if texture is not None else [])
+
+
+def _frame(W, H):
+    base = scenes.tiny_scene()
+    return camera.dolly_frames(base, W, H, 1)[0]
+
+
+@pytest.mark.gpu
+def test_gpu_orientation_and_coverage_of_a_quad_edge():
+    """A quad with a vertical edge at x = 20 + 17/32 and one with a horizontal edge at framebuffer row y = 12 + 13/32 (y down): the
+    samples covered in the edge's column / row are exactly those whose standard x / y offset lies on the quad's side.  The sample y
+    offsets are symmetric as a set, so a mirrored y would leave each pixel's count unchanged but move the coverage to other samples:
+    the per-sample pattern is asserted, and the mirrored pattern is shown to predict a different one."""
+    W, H = 48, 32
+    pfd = _frame(W, H)
+    fx, fy = 17 / 32, 13 / 32
+    cases = [("x", [(-20, -20), (20 + fx, -20), (20 + fx, H + 20), (-20, H + 20)], 20, SAMPLES_X, fx),
+             ("y", [(-20, -20), (W + 20, -20), (W + 20, 12 + fy), (-20, 12 + fy)], 12, SAMPLES_Y, fy)]
+    for axis, corners, edge, offs, frac in cases:
+        sc = _quad_scene(pfd, W, H, corners)
+        f = _Forward(sc, W, H)
+        try:
+            r = f.run(pfd)
+            lit = f.run(pfd, variant=0)
+        finally:
+            f.close()
+        _assert_same(r, lit, f"quad edge {axis}")
+        cov = r["hits"]["geometry_index"] != MISS
+        want = offs < frac
+        line = cov[:, edge] if axis == "x" else cov[edge, :]
+        assert (line == want[None, :]).all(), (axis, line[0], want)
+        inside = cov[:, :edge] if axis == "x" else cov[:edge, :]
+        outside = cov[:, edge + 1:] if axis == "x" else cov[edge + 1:, :]
+        assert inside.all() and not outside.any()
+        assert (r["frags"][:, edge] if axis == "x" else r["frags"][edge, :]).tolist() == [1] * (H if axis == "x" else W)
+        if axis == "y":
+            mirrored = (1.0 - offs) < frac
+            assert not np.array_equal(mirrored, want) and mirrored.sum() == want.sum()
+            assert (r["out"][edge, :, 3] == int(np.floor(255 * want.sum() / 8 + 0.5))).all()
+
+
+@pytest.mark.gpu
+def test_gpu_tile_border_slivers():
+    """Slivers 0.14 px wide centred on the 16x8 tile borders: only sample rays (1/16 px from a pixel's border) hit them, never a pixel
+    centre.  The queue kernel equals the literal kernel and the oracle, and the slivers are seen."""
+    W, H = 70, 41
+    pfd = _frame(W, H)
+    w = 0.07
+
+    def slivers(world):
+        pos, tris = [], []
+        for X in range(16, W, 16):
+            pos += [world(X - w, -5, 30), world(X + w, -5, 30), world(X + w, H + 5, 30), world(X - w, H + 5, 30)]
+        for Y in range(8, H, 8):
+            pos += [world(-5, Y - w, 30), world(W + 5, Y - w, 30), world(W + 5, Y + w, 30), world(-5, Y + w, 30)]
+        for q in range(len(pos) // 4):
+            tris += [[4 * q, 4 * q + 1, 4 * q + 2], [4 * q, 4 * q + 2, 4 * q + 3]]
+        pos = np.array(pos)
+        return pos, np.tile([0.0, 0.0, 1.0], (len(pos), 1)), np.zeros((len(pos), 2)), np.array(tris, np.uint32)
+    sc = _quad_scene(pfd, W, H, [(-30, -30), (W + 30, -30), (W + 30, H + 30), (-30, H + 30)], depth_scale=60.0, extra=(slivers,))
+    f = _Forward(sc, W, H)
+    try:
+        q = f.run(pfd)
+        lit = f.run(pfd, variant=0)
+    finally:
+        f.close()
+    _assert_same(q, lit, "slivers")
+    on_sliver = q["hits"]["geometry_index"] == 1
+    assert on_sliver[:, 16, 5].all() and on_sliver[:, 15, 7].all()       # sx = 1/16 of column 16, sx = 15/16 of column 15
+    assert on_sliver[8, :, 7].all() and on_sliver[7, :, 6].all()         # sy = 1/16 of row 8, sy = 15/16 of row 7
+    assert not (q["frags"] == 0).any() and (q["frags"] == 2).any()
+
+
+@pytest.mark.gpu
+def test_gpu_tile_border_slivers_against_the_oracle(oracle):
+    W, H = 70, 41
+    pfd = _frame(W, H)
+    w = 0.07
+
+    def slivers(world):
+        pos = np.array([world(16 - w, -5, 30), world(16 + w, -5, 30), world(16 + w, H + 5, 30), world(16 - w, H + 5, 30)])
+        return pos, np.tile([0.0, 0.0, 1.0], (4, 1)), np.zeros((4, 2)), np.array([[0, 1, 2], [0, 2, 3]], np.uint32)
+    sc = _quad_scene(pfd, W, H, [(-30, -30), (W + 30, -30), (W + 30, H + 30), (-30, H + 30)], depth_scale=60.0, extra=(slivers,))
+    f = _Forward(sc, W, H)
+    try:
+        r = f.run(pfd)
+    finally:
+        f.close()
+    pixels = [(x, y) for y in (0, 7, 8, 20) for x in (14, 15, 16, 17)]
+    want, near = _oracle_visibility(oracle, sc, pfd, W, H, 8, pixels)
+    assert near == 0
+    for (x, y), res in want.items():
+        for s, wv in enumerate(res):
+            g = r["hits"][y, x, s]
+            assert (g["geometry_index"], g["primitive_index"], g["t"]) == (wv[0], wv[1], wv[2]), (x, y, s)
+
+
+@pytest.mark.gpu
+def test_gpu_alpha_test_at_the_pixel_centre():
+    """A masked quad whose alpha texture has 4 x 4 texels per pixel (NEAREST, checker of 1-texel cells) in front of a wall.  Per pixel the
+    quad's samples are either all kept or all discarded, as default.frag's alpha at the pixel centre says; evaluated per sample the rule
+    would differ on some pixel."""
+    W, H = 40, 24
+    pfd = _frame(W, H)
+    n = 4 * 16
+    yy, xx = np.mgrid[0:n, 0:n]
+    tex = np.zeros((n, n, 4), np.uint8)
+    tex[..., :3] = 200
+    tex[..., 3] = np.where((xx % 4 == 1) == ((xx // 4 + yy // 4) % 2 == 0), 255, 0)    # the centre's texel column is 4k + 1
+    texture = dict(rgba8=tex, format=abi.FORMAT_R8G8B8A8_UNORM, mag=abi.FILTER_NEAREST, min=abi.FILTER_NEAREST,
+                   address_u=abi.ADDRESS_CLAMP_TO_EDGE, address_v=abi.ADDRESS_CLAMP_TO_EDGE)
+    x0, y0 = 10.0 + 1 / 32, 4.0 + 1 / 32                                 # 16 x 16 pixels; uv (0,0) at the top-left corner
+    corners = [(x0, y0), (x0 + 16, y0), (x0 + 16, y0 + 16), (x0, y0 + 16)]
+
+    def wall(world):
+        pos = np.array([world(-20, -20, 50), world(W + 20, -20, 50), world(W + 20, H + 20, 50), world(-20, H + 20, 50)])
+        return pos, np.tile([0.0, 0.0, 1.0], (4, 1)), np.zeros((4, 2)), np.array([[0, 1, 2], [0, 2, 3]], np.uint32)
+    sc = _quad_scene(pfd, W, H, corners, depth_scale=20.0, texture=texture, extra=(wall,))
+    f = _Forward(sc, W, H)
+    try:
+        r = f.run(pfd)
+        lit = f.run(pfd, variant=0)
+    finally:
+        f.close()
+    _assert_same(r, lit, "alpha at the centre")
+    quad = r["hits"]["geometry_index"] == 0
+    for y in range(int(y0), int(y0) + 16):
+        for x in range(int(x0), int(x0) + 16):
+            u, v = (x + 0.5 - x0) / 16, (y + 0.5 - y0) / 16
+            keep = tex[int(v * n), int(u * n), 3] >= 128
+            assert quad[y, x].all() == keep and quad[y, x].any() == keep, (x, y)
+    per_sample_differs = False
+    for y in range(int(y0), int(y0) + 16):
+        for x in range(int(x0), int(x0) + 16):
+            su, sv = (x + SAMPLES_X - x0) / 16, (y + SAMPLES_Y - y0) / 16
+            kept = tex[(sv * n).astype(int), (su * n).astype(int), 3] >= 128
+            per_sample_differs |= not np.array_equal(kept, quad[y, x])
+    assert per_sample_differs
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("scene_name,W,H", [("tiny", 200, 120), ("sponza", 480, 270)])
+def test_gpu_single_sample_hits_equal_the_rayquery_standin(scene_name, W, H):
+    """Without alpha-masked materials and without MSAA the sample is the pixel centre: its hit is the rayquery stand-in's primary hit
+    bit for bit, rows flipped (framebuffer rows against the G-buffer's)."""
+    import torch
+    sc = _scene(scene_name)
+    pfd = camera.dolly_frames(sc, W, H, 2)[1]
+    f = _Forward(sc, W, H, msaa=0)
+    try:
+        r = f.run(pfd)
+    finally:
+        f.close()
+    ctx = lib.Context(W, H)
+    ctx.upload_scene(sc)
+    hits = torch.zeros((W * H, 6), dtype=torch.int32, device="cuda")
+    present = ctx.upload_new_storage_image(W, H, abi.FORMAT_B8G8R8A8_SRGB)
+    path = lib.RayqueryRenderPath(ctx, forward_pass=lambda c: c.standin_rayquery_forward(present, 0, primary_hits_ptr=hits.data_ptr()))
+    path.build()
+    try:
+        ctx.update_per_frame_ubo(0, pfd)
+        ctx.execute(0, 0)
+        ctx.synchronize()
+        rq = np.ascontiguousarray(hits.cpu().numpy()).view(np.uint32).view(abi.ray_hit_dtype).reshape(H, W)
+        rq_depth = ctx.download(lib.DEPTH)
+    finally:
+        path.destroy()
+        ctx.close()
+    assert np.array_equal(_bits(r["hits"][:, :, 0]), _bits(rq[::-1]))
+    assert np.array_equal(_bits(r["depth"][:, :, 0]), _bits(rq_depth[::-1]))
+
+
+@pytest.mark.gpu
+def test_gpu_depth_prepass_equals_the_oracle(oracle):
+    """The path's "ShadowMap" (the Depth Prepass through vhr_standin_shadow_map) equals the oracle's shadow map."""
+    sc = scenes.tiny_scene()
+    W, H = 64, 48
+    pfd = camera.dolly_frames(sc, W, H, 2)[1]
+    f = _Forward(sc, W, H)
+    try:
+        f.run(pfd)
+        got = f.ctx.download(SHADOW_MAP)
+    finally:
+        f.close()
+    rows = (1984, 2112)
+    want = oracle.Scene(sc).shadow_map(pfd, 4096, rows=rows)
+    assert (got != 0).any()
+    assert np.array_equal(got[rows[0]:rows[1]].view(np.uint32), want[rows[0]:rows[1]].view(np.uint32))
+
+
+@pytest.mark.gpu
+def test_gpu_per_frame_data_follows_resource_idx():
+    sc = f2_scene.scene_f4()
+    W, H = 96, 64
+    a = camera.dolly_frames(sc, W, H, 2)[1]
+    b = a.copy()
+    d = np.array([-0.5, -0.7, 0.3])
+    b["directional_light"]["direction"][:3] = d / np.linalg.norm(d)
+    b["directional_light"]["color"][:3] = (0.6, 0.8, 1.0)
+    f = _Forward(sc, W, H)
+    try:
+        ra = f.run(None, resource_idx=0, pfds=[a, b])
+        rb = f.run(None, resource_idx=1, pfds=[a, b])
+        only_b = f.run(None, resource_idx=0, pfds=[b])
+    finally:
+        f.close()
+    assert not np.array_equal(ra["out"], rb["out"])
+    _assert_same(rb, only_b, "slot 1 against the same frame in slot 0")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("msaa", [1, 0])
+def test_gpu_empty_scene_is_all_clear(msaa):
+    sc = scenes.tiny_scene()
+    sc.primitives = sc.primitives[:0]
+    W, H = 70, 45
+    f = _Forward(sc, W, H, msaa)
+    try:
+        for variant in (1, 0):
+            r = f.run(camera.dolly_frames(sc, W, H, 2)[1], variant=variant)
+            assert not r["out"].any() and not r["depth"].any() and not r["msaa"].any() and not r["frags"].any()
+            assert (r["hits"]["geometry_index"] == MISS).all()
+            assert r["stats"]["unique_rays"] == W * H * f.S
+    finally:
+        f.close()
+
+
+@pytest.mark.gpu
+def test_gpu_resize_then_build_equals_a_fresh_context():
+    sc = f2_scene.scene_f4()
+    f = _Forward(sc, 160, 96)
+    try:
+        f.run(camera.dolly_frames(sc, 160, 96, 2)[1])
+        f.resize(333, 177)
+        pfd = camera.dolly_frames(sc, 333, 177, 2)[1]
+        got = f.run(pfd)
+    finally:
+        f.close()
+    fresh = _Forward(sc, 333, 177)
+    try:
+        want = fresh.run(pfd)
+    finally:
+        fresh.close()
+    assert got["out"].shape == (177, 333, 4) and got["msaa"].shape == (177, 333, 8, 4)
+    _assert_same(got, want, "after vhr_resize + build")

@@ -940,7 +940,7 @@ int vhr_get_display_size(vhr_context *ctx, uint32_t *width, uint32_t *height) {
 }
 
 static int image_info(vhr_context *ctx, const Image &im, vhr_image_info *out) {
-    out->device_ptr = im.ptr; out->width = im.width; out->height = im.height; out->format = im.format; out->bytes_per_pixel = im.bpp;
+    out->device_ptr = im.ptr; out->width = im.width; out->height = im.height; out->format = im.format; out->bytes_per_pixel = im.bpp * im.samples;
     (void)ctx;
     return VHR_OK;
 }
@@ -952,6 +952,14 @@ int vhr_get_transient_image(vhr_context *ctx, const char *name, vhr_image_info *
     // (the caller is about to use the pointer on the context's stream: the mirror ray's pending launch writes this image)
     if (!ctx->host_only && it->second.ptr == ctx->refl_writes) { const int jrc = ctx->join_refl(); if (jrc != VHR_OK) return jrc; }
     return image_info(ctx, it->second, out);
+}
+
+int vhr_get_transient_image_samples(vhr_context *ctx, const char *name, uint32_t *samples) {
+    if (!ctx || !name || !samples) return VHR_ERROR_INVALID_ARGUMENT;
+    auto it = ctx->images.find(name);
+    if (it == ctx->images.end()) return ctx->fail(VHR_ERROR_NOT_FOUND, std::string("no transient image named '") + name + "'");
+    *samples = it->second.samples;
+    return VHR_OK;
 }
 
 int vhr_get_storage_image(vhr_context *ctx, int32_t id, vhr_image_info *out) {
@@ -1071,6 +1079,28 @@ int vhr_standin_rayquery_forward(vhr_context *ctx, uint32_t resource_idx, const 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return launch_rayquery_forward(ctx, ctx->per_frame[resource_idx], ctx->storage_images[d->output_storage_image], it->second, d->primary_hits,
                                    d->positions, d->shadowed);
+}
+
+int vhr_standin_forward_raster(vhr_context *ctx, uint32_t resource_idx, const vhr_forward_raster_desc *d) {
+    if (!ctx || !d || !d->depth_image || resource_idx >= 3)
+        return ctx ? ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "standin_forward_raster: bad argument") : VHR_ERROR_INVALID_ARGUMENT;
+    auto it = ctx->images.find(d->depth_image);
+    if (it == ctx->images.end()) return ctx->fail(VHR_ERROR_NOT_FOUND, "standin_forward_raster: unknown transient image");
+    Image *msaa = nullptr;
+    if (it->second.samples == kMsaaSamples) {
+        if (!d->msaa_image) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "standin_forward_raster: \"Depth\" has 8 samples, so msaa_image is required");
+        auto m = ctx->images.find(d->msaa_image);
+        if (m == ctx->images.end()) return ctx->fail(VHR_ERROR_NOT_FOUND, "standin_forward_raster: unknown msaa image");
+        msaa = &m->second;
+    } else if (d->msaa_image) {
+        return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "standin_forward_raster: \"Depth\" has 1 sample, so msaa_image must be NULL");
+    }
+    if (ctx->host_only) return ctx->fail(VHR_ERROR_NO_DEVICE, "host-only context: no device work");
+    if (d->output_storage_image < 0 || uint32_t(d->output_storage_image) >= vhr_context::kMaxGlobalResources || !ctx->storage_images[d->output_storage_image].used)
+        return ctx->fail(VHR_ERROR_NOT_FOUND, "standin_forward_raster: output storage image is not allocated");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return launch_forward_raster(ctx, ctx->per_frame[resource_idx], ctx->storage_images[d->output_storage_image], it->second, msaa, d->sample_hits,
+                                 d->fragments);
 }
 
 }  // extern "C"

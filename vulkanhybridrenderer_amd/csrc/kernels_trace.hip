@@ -161,11 +161,18 @@ __device__ __forceinline__ void box_bounds(const DeviceScene &sc, f3 &omin, f3 &
 // tnear > best t only (strict), so equal-t candidates are always examined.
 // ALPHA: rays of the raytraced render path traced with gl_RayFlagsNoOpaqueEXT (raygen_test_alpha.rgen:20,
 // closesthit_test_alpha.rchit:42): every candidate first runs shadow_anyhit.rahit, an ignored candidate does not exist.
+// Reject (the forward raster path's fragment discard, decided per (pixel, triangle)): a candidate for which reject(triangle) -- in
+// wave_queue_walk reject(ray id, triangle) -- is true does not exist either.  NoReject: none, and no code.
 __device__ bool alpha_ignored(const DeviceScene &sc, uint32_t tri_index, float u, float v);
+struct NoReject {
+    static constexpr bool kActive = false;
+    __device__ __forceinline__ bool operator()(uint32_t) const { return false; }
+    __device__ __forceinline__ bool operator()(uint32_t, uint32_t) const { return false; }
+};
 
-template <bool ANY_HIT, bool ALPHA = false, int STRIDE = kTraceBlock>
+template <bool ANY_HIT, bool ALPHA = false, int STRIDE = kTraceBlock, typename Reject = NoReject>
 __device__ __forceinline__ bool traverse(const DeviceScene &sc, f3 o, f3 d, float tmin, float tmax, int *stack, Hit &best,
-                                         uint32_t &overflow) {
+                                         uint32_t &overflow, Reject reject = Reject{}) {
     if (sc.node_count == 0) return false;
     f3 bo, bd;
     box_ray(sc, o, d, bo, bd);                                  // "bvh_frame": the slab tests' ray; the triangle tests below keep (o, d)
@@ -201,6 +208,7 @@ __device__ __forceinline__ bool traverse(const DeviceScene &sc, f3 o, f3 d, floa
                 float t, u, w;
                 if (ray_triangle(o, d, f3{ a.x, a.y, a.z }, f3{ a.w, b.x, b.y }, f3{ b.z, b.w, c.x }, tmin, tmax, t, u, w)) {
                     if (ALPHA && alpha_ignored(sc, first + i, u, w)) continue;
+                    if constexpr (Reject::kActive) { if (reject(first + i)) continue; }
                     if (ANY_HIT) return true;
                     const uint32_t flat = __float_as_uint(c.w);
                     if (!found || t < best.t || (t == best.t && flat < best.flat)) {
@@ -1545,7 +1553,7 @@ __global__ __launch_bounds__(kTraceBlock) void reflection_kernel(const RaygenArg
 // decision vi), early exit of the node loop, LDS stack + scratch spill.  Leaves: every triangle, Moeller-Trumbore against the
 // full [tmin, tmax] interval, closest = min t then smaller flat index; with `any_hit` (wave-uniform) the first accepted
 // triangle ends the ray (gl_RayFlagsTerminateOnFirstHitEXT -- the boolean does not depend on the order).  ALPHA: every
-// candidate first runs shadow_anyhit.rahit (alpha_ignored).  PER_RAY (the batched ray query, ray_query_kernel): every ray brings
+// candidate first runs shadow_anyhit.rahit (alpha_ignored); Reject: then reject(pix, triangle) (forward_raster_queue_kernel).  PER_RAY (the batched ray query, ray_query_kernel): every ray brings
 // its own interval -- fetch(r, pix, origin, direction, tmin, tmax), the ray's tmax seeds the cull -- and commit(pix, triangle, u, v, t)
 // is also told the hit's t; `tmin` / `tmax` are then unused.
 // ---------------------------------------------------------------------------------------------
@@ -1556,12 +1564,13 @@ constexpr uint32_t kNoHit = 0xffffffffu;
 struct WalkCounters { uint32_t nodes = 0, leaves = 0, triangles = 0, wave_trips = 0, refills = 0; };
 
 struct NoFlag { __device__ __forceinline__ void operator()(uint32_t) const {} };
-template <bool SPILL, bool ALPHA, bool DEFER, bool STATS = false, bool PER_RAY = false, typename Fetch, typename Commit, typename Flag = NoFlag>
+template <bool SPILL, bool ALPHA, bool DEFER, bool STATS = false, bool PER_RAY = false, typename Fetch, typename Commit, typename Flag = NoFlag,
+          typename Reject = NoReject>
 __device__ __forceinline__ void wave_queue_walk(const DeviceScene &sc, int *stack, const uint32_t stack_levels, const uint32_t lane,
                                                 const uint32_t total, const uint32_t refill_threshold, const uint32_t early_exit,
                                                 const float tmin, const float tmax, const bool any_hit, uint32_t &overflow,
                                                 const float4 (*cut)[2], const uint32_t cut_n, Fetch fetch, Commit commit, WalkCounters *wc = nullptr,
-                                                Flag flag = Flag{}) {
+                                                Flag flag = Flag{}, Reject reject = Reject{}) {
     f3 ro = f3{ 0, 0, 0 }, rd = f3{ 0, 0, 1 }, rinv = f3{ 0, 0, 0 }, noi = f3{ 0, 0, 0 }, ainv = f3{ 0, 0, 0 };
     float tbest = 0.0f, best_u = 0.0f, best_v = 0.0f;
     uint32_t best_tri = kNoHit, best_flat = 0;
@@ -1649,6 +1658,7 @@ __device__ __forceinline__ void wave_queue_walk(const DeviceScene &sc, int *stac
                         if (!mt_binary64(ro, rd, v0, e1, e2, ray_tmin, ray_tmax, t, uu, ww)) continue;
                     }
                     if (ALPHA && alpha_ignored(sc, first + i, uu, ww)) continue;
+                    if constexpr (Reject::kActive) { if (reject(pix, first + i)) continue; }
                     const uint32_t flat = __float_as_uint(tc.w);
                     if (best_tri == kNoHit || t < tbest || (t == tbest && flat < best_flat)) {
                         tbest = t; best_tri = first + i; best_flat = flat; best_u = uu; best_v = ww;
@@ -3087,6 +3097,391 @@ int launch_rayquery_forward(vhr_context *ctx, const vhr_per_frame_data &pfd, Ima
     if (a.stats && hipMemcpyAsync(&ctx->h_ray_stats, ctx->d_ray_stats, sizeof(RayStats), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
         return ctx->fail(VHR_ERROR_DEVICE, "hipMemcpyAsync(ray stats) failed");
     ctx->raytraced_pixels = uint64_t(a.width) * a.height;      // ray statistics: one primary ray per pixel + one query per primary hit
+    return VHR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Stand-in for the forward raster path's "Forward Pass" (forward_raster_render_path.cpp:52-96, forward_raster_render_path/default.vert
+// + default.frag) with its multisampled attachments (render_graph.cpp:341, :399-423, :810-830, :921-945).  A ray caster, not a rasteriser:
+// S = 8 sample rays per pixel (1 without MSAA), each the G-buffer stand-in's camera ray through the sample's point on the near plane (tmin 1).
+// The visible triangle of a sample is its closest hit (ties: the smaller flat index) among the triangles whose FRAGMENT at this pixel is
+// not discarded -- default.frag's alpha test on the attributes at the pixel centre (no sample shading, no `centroid`: the centre ray
+// against the triangle's plane, extrapolated outside it), rejected inside the walk like the ALPHA walkers' candidates, so the answer is
+// exact at any depth complexity.  Each distinct visible triangle of a pixel is shaded once, at the pixel centre, and its colour goes to
+// every sample it covers; then the resolve.  Everything is in framebuffer rows (the pass contains RENDER_OUTPUT, so its viewport is
+// flipped, pipeline.cpp:174-178): framebuffer row fy is row H - 1 - fy of the G-buffer stand-in's ray parameterisation.
+// ---------------------------------------------------------------------------------------------
+struct ForwardRasterArgs {
+    DeviceScene scene;
+    vhr_per_frame_data pfd;
+    float projview[16];      // camera_proj * camera_view (the depth, as gbuffer_kernel computes it)
+    uint32_t *out;           // RENDER_OUTPUT, resolved: B8G8R8A8_SRGB texels (bytes b g r a), one per pixel
+    float *depth;            // "Depth", D32_SFLOAT, S per pixel
+    uint32_t *msaa;          // "Forward Pass_MSAA": S = 8 texels per pixel (nullptr when S = 1)
+    uint32_t *hits;          // probes, nullptr = not asked for: vhr_ray_hit (6 words) per sample
+    uint8_t *fragments;      // fragments shaded per pixel
+    uint32_t width, height;
+    RayStats *stats;         // nullptr = off; counts stack overflows
+};
+
+// Vulkan's standard 8-sample locations: pixel units from the pixel's top-left corner, y down in framebuffer rows
+__constant__ float c_msaa8_x[8] = { 0.5625f, 0.4375f, 0.8125f, 0.3125f, 0.1875f, 0.0625f, 0.6875f, 0.9375f };
+__constant__ float c_msaa8_y[8] = { 0.3125f, 0.6875f, 0.5625f, 0.1875f, 0.8125f, 0.4375f, 0.9375f, 0.0625f };
+
+// the camera ray of sample s of framebuffer pixel (x, fy): the G-buffer stand-in's ray (rayquery_primary_dir) through the sample's point.
+// The sample's y offset sy runs down the framebuffer, so in the stand-in's (upward) parameterisation it is 1 - sy above row H - 1 - fy.
+// S = 1: the pixel centre -- exactly rayquery_primary_dir(x, H - 1 - fy).
+template <uint32_t S>
+__device__ __forceinline__ f3 forward_sample_dir(const vhr_per_frame_data &pfd, f3 cam, uint32_t x, uint32_t fy, uint32_t s, uint32_t W, uint32_t H) {
+    const float sx = S == 1 ? 0.5f : c_msaa8_x[s], sy = S == 1 ? 0.5f : c_msaa8_y[s];
+    const float u = (float(x) + sx) / float(W), v = (float(H - 1u - fy) + (1.0f - sy)) / float(H);
+    return get_world_space_position(pfd, 1.0f, u, v) - cam;
+}
+
+// the barycentrics of the point where the ray (o, d) meets the triangle's PLANE: Moeller-Trumbore's u and v without its bounds (a pixel
+// centre outside the triangle extrapolates the attributes, as a rasteriser does); a ray parallel to the plane gets (0, 0)
+__device__ __forceinline__ void plane_barycentrics(const DeviceScene &sc, uint32_t tri_index, f3 o, f3 d, float &u, float &v) {
+    const float4 *tp = reinterpret_cast<const float4 *>(sc.tris + tri_index);
+    const float4 ta = tp[0], tb = tp[1], tc = tp[2];
+    const f3 v0 = f3{ ta.x, ta.y, ta.z }, e1 = f3{ ta.w, tb.x, tb.y }, e2 = f3{ tb.z, tb.w, tc.x };
+    const f3 pvec = cross3(d, e2);
+    const float det = dot3(e1, pvec);
+    u = 0.0f; v = 0.0f;
+    if (det == 0.0f) return;
+    const float inv = 1.0f / det;
+    const f3 tvec = o - v0;
+    u = dot3(tvec, pvec) * inv;
+    v = dot3(d, cross3(tvec, e1)) * inv;
+}
+
+// default.frag:19-27: the fragment of triangle tri_index at the pixel whose centre ray is (cam, cdir) is discarded
+__device__ bool forward_discarded(const DeviceScene &sc, uint32_t tri_index, f3 cam, f3 cdir) {
+    const BvhTri &bt = sc.tris[tri_index];
+    const vhr_primitive &prim = sc.primitives[bt.prim];
+    if (prim.material.alpha_mask != 1) return false;
+    if (prim.material.base_color_texture == -1) return prim.material.base_color[3] < prim.material.alpha_cutoff;   // :21-22
+    float u, v;
+    plane_barycentrics(sc, tri_index, cam, cdir, u, v);
+    const TriAttributes at = interpolate(sc, prim, bt.tri, u, v);
+    return sample_texture(sc, prim.material.base_color_texture, at.uvx, at.uvy).w < prim.material.alpha_cutoff;   // :24-27
+}
+
+// a candidate filter for traverse<> / wave_queue_walk from a callable
+template <typename F>
+struct RejectBy {
+    static constexpr bool kActive = true;
+    F f;
+    template <typename... A>
+    __device__ __forceinline__ bool operator()(A... args) const { return f(args...); }
+};
+
+// default.frag:19-53 for the fragment of triangle tri_index at the pixel whose centre ray is (cam, cdir): the texel through the sRGB
+// attachment (B8G8R8A8_SRGB, bytes b g r a, alpha 1).  in_normal is object space and not renormalised (as in the rayquery path); the
+// shadow-map term is overwritten with 1.0 (:47), so in_pos and the shadow map are unused.
+__device__ uint32_t forward_raster_fragment(const DeviceScene &sc, const vhr_per_frame_data &pfd, uint32_t tri_index, f3 cam, f3 cdir) {
+    float u, v;
+    plane_barycentrics(sc, tri_index, cam, cdir, u, v);
+    const BvhTri &bt = sc.tris[tri_index];
+    const vhr_primitive &prim = sc.primitives[bt.prim];
+    const TriAttributes at = interpolate(sc, prim, bt.tri, u, v);
+    f3 albedo;
+    if (prim.material.base_color_texture == -1) {                                        // :21-26
+        albedo = f3{ prim.material.base_color[0], prim.material.base_color[1], prim.material.base_color[2] };
+    } else {
+        const f4 t = sample_texture(sc, prim.material.base_color_texture, at.uvx, at.uvy);
+        albedo = f3{ t.x, t.y, t.z };
+    }
+    const f3 normal = at.normal;
+    f3 N = normal;                                                                       // :31-37
+    if (prim.material.normal_map >= 0) {
+        const f4 tg = interpolate_tangent(sc, prim, bt.tri, u, v);
+        const f3 T = f3{ tg.x, tg.y, tg.z };
+        const f4 tx = sample_texture(sc, prim.material.normal_map, at.uvx, at.uvy);
+        const f3 tsn = normalize3(f3{ tx.x * 2.0f - 1.0f, tx.y * 2.0f - 1.0f, tx.z * 2.0f - 1.0f });
+        const f3 bitangent = cross3(tsn, T) * tg.w;                                      // sic
+        const f3 tangent = normalize3(T - normal * dot3(T, normal));
+        N = (tangent * tsn.x + bitangent * tsn.y) + normal * tsn.z;
+    }
+    const f3 light_dir = -f3{ pfd.directional_light.direction[0], pfd.directional_light.direction[1], pfd.directional_light.direction[2] };
+    const f3 lc = f3{ pfd.directional_light.color[0], pfd.directional_light.color[1], pfd.directional_light.color[2] };
+    const f3 c = albedo * VHR_PI_INVERSE + mul3(albedo * fmaxf(dot3(N, light_dir), 0.0f), lc);     // :49-51 (shadow = 1.0)
+    return uint32_t(srgb8(c.z)) | (uint32_t(srgb8(c.y)) << 8) | (uint32_t(srgb8(c.x)) << 16) | (255u << 24);
+}
+
+// the resolve of an 8-sample texel: per channel the fp32 mean of the decoded samples, summed in sample order (colour from sRGB, alpha as
+// UNORM), encoded as every sRGB store here (srgb8) and alpha as UNORM -- the library's definition (Vulkan leaves an sRGB resolve's
+// arithmetic to the implementation)
+__device__ __forceinline__ void resolve_add(float (&acc)[4], uint32_t texel) {
+    acc[0] += c_srgb_lut[texel & 255u]; acc[1] += c_srgb_lut[(texel >> 8) & 255u]; acc[2] += c_srgb_lut[(texel >> 16) & 255u];
+    acc[3] += float(texel >> 24) / 255.0f;
+}
+__device__ __forceinline__ uint32_t resolve_texel(const float (&acc)[4]) {
+    return uint32_t(srgb8(acc[0] * 0.125f)) | (uint32_t(srgb8(acc[1] * 0.125f)) << 8) | (uint32_t(srgb8(acc[2] * 0.125f)) << 16) |
+           (unorm8(acc[3] * 0.125f) << 24);
+}
+
+// reverse-Z clip.z / clip.w of the sample's hit (gbuffer_kernel's depth)
+__device__ __forceinline__ float forward_depth(const ForwardRasterArgs &a, f3 cam, f3 dir, float t) {
+    const f3 P = cam + dir * t;
+    const f4 clip = mat4_mul(a.projview, f4{ P.x, P.y, P.z, 1.0f });
+    return clip.z / clip.w;
+}
+
+// the sample_hits probe of one sample (vhr_ray_hit; zeros and kNoHit for a miss)
+__device__ __forceinline__ void forward_store_hit(const ForwardRasterArgs &a, const size_t i, const bool hit, const uint32_t tri, const float t,
+                                                  const float u, const float v) {
+    uint32_t *const r = a.hits + i * 6u;
+    r[0] = hit ? __float_as_uint(t) : 0u; r[1] = hit ? __float_as_uint(u) : 0u; r[2] = hit ? __float_as_uint(v) : 0u;
+    r[3] = hit ? a.scene.tris[tri].prim : kNoHit; r[4] = hit ? a.scene.tris[tri].tri : kNoHit; r[5] = 0u;
+}
+
+// Literal form (`variant_standin_forward_raster` 0): one pixel per thread, its S sample rays one after the other through traverse<> with the
+// discard as the candidate filter, then the fragments and the resolve -- the definition of the bits.
+template <uint32_t S>
+__global__ __launch_bounds__(kTraceBlock) void forward_raster_kernel(const ForwardRasterArgs a, const Stamps st) {
+    vhr_stamp(st);
+    __shared__ int s_fr_stack[kTraceStack * kTraceBlock];
+    int *stack = s_fr_stack + threadIdx.x;
+    uint32_t x, fy;
+    pixel_of_thread(x, fy, 0);
+    uint32_t overflow = 0;
+    if (x < a.width && fy < a.height) {
+        const uint32_t W = a.width, H = a.height;
+        const size_t pix = size_t(fy) * W + x;
+        const f3 cam = f3{ a.pfd.camera_view_inverse[12], a.pfd.camera_view_inverse[13], a.pfd.camera_view_inverse[14] };
+        const f3 cdir = forward_sample_dir<1>(a.pfd, cam, x, fy, 0, W, H);
+        const DeviceScene *sc = &a.scene;
+        const auto discarded = [sc, cam, cdir](uint32_t tri) { return forward_discarded(*sc, tri, cam, cdir); };
+        const RejectBy<decltype(discarded)> reject{ discarded };
+        uint32_t tris[S], texels[S];
+#pragma unroll
+        for (uint32_t s = 0; s < S; ++s) {
+            const f3 dir = forward_sample_dir<S>(a.pfd, cam, x, fy, s, W, H);
+            Hit h;
+            h.t = h.u = h.v = 0.0f; h.tri_index = 0; h.flat = 0;
+            const bool hit = traverse<false, false, kTraceBlock>(a.scene, cam, dir, 1.0f, 3.0e38f, stack, h, overflow, reject);
+            tris[s] = hit ? h.tri_index : kNoHit;
+            a.depth[pix * S + s] = hit ? forward_depth(a, cam, dir, h.t) : 0.0f;
+            if (a.hits) forward_store_hit(a, pix * S + s, hit, h.tri_index, h.t, h.u, h.v);
+        }
+        uint32_t nfrag = 0;
+        float acc[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+#pragma unroll
+        for (uint32_t s = 0; s < S; ++s) {
+            uint32_t texel = 0u;                                                         // the clear (0, 0, 0, 0)
+            if (tris[s] != kNoHit) {
+                uint32_t owner = s;                                                      // the first sample of the same triangle
+#pragma unroll
+                for (uint32_t q = 0; q < s; ++q)
+                    if (owner == s && tris[q] == tris[s]) owner = q;
+                if (owner == s) { texels[s] = forward_raster_fragment(a.scene, a.pfd, tris[s], cam, cdir); ++nfrag; }
+                texel = texels[owner];
+            }
+            texels[s] = texel;
+            if (S == 1) a.out[pix] = texel;
+            else { a.msaa[pix * S + s] = texel; resolve_add(acc, texel); }
+        }
+        if (S > 1) a.out[pix] = resolve_texel(acc);
+        if (a.fragments) a.fragments[pix] = uint8_t(nfrag);
+    }
+    if (a.stats) {
+        const unsigned long long ovf = __ballot(overflow != 0);
+        if ((threadIdx.x & 63u) == 0 && ovf) atomicAdd(&a.stats->stack_overflows, (unsigned long long)__popcll(ovf));
+    }
+}
+
+// Work-queue form (default, `variant_standin_forward_raster` 1), rayquery_forward_queue_kernel's schedule: a wave owns a 16x8-pixel tile, makes the
+// tile's shared descent once and drains the tile's S x 128 sample rays as one queue (closest hit, PER_RAY for the depth's t, the discard
+// as the walk's candidate filter).  The cut is built around the rays' common origin, the camera, and culls nothing by direction, so a
+// sample ray that leaves the tile's pixel-centre frustum (up to 1/16 pixel beyond the tile border) finds every subtree it hits.  Then,
+// with the whole wave: the S hits of each pixel are grouped in LDS and de-duplicated into fragments, every (pixel, triangle) fragment is
+// shaded once, and the _MSAA texels, the Depth samples and the resolved texel are stored.  Decision (vi) is decided inline (!DEFER), the
+// same test as traverse<>: the bits are forward_raster_kernel's.
+template <uint32_t S, bool SPILL>
+__global__ __launch_bounds__(kQueueBlock * 2) __attribute__((amdgpu_waves_per_eu(3, 6))) void forward_raster_queue_kernel(
+    const ForwardRasterArgs a, const uint32_t stack_levels, const uint32_t refill_threshold, const uint32_t tiles_x, const uint32_t tiles_total,
+    const uint32_t early_exit, const Stamps st) {
+    vhr_stamp(st);
+    constexpr uint32_t R = S * 128u;                     // sample rays of a tile; slot p * S + s = sample s of pixel slot p
+    extern __shared__ int s_dyn[];                       // per wave: (stack_levels + 3) x 64 ints
+    __shared__ uint32_t s_tri_all[2][R];                 // per slot: the visible triangle (kNoHit: none) -> at a fragment's slot, its texel
+    __shared__ uint32_t s_t_all[2][R];                   // per slot: t -> the owner (the first sample of the same triangle; kNoHit: none)
+    __shared__ float s_cdir_all[2][3][128];              // per pixel slot: the centre ray's direction
+    __shared__ uint16_t s_frag_all[2][R];                // the tile's fragments: the slot of their first sample
+    __shared__ uint8_t s_list_all[2][128];
+    __shared__ float4 s_cut_all[2][kCutMax][2];
+    const uint32_t lane = threadIdx.x & 63u, wave = uint32_t(__builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)));
+    const uint32_t tile = blockIdx.x * 2u + wave;
+    if (tile >= tiles_total) return;                     // waves of a block share nothing and never synchronise
+    uint32_t (&s_tri)[R] = s_tri_all[wave];
+    uint32_t (&s_t)[R] = s_t_all[wave];
+    float (&s_cdir)[3][128] = s_cdir_all[wave];
+    uint16_t (&s_frag)[R] = s_frag_all[wave];
+    uint8_t (&s_list)[128] = s_list_all[wave];
+    int *stack = s_dyn + wave * (stack_levels + 3u) * kQueueBlock + lane;
+    stack[0] = kStackSentinel;
+    const uint32_t W = a.width, H = a.height;
+    const uint32_t tile_y = tile / tiles_x, tile_x = tile - tile_y * tiles_x;
+    const f3 cam = f3{ a.pfd.camera_view_inverse[12], a.pfd.camera_view_inverse[13], a.pfd.camera_view_inverse[14] };
+    auto px_of = [&](uint32_t p) { return tile_x * 16u + (p >> 6) * 8u + (p & 7u); };
+    auto fy_of = [&](uint32_t p) { return tile_y * 8u + ((p & 63u) >> 3); };
+
+    // ---- the tile's pixels: centre directions, compacted list ----
+    unsigned long long in_mask[2];
+    uint32_t npix = 0;
+#pragma unroll
+    for (uint32_t sub = 0; sub < 2; ++sub) {
+        const uint32_t p = sub * 64u + lane, x = px_of(p), fy = fy_of(p);
+        const bool in_range = x < W && fy < H;
+        if (in_range) {
+            const f3 c = forward_sample_dir<1>(a.pfd, cam, x, fy, 0, W, H);
+            s_cdir[0][p] = c.x; s_cdir[1][p] = c.y; s_cdir[2][p] = c.z;
+        }
+        const unsigned long long m = __ballot(in_range);
+        in_mask[sub] = m;
+        if (in_range) s_list[npix + lane_rank(m)] = uint8_t(p);
+        npix += uint32_t(__popcll(m));
+    }
+    wave_lds_sync();
+    const bool traced = a.scene.node_count != 0;
+    uint32_t overflow = 0;
+    const uint32_t total = traced ? npix * S : 0u;
+    // ---- the sample rays: closest hit among the candidates whose fragment is not discarded ----
+    const uint32_t cut_n = total ? build_tile_cut_uniform(a.scene, cam, cam, s_cut_all[wave], lane) : 0u;
+    const DeviceScene *sc = &a.scene;
+    const auto discarded = [sc, cam, &s_cdir](uint32_t slot, uint32_t tri) {
+        const uint32_t p = slot / S;
+        return forward_discarded(*sc, tri, cam, f3{ s_cdir[0][p], s_cdir[1][p], s_cdir[2][p] });
+    };
+    wave_queue_walk<SPILL, false, false, false, true>(
+        a.scene, stack, stack_levels, lane, total, refill_threshold, early_exit, 0.0f, 0.0f, false, overflow, s_cut_all[wave], cut_n,
+        [&](uint32_t r, uint32_t &slot, f3 &ro, f3 &rd, float &tmin, float &tmax) {
+            const uint32_t p = s_list[r / S], s = r % S;
+            slot = p * S + s;
+            ro = cam;
+            rd = forward_sample_dir<S>(a.pfd, cam, px_of(p), fy_of(p), s, W, H);
+            tmin = 1.0f; tmax = 3.0e38f;
+        },
+        [&](uint32_t slot, uint32_t tri, float u, float v, float t) {
+            s_tri[slot] = tri; s_t[slot] = __float_as_uint(t);
+            if (a.hits) {
+                const uint32_t p = slot / S;
+                forward_store_hit(a, (size_t(fy_of(p)) * W + px_of(p)) * S + slot % S, tri != kNoHit, tri, t, u, v);
+            }
+        },
+        nullptr, NoFlag{}, RejectBy<decltype(discarded)>{ discarded });
+    wave_lds_sync();
+    // ---- per pixel: the Depth samples, each sample's owner, the fragment list ----
+    uint32_t nfrag = 0;
+#pragma unroll
+    for (uint32_t sub = 0; sub < 2; ++sub) {
+        const uint32_t p = sub * 64u + lane, x = px_of(p), fy = fy_of(p);
+        const bool inside = (in_mask[sub] >> lane) & 1ull;
+        const size_t pix = size_t(fy) * W + x;
+        uint32_t tris[S];
+#pragma unroll
+        for (uint32_t s = 0; s < S; ++s) {
+            tris[s] = inside && traced ? s_tri[p * S + s] : kNoHit;
+            if (inside) {
+                const bool hit = tris[s] != kNoHit;
+                a.depth[pix * S + s] = hit ? forward_depth(a, cam, forward_sample_dir<S>(a.pfd, cam, x, fy, s, W, H), __uint_as_float(s_t[p * S + s])) : 0.0f;
+                if (!traced && a.hits) forward_store_hit(a, pix * S + s, false, 0u, 0.0f, 0.0f, 0.0f);      // (no walk, no commit: the misses)
+            }
+        }
+#pragma unroll
+        for (uint32_t s = 0; s < S; ++s) {
+            uint32_t owner = tris[s] != kNoHit ? s : kNoHit;
+#pragma unroll
+            for (uint32_t q = 0; q < s; ++q)
+                if (owner == s && tris[q] == tris[s]) owner = q;
+            if (inside) s_t[p * S + s] = owner;
+            const bool first = owner == s;
+            const unsigned long long m = __ballot(first);
+            if (first) s_frag[nfrag + lane_rank(m)] = uint16_t(p * S + s);
+            nfrag += uint32_t(__popcll(m));
+        }
+    }
+    wave_lds_sync();
+    // ---- default.frag once per fragment, whole wave: the texel replaces the triangle at the fragment's slot ----
+    for (uint32_t f = lane; f < nfrag; f += 64u) {
+        const uint32_t slot = s_frag[f], p = slot / S;
+        s_tri[slot] = forward_raster_fragment(a.scene, a.pfd, s_tri[slot], cam, f3{ s_cdir[0][p], s_cdir[1][p], s_cdir[2][p] });
+    }
+    wave_lds_sync();
+    // ---- the stores: _MSAA samples, the resolved texel, the fragment count ----
+#pragma unroll
+    for (uint32_t sub = 0; sub < 2; ++sub) {
+        if (!((in_mask[sub] >> lane) & 1ull)) continue;
+        const uint32_t p = sub * 64u + lane;
+        const size_t pix = size_t(fy_of(p)) * W + px_of(p);
+        uint32_t count = 0;
+        float acc[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+#pragma unroll
+        for (uint32_t s = 0; s < S; ++s) {
+            const uint32_t owner = s_t[p * S + s];
+            const uint32_t texel = owner == kNoHit ? 0u : s_tri[p * S + owner];
+            count += owner == s ? 1u : 0u;
+            if (S == 1) a.out[pix] = texel;
+            else { a.msaa[pix * S + s] = texel; resolve_add(acc, texel); }
+        }
+        if (S > 1) a.out[pix] = resolve_texel(acc);
+        if (a.fragments) a.fragments[pix] = uint8_t(count);
+    }
+    if (a.stats && lane == 0 && overflow) atomicAdd(&a.stats->stack_overflows, 1ull);
+}
+
+int launch_forward_raster(vhr_context *ctx, const vhr_per_frame_data &pfd, Image &out, Image &depth, Image *msaa, void *sample_hits, uint8_t *fragments) {
+    const uint32_t S = depth.samples;
+    if (out.width != depth.width || out.height != depth.height) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "standin_forward_raster: image extents differ");
+    if (out.bpp != 4 || out.samples != 1)
+        return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "standin_forward_raster: the output storage image must have 4-byte texels (B8G8R8A8_SRGB)");
+    if (depth.format != VHR_FORMAT_D32_SFLOAT) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "standin_forward_raster: \"Depth\" must be D32_SFLOAT (forward_raster_render_path.cpp:58)");
+    if (S != 1 && S != kMsaaSamples) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "standin_forward_raster: \"Depth\" must have 1 or 8 samples");
+    if ((S == kMsaaSamples) != (msaa != nullptr)) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "standin_forward_raster: msaa_image goes with an 8-sample \"Depth\"");
+    if (msaa && (msaa->width != depth.width || msaa->height != depth.height || msaa->bpp != 4 || msaa->samples != kMsaaSamples))
+        return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "standin_forward_raster: msaa_image must be B8G8R8A8 with 8 samples at Depth's extent");
+    if (reinterpret_cast<uintptr_t>(sample_hits) % 4u) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "standin_forward_raster: sample_hits must be 4-byte aligned");
+    ForwardRasterArgs a;
+    a.scene = ctx->device_scene();
+    a.pfd = pfd;
+    host_mat4_mul(pfd.camera_proj, pfd.camera_view, a.projview);
+    a.out = static_cast<uint32_t *>(out.ptr);
+    a.depth = static_cast<float *>(depth.ptr);
+    a.msaa = msaa ? static_cast<uint32_t *>(msaa->ptr) : nullptr;
+    a.hits = static_cast<uint32_t *>(sample_hits);
+    a.fragments = fragments;
+    a.width = depth.width;
+    a.height = depth.height;
+    a.stats = ctx->ray_stats_enabled ? ctx->d_ray_stats : nullptr;
+    if (a.width == 0 || a.height == 0) return VHR_OK;
+    if (a.stats && hipMemsetAsync(ctx->d_ray_stats, 0, sizeof(RayStats), ctx->stream) != hipSuccess)
+        return ctx->fail(VHR_ERROR_DEVICE, "hipMemsetAsync(ray stats) failed");
+    ctx->time_begin(kKernelForwardRaster);
+    if (ctx->options[kOptForwardRasterVariant] != 0) {
+        const uint32_t levels = std::max<uint32_t>(1u, std::min<uint32_t>(ctx->bvh_depth + 1u, uint32_t(std::max(1, ctx->options[kOptLdsStackLevels]))));
+        const uint32_t threshold = uint32_t(std::max(1, std::min(64, ctx->options[kOptRefillThreshold])));
+        const uint32_t early_exit = uint32_t(std::max(0, std::min(15, ctx->options[kOptEarlyExit])));
+        const uint32_t tiles_x = (a.width + 15) / 16, tiles_total = tiles_x * ((a.height + 7) / 8);
+        const size_t lds = size_t(levels + 3) * kQueueBlock * sizeof(int) * 2;
+        const dim3 grid((tiles_total + 1) / 2), block(kQueueBlock * 2);
+        const bool spill = levels < ctx->bvh_depth + 1u;
+        if (S == 1) {
+            if (spill) launch(ctx, forward_raster_queue_kernel<1, true>, grid, block, lds, a, levels, threshold, tiles_x, tiles_total, early_exit);
+            else launch(ctx, forward_raster_queue_kernel<1, false>, grid, block, lds, a, levels, threshold, tiles_x, tiles_total, early_exit);
+        } else {
+            if (spill) launch(ctx, forward_raster_queue_kernel<8, true>, grid, block, lds, a, levels, threshold, tiles_x, tiles_total, early_exit);
+            else launch(ctx, forward_raster_queue_kernel<8, false>, grid, block, lds, a, levels, threshold, tiles_x, tiles_total, early_exit);
+        }
+    } else {
+        const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
+        if (S == 1) launch(ctx, forward_raster_kernel<1>, grid, dim3(kTraceBlock), 0, a);
+        else launch(ctx, forward_raster_kernel<8>, grid, dim3(kTraceBlock), 0, a);
+    }
+    ctx->time_end(kKernelForwardRaster);
+    if (hipGetLastError() != hipSuccess) return ctx->fail(VHR_ERROR_DEVICE, "forward raster kernel launch failed");
+    if (a.stats && hipMemcpyAsync(&ctx->h_ray_stats, ctx->d_ray_stats, sizeof(RayStats), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+        return ctx->fail(VHR_ERROR_DEVICE, "hipMemcpyAsync(ray stats) failed");
+    ctx->raytraced_pixels = uint64_t(a.width) * a.height * S;      // ray statistics: S primary rays per pixel, nothing else
     return VHR_OK;
 }
 

@@ -217,16 +217,21 @@ int vhr_graph_add_compute_pass(vhr_context *ctx, const char *name, const vhr_tra
     return VHR_OK;
 }
 
-// ActualizeResource, render_graph.cpp:921-977
-static int actualize(vhr_context *ctx, const vhr_transient_resource &r) {
-    if (!std::strcmp(r.name, kRenderOutput)) return VHR_OK;
-    if (ctx->images.count(r.name)) return VHR_OK;
+// ActualizeResource, render_graph.cpp:921-977.  A multisampled image has kMsaaSamples samples per texel (VK_SAMPLE_COUNT_8_BIT, :341 --
+// GetMaxMultisampleCount on AMD parts); a multisampled RENDER_OUTPUT makes "<pass>_MSAA", the swapchain-format image it resolves from (:929-945).
+static int actualize(vhr_context *ctx, const vhr_transient_resource &r, const std::string &pass_name) {
+    const bool render_output = !std::strcmp(r.name, kRenderOutput);
+    if (render_output && !r.image.multisampled) return VHR_OK;
+    const std::string name = render_output ? pass_name + "_MSAA" : std::string(r.name);
+    if (ctx->images.count(name)) return VHR_OK;
     Image im;
-    im.width = (r.image.width == 0 && r.image.height == 0) ? ctx->width : r.image.width;      // swapchain sized, :960-964
-    im.height = (r.image.width == 0 && r.image.height == 0) ? ctx->height : r.image.height;
-    im.format = r.image.format;
-    im.bpp = format_stride(r.image.format);
-    if (!im.bpp || !im.width || !im.height) return ctx->fail(VHR_ERROR_GRAPH, std::string("transient image '") + r.name + "': unsupported format or empty extent");
+    const bool display_sized = render_output || (r.image.width == 0 && r.image.height == 0);
+    im.width = display_sized ? ctx->width : r.image.width;      // swapchain sized, :960-964
+    im.height = display_sized ? ctx->height : r.image.height;
+    im.format = render_output ? int32_t(VHR_FORMAT_B8G8R8A8_SRGB) : r.image.format;
+    im.bpp = format_stride(im.format);
+    im.samples = r.image.multisampled ? kMsaaSamples : 1u;
+    if (!im.bpp || !im.width || !im.height) return ctx->fail(VHR_ERROR_GRAPH, "transient image '" + name + "': unsupported format or empty extent");
     if (!ctx->host_only) {
         HIP_TRY(ctx, hipMalloc(&im.owned, im.bytes()));
         HIP_TRY(ctx, hipMemsetAsync(im.owned, 0, im.bytes(), ctx->stream));
@@ -240,7 +245,7 @@ static int actualize(vhr_context *ctx, const vhr_transient_resource &r) {
     }
     im.ptr = im.owned;
     im.used = true;
-    ctx->images[r.name] = im;
+    ctx->images[name] = im;
     return VHR_OK;
 }
 
@@ -298,8 +303,8 @@ int vhr_graph_build(vhr_context *ctx) {
     // the reference iterates an unordered_map; registration order is the deterministic choice here
     for (auto &name : ctx->registration_order) {
         PassDescription &p = ctx->pass_descriptions[name];
-        for (auto &r : p.dependencies) { int rc = actualize(ctx, r); if (rc) return rc; }
-        for (auto &r : p.outputs) { writers[r.name].push_back(p.name); int rc = actualize(ctx, r); if (rc) return rc; }
+        for (auto &r : p.dependencies) { int rc = actualize(ctx, r, p.name); if (rc) return rc; }
+        for (auto &r : p.outputs) { writers[r.name].push_back(p.name); int rc = actualize(ctx, r, p.name); if (rc) return rc; }
         if (!p.ev_begin && !ctx->host_only) {
             HIP_TRY(ctx, hipEventCreateWithFlags(&p.ev_begin, hipEventDisableSystemFence));
             HIP_TRY(ctx, hipEventCreateWithFlags(&p.ev_end, hipEventDisableSystemFence));

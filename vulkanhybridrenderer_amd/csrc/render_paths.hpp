@@ -1,7 +1,8 @@
-// The two render paths re-hosted on the vhr:: facade (include/vhr_render_graph.hpp): what an integrator instantiates.
+// The four render paths re-hosted on the vhr:: facade (include/vhr_render_graph.hpp): what an integrator instantiates.
 //   vhr::HybridRenderPath     <- src/render_paths/hybrid_render_path.{h,cpp}      (the hot path: Raytrace Pass + SVGF Denoise Pass)
 //   vhr::RaytracedRenderPath  <- src/render_paths/raytraced_render_path.{h,cpp}   
 //   vhr::RayqueryRenderPath   <- src/render_paths/rayquery_render_path.{h,cpp}    (one raster pass whose fragment stage traces an inline query)
+//   vhr::ForwardRasterRenderPath <- src/render_paths/forward_raster_render_path.{h,cpp}  (depth prepass + forward pass, 8x MSAA by default)
 // Settings the reference changes through ImGui radio buttons (then Rebuild()) are plain public members here.
 #pragma once
 
@@ -72,6 +73,20 @@ public:
 
     // the path's only pass is a raster pass (its fragment stage traces the inline query) and stays with the integrator
     ExternalPassCallback forward_pass;
+};
+
+class ForwardRasterRenderPath : public RenderPath {
+public:
+    using RenderPath::RenderPath;
+    void RegisterPath(DeviceContext &context, RenderGraph &render_graph, ResourceManager &resource_manager) override;
+    void DeregisterPath(DeviceContext &context, RenderGraph &render_graph, ResourceManager &resource_manager) override;
+
+    // both passes are raster passes and stay with the integrator ("Depth Prepass", "Forward Pass")
+    ExternalPassCallback depth_prepass;
+    ExternalPassCallback forward_pass;
+
+    // "Multisample Anti-Aliasing" (forward_raster_render_path.h:14; the UI sets it at forward_raster_render_path.cpp:99-111, then Rebuild())
+    int enable_msaa = 1;
 };
 
 }  // namespace vhr

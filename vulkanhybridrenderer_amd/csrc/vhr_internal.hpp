@@ -97,6 +97,7 @@ constexpr int kDefaultLeafTris = 2;  // r4 (scratch/ab_leaf.py, any-hit launch w
 // tree from the device builder sends the build to the host builder, whose forced median splits keep any scene below the bound).
 constexpr int kMaxBvhDepth = 40;
 constexpr int kTraceStack = 40;      // per-pixel kernels: the whole stack in LDS
+constexpr uint32_t kMsaaSamples = 8;  // multisampled transient images: VK_SAMPLE_COUNT_8_BIT (render_graph.cpp:341)
 constexpr int kSpillStack = 64;      // queue kernels: the part of the stack beyond their LDS levels lives in scratch (a power of two: masked indices)
 
 struct DeviceTexture {
@@ -141,9 +142,10 @@ struct Image {
     void select_slot(uint32_t s) { if (slot_owned[s]) owned = slot_owned[s]; ptr = slot_external[s] ? slot_external[s] : owned; }
     uint32_t width = 0, height = 0;
     int32_t format = 0;
-    uint32_t bpp = 0;
+    uint32_t bpp = 0;             // bytes of one sample
+    uint32_t samples = 1;         // 1, or 8 for a multisampled transient image: pixel-major, a pixel's samples consecutive in standard order
     bool used = false;
-    size_t bytes() const { return size_t(width) * height * bpp; }
+    size_t bytes() const { return size_t(width) * height * bpp * samples; }
 };
 
 struct HostBvh {
@@ -304,8 +306,9 @@ struct RayStats {
     /* instrumentation */                                                                                                               \
     X(kOptPassTimestamps, "pass_timestamps", 1, 0, 3)           /* 0 off, 1 in-kernel stamps, 2 + a stamp in front of external passes, 3 event pairs */ \
     X(kOptKernelTimingStride, "kernel_timing_stride", 1, 1, 1000000)   /* every n-th launch of a timed kind carries an event pair */ \
-    /* added after the table above (its entries keep their indices, and the name sorts after every older one) */                        \
-    X(kOptRayqueryVariant, "variant_rayquery", 1, 0, 1)         /* the rayquery path's forward pass: rayquery_forward_kernel / rayquery_forward_queue_kernel */
+    /* added after the table above (its entries keep their indices, and each name sorts after every older one) */                      \
+    X(kOptRayqueryVariant, "variant_rayquery", 1, 0, 1)         /* the rayquery path's forward pass: rayquery_forward_kernel / rayquery_forward_queue_kernel */ \
+    X(kOptForwardRasterVariant, "variant_standin_forward_raster", 1, 0, 1)   /* the forward raster path's forward pass: forward_raster_kernel / forward_raster_queue_kernel */
 
 enum Option {
 #define X(e, n, d, lo, hi) e,
@@ -322,7 +325,7 @@ inline constexpr OptionInfo kOptionInfo[kOptCount] = {
 
 // optional per-kernel timing with HIP events on the context stream (vhr_set_kernel_timing)
 enum KernelKind { kKernelRaygen = 0, kKernelTemporal = 1, kKernelAtrous = 2, kKernelCopy = 3, kKernelReflection = 4, kKernelSsao = 5, kKernelSsaoBlur = 6, kKernelSsr = 7, kKernelAtrousAsync = 8, kKernelRayQuery = 9,
-                  kKernelRayqueryForward = 10, kKernelKinds = 11 };
+                  kKernelRayqueryForward = 10, kKernelForwardRaster = 11, kKernelKinds = 12 };
 struct KernelTimer {
     std::vector<hipEvent_t> events;     // begin/end pairs
     size_t used = 0;                    // events recorded since the last drain
@@ -539,6 +542,9 @@ int launch_raytraced_composition(vhr_context *ctx, const Image &in, Image &out);
 int launch_standin_gbuffer(vhr_context *ctx, const vhr_per_frame_data &pfd, Image &normals, Image &motion, Image &depth, Image *albedo);
 // the rayquery render path's "Forward Pass" stand-in (vhr_standin_rayquery_forward); hits / positions / shadowed: device memory or nullptr
 int launch_rayquery_forward(vhr_context *ctx, const vhr_per_frame_data &pfd, Image &out, Image &depth, void *hits, float *positions, uint8_t *shadowed);
+// the forward raster path's "Forward Pass" stand-in (vhr_standin_forward_raster); msaa: the "<pass>_MSAA" image when depth has 8 samples, else nullptr;
+// sample_hits / fragments: device memory or nullptr
+int launch_forward_raster(vhr_context *ctx, const vhr_per_frame_data &pfd, Image &out, Image &depth, Image *msaa, void *sample_hits, uint8_t *fragments);
 int launch_composition(vhr_context *ctx, const vhr_per_frame_data &pfd, const vhr_composition_desc &d, const Image &albedo, const Image &normals,
                        const Image &motion, const Image &depth, const Image &shadow_ao, const Image *reflections, const Image *ssao, const Image *shadow_map, Image &out);
 int launch_standin_shadow_map(vhr_context *ctx, const vhr_per_frame_data &pfd, Image &shadow_map);

@@ -33,7 +33,8 @@ EXPORTS = [
     "vhr_upload_storage_image", "vhr_download_storage_image", "vhr_standin_gbuffer", "vhr_standin_gbuffer_with_albedo", "vhr_standin_composition", "vhr_standin_shadow_map", "vhr_set_strip", "vhr_set_tile",
     "vhr_standin_raytraced_composition", "vhr_raytraced_create", "vhr_raytraced_destroy", "vhr_raytraced_build", "vhr_raytraced_rebuild",
     "vhr_raytraced_last_error", "vhr_standin_rayquery_forward", "vhr_rayquery_create", "vhr_rayquery_destroy", "vhr_rayquery_build",
-    "vhr_rayquery_rebuild", "vhr_rayquery_last_error",
+    "vhr_rayquery_rebuild", "vhr_rayquery_last_error", "vhr_standin_forward_raster", "vhr_forward_raster_create", "vhr_forward_raster_destroy",
+    "vhr_forward_raster_build", "vhr_forward_raster_rebuild", "vhr_forward_raster_last_error", "vhr_get_transient_image_samples",
     "vhr_set_ray_statistics", "vhr_get_ray_statistics", "vhr_get_bvh_statistics", "vhr_get_current_stream", "vhr_get_bvh_builder", "vhr_get_bvh_presplit_level", "vhr_get_bvh_frame", "vhr_get_bvh_form_checks", "vhr_get_bvh_fingerprint", "vhr_get_bvh_tree_fingerprint", "vhr_set_kernel_timing",
     "vhr_get_kernel_time", "vhr_set_option", "vhr_get_option", "vhr_option_count", "vhr_option_info", "vhr_get_traversal_statistics", "vhr_source_fingerprint", "vhr_debug_wave_lifetimes", "vhr_get_reflection_statistics", "vhr_get_binary64_statistics", "vhr_debug_ray_triangle", "vhr_get_traversal_cycles", "vhr_get_drain_statistics", "vhr_get_build_times", "vhr_atrous_overlap", "vhr_atrous_output_extent", "vhr_strip_plan_make",
     "vhr_strip_plan_exchanges", "vhr_tile_grid_choose", "vhr_tile_plan_make", "vhr_tile_plan_make_weighted", "vhr_get_tile_cost_map", "vhr_tile_plan_exchanges", "vhr_tile_plan_replan", "vhr_comm_replan", "vhr_comm_get_unique_id", "vhr_comm_use_library", "vhr_comm_library", "vhr_comm_create", "vhr_comm_create_tiled", "vhr_comm_destroy", "vhr_comm_last_error", "vhr_comm_exchange_raytraced",
@@ -89,6 +90,12 @@ class RayqueryForwardDesc(C.Structure):
     """vhr_rayquery_forward_desc (include/vhr_amd.h); the three probes are device pointers (None = not written)."""
     _fields_ = [("output_storage_image", C.c_int32), ("depth_image", C.c_char_p), ("primary_hits", C.c_void_p), ("positions", C.c_void_p),
                 ("shadowed", C.c_void_p)]
+
+
+class ForwardRasterDesc(C.Structure):
+    """vhr_forward_raster_desc (include/vhr_amd.h); the two probes are device pointers (None = not written)."""
+    _fields_ = [("output_storage_image", C.c_int32), ("depth_image", C.c_char_p), ("msaa_image", C.c_char_p), ("sample_hits", C.c_void_p),
+                ("fragments", C.c_void_p)]
 
 
 class StripPlanC(C.Structure):
@@ -243,6 +250,15 @@ def load():
     L.vhr_rayquery_rebuild.argtypes = [vp]
     L.vhr_rayquery_last_error.argtypes = [vp]
     L.vhr_rayquery_last_error.restype = C.c_char_p
+    L.vhr_standin_forward_raster.argtypes = [vp, u32, C.POINTER(ForwardRasterDesc)]
+    L.vhr_forward_raster_create.argtypes = [vp, EXTERNAL_CB, vp, EXTERNAL_CB, vp, i32, C.POINTER(vp)]
+    L.vhr_forward_raster_destroy.argtypes = [vp]
+    L.vhr_forward_raster_destroy.restype = None
+    L.vhr_forward_raster_build.argtypes = [vp]
+    L.vhr_forward_raster_rebuild.argtypes = [vp, i32]
+    L.vhr_forward_raster_last_error.argtypes = [vp]
+    L.vhr_forward_raster_last_error.restype = C.c_char_p
+    L.vhr_get_transient_image_samples.argtypes = [vp, C.c_char_p, C.POINTER(u32)]
     L.vhr_set_strip.argtypes = [vp, u32, u32, u32, u32]
     L.vhr_set_tile.argtypes = [vp, u32, u32, u32, u32, u32, u32, u32]
     L.vhr_set_ray_statistics.argtypes = [vp, i32]
@@ -533,10 +549,18 @@ class Context:
         self.check(self.L.vhr_get_storage_image(self.handle, idx, C.byref(info)), "get_storage_image")
         return info
 
+    def transient_samples(self, name):
+        """vhr_get_transient_image_samples: 1, or 8 for a multisampled transient image."""
+        n = C.c_uint32()
+        self.check(self.L.vhr_get_transient_image_samples(self.handle, name.encode(), C.byref(n)), "get_transient_image_samples")
+        return int(n.value)
+
     @staticmethod
     def _host_array(info):
+        """(H, W[, C]); a multisampled image (bytes_per_pixel covers all its samples) gets a samples axis: (H, W, S[, C])."""
         dt, ch = _NP_FORMATS[info.format]
-        shape = (info.height, info.width, ch) if ch > 1 else (info.height, info.width)
+        samples = info.bytes_per_pixel // (np.dtype(dt).itemsize * ch)
+        shape = (info.height, info.width) + ((samples,) if samples > 1 else ()) + ((ch,) if ch > 1 else ())
         return np.zeros(shape, dt)
 
     def download(self, name_or_idx):
@@ -590,6 +614,14 @@ class Context:
         written), one entry per pixel in Depth's row order: abi.ray_hit_dtype, 4 float32 (in_pos, covered), uint8 (shadowed)."""
         d = RayqueryForwardDesc(output_storage_image, depth.encode(), primary_hits_ptr or None, positions_ptr or None, shadowed_ptr or None)
         self.check(self.L.vhr_standin_rayquery_forward(self.handle, resource_idx, C.byref(d)), "standin_rayquery_forward")
+
+    def standin_forward_raster(self, output_storage_image, resource_idx=0, depth=DEPTH, msaa=None, sample_hits_ptr=0, fragments_ptr=0):
+        """The forward raster path's "Forward Pass" stand-in (default.vert + forward_raster_render_path/default.frag, 8x MSAA when `depth` has 8
+        samples): resolved swapchain texels into the pool storage image, reverse-Z depth per sample into `depth`, the shaded samples into
+        `msaa` (the "Forward Pass_MSAA" image; None when `depth` has 1 sample).  The probes are device pointers (0 = not written):
+        abi.ray_hit_dtype per sample (pixel-major, samples consecutive) and uint8 fragments shaded per pixel."""
+        d = ForwardRasterDesc(output_storage_image, depth.encode(), msaa.encode() if msaa else None, sample_hits_ptr or None, fragments_ptr or None)
+        self.check(self.L.vhr_standin_forward_raster(self.handle, resource_idx, C.byref(d)), "standin_forward_raster")
 
     def set_ray_statistics(self, enable):
         self.check(self.L.vhr_set_ray_statistics(self.handle, int(enable)), "set_ray_statistics")
@@ -714,7 +746,7 @@ class Context:
         return dict(nodes=out[0], triangles=out[1], max_depth=out[2], node_bytes=out[3], triangle_bytes=out[4])
 
     KERNEL_KINDS = {"raygen": 0, "svgf_temporal": 1, "svgf_atrous": 2, "blit": 3, "reflection": 4, "ssao": 5, "ssao_blur": 6, "ssr": 7, "svgf_atrous_async": 8,
-                    "ray_query": 9, "rayquery_forward": 10}
+                    "ray_query": 9, "rayquery_forward": 10, "forward_raster": 11}
 
     @staticmethod
     def _rays_array(rays):
@@ -929,6 +961,39 @@ class RayqueryRenderPath:
     def destroy(self):
         if self.handle:
             self.ctx.L.vhr_rayquery_destroy(self.handle)
+            self.handle = None
+
+
+class ForwardRasterRenderPath:
+    """vhr_forward_raster_*: the C++ re-host of ForwardRasterRenderPath (csrc/forward_raster_render_path.cpp): the external passes "Depth
+    Prepass" (`depth_prepass(ctx)`, e.g. calling Context.standin_shadow_map) and "Forward Pass" (`forward_pass(ctx)`, e.g. calling
+    Context.standin_forward_raster), their bodies the integrator's; `enable_msaa` makes RENDER_OUTPUT and "Depth" 8-sample images."""
+
+    def __init__(self, ctx, depth_prepass=None, forward_pass=None, enable_msaa=1):
+        self.ctx = ctx
+        self.enable_msaa = int(enable_msaa)
+        self._d = EXTERNAL_CB(lambda user, c: ctx._guard(lambda: depth_prepass(ctx))) if depth_prepass else EXTERNAL_CB()
+        self._f = EXTERNAL_CB(lambda user, c: ctx._guard(lambda: forward_pass(ctx))) if forward_pass else EXTERNAL_CB()
+        self.handle = C.c_void_p()
+        ctx.check(ctx.L.vhr_forward_raster_create(ctx.handle, self._d, None, self._f, None, self.enable_msaa, C.byref(self.handle)),
+                  "vhr_forward_raster_create")
+
+    def _check(self, rc, what):
+        if rc < 0:
+            raise VhrError(f"{what}: {self.ctx.L.vhr_forward_raster_last_error(self.handle).decode()}")
+
+    def build(self):
+        self._check(self.ctx.L.vhr_forward_raster_build(self.handle), "ForwardRasterRenderPath::Build")
+
+    def rebuild(self, enable_msaa=None):
+        """The ImGui radio button (forward_raster_render_path.cpp:99-111): set enable_msaa (None = keep it), then Rebuild()."""
+        if enable_msaa is not None:
+            self.enable_msaa = int(enable_msaa)
+        self._check(self.ctx.L.vhr_forward_raster_rebuild(self.handle, self.enable_msaa), "ForwardRasterRenderPath::Rebuild")
+
+    def destroy(self):
+        if self.handle:
+            self.ctx.L.vhr_forward_raster_destroy(self.handle)
             self.handle = None
 
 
