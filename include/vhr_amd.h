@@ -735,6 +735,54 @@ int vhr_get_bvh_fingerprint(vhr_context *ctx, uint64_t *out);
  * algorithm, the same tree; the reference's BLAS / TLAS are the driver's, resource_manager.cpp:593-801). */
 int vhr_get_bvh_tree_fingerprint(vhr_context *ctx, uint64_t *out);
 
+/* ---- Refit: geometry that moves without a rebuild (an extension; what Vulkan calls VK_BUILD_ACCELERATION_STRUCTURE_MODE_UPDATE_KHR) ----
+ * The tree of the last vhr_update_geometry keeps its topology; its triangle records and boxes are recomputed from the current vertices and
+ * primitive transforms.  Per frame: vhr_update_vertices / vhr_update_primitive_transforms (any number), vhr_refit_geometry,
+ * vhr_update_per_frame_ubo, vhr_graph_execute.  Results do not depend on the tree, so a refitted tree publishes exactly the images and ray
+ * query answers a rebuild from the same arrays publishes; what degrades is speed (watch vhr_get_bvh_sah_cost and rebuild when it has grown).
+ *   - While updates are pending (an update call without a vhr_refit_geometry after it) vhr_graph_execute, vhr_ray_query and the vhr_standin_*
+ *     calls fail with VHR_ERROR_GRAPH and a message that names vhr_refit_geometry: a stale tree is never traced silently.
+ *   - Refused, with a message in vhr_last_error: no geometry yet (VHR_ERROR_GRAPH); a tree built with "bvh_presplit" whose references were
+ *     split (vhr_get_bvh_presplit_level >= 0: VHR_ERROR_UNSUPPORTED, rebuild instead); a range outside the buffer, a NULL array with a
+ *     non-zero count, an unknown flag, non-finite host data (VHR_ERROR_INVALID_ARGUMENT).  Argument checks come first, on every context.
+ *   - Topology changes (triangles or primitives added or removed) need vhr_update_geometry.  Frame state is left alone: the SVGF history,
+ *     cost orders, statistics.  Motion vectors stay what the G-buffer pass makes them (camera motion only), so moving geometry ghosts in the
+ *     SVGF history exactly as it would in the reference.
+ *   - A host-only context supports all of it on the host (the same arithmetic): it keeps the arrays and the tree of its last build.
+ *   - vhr_resize keeps the refitted tree; vhr_update_geometry discards pending updates and everything a refit prepared. */
+#define VHR_UPDATE_DEVICE_MEMORY 2u   /* vhr_update_vertices: `vertices` is device memory (the counterpart of VHR_RAY_QUERY_HOST_MEMORY's default) */
+/* Overwrites vertices [first_vertex, first_vertex + vertex_count) of the last vhr_update_geometry (whole records: the stand-in raster stages
+ * read normals, tangents and uvs too).  flags 0: a host array, validated here (finite positions), copied before the call returns.
+ * VHR_UPDATE_DEVICE_MEMORY: a device array, copied on the context's stream; the call does not wait for the copy, and finiteness is then
+ * checked by the refit.  On either route the FIRST update after a build or a refit waits for every stream of the context before it
+ * overwrites anything: frames still in flight read the vertices. */
+int vhr_update_vertices(vhr_context *ctx, uint32_t first_vertex, uint32_t vertex_count, const vhr_vertex *vertices, uint32_t flags);
+/* Replaces vhr_primitive::transform (16 floats each, host memory, finite) of primitives [first_primitive, first_primitive + count) and their
+ * normal matrices: the rigid-motion route (the transform is baked into the world-space triangle records, as at build time). */
+int vhr_update_primitive_transforms(vhr_context *ctx, uint32_t first_primitive, uint32_t count, const float *transforms);
+/* Brings the acceleration structure up to date: every leaf record re-derived in its slot, the boxes bottom-up in the tree's "bvh_frame" (one
+ * launch per level, the top levels in one), padded like a build's, the scene centre and the three derived node forms with their containment
+ * check (the half-precision form falls back to the 48-byte nodes exactly as after a build).  With nothing pending: VHR_OK, nothing launched.
+ * Synchronises like vhr_update_geometry (it reads its counters back); an asynchronous refit is out of scope.  If it meets non-finite
+ * coordinates (device-memory vertices) it fails with VHR_ERROR_INVALID_ARGUMENT, the tree's arrays are NOT valid and updates stay pending
+ * until a refit succeeds or the geometry is rebuilt. */
+int vhr_refit_geometry(vhr_context *ctx);
+/* out[0] = refits since the last build that succeeded, out[1] = triangle records written by the last refit, out[2] = nodes written, out[3] = records not
+ * inside their leaf's box, out[4] = child boxes not inside the slot their parent holds for them (both counted in exact comparisons by a
+ * check pass after the refit; must be 0), out[5] = non-finite coordinates met (must be 0), out[6] = 1 if the walkers are on the
+ * half-precision nodes after it, out[7] = launches of the upward pass (0 on a host-only context). */
+int vhr_get_refit_statistics(vhr_context *ctx, uint64_t out[8]);
+/* The last refit, milliseconds: out[0] = host wall time of vhr_refit_geometry; with bit 12 set in vhr_set_kernel_timing's mask also the
+ * device time of out[1] = the leaf pass, out[2] = the upward pass, out[3] = the node forms and the two check passes (else 0).  The scene
+ * centre's reduction and its 12-word read-back, which lie between out[2] and out[3], are in out[0] only.  (Bit 12 is a mask bit only:
+ * vhr_get_kernel_time has no kind 12.)
+ * vhr_get_build_times keeps its meaning (the last vhr_update_geometry). */
+int vhr_get_refit_times(vhr_context *ctx, double out[4]);
+/* The surface-area cost of the tree -- the sum over the inner nodes of child box area x (1 for an inner child, the triangle count for a
+ * leaf), over the root's area, on the padded boxes the walkers test: out[0] = as built, out[1] = as it is now.  The number to watch when
+ * deciding to rebuild.  One reduction, computed when asked (waits for the context's streams). */
+int vhr_get_bvh_sah_cost(vhr_context *ctx, double out[2]);
+
 /* ---- Batched ray queries on the scene's BVH (rayQueryEXT with an opaque TLAS, cull mask 0xFF) ----
  * Traces `count` caller-made rays against the geometry of the last vhr_update_geometry.  The flags of rayQueryInitializeEXT this
  * stands for are gl_RayFlagsTerminateOnFirstHitEXT (VHR_RAY_QUERY_TERMINATE_ON_FIRST_HIT) or none; the mask is 0xFF.

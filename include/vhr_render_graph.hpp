@@ -160,6 +160,15 @@ public:
     void QueryRays(const vhr_ray *rays, uint32_t count, uint32_t flags, void *results) {
         check(context.handle, vhr_ray_query(context.handle, rays, count, flags, results), "QueryRays");
     }
+    // Extension: geometry that moves without a rebuild (vhr_update_vertices, vhr_update_primitive_transforms, vhr_refit_geometry).  Per frame:
+    // UpdateVertices / UpdatePrimitiveTransforms ... RefitGeometry ... UpdatePerFrameUBO ... RenderGraph::Execute.
+    void UpdateVertices(uint32_t first_vertex, const std::vector<Vertex> &vertices) {
+        check(context.handle, vhr_update_vertices(context.handle, first_vertex, uint32_t(vertices.size()), vertices.data(), 0), "UpdateVertices");
+    }
+    void UpdatePrimitiveTransforms(uint32_t first_primitive, uint32_t count, const float *transforms) {
+        check(context.handle, vhr_update_primitive_transforms(context.handle, first_primitive, count, transforms), "UpdatePrimitiveTransforms");
+    }
+    void RefitGeometry() { check(context.handle, vhr_refit_geometry(context.handle), "RefitGeometry"); }
     DeviceContext &context;
 };
 

@@ -385,6 +385,8 @@ inline int32_t leaf_link(uint32_t first, uint32_t count) { return ~int32_t((firs
 
 }  // namespace
 
+void derive_node_forms(HostBvh &out, unsigned hw);
+
 void build_bvh(const vhr_vertex *vertices, const uint32_t *indices, const vhr_primitive *primitives,
                uint32_t primitive_count, HostBvh &out, int leaf_tris, int threads, int presplit_percent, int frame_mode) {
     const bool k0trace = std::getenv("VHR_K0_TRACE") != nullptr; auto k0t = std::chrono::steady_clock::now();
@@ -591,6 +593,49 @@ void build_bvh(const vhr_vertex *vertices, const uint32_t *indices, const vhr_pr
         (which == 0 ? node.child0 : node.child1) = link;
     };
 
+    const TmpNode &root = b.nodes[0];
+    if (root.left < 0) {                       // whole scene fits one leaf
+        BvhNode node{};
+        set_child(node, 0, root, leaf_link(leaf_pos[0], root.count));
+        for (int a = 0; a < 3; ++a) { node.box1[2 * a] = inf; node.box1[2 * a + 1] = -inf; }
+        node.child1 = node.child0;
+        out.nodes.push_back(node);
+        derive_node_forms(out, hw);
+        return;
+    }
+    // breadth-first numbering of the inner nodes
+    std::vector<int32_t> bfs_index(b.nodes.size(), -1);
+    std::vector<int32_t> bfs_order;
+    std::queue<int32_t> q;
+    q.push(0);
+    while (!q.empty()) {
+        int32_t id = q.front();
+        q.pop();
+        bfs_index[id] = int32_t(bfs_order.size());
+        bfs_order.push_back(id);
+        const TmpNode &t = b.nodes[id];
+        if (b.nodes[t.left].left >= 0) q.push(t.left);
+        if (b.nodes[t.right].left >= 0) q.push(t.right);
+    }
+    out.nodes.resize(bfs_order.size());
+    parallel_for(bfs_order.size(), hw, [&](size_t k0, size_t k1) {
+    for (size_t k = k0; k < k1; ++k) {
+        const TmpNode &t = b.nodes[bfs_order[k]];
+        BvhNode node{};
+        const TmpNode &l = b.nodes[t.left], &r = b.nodes[t.right];
+        set_child(node, 0, l, l.left >= 0 ? bfs_index[t.left] : leaf_link(leaf_pos[t.left], l.count));
+        set_child(node, 1, r, r.left >= 0 ? bfs_index[t.right] : leaf_link(leaf_pos[t.right], r.count));
+        out.nodes[k] = node;
+    }
+    });
+    lap("numbering + (lo, hi) nodes");
+    derive_node_forms(out, hw);
+    lap("derived node forms");
+}
+
+// The scene centre and the derived node forms of out.nodes (centre / half extent, 48-byte, half precision): the last stage of a build and of a refit
+void derive_node_forms(HostBvh &out, unsigned hw) {
+    const float inf = std::numeric_limits<float>::infinity();
     // centre / half-extent twin of every node (BvhNodeCH): c +- h must contain [lo, hi] in exact arithmetic
     auto finalize_ch = [&]() {
         out.nodes_ch.resize(out.nodes.size());
@@ -676,45 +721,7 @@ void build_bvh(const vhr_vertex *vertices, const uint32_t *indices, const vhr_pr
         });
         out.nodes16_valid = overflow == 0 && out.nodes.size() * sizeof(BvhNode16) < (size_t(1) << 31);
     };
-
-    const TmpNode &root = b.nodes[0];
-    if (root.left < 0) {                       // whole scene fits one leaf
-        BvhNode node{};
-        set_child(node, 0, root, leaf_link(leaf_pos[0], root.count));
-        for (int a = 0; a < 3; ++a) { node.box1[2 * a] = inf; node.box1[2 * a + 1] = -inf; }
-        node.child1 = node.child0;
-        out.nodes.push_back(node);
-        finalize16();
-        return;
-    }
-    // breadth-first numbering of the inner nodes
-    std::vector<int32_t> bfs_index(b.nodes.size(), -1);
-    std::vector<int32_t> bfs_order;
-    std::queue<int32_t> q;
-    q.push(0);
-    while (!q.empty()) {
-        int32_t id = q.front();
-        q.pop();
-        bfs_index[id] = int32_t(bfs_order.size());
-        bfs_order.push_back(id);
-        const TmpNode &t = b.nodes[id];
-        if (b.nodes[t.left].left >= 0) q.push(t.left);
-        if (b.nodes[t.right].left >= 0) q.push(t.right);
-    }
-    out.nodes.resize(bfs_order.size());
-    parallel_for(bfs_order.size(), hw, [&](size_t k0, size_t k1) {
-    for (size_t k = k0; k < k1; ++k) {
-        const TmpNode &t = b.nodes[bfs_order[k]];
-        BvhNode node{};
-        const TmpNode &l = b.nodes[t.left], &r = b.nodes[t.right];
-        set_child(node, 0, l, l.left >= 0 ? bfs_index[t.left] : leaf_link(leaf_pos[t.left], l.count));
-        set_child(node, 1, r, r.left >= 0 ? bfs_index[t.right] : leaf_link(leaf_pos[t.right], r.count));
-        out.nodes[k] = node;
-    }
-    });
-    lap("numbering + (lo, hi) nodes");
     finalize16();
-    lap("derived node forms");
 }
 
 // A 64-bit multiplicative hash over the (lo, hi) nodes and the leaf triangles in their final order, eight bytes at a time: the
@@ -816,6 +823,152 @@ bool nodes16_in_range(const HostBvh &bvh) {
             if (ec == 31 || (ec == 0 && n.c[i] != 0) || eh == 31 || eh == 0) return false;
         }
     return true;
+}
+
+// ---- refit: the host twin of csrc/kernels_bvh.hip's k0_refit_* kernels ----
+namespace {
+// the box of one leaf record in the tree's frame: build_bvh's "triangles + boxes" stage
+inline void record_box(const HostBvh &bvh, const BvhTri &t, Box &bx) {
+    bx.reset();
+    if (bvh.frame_on) {
+        bvh_frame::box_in_frame(bvh.frame, t, bx.lo, bx.hi);
+    } else {
+        float p1[3], p2[3];
+        for (int a = 0; a < 3; ++a) { p1[a] = t.v0[a] + t.e1[a]; p2[a] = t.v0[a] + t.e2[a]; }
+        bx.grow(t.v0);
+        bx.grow(p1);
+        bx.grow(p2);
+    }
+}
+inline bool absent_child1(const HostBvh &bvh, const BvhNode &nd) { return bvh.nodes.size() == 1 && nd.child1 == nd.child0; }     // (a one-leaf scene)
+}  // namespace
+
+bool refit_bvh(const vhr_vertex *vertices, const uint32_t *indices, const vhr_primitive *primitives, uint32_t primitive_count, HostBvh &bvh, uint64_t counts[3], int threads) {
+    counts[0] = counts[1] = counts[2] = 0;
+    const size_t n_nodes = bvh.nodes.size(), n_tris = bvh.tris.size();
+    if (!n_nodes || !n_tris) return false;
+    for (size_t k = 0; k < n_nodes; ++k) {                 // the walk below relies on this and on nothing else
+        const int32_t links[2] = { bvh.nodes[k].child0, bvh.nodes[k].child1 };
+        for (int32_t link : links) {
+            if (link >= 0) { if (size_t(link) <= k || size_t(link) >= n_nodes) return false; continue; }
+            const uint32_t v = ~uint32_t(link), first = v >> 2, count = (v & 3u) + 1u;
+            if (size_t(first) + count > n_tris) return false;
+        }
+    }
+    for (const BvhTri &t : bvh.tris)
+        if (t.prim >= primitive_count || t.tri >= primitives[t.prim].index_count / 3) return false;
+    const unsigned hw = host_threads(threads);
+    // 1. the records, each in its slot (build_bvh's first loop: the same expressions in the same order)
+    std::atomic<uint64_t> non_finite{ 0 };
+    parallel_for(n_tris, hw, [&](size_t i0, size_t i1) {
+        uint64_t bad = 0;
+        for (size_t i = i0; i < i1; ++i) {
+            BvhTri &tri = bvh.tris[i];
+            const vhr_primitive &pr = primitives[tri.prim];
+            const float *m = pr.transform;
+            float w[3][3];
+            for (int c = 0; c < 3; ++c) {
+                const float *v = vertices[pr.vertex_offset + indices[pr.index_offset + 3 * tri.tri + c]].pos;
+                w[c][0] = ((m[0] * v[0] + m[4] * v[1]) + m[8] * v[2]) + m[12];
+                w[c][1] = ((m[1] * v[0] + m[5] * v[1]) + m[9] * v[2]) + m[13];
+                w[c][2] = ((m[2] * v[0] + m[6] * v[1]) + m[10] * v[2]) + m[14];
+            }
+            for (int a = 0; a < 3; ++a) {
+                tri.v0[a] = w[0][a];
+                tri.e1[a] = w[1][a] - w[0][a];
+                tri.e2[a] = w[2][a] - w[0][a];
+                bad += uint64_t(!std::isfinite(tri.v0[a])) + uint64_t(!std::isfinite(tri.e1[a])) + uint64_t(!std::isfinite(tri.e2[a]));
+            }
+        }
+        non_finite += bad;
+    });
+    counts[2] = non_finite;
+    // 2. + 3. the boxes bottom-up (children have larger indices than their parents), padded into the parents' slots
+    std::vector<Box> self(n_nodes);
+    auto child_box = [&](int32_t link) {
+        if (link >= 0) return self[size_t(link)];
+        const uint32_t v = ~uint32_t(link), first = v >> 2, count = (v & 3u) + 1u;
+        Box bx, one;
+        bx.reset();
+        for (uint32_t i = 0; i < count; ++i) { record_box(bvh, bvh.tris[first + i], one); bx.grow(one); }
+        return bx;
+    };
+    auto put = [](float *dst, const Box &bx) {
+        float lo[3], hi[3];
+        padded(bx, lo, hi);
+        for (int a = 0; a < 3; ++a) { dst[2 * a] = lo[a]; dst[2 * a + 1] = hi[a]; }
+    };
+    for (size_t k = n_nodes; k-- > 0;) {
+        BvhNode &nd = bvh.nodes[k];
+        const Box b0 = child_box(nd.child0);
+        put(nd.box0, b0);
+        self[k] = b0;
+        if (!absent_child1(bvh, nd)) {
+            const Box b1 = child_box(nd.child1);
+            put(nd.box1, b1);
+            self[k].grow(b1);
+        }
+    }
+    // 4. the scene centre and the derived forms
+    derive_node_forms(bvh, hw);
+    // the check pass: exact comparisons of what the walkers will meet
+    std::atomic<uint64_t> records_outside{ 0 }, children_outside{ 0 };
+    parallel_for(n_nodes, hw, [&](size_t k0, size_t k1) {
+        uint64_t bad_records = 0, bad_children = 0;
+        auto inside = [](const float *lo, const float *hi, const float *slot) {
+            for (int a = 0; a < 3; ++a) if (!(lo[a] >= slot[2 * a] && hi[a] <= slot[2 * a + 1])) return false;
+            return true;
+        };
+        for (size_t k = k0; k < k1; ++k) {
+            const BvhNode &nd = bvh.nodes[k];
+            for (int which = 0; which < 2; ++which) {
+                if (which == 1 && absent_child1(bvh, nd)) continue;
+                const float *slot = which == 0 ? nd.box0 : nd.box1;
+                const int32_t link = which == 0 ? nd.child0 : nd.child1;
+                if (link >= 0) {
+                    const BvhNode &c = bvh.nodes[size_t(link)];
+                    for (int w = 0; w < 2; ++w) {
+                        const float *cb = w == 0 ? c.box0 : c.box1;
+                        const float lo[3] = { cb[0], cb[2], cb[4] }, hi[3] = { cb[1], cb[3], cb[5] };
+                        if (!inside(lo, hi, slot)) ++bad_children;
+                    }
+                } else {
+                    const uint32_t v = ~uint32_t(link), first = v >> 2, count = (v & 3u) + 1u;
+                    for (uint32_t i = 0; i < count; ++i) {
+                        Box one;
+                        record_box(bvh, bvh.tris[first + i], one);
+                        if (!inside(one.lo, one.hi, slot)) ++bad_records;
+                    }
+                }
+            }
+        }
+        records_outside += bad_records;
+        children_outside += bad_children;
+    });
+    counts[0] = records_outside;
+    counts[1] = children_outside;
+    return true;
+}
+
+double bvh_sah_cost(const HostBvh &bvh) {
+    if (bvh.nodes.empty()) return 0.0;
+    auto half_area = [](const float *b) {
+        const double dx = double(b[1]) - double(b[0]), dy = double(b[3]) - double(b[2]), dz = double(b[5]) - double(b[4]);
+        return dx * dy + dy * dz + dz * dx;
+    };
+    auto weight = [](int32_t link) { return link >= 0 ? 1.0 : double((~uint32_t(link) & 3u) + 1u); };
+    double sum = 0.0;
+    for (const BvhNode &nd : bvh.nodes) {
+        sum += half_area(nd.box0) * weight(nd.child0);
+        if (!absent_child1(bvh, nd)) sum += half_area(nd.box1) * weight(nd.child1);
+    }
+    const BvhNode &r = bvh.nodes[0];
+    float root[6];
+    for (int i = 0; i < 6; ++i) root[i] = r.box0[i];
+    if (!absent_child1(bvh, r))
+        for (int a = 0; a < 3; ++a) { root[2 * a] = std::min(root[2 * a], r.box1[2 * a]); root[2 * a + 1] = std::max(root[2 * a + 1], r.box1[2 * a + 1]); }
+    const double area = half_area(root);
+    return area > 0.0 ? sum / area : 0.0;
 }
 
 }  // namespace vhr

@@ -249,6 +249,7 @@ int vhr_create(const vhr_create_info *info, vhr_context **out) {
 }
 
 static void free_scene(vhr_context *ctx) {
+    vhr::free_refit_plan(ctx);
     hipFree(ctx->d_vertices); hipFree(ctx->d_indices); hipFree(ctx->d_primitives); hipFree(ctx->d_normal_matrices);
     hipFree(ctx->d_nodes); hipFree(ctx->d_nodes16); hipFree(ctx->d_nodes_ch); hipFree(ctx->d_nodes48); hipFree(ctx->d_tris);
     ctx->d_vertices = nullptr; ctx->d_indices = nullptr; ctx->d_primitives = nullptr; ctx->d_normal_matrices = nullptr;
@@ -370,6 +371,9 @@ int vhr_update_geometry(vhr_context *ctx, const vhr_vertex *vertices, uint32_t v
             return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "UpdateGeometry: vertex " + std::to_string(v) + " has a non-finite position");
     if (total_triangles >= (1ull << 29))            // a leaf link packs (first triangle << 2 | count - 1) into 31 bits
         return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "UpdateGeometry: 2^29 triangles or more");
+    // a build replaces whatever updates were pending and everything a refit had prepared
+    ctx->refit_pending = ctx->sah_cost_built_valid = false;
+    for (uint64_t &w : ctx->refit_stats) w = 0;
     if (!ctx->host_only) {
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         { const int src_ = ctx->sync_streams(); if (src_ != VHR_OK) return src_; }
@@ -450,6 +454,14 @@ int vhr_update_geometry(vhr_context *ctx, const vhr_vertex *vertices, uint32_t v
         ctx->tri_count = uint32_t(bvh.tris.size());
         ctx->bvh_depth = bvh.max_depth;
         ctx->geometry_upload_ms = 0.0;
+        // ... and keeps the arrays and the tree: the refit's host twin works on them (vhr_update_vertices, vhr_refit_geometry)
+        ctx->h_vertices.assign(vertices, vertices + vertex_count);
+        ctx->h_indices.assign(indices, indices + index_count);
+        ctx->h_primitives.assign(primitives, primitives + primitive_count);
+        ctx->h_bvh = std::move(bvh);
+        ctx->vertex_count = vertex_count;
+        ctx->index_count = index_count;
+        ctx->primitive_count = primitive_count;
         return VHR_OK;
     }
     if (!device_built) {
@@ -494,6 +506,148 @@ int vhr_get_build_times(vhr_context *ctx, double out[2]) {
     if (!ctx || !out) return VHR_ERROR_INVALID_ARGUMENT;
     out[0] = ctx->bvh_build_ms;
     out[1] = ctx->geometry_upload_ms;
+    return VHR_OK;
+}
+
+// ---- refit: vertices or primitive transforms change, the tree keeps its topology (VK_BUILD_ACCELERATION_STRUCTURE_MODE_UPDATE_KHR) ----
+static int refit_state_checks(vhr_context *ctx, const char *who) {
+    const bool has = ctx->host_only ? !ctx->h_bvh.nodes.empty() : (ctx->d_nodes != nullptr && ctx->node_count != 0);
+    if (!has) return ctx->fail(VHR_ERROR_GRAPH, std::string(who) + ": no geometry yet (vhr_update_geometry first)");
+    if (ctx->bvh_presplit_level >= 0)
+        return ctx->fail(VHR_ERROR_UNSUPPORTED, std::string(who) + ": the tree was built with \"bvh_presplit\" (its references are clipped boxes, which a refit cannot keep): rebuild with vhr_update_geometry");
+    return VHR_OK;
+}
+// what is about to be overwritten may still be read by frames in flight: the first update after a build or refit waits for them
+static int begin_update(vhr_context *ctx) {
+    if (ctx->host_only) return VHR_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!ctx->refit_pending) { const int src_ = ctx->sync_streams(); if (src_ != VHR_OK) return src_; }
+    return VHR_OK;
+}
+
+int vhr_update_vertices(vhr_context *ctx, uint32_t first_vertex, uint32_t vertex_count, const vhr_vertex *vertices, uint32_t flags) {
+    if (!ctx) return VHR_ERROR_INVALID_ARGUMENT;
+    if (flags & ~uint32_t(VHR_UPDATE_DEVICE_MEMORY)) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_update_vertices: unknown flag bits " + std::to_string(flags));
+    if (vertex_count > 0 && !vertices) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_update_vertices: vertices must not be NULL when vertex_count > 0");
+    if ((flags & VHR_UPDATE_DEVICE_MEMORY) && ctx->host_only) return ctx->fail(VHR_ERROR_NO_DEVICE, "vhr_update_vertices: host-only context: no device memory");
+    { const int rc = refit_state_checks(ctx, "vhr_update_vertices"); if (rc != VHR_OK) return rc; }
+    if (uint64_t(first_vertex) + vertex_count > ctx->vertex_count)
+        return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_update_vertices: range [" + std::to_string(first_vertex) + ", +" + std::to_string(vertex_count) + ") exceeds the vertex buffer (" + std::to_string(ctx->vertex_count) + ")");
+    if (vertex_count == 0) return VHR_OK;
+    if (!(flags & VHR_UPDATE_DEVICE_MEMORY))
+        for (uint32_t v = 0; v < vertex_count; ++v)
+            if (!std::isfinite(vertices[v].pos[0]) || !std::isfinite(vertices[v].pos[1]) || !std::isfinite(vertices[v].pos[2]))
+                return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_update_vertices: vertex " + std::to_string(first_vertex + v) + " has a non-finite position");
+    { const int rc = begin_update(ctx); if (rc != VHR_OK) return rc; }
+    if (ctx->host_only) {
+        std::memcpy(ctx->h_vertices.data() + first_vertex, vertices, sizeof(vhr_vertex) * vertex_count);
+    } else if (flags & VHR_UPDATE_DEVICE_MEMORY) {
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_vertices + first_vertex, vertices, sizeof(vhr_vertex) * vertex_count, hipMemcpyDeviceToDevice, ctx->stream));
+    } else {
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_vertices + first_vertex, vertices, sizeof(vhr_vertex) * vertex_count, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));          // the caller's array is free when the call returns
+    }
+    ctx->refit_pending = true;
+    return VHR_OK;
+}
+
+int vhr_update_primitive_transforms(vhr_context *ctx, uint32_t first_primitive, uint32_t count, const float *transforms) {
+    if (!ctx) return VHR_ERROR_INVALID_ARGUMENT;
+    if (count > 0 && !transforms) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_update_primitive_transforms: transforms must not be NULL when count > 0");
+    { const int rc = refit_state_checks(ctx, "vhr_update_primitive_transforms"); if (rc != VHR_OK) return rc; }
+    if (uint64_t(first_primitive) + count > ctx->primitive_count)
+        return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_update_primitive_transforms: range [" + std::to_string(first_primitive) + ", +" + std::to_string(count) + ") exceeds the primitives (" + std::to_string(ctx->primitive_count) + ")");
+    if (count == 0) return VHR_OK;
+    for (uint64_t k = 0; k < uint64_t(count) * 16u; ++k)
+        if (!std::isfinite(transforms[k])) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_update_primitive_transforms: primitive " + std::to_string(first_primitive + k / 16u) + " has a non-finite transform");
+    { const int rc = begin_update(ctx); if (rc != VHR_OK) return rc; }
+    if (ctx->host_only) {
+        for (uint32_t p = 0; p < count; ++p) std::memcpy(ctx->h_primitives[first_primitive + p].transform, transforms + size_t(p) * 16, sizeof(float) * 16);
+    } else {
+        // the primitives' other fields stay what the device holds: the range is fetched, patched and written back, with its normal matrices
+        std::vector<vhr_primitive> prims(count);
+        std::vector<float> nm(size_t(count) * 9);
+        HIP_TRY(ctx, hipMemcpyAsync(prims.data(), ctx->d_primitives + first_primitive, sizeof(vhr_primitive) * count, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        for (uint32_t p = 0; p < count; ++p) {
+            std::memcpy(prims[p].transform, transforms + size_t(p) * 16, sizeof(float) * 16);
+            normal_matrix3(prims[p].transform, &nm[size_t(p) * 9]);
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_primitives + first_primitive, prims.data(), sizeof(vhr_primitive) * count, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_normal_matrices + size_t(first_primitive) * 9, nm.data(), sizeof(float) * nm.size(), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    ctx->refit_pending = true;
+    return VHR_OK;
+}
+
+int vhr_refit_geometry(vhr_context *ctx) {
+    if (!ctx) return VHR_ERROR_INVALID_ARGUMENT;
+    { const int rc = refit_state_checks(ctx, "vhr_refit_geometry"); if (rc != VHR_OK) return rc; }
+    if (ctx->recording || ctx->cur_pass) return ctx->fail(VHR_ERROR_GRAPH, "vhr_refit_geometry: called from inside a pass");
+    if (!ctx->refit_pending) return VHR_OK;              // nothing changed: nothing is launched
+    const auto t0 = std::chrono::steady_clock::now();
+    if (ctx->host_only) {
+        if (!ctx->sah_cost_built_valid) { ctx->sah_cost_built = bvh_sah_cost(ctx->h_bvh); ctx->sah_cost_built_valid = true; }
+        uint64_t counts[3];
+        if (!refit_bvh(ctx->h_vertices.data(), ctx->h_indices.data(), ctx->h_primitives.data(), ctx->primitive_count, ctx->h_bvh, counts, ctx->bvh_build_threads))
+            return ctx->fail(VHR_ERROR_GRAPH, "vhr_refit_geometry: the tree's nodes are not numbered parents before children");
+        check_node_forms(ctx->h_bvh, ctx->bvh_form_checks, ctx->bvh_build_threads);
+        ctx->nodes16_valid = ctx->h_bvh.nodes16_valid && ctx->bvh_form_checks[3] == 0;
+        ctx->bvh_fingerprint = bvh_fingerprint(ctx->h_bvh);
+        ctx->bvh_tree_fingerprint = bvh_tree_fingerprint(ctx->h_bvh);
+        ctx->bvh_fingerprint_valid = true;
+        ctx->refit_stats[kRefitRecords] = ctx->h_bvh.tris.size();
+        ctx->refit_stats[kRefitNodes] = ctx->h_bvh.nodes.size();
+        ctx->refit_stats[kRefitRecordsOutside] = counts[0];
+        ctx->refit_stats[kRefitChildrenOutside] = counts[1];
+        ctx->refit_stats[kRefitNonFinite] = counts[2];
+        ctx->refit_stats[kRefitHalfNodes] = ctx->nodes16_valid ? 1u : 0u;
+        for (int i = 1; i < 4; ++i) ctx->refit_times_ms[i] = 0.0;
+    } else {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        { const int src_ = ctx->sync_streams(); if (src_ != VHR_OK) return src_; }
+        const int rc = device_refit_bvh(ctx);
+        if (rc != VHR_OK) return rc;
+        ctx->bvh_fingerprint_valid = false;              // the hashes describe the refitted arrays: taken again when somebody asks
+    }
+    ctx->refit_times_ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (ctx->refit_stats[kRefitNonFinite])               // (updates stay pending: nothing may trace these arrays; not counted as a refit)
+        return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_refit_geometry: " + std::to_string(ctx->refit_stats[kRefitNonFinite]) +
+                         " non-finite coordinates in the triangle records: the tree's arrays are not valid; update the vertices / transforms and refit again, or rebuild");
+    ++ctx->refit_stats[kRefitCount];
+    ctx->refit_pending = false;
+    return VHR_OK;
+}
+
+int vhr_get_refit_statistics(vhr_context *ctx, uint64_t out[8]) {
+    if (!ctx || !out) return VHR_ERROR_INVALID_ARGUMENT;
+    for (int i = 0; i < kRefitStatWords; ++i) out[i] = ctx->refit_stats[i];
+    return VHR_OK;
+}
+
+int vhr_get_refit_times(vhr_context *ctx, double out[4]) {
+    if (!ctx || !out) return VHR_ERROR_INVALID_ARGUMENT;
+    for (int i = 0; i < 4; ++i) out[i] = ctx->refit_times_ms[i];
+    return VHR_OK;
+}
+
+int vhr_get_bvh_sah_cost(vhr_context *ctx, double out[2]) {
+    if (!ctx || !out) return VHR_ERROR_INVALID_ARGUMENT;
+    if (ctx->host_only ? ctx->h_bvh.nodes.empty() : (!ctx->d_nodes || !ctx->node_count))
+        return ctx->fail(VHR_ERROR_GRAPH, "vhr_get_bvh_sah_cost: no geometry yet (vhr_update_geometry first)");
+    double now = 0.0;
+    if (ctx->host_only) {
+        now = bvh_sah_cost(ctx->h_bvh);
+    } else {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        { const int src_ = ctx->sync_streams(); if (src_ != VHR_OK) return src_; }
+        const int rc = device_bvh_sah_cost(ctx, &now);
+        if (rc != VHR_OK) return rc;
+    }
+    if (!ctx->sah_cost_built_valid) { ctx->sah_cost_built = now; ctx->sah_cost_built_valid = true; }      // no refit has touched the tree yet
+    out[0] = ctx->sah_cost_built;
+    out[1] = now;
     return VHR_OK;
 }
 
@@ -756,6 +910,7 @@ int vhr_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, uint32_
     if (count > 0 && reinterpret_cast<uintptr_t>(rays) % 16u) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_ray_query: rays must be 16-byte aligned");
     if (count > 0 && reinterpret_cast<uintptr_t>(results) % 4u) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_ray_query: results must be 4-byte aligned");
     if (ctx->host_only) return ctx->fail(VHR_ERROR_NO_DEVICE, "vhr_ray_query: host-only context: no device work");
+    { const int stale = ctx->refuse_if_stale("vhr_ray_query"); if (stale != VHR_OK) return stale; }
     if (count == 0) return VHR_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const bool any_hit = (flags & VHR_RAY_QUERY_TERMINATE_ON_FIRST_HIT) != 0;
@@ -1024,6 +1179,7 @@ int vhr_standin_composition(vhr_context *ctx, uint32_t resource_idx, const vhr_c
     if ((d->reflection_mode == 0 || d->reflection_mode == 1) && !re) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "composition: reflection_mode 0 / 1 needs a reflections image");
     if (d->output_storage_image < 0 || uint32_t(d->output_storage_image) >= vhr_context::kMaxGlobalResources || !ctx->storage_images[d->output_storage_image].used)
         return ctx->fail(VHR_ERROR_NOT_FOUND, "composition: output storage image is not allocated");
+    { const int stale = ctx->refuse_if_stale("vhr_standin_composition"); if (stale != VHR_OK) return stale; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return launch_composition(ctx, ctx->per_frame[resource_idx], *d, *al, *no, *mo, *de, *sa, re, ss, sm, ctx->storage_images[d->output_storage_image]);
 }
@@ -1033,6 +1189,7 @@ int vhr_standin_shadow_map(vhr_context *ctx, uint32_t resource_idx, const char *
     if (ctx->host_only) return ctx->fail(VHR_ERROR_NO_DEVICE, "host-only context: no device work");
     auto it = ctx->images.find(shadow_map_image);
     if (it == ctx->images.end()) return ctx->fail(VHR_ERROR_NOT_FOUND, "standin_shadow_map: unknown transient image");
+    { const int stale = ctx->refuse_if_stale("vhr_standin_shadow_map"); if (stale != VHR_OK) return stale; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return launch_standin_shadow_map(ctx, ctx->per_frame[resource_idx], it->second);
 }
@@ -1045,6 +1202,7 @@ int vhr_standin_raytraced_composition(vhr_context *ctx, const char *raytraced_ou
     if (it->second.format != VHR_FORMAT_B8G8R8A8_UNORM) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "raytraced composition: RaytracedOutput must be B8G8R8A8_UNORM (raytraced_render_path.cpp:15)");
     if (output_storage_image < 0 || uint32_t(output_storage_image) >= vhr_context::kMaxGlobalResources || !ctx->storage_images[output_storage_image].used)
         return ctx->fail(VHR_ERROR_NOT_FOUND, "raytraced composition: output storage image is not allocated");
+    { const int stale = ctx->refuse_if_stale("vhr_standin_raytraced_composition"); if (stale != VHR_OK) return stale; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return launch_raytraced_composition(ctx, it->second, ctx->storage_images[output_storage_image]);
 }
@@ -1064,6 +1222,7 @@ int vhr_standin_gbuffer_with_albedo(vhr_context *ctx, uint32_t resource_idx, con
         if (al == ctx->images.end()) return ctx->fail(VHR_ERROR_NOT_FOUND, "standin_gbuffer: unknown albedo image");
         albedo = &al->second;
     }
+    { const int stale = ctx->refuse_if_stale("vhr_standin_gbuffer"); if (stale != VHR_OK) return stale; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return launch_standin_gbuffer(ctx, ctx->per_frame[resource_idx], n->second, m->second, d->second, albedo);
 }
@@ -1076,6 +1235,7 @@ int vhr_standin_rayquery_forward(vhr_context *ctx, uint32_t resource_idx, const 
     if (it == ctx->images.end()) return ctx->fail(VHR_ERROR_NOT_FOUND, "standin_rayquery_forward: unknown transient image");
     if (d->output_storage_image < 0 || uint32_t(d->output_storage_image) >= vhr_context::kMaxGlobalResources || !ctx->storage_images[d->output_storage_image].used)
         return ctx->fail(VHR_ERROR_NOT_FOUND, "standin_rayquery_forward: output storage image is not allocated");
+    { const int stale = ctx->refuse_if_stale("vhr_standin_rayquery_forward"); if (stale != VHR_OK) return stale; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return launch_rayquery_forward(ctx, ctx->per_frame[resource_idx], ctx->storage_images[d->output_storage_image], it->second, d->primary_hits,
                                    d->positions, d->shadowed);
@@ -1098,6 +1258,7 @@ int vhr_standin_forward_raster(vhr_context *ctx, uint32_t resource_idx, const vh
     if (ctx->host_only) return ctx->fail(VHR_ERROR_NO_DEVICE, "host-only context: no device work");
     if (d->output_storage_image < 0 || uint32_t(d->output_storage_image) >= vhr_context::kMaxGlobalResources || !ctx->storage_images[d->output_storage_image].used)
         return ctx->fail(VHR_ERROR_NOT_FOUND, "standin_forward_raster: output storage image is not allocated");
+    { const int stale = ctx->refuse_if_stale("vhr_standin_forward_raster"); if (stale != VHR_OK) return stale; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return launch_forward_raster(ctx, ctx->per_frame[resource_idx], ctx->storage_images[d->output_storage_image], it->second, msaa, d->sample_hits,
                                  d->fragments);

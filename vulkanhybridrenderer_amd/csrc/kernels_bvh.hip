@@ -843,6 +843,168 @@ __global__ __launch_bounds__(256) void k0_iota_kernel(uint32_t *__restrict__ ord
     if (k < n) { order[k] = k; pos_node[k] = 0u; }
 }
 
+// ---- refit (vhr_refit_geometry): the topology stays, the records and the boxes follow the vertices and the transforms ----
+struct RefitFrame { float r[9]; uint32_t on; };
+struct RefitCounters { unsigned long long non_finite, records_outside, children_outside, pad; };
+// the leaf pass: record k re-derived in its slot from (prim, tri) with k0_triangles_kernel's arithmetic; three 16-byte loads' worth of gather
+// per corner, three 16-byte stores
+__global__ __launch_bounds__(256) void k0_refit_records_kernel(const vhr_vertex *__restrict__ vertices, const uint32_t *__restrict__ indices,
+                                                               const vhr_primitive *__restrict__ primitives, uint32_t primitive_count, uint32_t n,
+                                                               BvhTri *__restrict__ tris, RefitCounters *__restrict__ counters) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    uint32_t bad = 0;
+    if (k < n) {
+        float4 *slot = reinterpret_cast<float4 *>(tris + k);
+        const float4 q2 = slot[2];                                   // (e2.z, prim, tri, flat)
+        const uint32_t p = __float_as_uint(q2.y), local = __float_as_uint(q2.z);
+        if (p < primitive_count) {
+            const vhr_primitive &pr = primitives[p];
+            const float *m = pr.transform;
+            float w[3][3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float *v = vertices[pr.vertex_offset + indices[pr.index_offset + 3u * local + uint32_t(c)]].pos;
+                w[c][0] = ((m[0] * v[0] + m[4] * v[1]) + m[8] * v[2]) + m[12];
+                w[c][1] = ((m[1] * v[0] + m[5] * v[1]) + m[9] * v[2]) + m[13];
+                w[c][2] = ((m[2] * v[0] + m[6] * v[1]) + m[10] * v[2]) + m[14];
+            }
+            float e1[3], e2[3];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                e1[a] = w[1][a] - w[0][a];
+                e2[a] = w[2][a] - w[0][a];
+                bad += uint32_t(!isfinite(w[0][a])) + uint32_t(!isfinite(e1[a])) + uint32_t(!isfinite(e2[a]));
+            }
+            slot[0] = float4{ w[0][0], w[0][1], w[0][2], e1[0] };
+            slot[1] = float4{ e1[1], e1[2], e2[0], e2[1] };
+            slot[2] = float4{ e2[2], q2.y, q2.z, q2.w };
+        } else {
+            bad = 1u;                                                // (not a record of this scene: cannot happen, never dereferenced)
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) bad += uint32_t(__shfl_xor(int(bad), off));
+    if ((threadIdx.x & 63u) == 0u && bad) atomicAdd(&counters->non_finite, (unsigned long long)bad);
+}
+// the unpadded box of a record in the tree's frame: k0_triangles_kernel's (world axes) or k0_frame_boxes_kernel's
+__device__ __forceinline__ Box6 refit_record_box(const BvhTri &t, const RefitFrame &f) {
+    Box6 b;
+    if (f.on) {
+        bvh_frame::box_in_frame(f.r, t, b.lo, b.hi);
+    } else {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float p1 = t.v0[a] + t.e1[a], p2 = t.v0[a] + t.e2[a];
+            b.lo[a] = fminf(fminf(t.v0[a], p1), p2);
+            b.hi[a] = fmaxf(fmaxf(t.v0[a], p1), p2);
+        }
+    }
+    return b;
+}
+__device__ __forceinline__ void refit_grow(Box6 &b, const Box6 &o) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) { b.lo[a] = fminf(b.lo[a], o.lo[a]); b.hi[a] = fmaxf(b.hi[a], o.hi[a]); }
+}
+__device__ __forceinline__ Box6 refit_child_box(int32_t link, const BvhTri *tris, const Box6 *self_box, const RefitFrame &f) {
+    if (link >= 0) return self_box[link];
+    const uint32_t v = ~uint32_t(link), first = v >> 2, count = (v & 3u) + 1u;
+    Box6 b = refit_record_box(tris[first], f);
+    for (uint32_t i = 1; i < count; ++i) refit_grow(b, refit_record_box(tris[first + i], f));
+    return b;
+}
+// one node: its children's unpadded boxes (a leaf's from its records, an inner child's from the level below), padded into its two slots with
+// set_child; its own unpadded box for its parent.  Links are read, never written.
+__device__ __forceinline__ void refit_node(uint32_t k, BvhNode *nodes, const BvhTri *tris, Box6 *self_box, const RefitFrame &f, bool single) {
+    BvhNode nd = nodes[k];
+    Box6 mine = refit_child_box(nd.child0, tris, self_box, f);
+    set_child(nd, 0, mine, nd.child0);
+    if (!(single && nd.child1 == nd.child0)) {                     // (a one-leaf scene: child 1 is absent, its inverted box stays)
+        const Box6 other = refit_child_box(nd.child1, tris, self_box, f);
+        set_child(nd, 1, other, nd.child1);
+        refit_grow(mine, other);
+    }
+    nodes[k] = nd;
+    self_box[k] = mine;
+}
+// the upward pass, design (a): one launch per level, deepest first; nodes [begin, end) are one level (the plan checks that the tree is
+// numbered level by level, as both builders number it)
+__global__ __launch_bounds__(256) void k0_refit_level_kernel(BvhNode *__restrict__ nodes, const BvhTri *__restrict__ tris, Box6 *__restrict__ self_box,
+                                                             uint32_t begin, uint32_t end, RefitFrame f, uint32_t single) {
+    const uint32_t i = begin + blockIdx.x * 256u + threadIdx.x;
+    if (i >= end) return;
+    refit_node(i, nodes, tris, self_box, f, single != 0u);
+}
+// ... and the levels at the top, which have fewer nodes than a launch is worth: one workgroup, a barrier between levels
+constexpr int kRefitTopLevels = 16;
+constexpr uint32_t kRefitTopNodes = 1024;          // a level of at most this many nodes belongs to the top
+struct RefitTop { uint32_t begin[kRefitTopLevels + 1]; int levels; };
+__global__ __launch_bounds__(256) void k0_refit_top_kernel(BvhNode *__restrict__ nodes, const BvhTri *__restrict__ tris, Box6 *__restrict__ self_box,
+                                                           RefitTop top, RefitFrame f, uint32_t single) {
+    for (int level = top.levels - 1; level >= 0; --level) {
+        for (uint32_t i = top.begin[level] + threadIdx.x; i < top.begin[level + 1]; i += 256u) refit_node(i, nodes, tris, self_box, f, single != 0u);
+        __threadfence_block();
+        __syncthreads();
+    }
+}
+// the check pass: what the walkers will meet, in exact comparisons -- every record's corners inside its leaf's slot, every inner child's two
+// slots inside the slot its parent holds for it
+__global__ __launch_bounds__(256) void k0_refit_check_kernel(const BvhNode *__restrict__ nodes, const BvhTri *__restrict__ tris, uint32_t count, RefitFrame f,
+                                                             RefitCounters *__restrict__ counters) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    uint32_t bad_records = 0, bad_children = 0;
+    if (k < count) {
+        const BvhNode nd = nodes[k];
+        auto inside = [](const float *lo, const float *hi, const float *slot) {
+            bool in = true;
+            for (int a = 0; a < 3; ++a) in = in && lo[a] >= slot[2 * a] && hi[a] <= slot[2 * a + 1];
+            return in;
+        };
+        for (int which = 0; which < 2; ++which) {
+            if (which == 1 && count == 1u && nd.child1 == nd.child0) continue;
+            const float *slot = which == 0 ? nd.box0 : nd.box1;
+            const int32_t link = which == 0 ? nd.child0 : nd.child1;
+            if (link >= 0) {
+                const BvhNode c = nodes[link];
+                for (int w = 0; w < 2; ++w) {
+                    const float *cb = w == 0 ? c.box0 : c.box1;
+                    const float lo[3] = { cb[0], cb[2], cb[4] }, hi[3] = { cb[1], cb[3], cb[5] };
+                    if (!inside(lo, hi, slot)) ++bad_children;
+                }
+            } else {
+                const uint32_t v = ~uint32_t(link), first = v >> 2, n = (v & 3u) + 1u;
+                for (uint32_t i = 0; i < n; ++i) {
+                    const Box6 b = refit_record_box(tris[first + i], f);
+                    if (!inside(b.lo, b.hi, slot)) ++bad_records;
+                }
+            }
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) { bad_records += uint32_t(__shfl_xor(int(bad_records), off)); bad_children += uint32_t(__shfl_xor(int(bad_children), off)); }
+    if ((threadIdx.x & 63u) == 0u) {
+        if (bad_records) atomicAdd(&counters->records_outside, (unsigned long long)bad_records);
+        if (bad_children) atomicAdd(&counters->children_outside, (unsigned long long)bad_children);
+    }
+}
+// vhr_get_bvh_sah_cost: per workgroup the sum over its nodes of child half area x (1 | triangles of the leaf), reduced in a fixed order (the
+// host adds the workgroups' sums in index order: the same tree gives the same bits)
+__global__ __launch_bounds__(256) void k0_sah_cost_kernel(const BvhNode *__restrict__ nodes, uint32_t count, double *__restrict__ partial) {
+    __shared__ double s_wave[4];
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    double sum = 0.0;
+    if (k < count) {
+        const BvhNode nd = nodes[k];
+        auto term = [](const float *b, int32_t link) {
+            const double dx = double(b[1]) - double(b[0]), dy = double(b[3]) - double(b[2]), dz = double(b[5]) - double(b[4]);
+            return (dx * dy + dy * dz + dz * dx) * (link >= 0 ? 1.0 : double((~uint32_t(link) & 3u) + 1u));
+        };
+        sum = term(nd.box0, nd.child0);
+        if (!(count == 1u && nd.child1 == nd.child0)) sum += term(nd.box1, nd.child1);
+    }
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+    if ((threadIdx.x & 63u) == 0u) s_wave[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0u) partial[blockIdx.x] = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
+}
+
 struct Scratch {            // device allocations of one build, freed together
     std::vector<void *> ptrs;
     template <typename T>
@@ -1127,6 +1289,189 @@ int device_build_bvh(vhr_context *ctx, const std::vector<uint32_t> &tri_prefix, 
     ctx->bvh_depth = h_depth;
     if (std::getenv("VHR_K0_TRACE")) std::fprintf(stderr, "K0 device: %u triangles, %u inner nodes, depth %u\n", n, n_inner, h_depth);
     if (h_depth > uint32_t(std::min(kMaxBvhDepth, ctx->bvh_device_max_depth))) return VHR_ERROR_OUT_OF_SLOTS;
+    return VHR_OK;
+}
+
+// ---- refit on the device ----
+// What a refit needs beyond what a build leaves behind, made at the first refit from the nodes' links (fetched once) and kept until the next
+// build: the level ranges (checked, not assumed: the refit relies on parents-before-children only), the per-node unpadded boxes, counters.
+struct RefitPlan {
+    std::vector<uint32_t> level_begin;        // nodes [level_begin[l], level_begin[l + 1]) are level l
+    Box6 *d_self_box = nullptr;
+    RefitCounters *d_counters = nullptr;      // + the 5 words of k0_check_forms_kernel + 12 of the scene bounds behind it
+    double *d_partial = nullptr;              // k0_sah_cost_kernel's sums, one per workgroup
+    hipEvent_t ev[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
+    uint32_t launches = 0;                    // of the upward pass (reporting)
+};
+void free_refit_plan(vhr_context *ctx) {
+    RefitPlan *p = ctx->refit_plan;
+    if (!p) return;
+    hipFree(p->d_self_box); hipFree(p->d_counters); hipFree(p->d_partial);
+    for (hipEvent_t e : p->ev) if (e) hipEventDestroy(e);
+    delete p;
+    ctx->refit_plan = nullptr;
+}
+
+#define REFIT_TRY(expr)                                                                                    \
+    do {                                                                                                    \
+        hipError_t e_ = (expr);                                                                             \
+        if (e_ != hipSuccess) return ctx->fail(VHR_ERROR_DEVICE, std::string("refit: ") + #expr + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+static int make_refit_plan(vhr_context *ctx) {
+    if (ctx->refit_plan) return VHR_OK;
+    const uint32_t n = ctx->node_count;
+    std::vector<BvhNode> nodes(n);
+    REFIT_TRY(hipMemcpy(nodes.data(), ctx->d_nodes, sizeof(BvhNode) * n, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> depth(n, 0u);
+    uint32_t levels = 1;
+    for (uint32_t k = 0; k < n; ++k) {
+        const int32_t links[2] = { nodes[k].child0, nodes[k].child1 };
+        for (int32_t link : links) {
+            if (link >= 0) {
+                if (uint32_t(link) <= k || uint32_t(link) >= n) return ctx->fail(VHR_ERROR_GRAPH, "vhr_refit_geometry: the tree's nodes are not numbered parents before children");
+                depth[uint32_t(link)] = depth[k] + 1u;
+                levels = std::max(levels, depth[k] + 2u);
+            } else {
+                const uint32_t v = ~uint32_t(link), first = v >> 2, count = (v & 3u) + 1u;
+                if (uint64_t(first) + count > ctx->tri_count) return ctx->fail(VHR_ERROR_GRAPH, "vhr_refit_geometry: a leaf lies outside the triangle records");
+            }
+        }
+        // one launch per level needs every level to be a contiguous range of nodes: both builders number breadth first, anything else is refused
+        if (k && depth[k] < depth[k - 1]) return ctx->fail(VHR_ERROR_GRAPH, "vhr_refit_geometry: the tree's nodes are not numbered level by level");
+    }
+    // (the context gets the plan only when it is complete: a failed allocation leaves nothing half-made behind)
+    RefitPlan *p = new RefitPlan();
+    p->level_begin.assign(levels + 1u, 0u);
+    for (uint32_t k = 0; k < n; ++k) ++p->level_begin[depth[k] + 1u];
+    for (uint32_t l = 0; l < levels; ++l) p->level_begin[l + 1u] += p->level_begin[l];
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&p->d_self_box), sizeof(Box6) * n);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&p->d_counters), sizeof(RefitCounters) + 5 * sizeof(unsigned long long) + 12 * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&p->d_partial), sizeof(double) * ((n + 255u) / 256u));
+    if (e != hipSuccess) {
+        hipFree(p->d_self_box); hipFree(p->d_counters); hipFree(p->d_partial);
+        delete p;
+        return ctx->fail(VHR_ERROR_DEVICE, std::string("refit: allocating the plan: ") + hipGetErrorString(e));
+    }
+    ctx->refit_plan = p;
+    return VHR_OK;
+}
+
+int device_bvh_sah_cost(vhr_context *ctx, double *cost) {
+    *cost = 0.0;
+    const uint32_t n = ctx->node_count, blocks = (n + 255u) / 256u;
+    if (!n || !ctx->d_nodes) return VHR_OK;
+    double *d_partial = ctx->refit_plan ? ctx->refit_plan->d_partial : nullptr;
+    Scratch tmp;
+    if (!d_partial) REFIT_TRY(tmp.alloc(&d_partial, blocks));
+    hipLaunchKernelGGL(k0_sah_cost_kernel, dim3(blocks), dim3(256), 0, ctx->stream, ctx->d_nodes, n, d_partial);
+    std::vector<double> partial(blocks);
+    BvhNode root;
+    REFIT_TRY(hipMemcpyAsync(partial.data(), d_partial, sizeof(double) * blocks, hipMemcpyDeviceToHost, ctx->stream));
+    REFIT_TRY(hipMemcpyAsync(&root, ctx->d_nodes, sizeof(root), hipMemcpyDeviceToHost, ctx->stream));
+    REFIT_TRY(hipStreamSynchronize(ctx->stream));
+    REFIT_TRY(hipGetLastError());
+    double sum = 0.0;
+    for (double v : partial) sum += v;
+    float box[6];
+    for (int i = 0; i < 6; ++i) box[i] = root.box0[i];
+    if (!(n == 1u && root.child1 == root.child0))
+        for (int a = 0; a < 3; ++a) { box[2 * a] = std::min(box[2 * a], root.box1[2 * a]); box[2 * a + 1] = std::max(box[2 * a + 1], root.box1[2 * a + 1]); }
+    const double dx = double(box[1]) - double(box[0]), dy = double(box[3]) - double(box[2]), dz = double(box[5]) - double(box[4]);
+    const double area = dx * dy + dy * dz + dz * dx;
+    *cost = area > 0.0 ? sum / area : 0.0;
+    return VHR_OK;
+}
+
+// The refit proper; the caller (vhr_refit_geometry) has checked that there is a tree, that it is not a presplit one, and has waited for the
+// context's streams.  Fills ctx->refit_stats / refit_times_ms[1..3] and the context's tree state (centre, form checks, nodes16_valid).
+int device_refit_bvh(vhr_context *ctx) {
+    hipStream_t s = ctx->stream;
+    if (!ctx->sah_cost_built_valid) {           // the cost of the tree as built, before its boxes move
+        const int rc = device_bvh_sah_cost(ctx, &ctx->sah_cost_built);
+        if (rc != VHR_OK) return rc;
+        ctx->sah_cost_built_valid = true;
+    }
+    { const int rc = make_refit_plan(ctx); if (rc != VHR_OK) return rc; }
+    RefitPlan *p = ctx->refit_plan;
+    const uint32_t n_nodes = ctx->node_count, n_tris = ctx->tri_count;
+    const dim3 block(256);
+    auto grid = [](uint32_t count) { return dim3((count + 255u) / 256u); };
+    const bool timed = (ctx->kernel_timing_mask & (1u << kKernelRefit)) != 0;
+    if (timed)
+        for (hipEvent_t &e : p->ev) if (!e) REFIT_TRY(hipEventCreate(&e));
+    RefitFrame f;
+    for (int i = 0; i < 9; ++i) f.r[i] = ctx->bvh_frame[i];
+    f.on = ctx->bvh_frame_on ? 1u : 0u;
+    const uint32_t single = n_nodes == 1u ? 1u : 0u;
+    unsigned long long *d_checks = reinterpret_cast<unsigned long long *>(p->d_counters + 1);
+    uint32_t *d_bounds = reinterpret_cast<uint32_t *>(d_checks + 5);
+    struct { RefitCounters c; unsigned long long checks[5]; uint32_t bounds[12]; } init{}, got{};
+    for (int a = 0; a < 3; ++a) { init.bounds[a] = init.bounds[6 + a] = 0xffffffffu; }
+    REFIT_TRY(hipMemcpyAsync(p->d_counters, &init, sizeof(init), hipMemcpyHostToDevice, s));
+    if (timed) REFIT_TRY(hipEventRecord(p->ev[0], s));
+    // 1. the records
+    hipLaunchKernelGGL(k0_refit_records_kernel, grid(n_tris), block, 0, s, ctx->d_vertices, ctx->d_indices, ctx->d_primitives, ctx->primitive_count, n_tris, ctx->d_tris,
+                       p->d_counters);
+    if (timed) REFIT_TRY(hipEventRecord(p->ev[1], s));
+    // 2. + 3. the boxes, level by level from the deepest; the levels at the top in one launch
+    const uint32_t levels = uint32_t(p->level_begin.size()) - 1u;
+    uint32_t top_levels = 0;
+    while (top_levels < levels && top_levels < uint32_t(kRefitTopLevels) && p->level_begin[top_levels + 1u] - p->level_begin[top_levels] <= kRefitTopNodes) ++top_levels;
+    p->launches = 0;
+    for (uint32_t l = levels; l-- > top_levels;) {
+        const uint32_t begin = p->level_begin[l], end = p->level_begin[l + 1u];
+        hipLaunchKernelGGL(k0_refit_level_kernel, grid(end - begin), block, 0, s, ctx->d_nodes, ctx->d_tris, p->d_self_box, begin, end, f, single);
+        ++p->launches;
+    }
+    if (top_levels) {
+        RefitTop top{};
+        top.levels = int(top_levels);
+        for (uint32_t l = 0; l <= top_levels; ++l) top.begin[l] = p->level_begin[l];
+        hipLaunchKernelGGL(k0_refit_top_kernel, dim3(1), block, 0, s, ctx->d_nodes, ctx->d_tris, p->d_self_box, top, f, single);
+        ++p->launches;
+    }
+    if (timed) REFIT_TRY(hipEventRecord(p->ev[2], s));
+    // 4. the scene centre (one reduction and a read-back of 12 words: k0_forms_kernel takes the centre by value, like the build), the derived
+    // forms, their containment check and the refit's own
+    hipLaunchKernelGGL(k0_node_bounds_kernel, grid(n_nodes), block, 0, s, ctx->d_nodes, n_nodes, d_bounds + 6);
+    uint32_t h_bounds[12];
+    REFIT_TRY(hipMemcpyAsync(h_bounds, d_bounds, sizeof(h_bounds), hipMemcpyDeviceToHost, s));
+    REFIT_TRY(hipStreamSynchronize(s));
+    REFIT_TRY(hipGetLastError());
+    for (int a = 0; a < 3; ++a) {
+        const float lo = unordered(h_bounds[6 + a]), hi = unordered(h_bounds[9 + a]);
+        ctx->bvh_centre[a] = lo <= hi ? 0.5f * (lo + hi) : 0.0f;
+    }
+    if (timed) REFIT_TRY(hipEventRecord(p->ev[3], s));
+    hipLaunchKernelGGL(k0_forms_kernel, grid(n_nodes), block, 0, s, ctx->d_nodes, n_nodes, ctx->bvh_centre[0], ctx->bvh_centre[1], ctx->bvh_centre[2], ctx->d_nodes_ch,
+                       ctx->d_nodes48, ctx->d_nodes16);
+    hipLaunchKernelGGL(k0_check_forms_kernel, grid(n_nodes), block, 0, s, ctx->d_nodes, ctx->d_nodes_ch, ctx->d_nodes48, ctx->d_nodes16, n_nodes,
+                       ctx->bvh_centre[0], ctx->bvh_centre[1], ctx->bvh_centre[2], d_checks);
+    hipLaunchKernelGGL(k0_refit_check_kernel, grid(n_nodes), block, 0, s, ctx->d_nodes, ctx->d_tris, n_nodes, f, p->d_counters);
+    if (timed) REFIT_TRY(hipEventRecord(p->ev[4], s));
+    REFIT_TRY(hipMemcpyAsync(&got, p->d_counters, sizeof(got), hipMemcpyDeviceToHost, s));
+    REFIT_TRY(hipStreamSynchronize(s));
+    REFIT_TRY(hipGetLastError());
+    const bool in_range = got.checks[4] == 0ull && size_t(n_nodes) * sizeof(BvhNode16) < (size_t(1) << 31);
+    for (int i = 0; i < 3; ++i) ctx->bvh_form_checks[i] = got.checks[i];
+    ctx->bvh_form_checks[3] = in_range ? got.checks[3] : 0ull;
+    ctx->nodes16_valid = in_range && got.checks[3] == 0ull;      // else the walkers stay on the 48-byte nodes, as after a build
+    ctx->refit_stats[kRefitRecords] = n_tris;
+    ctx->refit_stats[kRefitNodes] = n_nodes;
+    ctx->refit_stats[kRefitRecordsOutside] = got.c.records_outside;
+    ctx->refit_stats[kRefitChildrenOutside] = got.c.children_outside;
+    ctx->refit_stats[kRefitNonFinite] = got.c.non_finite;
+    ctx->refit_stats[kRefitHalfNodes] = ctx->nodes16_valid ? 1u : 0u;
+    ctx->refit_stats[7] = p->launches;
+    for (int i = 1; i < 4; ++i) ctx->refit_times_ms[i] = 0.0;
+    if (timed) {                               // kernels only: the scene bounds' reduction and its read-back lie between ev[2] and ev[3]
+        const int pairs[3][2] = { { 0, 1 }, { 1, 2 }, { 3, 4 } };
+        for (int i = 0; i < 3; ++i) {
+            float ms = 0.0f;
+            if (hipEventElapsedTime(&ms, p->ev[pairs[i][0]], p->ev[pairs[i][1]]) == hipSuccess) ctx->refit_times_ms[i + 1] = ms;
+        }
+    }
     return VHR_OK;
 }
 

@@ -340,6 +340,7 @@ int vhr_graph_execute(vhr_context *ctx, uint32_t resource_idx, uint32_t image_id
     if (ctx->host_only) return ctx->fail(VHR_ERROR_NO_DEVICE, "host-only context: Execute needs a device");
     if (!ctx->built) return ctx->fail(VHR_ERROR_GRAPH, "Execute before Build");
     if (resource_idx >= 3) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "resource_idx >= MAX_FRAMES_IN_FLIGHT");
+    { const int stale = ctx->refuse_if_stale("vhr_graph_execute"); if (stale != VHR_OK) return stale; }      // a stale tree is never traced silently
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ctx->error.clear();
     ctx->last_resource_idx = resource_idx;

@@ -173,6 +173,21 @@ void build_bvh(const vhr_vertex *vertices, const uint32_t *indices, const vhr_pr
 // context's node and triangle arrays; VHR_ERROR_OUT_OF_SLOTS = fall back to the host builder (tree deeper than the walkers' stacks)
 int device_build_bvh(vhr_context *ctx, const std::vector<uint32_t> &tri_prefix, uint32_t total_tris, int leaf_tris, int presplit_percent, int frame_mode);
 
+// ---- refit (vhr_refit_geometry): the tree's topology stays, its records and boxes follow the vertices and transforms ----
+// vhr_get_refit_statistics' words
+enum RefitStat { kRefitCount = 0, kRefitRecords = 1, kRefitNodes = 2, kRefitRecordsOutside = 3, kRefitChildrenOutside = 4, kRefitNonFinite = 5, kRefitHalfNodes = 6, kRefitStatWords = 8 };
+// the host twin (csrc/bvh_build.cpp; the arithmetic of build_bvh): every leaf record re-derived in its slot, the boxes bottom-up in the tree's
+// frame, the derived forms; counts[0] = records outside their leaf's box, [1] = child boxes outside their parent's slot, [2] = non-finite
+// coordinates met.  false: `bvh` is not a tree a refit can walk (links out of range, children numbered before their parents)
+bool refit_bvh(const vhr_vertex *vertices, const uint32_t *indices, const vhr_primitive *primitives, uint32_t primitive_count, HostBvh &bvh, uint64_t counts[3], int threads = 0);
+// surface-area cost of the tree: sum over the inner nodes of child area x (1 for an inner child, the triangle count for a leaf), over the root's area
+double bvh_sah_cost(const HostBvh &bvh);
+// the device side (csrc/kernels_bvh.hip): what a refit needs beyond what a build leaves behind, prepared at the first refit
+struct RefitPlan;
+void free_refit_plan(vhr_context *ctx);
+int device_refit_bvh(vhr_context *ctx);
+int device_bvh_sah_cost(vhr_context *ctx, double *cost);
+
 enum class PassKind { Graphics, Raytracing, Compute };
 
 // Pass time stamps written by the kernels themselves (r3c).  vkCmdWriteTimestamp pairs (render_graph.cpp:167-182) used to ride on the
@@ -325,7 +340,8 @@ inline constexpr OptionInfo kOptionInfo[kOptCount] = {
 
 // optional per-kernel timing with HIP events on the context stream (vhr_set_kernel_timing)
 enum KernelKind { kKernelRaygen = 0, kKernelTemporal = 1, kKernelAtrous = 2, kKernelCopy = 3, kKernelReflection = 4, kKernelSsao = 5, kKernelSsaoBlur = 6, kKernelSsr = 7, kKernelAtrousAsync = 8, kKernelRayQuery = 9,
-                  kKernelRayqueryForward = 10, kKernelForwardRaster = 11, kKernelKinds = 12 };
+                  kKernelRayqueryForward = 10, kKernelForwardRaster = 11, kKernelKinds = 12,
+                  kKernelRefit = 12 };      // a mask bit only (vhr_set_kernel_timing): vhr_refit_geometry times its three stages itself (vhr_get_refit_times)
 struct KernelTimer {
     std::vector<hipEvent_t> events;     // begin/end pairs
     size_t used = 0;                    // events recorded since the last drain
@@ -396,6 +412,22 @@ struct vhr_context {
     int bvh_device_max_depth = vhr::kMaxBvhDepth; // "bvh_device_max_depth": the device builder hands a deeper tree to the host builder (kMaxBvhDepth = the walkers' stacks; tests lower it)
     double bvh_build_ms = 0.0, geometry_upload_ms = 0.0;      // K0: host build / device upload of the last vhr_update_geometry
     double bvh_check_ms = 0.0;                                 // the self-checks of the node forms + the fingerprint (not part of K0)
+    // refit (vhr_update_vertices / vhr_update_primitive_transforms / vhr_refit_geometry)
+    bool refit_pending = false;                  // vertices or transforms changed since the last build or refit: the tree is stale, nothing may trace it
+    uint64_t refit_stats[vhr::kRefitStatWords] = {};
+    double refit_times_ms[4] = { 0, 0, 0, 0 };   // the last refit: host wall time; device time of the leaf pass, the upward pass, forms + checks (kernel timing bit kKernelRefit)
+    double sah_cost_built = 0.0;                 // vhr_get_bvh_sah_cost out[0]: taken before the first refit touches the tree, or when first asked
+    bool sah_cost_built_valid = false;
+    vhr::RefitPlan *refit_plan = nullptr;        // device contexts: level ranges, per-node boxes, counters (kept until the next build or vhr_destroy)
+    // a host-only context keeps the arrays and the tree of its last build: the refit's host twin works on them
+    std::vector<vhr_vertex> h_vertices;
+    std::vector<uint32_t> h_indices;
+    std::vector<vhr_primitive> h_primitives;
+    vhr::HostBvh h_bvh;
+    int refuse_if_stale(const char *who) {
+        if (!refit_pending) return VHR_OK;
+        return fail(VHR_ERROR_GRAPH, std::string(who) + ": geometry updates are pending (vhr_update_vertices / vhr_update_primitive_transforms): call vhr_refit_geometry first");
+    }
 
     // RenderGraph state
     std::map<std::string, vhr::PassDescription> pass_descriptions;

@@ -40,6 +40,8 @@ EXPORTS = [
     "vhr_strip_plan_exchanges", "vhr_tile_grid_choose", "vhr_tile_plan_make", "vhr_tile_plan_make_weighted", "vhr_get_tile_cost_map", "vhr_tile_plan_exchanges", "vhr_tile_plan_replan", "vhr_comm_replan", "vhr_comm_get_unique_id", "vhr_comm_use_library", "vhr_comm_library", "vhr_comm_create", "vhr_comm_create_tiled", "vhr_comm_destroy", "vhr_comm_last_error", "vhr_comm_exchange_raytraced",
     "vhr_comm_start_frame_exchanges", "vhr_comm_finish_frame_exchanges",
     "vhr_calibration_stream_read", "vhr_ray_query", "vhr_get_ray_query_statistics", "vhr_ray_query_struct_layout",
+    "vhr_update_vertices", "vhr_update_primitive_transforms", "vhr_refit_geometry", "vhr_get_refit_statistics", "vhr_get_refit_times",
+    "vhr_get_bvh_sah_cost",
 ]
 
 
@@ -312,6 +314,12 @@ def load():
     L.vhr_ray_query.argtypes = [vp, vp, u32, u32, vp]
     L.vhr_get_ray_query_statistics.argtypes = [vp, C.POINTER(u64)]
     L.vhr_ray_query_struct_layout.argtypes = [C.POINTER(u32)]
+    L.vhr_update_vertices.argtypes = [vp, u32, u32, vp, u32]
+    L.vhr_update_primitive_transforms.argtypes = [vp, u32, u32, vp]
+    L.vhr_refit_geometry.argtypes = [vp]
+    L.vhr_get_refit_statistics.argtypes = [vp, C.POINTER(u64)]
+    L.vhr_get_refit_times.argtypes = [vp, C.POINTER(C.c_double)]
+    L.vhr_get_bvh_sah_cost.argtypes = [vp, C.POINTER(C.c_double)]
     L.vhr_set_kernel_timing.argtypes = [vp, i32]
     L.vhr_get_kernel_time.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(u64), i32]
     _lib = L
@@ -338,6 +346,7 @@ SSAO_BLUR_SHADER = "hybrid_render_path/ssao_blur.comp"
 SSR_SHADER = "hybrid_render_path/ssr.comp"
 
 ATTACHMENT_IMAGE, SAMPLED_IMAGE, STORAGE_IMAGE = 0, 1, 2
+UPDATE_DEVICE_MEMORY = 2          # vhr_update_vertices: VHR_UPDATE_DEVICE_MEMORY
 
 
 def transient(name, fmt, binding, kind=STORAGE_IMAGE, width=0, height=0, clear=(0, 0, 0, 0)):
@@ -420,6 +429,43 @@ class Context:
         p = np.ascontiguousarray(primitives)
         assert v.dtype == abi.vertex_dtype and p.dtype == abi.primitive_dtype
         self.check(self.L.vhr_update_geometry(self.handle, _p(v), len(v), _p(i), len(i), _p(p), len(p)), "UpdateGeometry")
+
+    # ---- refit: geometry that moves without a rebuild ----
+    def update_vertices(self, vertices, first_vertex=0):
+        """vhr_update_vertices from a host array (abi.vertex_dtype): overwrites vertices [first_vertex, first_vertex + len).  Follow with refit_geometry()."""
+        v = np.ascontiguousarray(vertices)
+        assert v.dtype == abi.vertex_dtype
+        self.check(self.L.vhr_update_vertices(self.handle, int(first_vertex), len(v), _p(v) if len(v) else None, 0), "update_vertices")
+
+    def update_vertices_device(self, vertices_ptr, count, first_vertex=0):
+        """vhr_update_vertices from device memory (e.g. a torch tensor's data_ptr()): `count` vhr_vertex records, copied on the context's stream."""
+        self.check(self.L.vhr_update_vertices(self.handle, int(first_vertex), int(count), vertices_ptr or None, UPDATE_DEVICE_MEMORY), "update_vertices_device")
+
+    def update_primitive_transforms(self, transforms, first_primitive=0):
+        """vhr_update_primitive_transforms: (n, 16) float32, the layout of vhr_primitive::transform (scene.primitives["transform"])."""
+        t = np.ascontiguousarray(transforms, np.float32).reshape(-1, 16)
+        self.check(self.L.vhr_update_primitive_transforms(self.handle, int(first_primitive), len(t), _p(t) if len(t) else None), "update_primitive_transforms")
+
+    def refit_geometry(self):
+        self.check(self.L.vhr_refit_geometry(self.handle), "refit_geometry")
+
+    def refit_statistics(self):
+        out = (C.c_uint64 * 8)()
+        self.check(self.L.vhr_get_refit_statistics(self.handle, out), "refit_statistics")
+        return dict(refits=int(out[0]), records=int(out[1]), nodes=int(out[2]), records_outside=int(out[3]), children_outside=int(out[4]),
+                    non_finite=int(out[5]), half_nodes=int(out[6]), upward_launches=int(out[7]))
+
+    def refit_times_ms(self):
+        """(host wall time, leaf pass, upward pass, forms + checks) of the last refit; the device times need set_kernel_timing(False, refit=True)."""
+        out = (C.c_double * 4)()
+        self.check(self.L.vhr_get_refit_times(self.handle, out), "refit_times")
+        return tuple(float(v) for v in out)
+
+    def bvh_sah_cost(self):
+        """(as built, now): the tree's surface-area cost, the number to watch when deciding to rebuild."""
+        out = (C.c_double * 2)()
+        self.check(self.L.vhr_get_bvh_sah_cost(self.handle, out), "bvh_sah_cost")
+        return float(out[0]), float(out[1])
 
     def upload_scene(self, scene):
         for t in scene.textures:
@@ -747,6 +793,7 @@ class Context:
 
     KERNEL_KINDS = {"raygen": 0, "svgf_temporal": 1, "svgf_atrous": 2, "blit": 3, "reflection": 4, "ssao": 5, "ssao_blur": 6, "ssr": 7, "svgf_atrous_async": 8,
                     "ray_query": 9, "rayquery_forward": 10, "forward_raster": 11}
+    REFIT_TIMING_BIT = 12          # a bit of vhr_set_kernel_timing's mask only (set_kernel_timing(..., refit=True)); the times come from refit_times_ms()
 
     @staticmethod
     def _rays_array(rays):
@@ -800,14 +847,16 @@ class Context:
     def set_option(self, key, value):
         self.check(self.L.vhr_set_option(self.handle, key.encode(), int(value)), "set_option")
 
-    def set_kernel_timing(self, kinds):
-        """kinds: True (all), False (off) or an iterable of kind names from KERNEL_KINDS."""
+    def set_kernel_timing(self, kinds, refit=False):
+        """kinds: True (all), False (off) or an iterable of kind names from KERNEL_KINDS.  refit=True: vhr_refit_geometry times its stages too (refit_times_ms)."""
         if kinds is True:
             mask = 0xFF
         elif not kinds:
             mask = 0
         else:
             mask = sum(1 << self.KERNEL_KINDS[k] for k in kinds)
+        if refit:
+            mask |= 1 << self.REFIT_TIMING_BIT
         self.check(self.L.vhr_set_kernel_timing(self.handle, mask), "set_kernel_timing")
 
     def kernel_time(self, kind, reset=False):
