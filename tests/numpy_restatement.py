@@ -99,6 +99,66 @@ def atrous(normals_bits, in_bits, step):
     return f2h(out)
 
 
+def atrous_f64(normals_bits, in_bits, step, display_size=None):
+    """svgf_atrous_filter.comp:17-101 in binary64: a truth of higher precision than the fp32 evaluations (the oracle, `atrous` above, the
+    HIP kernels), which all share one operation order.  A true pow(max(d, 0), 128) with pow of a non-positive base = 0 (oracle decision
+    v), np.exp, true divisions, ids as int(w) with a NaN id = 0 (decision viii), the shader's bounds test ((float)sx >= display_size
+    skips the tap; default: the image extent), ONE rounding at the end, binary64 -> fp16 directly.
+
+    Returns (out_bits (H, W, 4) uint16, live (H, W, 2) int): per pixel and channel (shadow, AO), the number of in-image taps whose
+    binary64 weight is non-zero."""
+    n = np.asarray(normals_bits, np.uint16).view(np.float16).astype(np.float64)
+    p = np.asarray(in_bits, np.uint16).view(np.float16).astype(np.float64)
+    H, W = p.shape[:2]
+    dw, dh = (float(W), float(H)) if display_size is None else (float(display_size[0]), float(display_size[1]))
+    assert dw <= W and dh <= H, "taps inside display_size must lie in the image"
+    ys, xs = np.mgrid[0:H, 0:W]
+
+    def inside(dx, dy):          # :28-29, :75-76: an int coordinate against the float display size
+        sx, sy = xs + dx, ys + dy
+        return (sx >= 0) & ~(sx.astype(np.float32) >= np.float32(dw)) & (sy >= 0) & ~(sy.astype(np.float32) >= np.float32(dh))
+
+    with np.errstate(invalid="ignore"):
+        ids = np.where(np.isnan(n[..., 3]), 0.0, np.trunc(n[..., 3])).astype(np.int64)
+    var = np.zeros((H, W, 2))
+    for y in (-1, 0, 1):                                                                   # :17-38
+        for x in (-1, 0, 1):
+            q, _ = _shift(p, x, y)
+            g = (0.5 if x == 0 else 0.25) * (0.5 if y == 0 else 0.25)
+            var = var + np.where(inside(x, y)[..., None], g * q[..., 2:4], 0.0)
+    with np.errstate(invalid="ignore"):
+        denom = 4.0 * np.sqrt(var) + 1e-6                                                  # :49
+    k1 = [1 / 16, 1 / 4, 3 / 8, 1 / 4, 1 / 16]
+    sum_w = np.ones((H, W, 2))
+    acc = p.copy()
+    live = np.zeros((H, W, 2), np.int64)
+    for y in range(-2, 3):
+        for x in range(-2, 3):                                                             # :72-94
+            if x == 0 and y == 0:
+                continue
+            m = inside(x * step, y * step)
+            if not m.any():
+                continue
+            q, _ = _shift(p, x * step, y * step)
+            nq, _ = _shift(n, x * step, y * step)
+            idq, _ = _shift(ids, x * step, y * step)
+            d = (n[..., 0] * nq[..., 0] + n[..., 1] * nq[..., 1]) + n[..., 2] * nq[..., 2]
+            with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+                wn = np.where(d > 0, np.power(np.where(d > 0, d, 0.0), 128.0), 0.0)       # :45 (decision v)
+                w = (k1[y + 2] * k1[x + 2]) * wn * (ids == idq)                            # :89
+                lw = np.exp(-(np.abs(p[..., 0:2] - q[..., 0:2]) / denom))                  # :48-50
+                wxy = np.where(m[..., None], w[..., None] * lw, 0.0)
+                live += wxy != 0
+                sum_w = sum_w + wxy
+                acc[..., 0:2] += wxy * q[..., 0:2]                                         # :94
+                acc[..., 2:4] += (wxy * wxy) * q[..., 2:4]
+    out = np.empty_like(acc)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        out[..., 0:2] = acc[..., 0:2] / sum_w
+        out[..., 2:4] = acc[..., 2:4] / (sum_w * sum_w)
+        return out.astype(np.float16).view(np.uint16), live
+
+
 def temporal(W, H, normals_bits, motion_bits, rt_bits, prev_normals_bits, history_bits, moments_bits):
     n = h2f(normals_bits)
     mv = h2f(motion_bits)

@@ -737,6 +737,11 @@ static int issue_atrous(vhr_context *ctx, const AtrousArgs &a) {
     if (a.row_end <= a.row_begin || a.limit_x <= a.col_begin || !a.limit_y) return VHR_OK;
     ctx->time_begin(ctx->async_atrous ? kKernelAtrousAsync : kKernelAtrous);
     bool tiled = ctx->options[kOptAtrousVariant] != 0;          // 0: the literal form of the shader (svgf_atrous_kernel), every step size
+    // The tile kernel stages a texel outside display_size as "not there" (zeros, a NaN id).  That is the shader's `continue` for a TAP
+    // (:75-76), but a CENTRE is loaded without a bounds test (:55-59): with a display size smaller than the dispatched region the tile
+    // kernel wrote zeros where the shader filters (tests/test_gpu_atrous_parity.py).  Such a dispatch takes the literal kernel.
+    const uint32_t last_x = a.limit_x - 1u, last_y = std::min(a.row_end, a.limit_y) - 1u;
+    if (!(float(last_x) < a.display_w && float(last_y) < a.display_h)) tiled = false;
     if (tiled) {
         switch (step) {                                          // the step sizes of the reference's schedule (hybrid_render_path.cpp:299-319)
             case 1: launch_atrous_tiles_auto<1>(ctx, a); break;
