@@ -20,9 +20,6 @@ namespace vhr {
 
 __constant__ float c_srgb_lut[256];
 
-#ifndef VHR_K1_POSTPONE
-#define VHR_K1_POSTPONE 0            // 1: a scratch build of the any-hit queue kernel WITH the postponed-leaf step (measured slower: profiles/r6_k1_postponed_leaf.txt)
-#endif
 #ifndef VHR_REDO_INLINE
 #define VHR_REDO_INLINE __attribute__((noinline))
 #endif
@@ -1152,9 +1149,6 @@ __global__ __launch_bounds__(kQueueBlock *WAVES) __attribute__((amdgpu_waves_per
     f3 ro = f3{ 0, 0, 0 }, rd = f3{ 0, 0, 1 }, rinv = f3{ 0, 0, 0 }, noi = f3{ 0, 0, 0 }, ainv = f3{ 0, 0, 0 };
     float tmax = 0.0f;
     int cur = 0, sp = 0;
-#if VHR_K1_POSTPONE
-    int parked = kStackSentinel;                      // "postponed leaf": a leaf this lane has reached and not tested yet (kStackSentinel = none)
-#endif
     int sbase = 0;                                    // "raygen_steal": stack rows 1 .. sbase have been taken by other lanes (row sbase holds a sentinel)
     uint32_t pix = 0, kind = 0;
     bool has = false;
@@ -1200,9 +1194,6 @@ __global__ __launch_bounds__(kQueueBlock *WAVES) __attribute__((amdgpu_waves_per
                 noi = f3{ -(oc.x * rinv.x), -(oc.y * rinv.y), -(oc.z * rinv.z) };
                 if (!COMPACT) ainv = f3{ fabsf(rinv.x), fabsf(rinv.y), fabsf(rinv.z) };
                 sbase = 0;
-#if VHR_K1_POSTPONE
-                parked = kStackSentinel;
-#endif
                 cut_to_stack(s_cut, cut_n, stack, stack_levels, rinv, noi, tmin_v, tmax, cur, sp, emask);      // (its boxes are relative to the centre `noi` is)
                 has = true;
             }
@@ -1241,9 +1232,6 @@ __global__ __launch_bounds__(kQueueBlock *WAVES) __attribute__((amdgpu_waves_per
                     if (!COMPACT) ainv = f3{ t_ax, t_ay, t_az };
                     tmax = t_tmax; pix = t_pk & 0xffu; kind = t_pk >> 8;
                     cur = link; sp = 0; sbase = 0; emask = 0;
-#if VHR_K1_POSTPONE
-                    parked = kStackSentinel;          // (a lane that dropped a ray another lane had found blocked may still hold one)
-#endif
                     has = true;
                 }
                 if (stats) ++n_refills;
@@ -1305,24 +1293,6 @@ __global__ __launch_bounds__(kQueueBlock *WAVES) __attribute__((amdgpu_waves_per
                     else overflow |= uint32_t((h0 & h1) >> lane) & 1u;            // cannot happen (builder depth bound); counted
                 }
             }
-#if VHR_K1_POSTPONE
-            // Postponed leaf (round 6): a lane whose next stop would be a LEAF parks it -- one slot per lane -- and goes on with what the stack holds
-            // instead of sitting out the rest of the loop (10 % of the loop's lane-trips on sponza_proc, 15 % on bistro_proc, were lanes holding a
-            // leaf: profiles/r6_k1_postponed_leaf.txt).  Both children hit: the far child is entered at once (it was just written above the top, sp stays);
-            // one child hit: the old top is popped.  The parked leaf is tested in the leaf stage below; any hit = OR over the leaves a ray touches, in
-            // any order.  Five vector instructions per trip, the masks on the scalar unit.
-            const unsigned long long any_hit = h0 | h1;
-            const unsigned long long park = cmp_gt_i32_mask_s(0, nearc) & any_hit & cmp_eq_i32_mask_s(kStackSentinel, parked);
-            parked = select_mask(parked, nearc, park);
-            cur = select_mask(select_mask(top, nearc, any_hit & ~park), farc, park & h0 & h1);
-            {   // sp += h0 + h1 - 1 - park
-                int t;
-                unsigned long long carry_out;
-                asm("v_addc_co_u32_e64 %0, %1, %2, -1, %3" : "=v"(t), "=s"(carry_out) : "v"(sp), "s"(h0));
-                asm("v_addc_co_u32_e64 %0, %1, %2, 0, %3" : "=v"(t), "=s"(carry_out) : "v"(t), "s"(h1));
-                asm("v_subb_co_u32_e64 %0, %1, %2, 0, %3" : "=v"(sp), "=s"(carry_out) : "v"(t), "s"(park));
-            }
-#else
             cur = select_mask(top, nearc, h0 | h1);                               // no child hit: popping the empty stack yields the sentinel
             {   // sp += h0 + h1 - 1: +1 both, 0 one, -1 none (with the sentinel) -- two add-with-carry, the hit masks as the carries
                 int t;
@@ -1330,7 +1300,6 @@ __global__ __launch_bounds__(kQueueBlock *WAVES) __attribute__((amdgpu_waves_per
                 asm("v_addc_co_u32_e64 %0, %1, %2, -1, %3" : "=v"(t), "=s"(carry_out) : "v"(sp), "s"(h0));
                 asm("v_addc_co_u32_e64 %0, %1, %2, 0, %3" : "=v"(sp), "=s"(carry_out) : "v"(t), "s"(h1));
             }
-#endif
         }
 #ifdef VHR_K1_COUNT_IDLE
         // (scratch builds, profiles/r6_k1_postponed_leaf.txt) who sat out how many trips of this pass through the node loop: lanes holding a leaf -- what a
@@ -1376,15 +1345,7 @@ __global__ __launch_bounds__(kQueueBlock *WAVES) __attribute__((amdgpu_waves_per
                 }
             }
         };
-#if VHR_K1_POSTPONE
-        if (has && parked != kStackSentinel) {                                      // the leaf the lane parked on its way
-            test_leaf(parked);
-            parked = kStackSentinel;
-        }
-        if (has && !found && cur < 0 && cur != kStackSentinel) {                    // ... and the one it stopped at
-#else
         if (has && cur < 0 && cur != kStackSentinel) {
-#endif
             test_leaf(cur);
             if (!found) {                                                          // pop (the sentinel if nothing is pending)
                 cur = stack[min(uint32_t(sp), stack_levels + 1u) * kQueueBlock];
@@ -1916,6 +1877,63 @@ __global__ __launch_bounds__(kQueueBlock * 2) __attribute__((amdgpu_waves_per_eu
     if (a.co.wave_cost && lane == 0) a.co.wave_cost[tile] = uint32_t(min(__builtin_readcyclecounter() - t_cost0, 0xffffffffull));
 }
 
+// ---------------------------------------------------------------------------------------------
+// What the launchers of the queue kernels share (host).
+// ---------------------------------------------------------------------------------------------
+// The walk's parameters by the options in force.  `levels`: the LDS part of the traversal stack, sized by the tree actually built (depth <=
+// kMaxBvhDepth): less LDS, more waves per CU; deeper entries spill to scratch (`spill`: the SPILL instantiation) unless the whole stack fits
+// the configured levels.  `lds_bytes`: a block's dynamic LDS -- the kernels index s_dyn by the same (levels + 3) rows per wave.
+struct QueueLaunch {
+    uint32_t levels, threshold, early_exit;
+    size_t lds_bytes;
+    bool spill;
+};
+static QueueLaunch queue_launch(const vhr_context *ctx, const int lds_levels_option, const int early_exit_option, const uint32_t waves_per_block) {
+    QueueLaunch q;
+    q.levels = std::max<uint32_t>(1u, std::min<uint32_t>(ctx->bvh_depth + 1u, uint32_t(std::max(1, ctx->options[lds_levels_option]))));
+    q.threshold = uint32_t(std::max(1, std::min(64, ctx->options[kOptRefillThreshold])));
+    q.early_exit = uint32_t(std::max(0, std::min(15, ctx->options[early_exit_option])));
+    q.lds_bytes = size_t(q.levels + 3) * kQueueBlock * sizeof(int) * waves_per_block;
+    q.spill = q.levels < ctx->bvh_depth + 1u;
+    return q;
+}
+
+// The grid of a launch whose waves own one tile_w x 8 pixel tile each, two waves to a block.
+struct TileGrid {
+    uint32_t tiles_x, tiles_total;
+    dim3 grid, block;
+};
+static TileGrid tile_grid(const uint32_t columns, const uint32_t rows, const uint32_t tile_w) {
+    TileGrid g;
+    g.tiles_x = (columns + tile_w - 1u) / tile_w;
+    g.tiles_total = g.tiles_x * ((rows + 7u) / 8u);
+    g.grid = dim3((g.tiles_total + 1u) / 2u);
+    g.block = dim3(kQueueBlock * 2);
+    return g;
+}
+
+// Ray statistics (vhr_set_ray_statistics) around a path's launches: `count` RayStats cleared on the stream before them, copied to the context
+// behind them -- [0] the path's own, [1] the hybrid path's mirror-ray launch.  The end also reports a launch that failed, in the launcher's words.
+static int ray_stats_begin(vhr_context *ctx, const bool on, const uint32_t count = 1u) {
+    if (on && hipMemsetAsync(ctx->d_ray_stats, 0, count * sizeof(RayStats), ctx->stream) != hipSuccess)
+        return ctx->fail(VHR_ERROR_DEVICE, "hipMemsetAsync(ray stats) failed");
+    return VHR_OK;
+}
+static int ray_stats_end(vhr_context *ctx, const bool on, const char *launch_failed, const uint32_t count = 1u) {
+    if (hipGetLastError() != hipSuccess) return ctx->fail(VHR_ERROR_DEVICE, launch_failed);
+    if (on && (hipMemcpyAsync(&ctx->h_ray_stats, ctx->d_ray_stats, sizeof(RayStats), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+               (count > 1u && hipMemcpyAsync(&ctx->h_refl_stats, ctx->d_ray_stats + 1, sizeof(RayStats), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)))
+        return ctx->fail(VHR_ERROR_DEVICE, "hipMemcpyAsync(ray stats) failed");
+    return VHR_OK;
+}
+
+// A run-time flag as a template argument: f(std::true_type{}) or f(std::false_type{}); nested for several flags.
+template <typename F>
+static void with_bool(const bool flag, F &&f) {
+    if (flag) f(std::true_type{});
+    else f(std::false_type{});
+}
+
 // The shadow / AO launch itself, by the options in force (everything launch_raygen decided is in `a`).
 // "raygen_cost_order": the cost / order pointers of a queue-kernel launch of `n_blocks` blocks of `wv` waves (see vhr_context::CostOrder).
 // 1 (default) = launches of at least 2 048 blocks (a full round of waves or more), 2 = any launch (tests); the two launches an order connects must
@@ -1968,11 +1986,6 @@ static void issue_raygen(vhr_context *ctx, const RaygenArgs &a_in, const uint32_
     if (ctx->options[kOptRaygenVariant] == 0) {
         launch(ctx, raygen_kernel, dim3((width + 15) / 16, (a.row_end - a.row_begin + 15) / 16), dim3(kTraceBlock), 0, a);
     } else {
-        // LDS part of the traversal stack, sized by the tree actually built (depth <= kMaxBvhDepth): less LDS, more waves per CU; deeper
-        // entries spill to scratch (see the kernel)
-        const uint32_t levels = std::max<uint32_t>(1u, std::min<uint32_t>(ctx->bvh_depth + 1u, uint32_t(std::max(1, ctx->options[kOptLdsStackLevels]))));
-        const uint32_t threshold = uint32_t(std::max(1, std::min(64, ctx->options[kOptRefillThreshold])));
-        const size_t stack_bytes = size_t(levels + 3) * kQueueBlock * sizeof(int);
         const uint32_t rows_traced = a.row_end - a.row_begin;
         // rows of a wave's tile: 8, or ("raygen_tile_rows" 0 = auto, the default) 6 for a launch whose 8x8 tiles would fill less than 70 % of the
         // chip's wave slots -- a single partial round of waves lasts as long as its slowest wave, and a wave with three quarters of the rays
@@ -1986,33 +1999,27 @@ static void issue_raygen(vhr_context *ctx, const RaygenArgs &a_in, const uint32_
         const uint32_t tiles_x = (a.col_end - a.col_begin + 7) / 8, tiles_y = (rows_traced + tile_rows - 1) / tile_rows;
         const int waves = ctx->options[kOptWavesPerBlock];
         const uint32_t wv = waves >= 4 ? 4u : (waves >= 2 ? 2u : 1u);
-        const uint32_t early_exit = uint32_t(std::max(0, std::min(15, ctx->options[kOptEarlyExit])));
+        const QueueLaunch q = queue_launch(ctx, kOptLdsStackLevels, kOptEarlyExit, wv);
         const bool compact = ctx->options[kOptCompactNodes] != 0 && ctx->nodes16_valid;      // the 32-byte half-precision nodes (two loads per visit instead of three)
-        const bool spill = levels < ctx->bvh_depth + 1u;           // the whole stack in LDS (no scratch) whenever the tree's depth fits the configured LDS levels
         const uint32_t n_blocks = ((tiles_x + wv - 1u) / wv) * tiles_y;
         {   // "raygen_cost_order" (see vhr_context::CostOrder)
             const uint32_t key = (tiles_x * 2654435761u) ^ (tiles_y * 40503u) ^ (wv << 28) ^ (tile_rows << 24) ^ (a.row_begin * 97u) ^ (a.col_begin * 193u);
-            if (!a.stats && levels >= 5u) prepare_cost_order(ctx, ctx->cost_order_raygen, n_blocks, wv, key, a.co, { tiles_x, (tiles_x + wv - 1u) / wv, wv, 8u, tile_rows, a.col_begin, a.row_begin });
+            if (!a.stats && q.levels >= 5u) prepare_cost_order(ctx, ctx->cost_order_raygen, n_blocks, wv, key, a.co, { tiles_x, (tiles_x + wv - 1u) / wv, wv, 8u, tile_rows, a.col_begin, a.row_begin });
         }
         const uint32_t steal = uint32_t(std::max(0, std::min(63, ctx->options[kOptRaygenSteal])));
-        auto go = [&](auto kernel) { launch(ctx, kernel, dim3(n_blocks), dim3(kQueueBlock * wv), stack_bytes * wv, a, levels, threshold, (tiles_x + wv - 1u) / wv, early_exit, tile_rows, steal); };
+        auto go = [&](auto kernel) { launch(ctx, kernel, dim3(n_blocks), dim3(kQueueBlock * wv), q.lds_bytes, a, q.levels, q.threshold, (tiles_x + wv - 1u) / wv, q.early_exit, tile_rows, steal); };
         auto by_flags = [&](auto waves_c) {
             constexpr int WV = decltype(waves_c)::value;
-            const int sel = (compact ? 4 : 0) | (spill ? 2 : 0) | (a.stats ? 1 : 0);
-            if (a.fuse_temporal && compact && !a.stats) {       // "fuse_temporal": svgf.comp in the tiles' epilogues (the default node form only)
-                if (spill) go(raygen_queue_kernel<WV, true, true, false, true>); else go(raygen_queue_kernel<WV, true, false, false, true>);
-                return;
-            }
-            switch (sel) {
-                case 0: go(raygen_queue_kernel<WV, false, false, false>); break;
-                case 1: go(raygen_queue_kernel<WV, false, false, true>); break;
-                case 2: go(raygen_queue_kernel<WV, false, true, false>); break;
-                case 3: go(raygen_queue_kernel<WV, false, true, true>); break;
-                case 4: go(raygen_queue_kernel<WV, true, false, false>); break;
-                case 5: go(raygen_queue_kernel<WV, true, false, true>); break;
-                case 6: go(raygen_queue_kernel<WV, true, true, false>); break;
-                default: go(raygen_queue_kernel<WV, true, true, true>); break;
-            }
+            with_bool(q.spill, [&](auto sp) {
+                constexpr bool SP = decltype(sp)::value;
+                if (a.fuse_temporal && compact && !a.stats) {   // "fuse_temporal": svgf.comp in the tiles' epilogues (the default node form only)
+                    go(raygen_queue_kernel<WV, true, SP, false, true>);
+                    return;
+                }
+                with_bool(compact, [&](auto co) {
+                    with_bool(a.stats != nullptr, [&](auto st) { go(raygen_queue_kernel<WV, decltype(co)::value, SP, decltype(st)::value>); });
+                });
+            });
         };
         if (wv == 4u) by_flags(std::integral_constant<int, 4>{});
         else if (wv == 2u) by_flags(std::integral_constant<int, 2>{});
@@ -2088,10 +2095,7 @@ int launch_raygen(vhr_context *ctx, const vhr_per_frame_data &pfd, uint32_t widt
         a.col_begin = (owned_col_begin > ctx->overlap ? owned_col_begin - ctx->overlap : 0u) & ~15u;
         a.col_end = uint32_t(std::min<uint64_t>(width, uint64_t(owned_col_end) + ctx->overlap));
     }
-    if (a.stats) {
-        if (hipMemsetAsync(ctx->d_ray_stats, 0, 2 * sizeof(RayStats), ctx->stream) != hipSuccess)     // [0] shadow / AO launch, [1] mirror-ray launch
-            return ctx->fail(VHR_ERROR_DEVICE, "hipMemsetAsync(ray stats) failed");
-    }
+    if (const int rc = ray_stats_begin(ctx, a.stats != nullptr, 2u)) return rc;      // [0] shadow / AO launch, [1] mirror-ray launch
     // "fuse_temporal" (opt-in): hold the launch back until the next pass shows its first command -- if that is svgf.comp on this launch's
     // images, the queue kernel runs it in its tiles' epilogues (flush_deferred_raygen).  Only the default kernel has that epilogue, only
     // whole-image work on one stream qualifies, and only a pass nobody hooked an epilogue to (its owner expects the image when it runs).
@@ -2146,24 +2150,17 @@ int launch_raygen(vhr_context *ctx, const vhr_per_frame_data &pfd, uint32_t widt
         }
         ctx->time_begin(kKernelReflection);
         if (m.tp.reflections <= 2 && ctx->options[kOptReflectionVariant] != 0) {
-            const uint32_t levels = std::max<uint32_t>(1u, std::min<uint32_t>(ctx->bvh_depth + 1u, uint32_t(std::max(1, ctx->options[kOptReflectionLdsStackLevels]))));
-            const uint32_t threshold = uint32_t(std::max(1, std::min(64, ctx->options[kOptRefillThreshold])));
-            const uint32_t early_exit = uint32_t(std::max(0, std::min(15, ctx->options[kOptReflectionEarlyExit])));
-            const uint32_t tile_w = 8u;                                    // (reflection_queue_kernel: 8 x 8 pixels per wave)
-            const uint32_t tiles_x = (m.col_end - m.col_begin + tile_w - 1u) / tile_w, tiles_total = tiles_x * ((owned_end - owned_begin + 7) / 8);
-            const size_t lds = size_t(levels + 3) * kQueueBlock * sizeof(int) * 2;
+            const QueueLaunch q = queue_launch(ctx, kOptReflectionLdsStackLevels, kOptReflectionEarlyExit, 2u);
+            const TileGrid g = tile_grid(m.col_end - m.col_begin, owned_end - owned_begin, 8u);      // (reflection_queue_kernel: 8 x 8 pixels per wave)
             m.co = CostOrderArgs{};
-            if (levels >= 5u && !m.stats)                  // "raygen_cost_order" for the mirror-ray launch (its own lifetimes and orders)
-                prepare_cost_order(ctx, ctx->cost_order_reflection, (tiles_total + 1u) / 2u, 2u,
-                                   (tiles_x * 2654435761u) ^ (tiles_total * 40503u) ^ (uint32_t(m.tp.reflections) << 28) ^ (m.row_begin * 97u) ^ (m.col_begin * 193u), m.co,
-                                   { tiles_x, tiles_x, 1u, 8u, 8u, m.col_begin, m.row_begin });
-#define VHR_LAUNCH_REFL(SP, B, ST) launch(ctx, (reflection_queue_kernel<SP, B, ST>), dim3((tiles_total + 1) / 2), dim3(kQueueBlock * 2), lds, m, levels, threshold, tiles_x, tiles_total, early_exit)
-#define VHR_LAUNCH_REFL_S(SP, B) do { if (m.stats) VHR_LAUNCH_REFL(SP, B, true); else VHR_LAUNCH_REFL(SP, B, false); } while (0)
-            const bool spill = levels < ctx->bvh_depth + 1u;
-            if (m.tp.reflections == 2) { if (spill) VHR_LAUNCH_REFL_S(true, 2); else VHR_LAUNCH_REFL_S(false, 2); }
-            else { if (spill) VHR_LAUNCH_REFL_S(true, 1); else VHR_LAUNCH_REFL_S(false, 1); }
-#undef VHR_LAUNCH_REFL_S
-#undef VHR_LAUNCH_REFL
+            if (q.levels >= 5u && !m.stats)                // "raygen_cost_order" for the mirror-ray launch (its own lifetimes and orders)
+                prepare_cost_order(ctx, ctx->cost_order_reflection, (g.tiles_total + 1u) / 2u, 2u,
+                                   (g.tiles_x * 2654435761u) ^ (g.tiles_total * 40503u) ^ (uint32_t(m.tp.reflections) << 28) ^ (m.row_begin * 97u) ^ (m.col_begin * 193u), m.co,
+                                   { g.tiles_x, g.tiles_x, 1u, 8u, 8u, m.col_begin, m.row_begin });
+            with_bool(q.spill, [&](auto sp) { with_bool(m.tp.reflections == 2, [&](auto two) { with_bool(m.stats != nullptr, [&](auto st) {
+                launch(ctx, reflection_queue_kernel<decltype(sp)::value, decltype(two)::value ? 2 : 1, decltype(st)::value>, g.grid, g.block, q.lds_bytes, m, q.levels, q.threshold,
+                       g.tiles_x, g.tiles_total, q.early_exit);
+            }); }); });
         } else {
             launch(ctx, reflection_kernel, dim3((width + 15) / 16, (owned_end - owned_begin + 15) / 16), dim3(kTraceBlock), 0, m);
         }
@@ -2179,13 +2176,7 @@ int launch_raygen(vhr_context *ctx, const vhr_per_frame_data &pfd, uint32_t widt
             if (!rec) return ctx->fail(VHR_ERROR_DEVICE, "hipEventRecord(mirror-ray stream) failed");
         }
     }
-    if (hipGetLastError() != hipSuccess) return ctx->fail(VHR_ERROR_DEVICE, "raygen kernel launch failed");
-    if (a.stats) {
-        if (hipMemcpyAsync(&ctx->h_ray_stats, ctx->d_ray_stats, sizeof(RayStats), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-            hipMemcpyAsync(&ctx->h_refl_stats, ctx->d_ray_stats + 1, sizeof(RayStats), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-            return ctx->fail(VHR_ERROR_DEVICE, "hipMemcpyAsync(ray stats) failed");
-    }
-    return VHR_OK;
+    return ray_stats_end(ctx, a.stats != nullptr, "raygen kernel launch failed", 2u);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2446,34 +2437,26 @@ int launch_raytraced(vhr_context *ctx, const vhr_per_frame_data &pfd, uint32_t w
     a.row_end = std::min(ctx->row_end, height);
     a.stats = ctx->ray_stats_enabled ? ctx->d_ray_stats : nullptr;
     if (a.row_end <= a.row_begin) return VHR_OK;
-    if (a.stats && hipMemsetAsync(ctx->d_ray_stats, 0, sizeof(RayStats), ctx->stream) != hipSuccess)
-        return ctx->fail(VHR_ERROR_DEVICE, "hipMemsetAsync(ray stats) failed");
-    const dim3 grid((width + 15) / 16, (a.row_end - a.row_begin + 15) / 16);
+    if (const int rc = ray_stats_begin(ctx, a.stats != nullptr)) return rc;
     ctx->time_begin(kKernelRaygen);
-    if (ctx->options[kOptRaytracedVariant] != 0) {
-        const uint32_t levels = std::max<uint32_t>(1u, std::min<uint32_t>(ctx->bvh_depth + 1u, uint32_t(std::max(1, ctx->options[kOptLdsStackLevels]))));
-        const uint32_t threshold = uint32_t(std::max(1, std::min(64, ctx->options[kOptRefillThreshold])));
-        const uint32_t early_exit = uint32_t(std::max(0, std::min(15, ctx->options[kOptEarlyExit])));
-        const uint32_t tiles_x = (width + 15) / 16, tiles_total = tiles_x * ((a.row_end - a.row_begin + 7) / 8);
-        const size_t lds = size_t(levels + 3) * kQueueBlock * sizeof(int) * 2;
-        const bool spill = levels < ctx->bvh_depth + 1u;
+    with_bool(alpha_test, [&](auto al) {
+        constexpr bool AL = decltype(al)::value;
+        if (ctx->options[kOptRaytracedVariant] == 0) {
+            launch(ctx, raytraced_kernel<AL>, dim3((width + 15) / 16, (a.row_end - a.row_begin + 15) / 16), dim3(kTraceBlock), 0, a);
+            return;
+        }
+        const QueueLaunch q = queue_launch(ctx, kOptLdsStackLevels, kOptEarlyExit, 2u);
+        const TileGrid g = tile_grid(width, a.row_end - a.row_begin, 16u);
         a.co = CostOrderArgs{};
-        if (levels >= 5u && !a.stats)                      // "raygen_cost_order" for this path's launch (its own lifetimes and orders)
-            prepare_cost_order(ctx, ctx->cost_order_raytraced, (tiles_total + 1u) / 2u, 2u,
-                               (tiles_x * 2654435761u) ^ (tiles_total * 40503u) ^ (uint32_t(alpha_test) << 28) ^ (a.row_begin * 97u), a.co, { tiles_x, tiles_x, 1u, 16u, 8u, 0u, a.row_begin });
-#define VHR_LAUNCH_RT(SP, AL) launch(ctx, (raytraced_queue_kernel<SP, AL>), dim3((tiles_total + 1) / 2), dim3(kQueueBlock * 2), lds, a, levels, threshold, tiles_x, tiles_total, early_exit)
-        if (alpha_test) { if (spill) VHR_LAUNCH_RT(true, true); else VHR_LAUNCH_RT(false, true); }
-        else { if (spill) VHR_LAUNCH_RT(true, false); else VHR_LAUNCH_RT(false, false); }
-#undef VHR_LAUNCH_RT
-    } else if (alpha_test) {
-        launch(ctx, raytraced_kernel<true>, grid, dim3(kTraceBlock), 0, a);
-    } else {
-        launch(ctx, raytraced_kernel<false>, grid, dim3(kTraceBlock), 0, a);
-    }
+        if (q.levels >= 5u && !a.stats)                    // "raygen_cost_order" for this path's launch (its own lifetimes and orders)
+            prepare_cost_order(ctx, ctx->cost_order_raytraced, (g.tiles_total + 1u) / 2u, 2u,
+                               (g.tiles_x * 2654435761u) ^ (g.tiles_total * 40503u) ^ (uint32_t(alpha_test) << 28) ^ (a.row_begin * 97u), a.co, { g.tiles_x, g.tiles_x, 1u, 16u, 8u, 0u, a.row_begin });
+        with_bool(q.spill, [&](auto sp) {
+            launch(ctx, raytraced_queue_kernel<decltype(sp)::value, AL>, g.grid, g.block, q.lds_bytes, a, q.levels, q.threshold, g.tiles_x, g.tiles_total, q.early_exit);
+        });
+    });
     ctx->time_end(kKernelRaygen);
-    if (hipGetLastError() != hipSuccess) return ctx->fail(VHR_ERROR_DEVICE, "raytraced kernel launch failed");
-    if (a.stats && hipMemcpyAsync(&ctx->h_ray_stats, ctx->d_ray_stats, sizeof(RayStats), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-        return ctx->fail(VHR_ERROR_DEVICE, "hipMemcpyAsync(ray stats) failed");
+    if (const int rc = ray_stats_end(ctx, a.stats != nullptr, "raytraced kernel launch failed")) return rc;
     ctx->raytraced_pixels = uint64_t(width) * (a.row_end - a.row_begin);
     return VHR_OK;
 }
@@ -3076,26 +3059,19 @@ int launch_rayquery_forward(vhr_context *ctx, const vhr_per_frame_data &pfd, Ima
     a.height = depth.height;
     a.stats = ctx->ray_stats_enabled ? ctx->d_ray_stats : nullptr;
     if (a.width == 0 || a.height == 0) return VHR_OK;
-    if (a.stats && hipMemsetAsync(ctx->d_ray_stats, 0, sizeof(RayStats), ctx->stream) != hipSuccess)
-        return ctx->fail(VHR_ERROR_DEVICE, "hipMemsetAsync(ray stats) failed");
+    if (const int rc = ray_stats_begin(ctx, a.stats != nullptr)) return rc;
     ctx->time_begin(kKernelRayqueryForward);
     if (ctx->options[kOptRayqueryVariant] != 0) {
-        const uint32_t levels = std::max<uint32_t>(1u, std::min<uint32_t>(ctx->bvh_depth + 1u, uint32_t(std::max(1, ctx->options[kOptLdsStackLevels]))));
-        const uint32_t threshold = uint32_t(std::max(1, std::min(64, ctx->options[kOptRefillThreshold])));
-        const uint32_t early_exit = uint32_t(std::max(0, std::min(15, ctx->options[kOptEarlyExit])));
-        const uint32_t tiles_x = (a.width + 15) / 16, tiles_total = tiles_x * ((a.height + 7) / 8);
-        const size_t lds = size_t(levels + 3) * kQueueBlock * sizeof(int) * 2;
-        if (levels < ctx->bvh_depth + 1u)
-            launch(ctx, rayquery_forward_queue_kernel<true>, dim3((tiles_total + 1) / 2), dim3(kQueueBlock * 2), lds, a, levels, threshold, tiles_x, tiles_total, early_exit);
-        else
-            launch(ctx, rayquery_forward_queue_kernel<false>, dim3((tiles_total + 1) / 2), dim3(kQueueBlock * 2), lds, a, levels, threshold, tiles_x, tiles_total, early_exit);
+        const QueueLaunch q = queue_launch(ctx, kOptLdsStackLevels, kOptEarlyExit, 2u);
+        const TileGrid g = tile_grid(a.width, a.height, 16u);
+        with_bool(q.spill, [&](auto sp) {
+            launch(ctx, rayquery_forward_queue_kernel<decltype(sp)::value>, g.grid, g.block, q.lds_bytes, a, q.levels, q.threshold, g.tiles_x, g.tiles_total, q.early_exit);
+        });
     } else {
         launch(ctx, rayquery_forward_kernel, dim3((a.width + 15) / 16, (a.height + 15) / 16), dim3(kTraceBlock), 0, a);
     }
     ctx->time_end(kKernelRayqueryForward);
-    if (hipGetLastError() != hipSuccess) return ctx->fail(VHR_ERROR_DEVICE, "rayquery forward kernel launch failed");
-    if (a.stats && hipMemcpyAsync(&ctx->h_ray_stats, ctx->d_ray_stats, sizeof(RayStats), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-        return ctx->fail(VHR_ERROR_DEVICE, "hipMemcpyAsync(ray stats) failed");
+    if (const int rc = ray_stats_end(ctx, a.stats != nullptr, "rayquery forward kernel launch failed")) return rc;
     ctx->raytraced_pixels = uint64_t(a.width) * a.height;      // ray statistics: one primary ray per pixel + one query per primary hit
     return VHR_OK;
 }
@@ -3454,33 +3430,22 @@ int launch_forward_raster(vhr_context *ctx, const vhr_per_frame_data &pfd, Image
     a.height = depth.height;
     a.stats = ctx->ray_stats_enabled ? ctx->d_ray_stats : nullptr;
     if (a.width == 0 || a.height == 0) return VHR_OK;
-    if (a.stats && hipMemsetAsync(ctx->d_ray_stats, 0, sizeof(RayStats), ctx->stream) != hipSuccess)
-        return ctx->fail(VHR_ERROR_DEVICE, "hipMemsetAsync(ray stats) failed");
+    if (const int rc = ray_stats_begin(ctx, a.stats != nullptr)) return rc;
     ctx->time_begin(kKernelForwardRaster);
-    if (ctx->options[kOptForwardRasterVariant] != 0) {
-        const uint32_t levels = std::max<uint32_t>(1u, std::min<uint32_t>(ctx->bvh_depth + 1u, uint32_t(std::max(1, ctx->options[kOptLdsStackLevels]))));
-        const uint32_t threshold = uint32_t(std::max(1, std::min(64, ctx->options[kOptRefillThreshold])));
-        const uint32_t early_exit = uint32_t(std::max(0, std::min(15, ctx->options[kOptEarlyExit])));
-        const uint32_t tiles_x = (a.width + 15) / 16, tiles_total = tiles_x * ((a.height + 7) / 8);
-        const size_t lds = size_t(levels + 3) * kQueueBlock * sizeof(int) * 2;
-        const dim3 grid((tiles_total + 1) / 2), block(kQueueBlock * 2);
-        const bool spill = levels < ctx->bvh_depth + 1u;
-        if (S == 1) {
-            if (spill) launch(ctx, forward_raster_queue_kernel<1, true>, grid, block, lds, a, levels, threshold, tiles_x, tiles_total, early_exit);
-            else launch(ctx, forward_raster_queue_kernel<1, false>, grid, block, lds, a, levels, threshold, tiles_x, tiles_total, early_exit);
-        } else {
-            if (spill) launch(ctx, forward_raster_queue_kernel<8, true>, grid, block, lds, a, levels, threshold, tiles_x, tiles_total, early_exit);
-            else launch(ctx, forward_raster_queue_kernel<8, false>, grid, block, lds, a, levels, threshold, tiles_x, tiles_total, early_exit);
+    with_bool(S == 1, [&](auto one) {
+        constexpr uint32_t SAMPLES = decltype(one)::value ? 1u : 8u;
+        if (ctx->options[kOptForwardRasterVariant] == 0) {
+            launch(ctx, forward_raster_kernel<SAMPLES>, dim3((a.width + 15) / 16, (a.height + 15) / 16), dim3(kTraceBlock), 0, a);
+            return;
         }
-    } else {
-        const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
-        if (S == 1) launch(ctx, forward_raster_kernel<1>, grid, dim3(kTraceBlock), 0, a);
-        else launch(ctx, forward_raster_kernel<8>, grid, dim3(kTraceBlock), 0, a);
-    }
+        const QueueLaunch q = queue_launch(ctx, kOptLdsStackLevels, kOptEarlyExit, 2u);
+        const TileGrid g = tile_grid(a.width, a.height, 16u);
+        with_bool(q.spill, [&](auto sp) {
+            launch(ctx, forward_raster_queue_kernel<SAMPLES, decltype(sp)::value>, g.grid, g.block, q.lds_bytes, a, q.levels, q.threshold, g.tiles_x, g.tiles_total, q.early_exit);
+        });
+    });
     ctx->time_end(kKernelForwardRaster);
-    if (hipGetLastError() != hipSuccess) return ctx->fail(VHR_ERROR_DEVICE, "forward raster kernel launch failed");
-    if (a.stats && hipMemcpyAsync(&ctx->h_ray_stats, ctx->d_ray_stats, sizeof(RayStats), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-        return ctx->fail(VHR_ERROR_DEVICE, "hipMemcpyAsync(ray stats) failed");
+    if (const int rc = ray_stats_end(ctx, a.stats != nullptr, "forward raster kernel launch failed")) return rc;
     ctx->raytraced_pixels = uint64_t(a.width) * a.height * S;      // ray statistics: S primary rays per pixel, nothing else
     return VHR_OK;
 }
@@ -3658,15 +3623,10 @@ int launch_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, bool
     a.any_hit = any_hit ? 1u : 0u;
     if (hipMemsetAsync(q->counters, 0, sizeof(RayQueryCounters), ctx->stream) != hipSuccess)
         return ctx->fail(VHR_ERROR_DEVICE, "vhr_ray_query: hipMemsetAsync failed");
-    const uint32_t levels = std::max<uint32_t>(1u, std::min<uint32_t>(ctx->bvh_depth + 1u, uint32_t(std::max(1, ctx->options[kOptLdsStackLevels]))));
-    const uint32_t threshold = uint32_t(std::max(1, std::min(64, ctx->options[kOptRefillThreshold])));
-    const uint32_t early_exit = uint32_t(std::max(0, std::min(15, ctx->options[kOptEarlyExit])));
-    const size_t lds = size_t(levels + 3) * kQueueBlock * sizeof(int) * 2;
-    const bool spill = levels < ctx->bvh_depth + 1u;
+    const QueueLaunch ql = queue_launch(ctx, kOptLdsStackLevels, kOptEarlyExit, 2u);
     const dim3 grid(uint32_t((uint64_t(count) + 2u * kQueryWaveRays - 1u) / (2u * kQueryWaveRays)));
     ctx->time_begin(kKernelRayQuery);
-    if (spill) launch(ctx, ray_query_kernel<true>, grid, dim3(kQueueBlock * 2), lds, a, levels, threshold, early_exit);
-    else launch(ctx, ray_query_kernel<false>, grid, dim3(kQueueBlock * 2), lds, a, levels, threshold, early_exit);
+    with_bool(ql.spill, [&](auto sp) { launch(ctx, ray_query_kernel<decltype(sp)::value>, grid, dim3(kQueueBlock * 2), ql.lds_bytes, a, ql.levels, ql.threshold, ql.early_exit); });
     if (a.scene.node_count != 0) {
         const uint32_t redo_blocks = std::min<uint32_t>((count + kTraceBlock - 1u) / kTraceBlock, uint32_t(ctx->cu_count) * 4u);
         launch(ctx, ray_query_redo_kernel, dim3(redo_blocks), dim3(kTraceBlock), 0, a);
