@@ -1,7 +1,8 @@
 """Shared test scaffolding: drive the product (C ABI) and the oracle over the same inputs."""
 import numpy as np
 
-from vulkanhybridrenderer_amd import abi, camera, lib
+from tests import f2_scene
+from vulkanhybridrenderer_amd import abi, camera, lib, scenes
 
 
 def f16(a):
@@ -165,4 +166,127 @@ class GpuSvgfHarness:
         self.ctx.synchronize()
 
     def close(self):
+        self.ctx.close()
+
+
+# ---- the raster-pass paths (rayquery, forward raster): shared by tests/test_rayquery_path.py and tests/test_forward_raster_path.py ----
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint8)
+
+
+def named_scene(name):
+    return {"f4": f2_scene.scene_f4, "f2": f2_scene.scene, "sponza": scenes.sponza_proc, "bistro": scenes.bistro_proc, "tiny": scenes.tiny_scene}[name]()
+
+
+def srgb_decode_lut():
+    c = np.arange(256) / 255.0
+    return np.where(c <= 0.04045, c / 12.92, ((c + 0.055) / 1.055) ** 2.4).astype(np.float32).astype(np.float64)
+
+
+def _wrap(i, n, mode):
+    if mode == abi.ADDRESS_CLAMP_TO_EDGE:
+        return np.clip(i, 0, n - 1)
+    if mode == abi.ADDRESS_MIRRORED_REPEAT:
+        m = np.mod(i, 2 * n)
+        return np.where(m < n, m, 2 * n - 1 - m)
+    return np.mod(i, n)
+
+
+def sample_texture(tex, u, v):
+    """texture() with the texture's own sampler (filter, address modes) at LOD 0, float64, on an sRGB or UNORM RGBA8 image."""
+    img = np.asarray(tex["rgba8"])
+    h, w = img.shape[:2]
+    texel = img.astype(np.float64) / 255.0
+    if tex["format"] == abi.FORMAT_R8G8B8A8_SRGB:
+        texel[..., :3] = srgb_decode_lut()[img[..., :3]]
+    x, y = u * w, v * h
+    if tex["mag"] == abi.FILTER_NEAREST:
+        return texel[_wrap(np.floor(y).astype(np.int64), h, tex["address_v"]), _wrap(np.floor(x).astype(np.int64), w, tex["address_u"])]
+    x, y = x - 0.5, y - 0.5
+    x0, y0 = np.floor(x), np.floor(y)
+    fx, fy = (x - x0)[:, None], (y - y0)[:, None]
+    xi, yi = x0.astype(np.int64), y0.astype(np.int64)
+    xa, xb = _wrap(xi, w, tex["address_u"]), _wrap(xi + 1, w, tex["address_u"])
+    ya, yb = _wrap(yi, h, tex["address_v"]), _wrap(yi + 1, h, tex["address_v"])
+    return (texel[ya, xa] * (1 - fx) + texel[ya, xb] * fx) * (1 - fy) + (texel[yb, xa] * (1 - fx) + texel[yb, xb] * fx) * fy
+
+
+def albedo_and_shading_normal(sc, prim, normal, tangent, uv):
+    """default.frag's albedo (base colour, or its texture) and normal (the normal map through the re-orthogonalised tangent frame) of
+    fragments on primitives `prim` with interpolated normal / tangent / uv0, float64: (n, 3) each."""
+    mat = sc.primitives["material"][prim]
+    albedo = np.asarray(mat["base_color"], np.float64)[:, :3].copy()
+    for t in np.unique(mat["base_color_texture"]):
+        if t >= 0:
+            m = mat["base_color_texture"] == t
+            albedo[m] = sample_texture(sc.textures[t], uv[m, 0], uv[m, 1])[:, :3]
+    N = normal.copy()
+    for t in np.unique(mat["normal_map"]):
+        if t >= 0:
+            m = mat["normal_map"] == t
+            tsn = sample_texture(sc.textures[t], uv[m, 0], uv[m, 1])[:, :3] * 2.0 - 1.0
+            tsn /= np.linalg.norm(tsn, axis=1, keepdims=True)
+            T, n = tangent[m, :3], normal[m]
+            bit = np.cross(tsn, T) * tangent[m, 3:4]
+            tg = T - n * (T * n).sum(1, keepdims=True)
+            tg /= np.linalg.norm(tg, axis=1, keepdims=True)
+            N[m] = tg * tsn[:, 0:1] + bit * tsn[:, 1:2] + n * tsn[:, 2:3]
+    return albedo, N
+
+
+def srgb_store_bgra(col):
+    """(n, 3) linear RGB, float64 -> (n, 4) uint8 texels as a B8G8R8A8_SRGB attachment stores them, alpha 255."""
+    with np.errstate(invalid="ignore"):
+        enc = np.where(col <= 0.0031308, 12.92 * col, 1.055 * np.power(np.maximum(col, 0.0), 1 / 2.4) - 0.055)
+        q = np.where(col > 0.0, np.where(col >= 1.0, 255.0, np.floor(enc * 255.0 + 0.5)), 0.0)
+    return np.concatenate([q[:, ::-1], np.full((len(q), 1), 255.0)], 1).astype(np.uint8)
+
+
+class GpuForwardRig:
+    """A context with the scene uploaded, ray statistics on, a present image and probe tensors, and a render path built whose pass bodies
+    are stand-ins writing them.  A subclass says what differs: OPTION (the variant option run() sets), make_path(), alloc_probes(n) and
+    results() (the dict run() returns)."""
+    OPTION = None
+
+    def __init__(self, sc, W, H):
+        import torch
+        self.torch = torch
+        self.W, self.H = W, H
+        self.ctx = lib.Context(W, H)
+        self.ctx.upload_scene(sc)
+        self.ctx.set_ray_statistics(True)
+        self.resource_idx = 0
+        self._alloc()
+        self.path = self.make_path()
+        self.path.build()
+
+    def _alloc(self):
+        self.present = self.ctx.upload_new_storage_image(self.W, self.H, abi.FORMAT_B8G8R8A8_SRGB)
+        self.alloc_probes(self.W * self.H)
+        self.torch.cuda.synchronize()
+
+    def zeros(self, shape, dtype):
+        return self.torch.zeros(shape, dtype=getattr(self.torch, dtype), device="cuda")
+
+    def ray_hits(self, shape):
+        """The `hits` probe (int32 x 6 per ray) as abi.ray_hit_dtype records of the given shape."""
+        return np.ascontiguousarray(self.hits.cpu().numpy()).view(np.uint32).view(abi.ray_hit_dtype).reshape(shape)
+
+    def resize(self, W, H):
+        self.ctx.resize(W, H)
+        self.W, self.H = W, H
+        self._alloc()
+        self.path.build()
+
+    def run(self, pfd, variant=1, resource_idx=0, pfds=None):
+        self.ctx.set_option(self.OPTION, variant)
+        self.resource_idx = resource_idx
+        for i, p in enumerate(pfds or [pfd]):
+            self.ctx.update_per_frame_ubo(i, p)
+        self.ctx.execute(0, 0)
+        self.ctx.synchronize()
+        return self.results()
+
+    def close(self):
+        self.path.destroy()
         self.ctx.close()

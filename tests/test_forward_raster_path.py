@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from tests import f2_scene
-from tests.test_rayquery_path import _sample, _srgb_decode_lut
+from tests.helpers import GpuForwardRig, albedo_and_shading_normal, bits, named_scene, sample_texture, srgb_store_bgra, srgb_decode_lut
 from vulkanhybridrenderer_amd import abi, camera, lib, scenes
 from vulkanhybridrenderer_amd.scenes import _Builder
 
@@ -42,7 +42,7 @@ def _srgb8(c):
 def resolve(msaa):
     """(..., 8, 4) B8G8R8A8_SRGB samples -> (..., 4): per channel the float32 mean, summed in sample order, of the decoded samples (colour
     from sRGB, alpha as UNORM), colour encoded with srgb8 and alpha as UNORM.  Returns (texels, margin of the colour encode)."""
-    lut = _srgb_decode_lut().astype(np.float32)
+    lut = srgb_decode_lut().astype(np.float32)
     acc = np.zeros(msaa.shape[:-2] + (4,), np.float32)
     for s in range(msaa.shape[-2]):
         acc[..., :3] += lut[msaa[..., s, :3]]
@@ -209,27 +209,19 @@ def _sample_dirs(pfd, x, fy, W, H, S):
 
 
 # --------------------------------------------------------------------------------------------- GPU
-class _Forward:
-    """A context with the path built, the shadow-map stand-in and the forward stand-in as its pass bodies, writing both probes."""
+class _Forward(GpuForwardRig):
+    """The forward raster path with the shadow-map stand-in and the forward stand-in as its pass bodies, writing both probes."""
+    OPTION = "variant_standin_forward_raster"
 
     def __init__(self, sc, W, H, msaa=1):
-        import torch
-        self.torch = torch
-        self.W, self.H, self.S = W, H, 8 if msaa else 1
-        self.ctx = lib.Context(W, H)
-        self.ctx.upload_scene(sc)
-        self.ctx.set_ray_statistics(True)
-        self.resource_idx = 0
-        self._alloc()
-        self.path = lib.ForwardRasterRenderPath(self.ctx, depth_prepass=self._prepass, forward_pass=self._body, enable_msaa=msaa)
-        self.path.build()
+        self.S = 8 if msaa else 1
+        super().__init__(sc, W, H)
 
-    def _alloc(self):
-        n = self.W * self.H
-        self.present = self.ctx.upload_new_storage_image(self.W, self.H, abi.FORMAT_B8G8R8A8_SRGB)
-        self.hits = self.torch.zeros((n * self.S, 6), dtype=self.torch.int32, device="cuda")
-        self.frags = self.torch.zeros(n, dtype=self.torch.uint8, device="cuda")
-        self.torch.cuda.synchronize()
+    def make_path(self):
+        return lib.ForwardRasterRenderPath(self.ctx, depth_prepass=self._prepass, forward_pass=self._body, enable_msaa=int(self.S == 8))
+
+    def alloc_probes(self, n):
+        self.hits, self.frags = self.zeros((n * self.S, 6), "int32"), self.zeros(n, "uint8")
 
     def _prepass(self, c):
         c.standin_shadow_map(self.resource_idx, SHADOW_MAP)
@@ -238,39 +230,17 @@ class _Forward:
         c.standin_forward_raster(self.present, self.resource_idx, msaa=MSAA if self.S == 8 else None, sample_hits_ptr=self.hits.data_ptr(),
                                  fragments_ptr=self.frags.data_ptr())
 
-    def resize(self, W, H):
-        self.ctx.resize(W, H)
-        self.W, self.H = W, H
-        self._alloc()
-        self.path.build()
-
-    def run(self, pfd, variant=1, resource_idx=0, pfds=None):
-        self.ctx.set_option("variant_standin_forward_raster", variant)
-        self.resource_idx = resource_idx
-        for i, p in enumerate(pfds or [pfd]):
-            self.ctx.update_per_frame_ubo(i, p)
-        self.ctx.execute(0, 0)
-        self.ctx.synchronize()
+    def results(self):
         H, W, S = self.H, self.W, self.S
-        hits = np.ascontiguousarray(self.hits.cpu().numpy()).view(np.uint32).view(abi.ray_hit_dtype).reshape(H, W, S)
-        depth = self.ctx.download(lib.DEPTH).reshape(H, W, S)
-        r = dict(out=self.ctx.download(self.present), depth=depth, hits=hits, frags=self.frags.cpu().numpy().reshape(H, W),
-                 stats=self.ctx.ray_statistics())
+        r = dict(out=self.ctx.download(self.present), depth=self.ctx.download(lib.DEPTH).reshape(H, W, S), hits=self.ray_hits((H, W, S)),
+                 frags=self.frags.cpu().numpy().reshape(H, W), stats=self.ctx.ray_statistics())
         r["msaa"] = self.ctx.download(MSAA) if S == 8 else r["out"].reshape(H, W, 1, 4)
         return r
-
-    def close(self):
-        self.path.destroy()
-        self.ctx.close()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint8)
 
 
 def _assert_same(a, b, what):
     for k in ("out", "depth", "hits", "frags", "msaa"):
-        assert np.array_equal(_bits(a[k]), _bits(b[k])), f"{what}: {k} differs"
+        assert np.array_equal(bits(a[k]), bits(b[k])), f"{what}: {k} differs"
     assert a["stats"] == b["stats"], what
 
 
@@ -294,17 +264,13 @@ def _check_invariants(r, W, H, S):
     return hit
 
 
-def _scene(name):
-    return {"f4": f2_scene.scene_f4, "f2": f2_scene.scene, "sponza": scenes.sponza_proc, "bistro": scenes.bistro_proc, "tiny": scenes.tiny_scene}[name]()
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("scene_name,W,H", [("f4", 160, 96), ("f4", 333, 177), ("f2", 203, 121), ("sponza", 480, 270), ("bistro", 333, 177)])
 @pytest.mark.parametrize("msaa", [1, 0])
 def test_gpu_queue_kernel_equals_literal_kernel(scene_name, W, H, msaa):
     """variant_standin_forward_raster 1 (work queue, default) and 0 (one pixel per thread): every output and both probes bit for bit, with deep and
     shallow LDS stacks (the second spills to scratch), at extents that are not multiples of the 16x8 tile."""
-    sc = _scene(scene_name)
+    sc = named_scene(scene_name)
     pfd = camera.dolly_frames(sc, W, H, 2)[1]
     f = _Forward(sc, W, H, msaa)
     try:
@@ -348,7 +314,7 @@ def _centre_alpha(sc, mats, prim, tri, cam, cdir):
     tvec = np.asarray(cam, np.float64) - pw[0]
     u, v = (tvec @ pvec) / det, (d @ np.cross(tvec, e1)) / det
     uv = sum(np.asarray(vs[k]["uv0"], np.float64) * b for k, b in enumerate((1 - u - v, u, v)))
-    return float(_sample(sc.textures[int(m["base_color_texture"])], np.array([uv[0]]), np.array([uv[1]]))[0, 3])
+    return float(sample_texture(sc.textures[int(m["base_color_texture"])], np.array([uv[0]]), np.array([uv[1]]))[0, 3])
 
 
 def _oracle_visibility(oracle, sc, pfd, W, H, S, pixels, tol=1e-4):
@@ -389,7 +355,7 @@ def _oracle_visibility(oracle, sc, pfd, W, H, S, pixels, tol=1e-4):
 def test_gpu_visibility_against_the_oracle(oracle, scene_name, W, H, step):
     """Per sample: the visible triangle and its t equal the oracle's tmin-stepped closest hit with the discard restated at the pixel
     centre, except samples that met a centre alpha within 1e-4 of the cutoff (counted, <= 0.01 %); depth is clip.z / clip.w of that t."""
-    sc = _scene(scene_name)
+    sc = named_scene(scene_name)
     pfd = camera.dolly_frames(sc, W, H, 2)[1]
     f = _Forward(sc, W, H)
     try:
@@ -436,32 +402,13 @@ def _restate_msaa(sc, pfd, r):
     b = np.stack([1.0 - u - v, u, v], 1)
     lerp = lambda field: sum(np.asarray(verts[k][field], np.float64) * b[:, k:k + 1] for k in range(3))    # noqa: E731
     normal, tangent, uv = lerp("normal"), lerp("tangent"), lerp("uv0")
-    mat = P["material"][prim]
-    albedo = np.asarray(mat["base_color"], np.float64)[:, :3].copy()
-    for t in np.unique(mat["base_color_texture"]):
-        if t >= 0:
-            m = mat["base_color_texture"] == t
-            albedo[m] = _sample(sc.textures[t], uv[m, 0], uv[m, 1])[:, :3]
-    N = normal.copy()
-    for t in np.unique(mat["normal_map"]):
-        if t >= 0:
-            m = mat["normal_map"] == t
-            tsn = _sample(sc.textures[t], uv[m, 0], uv[m, 1])[:, :3] * 2.0 - 1.0
-            tsn /= np.linalg.norm(tsn, axis=1, keepdims=True)
-            T, n = tangent[m, :3], normal[m]
-            bit = np.cross(tsn, T) * tangent[m, 3:4]
-            tg = T - n * (T * n).sum(1, keepdims=True)
-            tg /= np.linalg.norm(tg, axis=1, keepdims=True)
-            N[m] = tg * tsn[:, 0:1] + bit * tsn[:, 1:2] + n * tsn[:, 2:3]
+    albedo, N = albedo_and_shading_normal(sc, prim, normal, tangent, uv)
     light = pfd["directional_light"]
     L = -np.asarray(light["direction"], np.float64)[:3]
     lc = np.asarray(light["color"], np.float64)[:3]
     col = albedo / np.pi + np.maximum(N @ L, 0.0)[:, None] * albedo * lc
-    with np.errstate(invalid="ignore"):
-        enc = np.where(col <= 0.0031308, 12.92 * col, 1.055 * np.power(np.maximum(col, 0.0), 1 / 2.4) - 0.055)
-        q = np.where(col > 0.0, np.where(col >= 1.0, 255.0, np.floor(enc * 255.0 + 0.5)), 0.0)
     out = np.zeros((H, W, S, 4), np.uint8)
-    out[cov] = np.concatenate([q[:, ::-1], np.full((len(q), 1), 255.0)], 1).astype(np.uint8)
+    out[cov] = srgb_store_bgra(col)
     return out, cov
 
 
@@ -470,7 +417,7 @@ def _restate_msaa(sc, pfd, r):
 def test_gpu_colour_msaa_and_resolve(scene_name, W, H):
     """_MSAA texels against default.frag restated in float64 at the pixel centre (1 LSB on >= 99.9 % of the covered samples), misses
     exactly clear; the resolved output is the resolve of the downloaded _MSAA image, its alpha round(255 k / 8)."""
-    sc = _scene(scene_name)
+    sc = named_scene(scene_name)
     pfd = camera.dolly_frames(sc, W, H, 2)[1]
     f = _Forward(sc, W, H)
     try:
@@ -656,7 +603,7 @@ def test_gpu_single_sample_hits_equal_the_rayquery_standin(scene_name, W, H):
     """Without alpha-masked materials and without MSAA the sample is the pixel centre: its hit is the rayquery stand-in's primary hit
     bit for bit, rows flipped (framebuffer rows against the G-buffer's)."""
     import torch
-    sc = _scene(scene_name)
+    sc = named_scene(scene_name)
     pfd = camera.dolly_frames(sc, W, H, 2)[1]
     f = _Forward(sc, W, H, msaa=0)
     try:
@@ -678,8 +625,8 @@ def test_gpu_single_sample_hits_equal_the_rayquery_standin(scene_name, W, H):
     finally:
         path.destroy()
         ctx.close()
-    assert np.array_equal(_bits(r["hits"][:, :, 0]), _bits(rq[::-1]))
-    assert np.array_equal(_bits(r["depth"][:, :, 0]), _bits(rq_depth[::-1]))
+    assert np.array_equal(bits(r["hits"][:, :, 0]), bits(rq[::-1]))
+    assert np.array_equal(bits(r["depth"][:, :, 0]), bits(rq_depth[::-1]))
 
 
 @pytest.mark.gpu

@@ -9,34 +9,16 @@ source fingerprint in each.
   python tools/forward_raster_rate.py [--reps 20] [--warmup 3] [--out profiles/forward_raster_rate_1080p.jsonl]
 """
 import argparse
-import json
 import os
 import sys
-
-import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from rate_common import Records, kernel_timing, timed  # noqa: E402
 from vulkanhybridrenderer_amd import abi, camera, lib, scenes  # noqa: E402
 
 MSAA = "Forward Pass_MSAA"
-
-
-def timed(torch, stream, body, reps, warmup):
-    """Mean milliseconds of body() between HIP events recorded on `stream`, after `warmup` untimed calls."""
-    for _ in range(warmup):
-        body()
-    torch.cuda.synchronize()
-    start = [torch.cuda.Event(enable_timing=True) for _ in range(reps)]
-    stop = [torch.cuda.Event(enable_timing=True) for _ in range(reps)]
-    with torch.cuda.stream(stream):
-        for i in range(reps):
-            start[i].record(stream)
-            body()
-            stop[i].record(stream)
-    torch.cuda.synchronize()
-    return float(np.mean([a.elapsed_time(b) for a, b in zip(start, stop)]))
 
 
 def main():
@@ -50,14 +32,9 @@ def main():
     args = ap.parse_args()
     import torch
     W, H = args.width, args.height
-    fp = lib.source_fingerprint()
     stream = torch.cuda.Stream()
-    lines, res = [], {}
-
-    def emit(rec):
-        rec = dict(rec, width=W, height=H, frame=1, reps=args.reps, fingerprint=fp)
-        print(json.dumps(rec), flush=True)
-        lines.append(rec)
+    res = {}
+    emit = Records(args.out, width=W, height=H, frame=1, reps=args.reps, fingerprint=lib.source_fingerprint()).emit
 
     for scene_name in args.scenes.split(","):
         scene = getattr(scenes, scene_name)()
@@ -80,14 +57,10 @@ def main():
                 for variant in (1, 0):
                     ctx.set_option("variant_standin_forward_raster", variant)
                     wall = timed(torch, stream, run, args.reps, args.warmup)
-                    ctx.kernel_time("forward_raster", reset=True)
-                    ctx.set_kernel_timing(["forward_raster"])
-                    for _ in range(args.reps):
-                        run()
-                    ctx.synchronize()
-                    ctx.set_kernel_timing(False)
-                    ms, launches = ctx.kernel_time("forward_raster", reset=True)
-                    kms = ms / args.reps
+                    with kernel_timing(ctx, "forward_raster") as t:
+                        for _ in range(args.reps):
+                            run()
+                    kms = t.ms / args.reps
                     ctx.set_ray_statistics(True)
                     probe["on"] = True
                     run()
@@ -99,7 +72,7 @@ def main():
                     covered = f > 0
                     res[(scene_name, S, variant)] = kms
                     emit(dict(scene=scene_name, samples=S, kernel="forward_raster_queue_kernel" if variant else "forward_raster_kernel",
-                              kernel_ms=kms, launches_per_frame=launches / args.reps, wall_ms=wall, sample_rays=st["unique_rays"],
+                              kernel_ms=kms, launches_per_frame=t.launches / args.reps, wall_ms=wall, sample_rays=st["unique_rays"],
                               sample_rays_per_s=st["unique_rays"] / (kms * 1e-3), stack_overflows=st["stack_overflows"],
                               covered_pixels=int(covered.sum()), fragments_per_covered_pixel=float(f[covered].mean()) if covered.any() else 0.0))
             finally:
@@ -108,11 +81,6 @@ def main():
         q8, q1, l8 = res[(scene_name, 8, 1)], res[(scene_name, 1, 1)], res[(scene_name, 8, 0)]
         emit(dict(scene=scene_name, measure="targets", queue_s8_ms=q8, target_s8_ms=1.85, s8_within_target=q8 <= 1.85, queue_over_literal_s8=q8 / l8,
                   queue_faster_than_literal=q8 < l8, s8_over_s1=q8 / q1, s8_over_s1_within_5=q8 / q1 <= 5.0))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            for rec in lines:
-                f.write(json.dumps(rec) + "\n")
 
 
 if __name__ == "__main__":

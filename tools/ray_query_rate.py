@@ -14,7 +14,6 @@ per measurement, the library's source fingerprint in each.
   python tools/ray_query_rate.py [--reps 20] [--warmup 3] [--frames 20] [--out profiles/ray_query_rate.jsonl]
 """
 import argparse
-import json
 import os
 import sys
 
@@ -23,6 +22,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from rate_common import Records, kernel_timing  # noqa: E402
 from vulkanhybridrenderer_amd import lib, ray_queries, scenes  # noqa: E402
 from vulkanhybridrenderer_amd.harness import HybridFrameLoop  # noqa: E402
 
@@ -62,26 +62,17 @@ def main():
     import torch
     W, H = args.width, args.height
     scene = scenes.sponza_proc()
-    fp = lib.load().vhr_source_fingerprint().decode()
-    lines = []
-
-    def emit(rec):
-        rec = dict(rec, scene="sponza_proc", width=W, height=H, fingerprint=fp)
-        print(json.dumps(rec), flush=True)
-        lines.append(rec)
+    emit = Records(args.out, scene="sponza_proc", width=W, height=H, fingerprint=lib.source_fingerprint()).emit
 
     def k1(loop, what):
         ctx = loop.ctx
         for i in range(3):
             loop.frame(i)
         ctx.synchronize()
-        ctx.kernel_time("raygen", reset=True)
-        ctx.set_kernel_timing(["raygen"])
-        for i in range(args.frames):
-            loop.frame(i)
-        ctx.synchronize()
-        ctx.set_kernel_timing(False)
-        ms, launches = ctx.kernel_time("raygen", reset=True)
+        with kernel_timing(ctx, "raygen") as t:
+            for i in range(args.frames):
+                loop.frame(i)
+        ms, launches = t.ms, t.launches
         covered = float(np.mean([loop.covered_pixels[loop.frame_slot(i)] for i in range(args.frames)]))
         rays = covered * loop.rays_per_pixel
         rec = dict(measure=what, ms=ms / max(1, launches), launches=launches, rays=rays, ns_per_ray=ms / max(1, launches) * 1e6 / rays)
@@ -120,11 +111,6 @@ def main():
                 emit(r)
     finally:
         loop.close()
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            for rec in lines:
-                f.write(json.dumps(rec) + "\n")
 
 
 if __name__ == "__main__":

@@ -13,7 +13,6 @@ One JSON line per measure, the library's source fingerprint in each.
   python tools/rayquery_path_rate.py [--reps 30] [--warmup 5] [--out profiles/rayquery_path_rate_sponza_proc_1080p.jsonl]
 """
 import argparse
-import json
 import os
 import sys
 
@@ -22,23 +21,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from rate_common import Records, kernel_timing, timed  # noqa: E402
 from vulkanhybridrenderer_amd import abi, camera, lib, ray_queries, scenes  # noqa: E402
-
-
-def timed(torch, stream, body, reps, warmup):
-    """Mean milliseconds of body() between HIP events recorded on `stream`, after `warmup` untimed calls."""
-    for _ in range(warmup):
-        body()
-    torch.cuda.synchronize()
-    start = [torch.cuda.Event(enable_timing=True) for _ in range(reps)]
-    stop = [torch.cuda.Event(enable_timing=True) for _ in range(reps)]
-    with torch.cuda.stream(stream):
-        for i in range(reps):
-            start[i].record(stream)
-            body()
-            stop[i].record(stream)
-    torch.cuda.synchronize()
-    return float(np.mean([a.elapsed_time(b) for a, b in zip(start, stop)]))
 
 
 def main():
@@ -53,23 +37,13 @@ def main():
     W, H = args.width, args.height
     scene = scenes.sponza_proc()
     pfd = camera.dolly_frames(scene, W, H, 2)[1]
-    fp = lib.source_fingerprint()
-    lines = []
-
-    def emit(rec):
-        rec = dict(rec, scene="sponza_proc", width=W, height=H, frame=1, reps=args.reps, fingerprint=fp)
-        print(json.dumps(rec), flush=True)
-        lines.append(rec)
+    emit = Records(args.out, scene="sponza_proc", width=W, height=H, frame=1, reps=args.reps, fingerprint=lib.source_fingerprint()).emit
 
     def kernel_ms(ctx, kind, body):
-        ctx.kernel_time(kind, reset=True)
-        ctx.set_kernel_timing([kind])
-        for _ in range(args.reps):
-            body()
-        ctx.synchronize()
-        ctx.set_kernel_timing(False)
-        ms, launches = ctx.kernel_time(kind, reset=True)
-        return ms / args.reps, launches / args.reps
+        with kernel_timing(ctx, kind) as t:
+            for _ in range(args.reps):
+                body()
+        return t.ms / args.reps, t.launches / args.reps
 
     stream = torch.cuda.Stream()
     res = {}
@@ -147,11 +121,6 @@ def main():
 
     emit(dict(measure="ratios", a_over_b=res["a"] / res["b"], a_over_c=res["a"] / res["c"],
               target_a_below_b=res["a"] < res["b"], target_a_within_1_15_c=res["a"] <= 1.15 * res["c"]))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            for rec in lines:
-                f.write(json.dumps(rec) + "\n")
 
 
 if __name__ == "__main__":

@@ -17,7 +17,6 @@ Per scene, after one build and one refit that are not timed (the first calls loa
   python tools/refit_rate.py [--reps 12] [--frames 20] [--out profiles/refit_rate.jsonl] [--scenes sponza_proc,bistro_proc]
 """
 import argparse
-import json
 import os
 import sys
 import time
@@ -27,6 +26,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from rate_common import Records, kernel_timing  # noqa: E402
 from vulkanhybridrenderer_amd import abi, camera, lib, scenes  # noqa: E402
 
 COPY_CEILING_TBS = 5.5
@@ -56,15 +56,11 @@ class Frames:
             ctx.execute(0, 0)
         ctx.synchronize()
         wall = (time.perf_counter() - t0) * 1e3 / len(self.pfds)
-        ctx.kernel_time("raygen", reset=True)
-        ctx.set_kernel_timing(["raygen"])
-        for pfd in self.pfds:
-            ctx.update_per_frame_ubo(0, pfd)
-            ctx.execute(0, 0)
-        ctx.synchronize()
-        ctx.set_kernel_timing(False)
-        ms, launches = ctx.kernel_time("raygen", reset=True)
-        return wall, ms / max(1, launches)
+        with kernel_timing(ctx, "raygen") as t:
+            for pfd in self.pfds:
+                ctx.update_per_frame_ubo(0, pfd)
+                ctx.execute(0, 0)
+        return wall, t.ms / max(1, t.launches)
 
 
 def wave(scene, amplitude):
@@ -169,15 +165,7 @@ def main():
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("refit_rate: no GPU (this measurement has no CPU fallback)")
-    out = open(args.out, "w") if args.out else None
-
-    def emit(rec):
-        line = json.dumps(rec)
-        print(line, flush=True)
-        if out:
-            out.write(line + "\n")
-            out.flush()
-
+    emit = Records(args.out).emit
     for name in args.scenes.split(","):
         scene = scenes.bistro_proc(texture_size=64) if name == "bistro_proc" else getattr(scenes, name)()      # (full-size geometry; small texels: nothing timed here samples them)
         measure(name, scene, args, emit)

@@ -5,7 +5,7 @@
 //
 // Written against the vhr:: facade only (no access to library internals), i.e. exactly what a maintainer of
 // the reference would compile after swapping the Vulkan render graph for this one.
-#include "render_paths.hpp"
+#include "path_handle.hpp"
 
 #include <cstring>
 #include <string>
@@ -196,19 +196,7 @@ void HybridRenderPath::DeregisterPath(DeviceContext &, RenderGraph &, ResourceMa
 // ---------------------------------------------------------------------------------------------------------
 // C entry points (vhr_amd.h, "HybridRenderPath" section) for callers without a C++ toolchain
 // ---------------------------------------------------------------------------------------------------------
-struct vhr_hybrid_render_path {
-    vhr::DeviceContext context;
-    vhr::ResourceManager resource_manager;
-    vhr::RenderGraph render_graph;
-    vhr::HybridRenderPath path;
-    vhr_external_pass_callback gbuffer_cb = nullptr, composition_cb = nullptr;
-    void *gbuffer_user = nullptr, *composition_user = nullptr;
-    std::string error;
-    vhr_hybrid_render_path(vhr_context *ctx, uint32_t w, uint32_t h)
-        : context(ctx), resource_manager(context), render_graph(context, resource_manager), path(context, render_graph, resource_manager) {
-        context.swapchain.extent = { w, h };
-    }
-};
+struct vhr_hybrid_render_path : vhr::PathHandle<vhr::HybridRenderPath> { using PathHandle::PathHandle; };
 
 static void apply_settings(vhr_hybrid_render_path *p, const vhr_hybrid_settings *s) {
     p->path.shadow_mode = s->shadow_mode;
@@ -218,56 +206,26 @@ static void apply_settings(vhr_hybrid_render_path *p, const vhr_hybrid_settings 
     p->path.atrous_steps = s->atrous_steps > 0 ? s->atrous_steps : 5;
 }
 
-template <typename F>
-static int guarded(vhr_hybrid_render_path *p, F &&f) {
-    try {
-        f();
-        return VHR_OK;
-    } catch (const std::exception &e) {
-        p->error = e.what();
-        return VHR_ERROR_GRAPH;
-    }
-}
-
 extern "C" {
 
 int vhr_hybrid_create(vhr_context *ctx, const vhr_hybrid_settings *settings, vhr_external_pass_callback gbuffer_pass, void *gbuffer_user,
                       vhr_external_pass_callback composition_pass, void *composition_user, vhr_hybrid_render_path **out) {
-    if (!ctx || !settings || !out) return VHR_ERROR_INVALID_ARGUMENT;
-    uint32_t w = 0, h = 0;
-    if (vhr_get_display_size(ctx, &w, &h) < 0) return VHR_ERROR_INVALID_ARGUMENT;
-    auto *p = new vhr_hybrid_render_path(ctx, w, h);
-    apply_settings(p, settings);
-    p->gbuffer_cb = gbuffer_pass; p->gbuffer_user = gbuffer_user;
-    p->composition_cb = composition_pass; p->composition_user = composition_user;
-    if (gbuffer_pass) p->path.gbuffer_pass = [p](vhr::DeviceContext &c) { p->gbuffer_cb(p->gbuffer_user, c.handle); };
-    if (composition_pass) p->path.composition_pass = [p](vhr::DeviceContext &c) { p->composition_cb(p->composition_user, c.handle); };
-    *out = p;
+    if (!settings) return VHR_ERROR_INVALID_ARGUMENT;
+    const int rc = vhr::path_create(ctx, out);
+    if (rc < 0) return rc;
+    apply_settings(*out, settings);
+    (*out)->Bind(0, &vhr::HybridRenderPath::gbuffer_pass, gbuffer_pass, gbuffer_user);
+    (*out)->Bind(1, &vhr::HybridRenderPath::composition_pass, composition_pass, composition_user);
     return VHR_OK;
 }
 
-void vhr_hybrid_destroy(vhr_hybrid_render_path *p) {
-    if (!p) return;
-    try {
-        p->path.DeregisterPath(p->context, p->render_graph, p->resource_manager);
-        p->render_graph.DestroyResources();
-    } catch (...) {
-    }
-    delete p;
-}
+void vhr_hybrid_destroy(vhr_hybrid_render_path *p) { vhr::path_destroy(p); }
 
-int vhr_hybrid_build(vhr_hybrid_render_path *p) {
-    if (!p) return VHR_ERROR_INVALID_ARGUMENT;
-    // (the display extent as the context has it NOW: after vhr_resize this is the second half of the reference's resize route, renderer.cpp:113-118)
-    uint32_t w = 0, h = 0;
-    if (vhr_get_display_size(p->context.handle, &w, &h) < 0) return VHR_ERROR_INVALID_ARGUMENT;
-    p->context.swapchain.extent = { w, h };
-    return guarded(p, [&] { p->path.Build(); });
-}
+int vhr_hybrid_build(vhr_hybrid_render_path *p) { return vhr::path_build(p); }
 
 int vhr_hybrid_rebuild(vhr_hybrid_render_path *p, const vhr_hybrid_settings *settings) {
     if (!p) return VHR_ERROR_INVALID_ARGUMENT;
-    return guarded(p, [&] {
+    return vhr::guarded(p, [&] {
         // the UI applies the new modes, then calls Rebuild() (hybrid_render_path.cpp:394-441)
         p->path.DeregisterPath(p->context, p->render_graph, p->resource_manager);
         if (settings) apply_settings(p, settings);
@@ -281,7 +239,7 @@ int vhr_hybrid_get_push_constants(vhr_hybrid_render_path *p, vhr_svgf_push_const
     return VHR_OK;
 }
 
-const char *vhr_hybrid_last_error(vhr_hybrid_render_path *p) { return p ? p->error.c_str() : ""; }
+const char *vhr_hybrid_last_error(vhr_hybrid_render_path *p) { return vhr::path_last_error(p); }
 
 }  // extern "C"
 
@@ -298,7 +256,7 @@ struct SvgfStateHeader {
 constexpr char kStateMagic[8] = { 'V', 'H', 'R', 'S', 'V', 'G', 'F', '1' };
 
 // the five images in blob order, as the NEXT frame addresses them (the frame-start order of the ping-pong pair, :328)
-int svgf_state_images(vhr_context *ctx, const vhr::HybridRenderPath &path, int32_t ids[5], vhr_image_info info[5], std::string &error) {
+int svgf_state_images(vhr_context *ctx, const vhr::HybridRenderPath &path, int32_t ids[5], vhr_image_info info[5], uint64_t image_bytes[5], std::string &error) {
     if (!path.svgf_textures_created) { error = "SVGF state: the path has no SVGF images (denoise off, or not built)"; return VHR_ERROR_GRAPH; }
     const vhr::SVGFPushConstants &pc = path.svgf_push_constants;
     ids[0] = pc.integrated_shadow_and_ao[0]; ids[1] = pc.integrated_shadow_and_ao[1]; ids[2] = pc.prev_frame_normals_and_object_ids;
@@ -306,31 +264,31 @@ int svgf_state_images(vhr_context *ctx, const vhr::HybridRenderPath &path, int32
     for (int i = 0; i < 5; ++i) {
         const int rc = vhr_get_storage_image(ctx, ids[i], &info[i]);
         if (rc < 0) { error = std::string("SVGF state: ") + vhr_last_error(ctx); return rc; }
+        image_bytes[i] = uint64_t(info[i].width) * info[i].height * info[i].bytes_per_pixel;
     }
     return VHR_OK;
 }
 
 int svgf_state_size(vhr_context *ctx, const vhr::HybridRenderPath &path, uint64_t *bytes, std::string &error) {
-    int32_t ids[5]; vhr_image_info info[5];
-    const int rc = svgf_state_images(ctx, path, ids, info, error);
+    int32_t ids[5]; vhr_image_info info[5]; uint64_t image_bytes[5];
+    const int rc = svgf_state_images(ctx, path, ids, info, image_bytes, error);
     if (rc < 0) return rc;
     uint64_t total = sizeof(SvgfStateHeader);
-    for (int i = 0; i < 5; ++i) total += uint64_t(info[i].width) * info[i].height * info[i].bytes_per_pixel;
+    for (int i = 0; i < 5; ++i) total += image_bytes[i];
     *bytes = total;
     return VHR_OK;
 }
 
 int svgf_state_save(vhr_context *ctx, const vhr::HybridRenderPath &path, void *blob, uint64_t bytes, std::string &error) {
     int32_t ids[5]; vhr_image_info info[5];
-    int rc = svgf_state_images(ctx, path, ids, info, error);
-    if (rc < 0) return rc;
     SvgfStateHeader h{};
+    int rc = svgf_state_images(ctx, path, ids, info, h.image_bytes, error);
+    if (rc < 0) return rc;
     std::memcpy(h.magic, kStateMagic, 8);
     h.version = 1; h.width = info[0].width; h.height = info[0].height; h.image_count = 5;
     h.total_bytes = sizeof h;
     for (int i = 0; i < 5; ++i) {
         h.format[i] = info[i].format;
-        h.image_bytes[i] = uint64_t(info[i].width) * info[i].height * info[i].bytes_per_pixel;
         h.total_bytes += h.image_bytes[i];
     }
     if (bytes != h.total_bytes) { error = "SVGF state: the blob must hold exactly vhr_hybrid_state_size bytes"; return VHR_ERROR_INVALID_ARGUMENT; }
@@ -348,8 +306,8 @@ int svgf_state_save(vhr_context *ctx, const vhr::HybridRenderPath &path, void *b
 }
 
 int svgf_state_load(vhr_context *ctx, const vhr::HybridRenderPath &path, const void *blob, uint64_t bytes, vhr_per_frame_data *last_frame, std::string &error) {
-    int32_t ids[5]; vhr_image_info info[5];
-    int rc = svgf_state_images(ctx, path, ids, info, error);
+    int32_t ids[5]; vhr_image_info info[5]; uint64_t image_bytes[5];
+    int rc = svgf_state_images(ctx, path, ids, info, image_bytes, error);
     if (rc < 0) return rc;
     SvgfStateHeader h;
     if (bytes < sizeof h) { error = "SVGF state: blob shorter than its header"; return VHR_ERROR_INVALID_ARGUMENT; }
@@ -358,8 +316,7 @@ int svgf_state_load(vhr_context *ctx, const vhr::HybridRenderPath &path, const v
     if (h.total_bytes != bytes) { error = "SVGF state: byte count differs from the header's"; return VHR_ERROR_INVALID_ARGUMENT; }
     uint64_t total = sizeof h;
     for (int i = 0; i < 5; ++i) {
-        if (h.width != info[i].width || h.height != info[i].height || h.format[i] != info[i].format ||
-            h.image_bytes[i] != uint64_t(info[i].width) * info[i].height * info[i].bytes_per_pixel) {
+        if (h.width != info[i].width || h.height != info[i].height || h.format[i] != info[i].format || h.image_bytes[i] != image_bytes[i]) {
             error = "SVGF state: the blob was saved from a path of another extent or image format";
             return VHR_ERROR_INVALID_ARGUMENT;
         }

@@ -4,10 +4,7 @@
 // query) stays with the integrator, and vhr_standin_rayquery_forward is the library's stand-in for it.
 //
 // Written against the vhr:: facade only, like hybrid_render_path.cpp.
-#include "render_paths.hpp"
-
-#include <string>
-#include <utility>
+#include "path_handle.hpp"
 
 namespace vhr {
 
@@ -25,69 +22,26 @@ void RayqueryRenderPath::DeregisterPath(DeviceContext &, RenderGraph &, Resource
 // ---------------------------------------------------------------------------------------------------------
 // C entry points (vhr_amd.h, "RayqueryRenderPath" section) for callers without a C++ toolchain
 // ---------------------------------------------------------------------------------------------------------
-struct vhr_rayquery_render_path {
-    vhr::DeviceContext context;
-    vhr::ResourceManager resource_manager;
-    vhr::RenderGraph render_graph;
-    vhr::RayqueryRenderPath path;
-    vhr_external_pass_callback forward_cb = nullptr;
-    void *forward_user = nullptr;
-    std::string error;
-    vhr_rayquery_render_path(vhr_context *ctx, uint32_t w, uint32_t h)
-        : context(ctx), resource_manager(context), render_graph(context, resource_manager), path(context, render_graph, resource_manager) {
-        context.swapchain.extent = { w, h };
-    }
-};
-
-template <typename F>
-static int guarded(vhr_rayquery_render_path *p, F &&f) {
-    try {
-        f();
-        return VHR_OK;
-    } catch (const std::exception &e) {
-        p->error = e.what();
-        return VHR_ERROR_GRAPH;
-    }
-}
+struct vhr_rayquery_render_path : vhr::PathHandle<vhr::RayqueryRenderPath> { using PathHandle::PathHandle; };
 
 extern "C" {
 
 int vhr_rayquery_create(vhr_context *ctx, vhr_external_pass_callback forward_pass, void *forward_user, vhr_rayquery_render_path **out) {
-    if (!ctx || !out) return VHR_ERROR_INVALID_ARGUMENT;
-    uint32_t w = 0, h = 0;
-    if (vhr_get_display_size(ctx, &w, &h) < 0) return VHR_ERROR_INVALID_ARGUMENT;
-    auto *p = new vhr_rayquery_render_path(ctx, w, h);
-    p->forward_cb = forward_pass;
-    p->forward_user = forward_user;
-    if (forward_pass) p->path.forward_pass = [p](vhr::DeviceContext &c) { p->forward_cb(p->forward_user, c.handle); };
-    *out = p;
+    const int rc = vhr::path_create(ctx, out);
+    if (rc < 0) return rc;
+    (*out)->Bind(0, &vhr::RayqueryRenderPath::forward_pass, forward_pass, forward_user);
     return VHR_OK;
 }
 
-void vhr_rayquery_destroy(vhr_rayquery_render_path *p) {
-    if (!p) return;
-    try {
-        p->path.DeregisterPath(p->context, p->render_graph, p->resource_manager);
-        p->render_graph.DestroyResources();
-    } catch (...) {
-    }
-    delete p;
-}
+void vhr_rayquery_destroy(vhr_rayquery_render_path *p) { vhr::path_destroy(p); }
 
-int vhr_rayquery_build(vhr_rayquery_render_path *p) {
-    if (!p) return VHR_ERROR_INVALID_ARGUMENT;
-    // (the display extent as the context has it NOW: after vhr_resize this is the second half of the reference's resize route, renderer.cpp:113-118)
-    uint32_t w = 0, h = 0;
-    if (vhr_get_display_size(p->context.handle, &w, &h) < 0) return VHR_ERROR_INVALID_ARGUMENT;
-    p->context.swapchain.extent = { w, h };
-    return guarded(p, [&] { p->path.Build(); });
-}
+int vhr_rayquery_build(vhr_rayquery_render_path *p) { return vhr::path_build(p); }
 
 int vhr_rayquery_rebuild(vhr_rayquery_render_path *p) {
     if (!p) return VHR_ERROR_INVALID_ARGUMENT;
-    return guarded(p, [&] { p->path.Rebuild(); });
+    return vhr::guarded(p, [&] { p->path.Rebuild(); });
 }
 
-const char *vhr_rayquery_last_error(vhr_rayquery_render_path *p) { return p ? p->error.c_str() : ""; }
+const char *vhr_rayquery_last_error(vhr_rayquery_render_path *p) { return vhr::path_last_error(p); }
 
 }  // extern "C"

@@ -3,10 +3,7 @@
 // DeregisterPath :79 (owns nothing), use_anyhit_shader toggle :81-93.
 //
 // Written against the vhr:: facade only, like hybrid_render_path.cpp.
-#include "render_paths.hpp"
-
-#include <string>
-#include <utility>
+#include "path_handle.hpp"
 
 namespace vhr {
 
@@ -49,74 +46,31 @@ void RaytracedRenderPath::DeregisterPath(DeviceContext &, RenderGraph &, Resourc
 // ---------------------------------------------------------------------------------------------------------
 // C entry points (vhr_amd.h, "RaytracedRenderPath" section) for callers without a C++ toolchain
 // ---------------------------------------------------------------------------------------------------------
-struct vhr_raytraced_render_path {
-    vhr::DeviceContext context;
-    vhr::ResourceManager resource_manager;
-    vhr::RenderGraph render_graph;
-    vhr::RaytracedRenderPath path;
-    vhr_external_pass_callback composition_cb = nullptr;
-    void *composition_user = nullptr;
-    std::string error;
-    vhr_raytraced_render_path(vhr_context *ctx, uint32_t w, uint32_t h)
-        : context(ctx), resource_manager(context), render_graph(context, resource_manager), path(context, render_graph, resource_manager) {
-        context.swapchain.extent = { w, h };
-    }
-};
-
-template <typename F>
-static int guarded(vhr_raytraced_render_path *p, F &&f) {
-    try {
-        f();
-        return VHR_OK;
-    } catch (const std::exception &e) {
-        p->error = e.what();
-        return VHR_ERROR_GRAPH;
-    }
-}
+struct vhr_raytraced_render_path : vhr::PathHandle<vhr::RaytracedRenderPath> { using PathHandle::PathHandle; };
 
 extern "C" {
 
 int vhr_raytraced_create(vhr_context *ctx, int32_t use_anyhit_shader, vhr_external_pass_callback composition_pass, void *composition_user,
                          vhr_raytraced_render_path **out) {
-    if (!ctx || !out) return VHR_ERROR_INVALID_ARGUMENT;
-    uint32_t w = 0, h = 0;
-    if (vhr_get_display_size(ctx, &w, &h) < 0) return VHR_ERROR_INVALID_ARGUMENT;
-    auto *p = new vhr_raytraced_render_path(ctx, w, h);
-    p->path.use_anyhit_shader = use_anyhit_shader != 0;
-    p->composition_cb = composition_pass;
-    p->composition_user = composition_user;
-    if (composition_pass) p->path.composition_pass = [p](vhr::DeviceContext &c) { p->composition_cb(p->composition_user, c.handle); };
-    *out = p;
+    const int rc = vhr::path_create(ctx, out);
+    if (rc < 0) return rc;
+    (*out)->path.use_anyhit_shader = use_anyhit_shader != 0;
+    (*out)->Bind(0, &vhr::RaytracedRenderPath::composition_pass, composition_pass, composition_user);
     return VHR_OK;
 }
 
-void vhr_raytraced_destroy(vhr_raytraced_render_path *p) {
-    if (!p) return;
-    try {
-        p->path.DeregisterPath(p->context, p->render_graph, p->resource_manager);
-        p->render_graph.DestroyResources();
-    } catch (...) {
-    }
-    delete p;
-}
+void vhr_raytraced_destroy(vhr_raytraced_render_path *p) { vhr::path_destroy(p); }
 
-int vhr_raytraced_build(vhr_raytraced_render_path *p) {
-    if (!p) return VHR_ERROR_INVALID_ARGUMENT;
-    // (the display extent as the context has it NOW: after vhr_resize this is the second half of the reference's resize route, renderer.cpp:113-118)
-    uint32_t w = 0, h = 0;
-    if (vhr_get_display_size(p->context.handle, &w, &h) < 0) return VHR_ERROR_INVALID_ARGUMENT;
-    p->context.swapchain.extent = { w, h };
-    return guarded(p, [&] { p->path.Build(); });
-}
+int vhr_raytraced_build(vhr_raytraced_render_path *p) { return vhr::path_build(p); }
 
 int vhr_raytraced_rebuild(vhr_raytraced_render_path *p, int32_t use_anyhit_shader) {
     if (!p) return VHR_ERROR_INVALID_ARGUMENT;
-    return guarded(p, [&] {
+    return vhr::guarded(p, [&] {
         p->path.use_anyhit_shader = use_anyhit_shader != 0;      // the radio button, then Rebuild() (:90-92)
         p->path.Rebuild();
     });
 }
 
-const char *vhr_raytraced_last_error(vhr_raytraced_render_path *p) { return p ? p->error.c_str() : ""; }
+const char *vhr_raytraced_last_error(vhr_raytraced_render_path *p) { return vhr::path_last_error(p); }
 
 }  // extern "C"

@@ -44,6 +44,8 @@ EXPORTS = [
     "vhr_get_bvh_sah_cost",
 ]
 
+PATH_PREFIXES = ("hybrid", "raytraced", "rayquery", "forward_raster")      # vhr_<prefix>_{create,destroy,build,rebuild,last_error}
+
 
 class VhrError(RuntimeError):
     pass
@@ -213,14 +215,15 @@ def load():
     L.vhr_compute_blit_image_storage_to_transient.argtypes = [vp, i32, C.c_char_p]
     L.vhr_compute_blit_image_transient_to_storage.argtypes = [vp, C.c_char_p, i32]
     L.vhr_compute_blit_image_storage_to_storage.argtypes = [vp, i32, i32]
+    for prefix in PATH_PREFIXES:         # what every render path's C entry points share (csrc/path_handle.hpp); create / rebuild differ and follow
+        getattr(L, f"vhr_{prefix}_destroy").argtypes = [vp]
+        getattr(L, f"vhr_{prefix}_destroy").restype = None
+        getattr(L, f"vhr_{prefix}_build").argtypes = [vp]
+        getattr(L, f"vhr_{prefix}_last_error").argtypes = [vp]
+        getattr(L, f"vhr_{prefix}_last_error").restype = C.c_char_p
     L.vhr_hybrid_create.argtypes = [vp, C.POINTER(HybridSettings), EXTERNAL_CB, vp, EXTERNAL_CB, vp, C.POINTER(vp)]
-    L.vhr_hybrid_destroy.argtypes = [vp]
-    L.vhr_hybrid_destroy.restype = None
-    L.vhr_hybrid_build.argtypes = [vp]
     L.vhr_hybrid_rebuild.argtypes = [vp, C.POINTER(HybridSettings)]
     L.vhr_hybrid_get_push_constants.argtypes = [vp, vp]
-    L.vhr_hybrid_last_error.argtypes = [vp]
-    L.vhr_hybrid_last_error.restype = C.c_char_p
     L.vhr_hybrid_state_size.argtypes = [vp, C.POINTER(u64)]
     L.vhr_hybrid_save_state.argtypes = [vp, vp, u64]
     L.vhr_hybrid_load_state.argtypes = [vp, vp, u64, vp]
@@ -238,28 +241,13 @@ def load():
     L.vhr_standin_raytraced_composition.argtypes = [vp, C.c_char_p, i32]
     L.vhr_standin_shadow_map.argtypes = [vp, u32, C.c_char_p]
     L.vhr_raytraced_create.argtypes = [vp, i32, EXTERNAL_CB, vp, C.POINTER(vp)]
-    L.vhr_raytraced_destroy.argtypes = [vp]
-    L.vhr_raytraced_destroy.restype = None
-    L.vhr_raytraced_build.argtypes = [vp]
     L.vhr_raytraced_rebuild.argtypes = [vp, i32]
-    L.vhr_raytraced_last_error.argtypes = [vp]
-    L.vhr_raytraced_last_error.restype = C.c_char_p
     L.vhr_standin_rayquery_forward.argtypes = [vp, u32, C.POINTER(RayqueryForwardDesc)]
     L.vhr_rayquery_create.argtypes = [vp, EXTERNAL_CB, vp, C.POINTER(vp)]
-    L.vhr_rayquery_destroy.argtypes = [vp]
-    L.vhr_rayquery_destroy.restype = None
-    L.vhr_rayquery_build.argtypes = [vp]
     L.vhr_rayquery_rebuild.argtypes = [vp]
-    L.vhr_rayquery_last_error.argtypes = [vp]
-    L.vhr_rayquery_last_error.restype = C.c_char_p
     L.vhr_standin_forward_raster.argtypes = [vp, u32, C.POINTER(ForwardRasterDesc)]
     L.vhr_forward_raster_create.argtypes = [vp, EXTERNAL_CB, vp, EXTERNAL_CB, vp, i32, C.POINTER(vp)]
-    L.vhr_forward_raster_destroy.argtypes = [vp]
-    L.vhr_forward_raster_destroy.restype = None
-    L.vhr_forward_raster_build.argtypes = [vp]
     L.vhr_forward_raster_rebuild.argtypes = [vp, i32]
-    L.vhr_forward_raster_last_error.argtypes = [vp]
-    L.vhr_forward_raster_last_error.restype = C.c_char_p
     L.vhr_get_transient_image_samples.argtypes = [vp, C.c_char_p, C.POINTER(u32)]
     L.vhr_set_strip.argtypes = [vp, u32, u32, u32, u32]
     L.vhr_set_tile.argtypes = [vp, u32, u32, u32, u32, u32, u32, u32]
@@ -908,30 +896,57 @@ class ComputeExecutionContext:
         self.ctx.check(self.ctx.L.vhr_compute_blit_image_storage_to_storage(self.handle, src, dst), "BlitImageStorageToStorage")
 
 
-class HybridRenderPath:
-    """vhr_hybrid_*: the C++ re-host of HybridRenderPath (csrc/hybrid_render_path.cpp)."""
+class _RenderPath:
+    """What the four vhr_<PREFIX>_* bindings share: the handle, its error text, build and destroy.  A binding is named like its C++
+    class: errors quote that name."""
+    PREFIX = None
 
-    def __init__(self, ctx, shadow_mode=0, ambient_occlusion_mode=2, reflection_mode=2, denoise=False, atrous_steps=5,
-                 gbuffer_pass=None, composition_pass=None):
-        self.ctx = ctx
-        self.settings = HybridSettings(shadow_mode, ambient_occlusion_mode, reflection_mode, int(denoise), atrous_steps)
-        self._g = EXTERNAL_CB(lambda user, c: ctx._guard(lambda: gbuffer_pass(ctx))) if gbuffer_pass else EXTERNAL_CB()
-        self._c = EXTERNAL_CB(lambda user, c: ctx._guard(lambda: composition_pass(ctx))) if composition_pass else EXTERNAL_CB()
-        self.handle = C.c_void_p()
-        ctx.check(ctx.L.vhr_hybrid_create(ctx.handle, C.byref(self.settings), self._g, None, self._c, None, C.byref(self.handle)),
-                  "vhr_hybrid_create")
+    def __init__(self, ctx):
+        self.ctx, self.handle, self._callbacks = ctx, C.c_void_p(), []
+
+    def _create(self, *args):
+        self.ctx.check(self._fn("create")(self.ctx.handle, *args, C.byref(self.handle)), f"vhr_{self.PREFIX}_create")
+
+    def _callback(self, body):
+        """An optional Python pass body `body(ctx)` as the C callback and its user pointer.  ctypes callbacks must outlive the handle: kept here."""
+        ctx = self.ctx
+        cb = EXTERNAL_CB(lambda user, c: ctx._guard(lambda: body(ctx))) if body else EXTERNAL_CB()
+        self._callbacks.append(cb)
+        return cb, None
+
+    def _fn(self, name):
+        return getattr(self.ctx.L, f"vhr_{self.PREFIX}_{name}")
 
     def _check(self, rc, what):
         if rc < 0:
-            raise VhrError(f"{what}: {self.ctx.L.vhr_hybrid_last_error(self.handle).decode()}")
+            raise VhrError(f"{what}: {self._fn('last_error')(self.handle).decode()}")
 
     def build(self):
-        self._check(self.ctx.L.vhr_hybrid_build(self.handle), "HybridRenderPath::Build")
+        self._check(self._fn("build")(self.handle), f"{type(self).__name__}::Build")
+
+    def _rebuild(self, *args):
+        self._check(self._fn("rebuild")(self.handle, *args), f"{type(self).__name__}::Rebuild")
+
+    def destroy(self):
+        if self.handle:
+            self._fn("destroy")(self.handle)
+            self.handle = None
+
+
+class HybridRenderPath(_RenderPath):
+    """vhr_hybrid_*: the C++ re-host of HybridRenderPath (csrc/hybrid_render_path.cpp)."""
+    PREFIX = "hybrid"
+
+    def __init__(self, ctx, shadow_mode=0, ambient_occlusion_mode=2, reflection_mode=2, denoise=False, atrous_steps=5,
+                 gbuffer_pass=None, composition_pass=None):
+        super().__init__(ctx)
+        self.settings = HybridSettings(shadow_mode, ambient_occlusion_mode, reflection_mode, int(denoise), atrous_steps)
+        self._create(C.byref(self.settings), *self._callback(gbuffer_pass), *self._callback(composition_pass))
 
     def rebuild(self, **changes):
         for k, v in changes.items():
             setattr(self.settings, k, int(v))
-        self._check(self.ctx.L.vhr_hybrid_rebuild(self.handle, C.byref(self.settings)), "HybridRenderPath::Rebuild")
+        self._rebuild(C.byref(self.settings))
 
     def push_constants(self):
         pc = np.zeros((), abi.svgf_push_constants_dtype)
@@ -953,97 +968,50 @@ class HybridRenderPath:
         self._check(self.ctx.L.vhr_hybrid_load_state(self.handle, _p(blob), blob.size, _p(last)), "vhr_hybrid_load_state")
         return last
 
-    def destroy(self):
-        if self.handle:
-            self.ctx.L.vhr_hybrid_destroy(self.handle)
-            self.handle = None
 
-
-class RaytracedRenderPath:
+class RaytracedRenderPath(_RenderPath):
     """vhr_raytraced_*: the C++ re-host of RaytracedRenderPath (csrc/raytraced_render_path.cpp)."""
+    PREFIX = "raytraced"
 
     def __init__(self, ctx, use_anyhit_shader=False, composition_pass=None):
-        self.ctx = ctx
+        super().__init__(ctx)
         self.use_anyhit_shader = bool(use_anyhit_shader)
-        self._c = EXTERNAL_CB(lambda user, c: ctx._guard(lambda: composition_pass(ctx))) if composition_pass else EXTERNAL_CB()
-        self.handle = C.c_void_p()
-        ctx.check(ctx.L.vhr_raytraced_create(ctx.handle, int(self.use_anyhit_shader), self._c, None, C.byref(self.handle)),
-                  "vhr_raytraced_create")
-
-    def _check(self, rc, what):
-        if rc < 0:
-            raise VhrError(f"{what}: {self.ctx.L.vhr_raytraced_last_error(self.handle).decode()}")
-
-    def build(self):
-        self._check(self.ctx.L.vhr_raytraced_build(self.handle), "RaytracedRenderPath::Build")
+        self._create(int(self.use_anyhit_shader), *self._callback(composition_pass))
 
     def rebuild(self, use_anyhit_shader):
         self.use_anyhit_shader = bool(use_anyhit_shader)
-        self._check(self.ctx.L.vhr_raytraced_rebuild(self.handle, int(self.use_anyhit_shader)), "RaytracedRenderPath::Rebuild")
-
-    def destroy(self):
-        if self.handle:
-            self.ctx.L.vhr_raytraced_destroy(self.handle)
-            self.handle = None
+        self._rebuild(int(self.use_anyhit_shader))
 
 
-class RayqueryRenderPath:
+class RayqueryRenderPath(_RenderPath):
     """vhr_rayquery_*: the C++ re-host of RayqueryRenderPath (csrc/rayquery_render_path.cpp): one external "Forward Pass" whose body
     (`forward_pass(ctx)`, e.g. calling Context.standin_rayquery_forward) is the integrator's."""
+    PREFIX = "rayquery"
 
     def __init__(self, ctx, forward_pass=None):
-        self.ctx = ctx
-        self._f = EXTERNAL_CB(lambda user, c: ctx._guard(lambda: forward_pass(ctx))) if forward_pass else EXTERNAL_CB()
-        self.handle = C.c_void_p()
-        ctx.check(ctx.L.vhr_rayquery_create(ctx.handle, self._f, None, C.byref(self.handle)), "vhr_rayquery_create")
-
-    def _check(self, rc, what):
-        if rc < 0:
-            raise VhrError(f"{what}: {self.ctx.L.vhr_rayquery_last_error(self.handle).decode()}")
-
-    def build(self):
-        self._check(self.ctx.L.vhr_rayquery_build(self.handle), "RayqueryRenderPath::Build")
+        super().__init__(ctx)
+        self._create(*self._callback(forward_pass))
 
     def rebuild(self):
-        self._check(self.ctx.L.vhr_rayquery_rebuild(self.handle), "RayqueryRenderPath::Rebuild")
-
-    def destroy(self):
-        if self.handle:
-            self.ctx.L.vhr_rayquery_destroy(self.handle)
-            self.handle = None
+        self._rebuild()
 
 
-class ForwardRasterRenderPath:
+class ForwardRasterRenderPath(_RenderPath):
     """vhr_forward_raster_*: the C++ re-host of ForwardRasterRenderPath (csrc/forward_raster_render_path.cpp): the external passes "Depth
     Prepass" (`depth_prepass(ctx)`, e.g. calling Context.standin_shadow_map) and "Forward Pass" (`forward_pass(ctx)`, e.g. calling
     Context.standin_forward_raster), their bodies the integrator's; `enable_msaa` makes RENDER_OUTPUT and "Depth" 8-sample images."""
+    PREFIX = "forward_raster"
 
     def __init__(self, ctx, depth_prepass=None, forward_pass=None, enable_msaa=1):
-        self.ctx = ctx
+        super().__init__(ctx)
         self.enable_msaa = int(enable_msaa)
-        self._d = EXTERNAL_CB(lambda user, c: ctx._guard(lambda: depth_prepass(ctx))) if depth_prepass else EXTERNAL_CB()
-        self._f = EXTERNAL_CB(lambda user, c: ctx._guard(lambda: forward_pass(ctx))) if forward_pass else EXTERNAL_CB()
-        self.handle = C.c_void_p()
-        ctx.check(ctx.L.vhr_forward_raster_create(ctx.handle, self._d, None, self._f, None, self.enable_msaa, C.byref(self.handle)),
-                  "vhr_forward_raster_create")
-
-    def _check(self, rc, what):
-        if rc < 0:
-            raise VhrError(f"{what}: {self.ctx.L.vhr_forward_raster_last_error(self.handle).decode()}")
-
-    def build(self):
-        self._check(self.ctx.L.vhr_forward_raster_build(self.handle), "ForwardRasterRenderPath::Build")
+        self._create(*self._callback(depth_prepass), *self._callback(forward_pass), self.enable_msaa)
 
     def rebuild(self, enable_msaa=None):
         """The ImGui radio button (forward_raster_render_path.cpp:99-111): set enable_msaa (None = keep it), then Rebuild()."""
         if enable_msaa is not None:
             self.enable_msaa = int(enable_msaa)
-        self._check(self.ctx.L.vhr_forward_raster_rebuild(self.handle, self.enable_msaa), "ForwardRasterRenderPath::Rebuild")
-
-    def destroy(self):
-        if self.handle:
-            self.ctx.L.vhr_forward_raster_destroy(self.handle)
-            self.handle = None
+        self._rebuild(self.enable_msaa)
 
 
 def strip_plan(height, world, rank, max_motion_rows, atrous_steps=5):
