@@ -778,6 +778,27 @@ int vhr_get_refit_statistics(vhr_context *ctx, uint64_t out[8]);
  * vhr_get_kernel_time has no kind 12.)
  * vhr_get_build_times keeps its meaning (the last vhr_update_geometry). */
 int vhr_get_refit_times(vhr_context *ctx, double out[4]);
+/* ---- Partial refit: only the subtrees that moved geometry touches ----
+ * vhr_update_vertices and vhr_update_primitive_transforms also remember the ranges they were given (up to 16 disjoint vertex ranges and 16
+ * primitive ranges, merged where they touch; beyond that the two nearest are joined).  vhr_refit_geometry_partial re-derives only the records
+ * with a vertex (vertex_offset + index) or a primitive in those ranges, recomputes only the boxes of their leaves' ancestors, level by level,
+ * and rewrites the derived forms of those nodes only.  Every array the walkers read is bit for bit what vhr_refit_geometry gives for the same
+ * updates, and so are vhr_get_bvh_form_checks and the half-precision fallback.  Preconditions, refusals, error codes and synchronisation are
+ * vhr_refit_geometry's; an unknown flag bit is VHR_ERROR_INVALID_ARGUMENT, checked first on every context.
+ *   flags 0: the whole-tree refit runs instead where that is cheaper -- the first refit since the build (the per-node boxes a dirty pass
+ *     starts from do not exist yet) and a dirty share above the library's threshold.  Where both hold, the first is the reason reported.
+ *   VHR_REFIT_FORCE_PARTIAL: the dirty path whatever the share (tests and measurement); the first refit since the build is still whole-tree.
+ * If the scene centre's bits change, the half-precision form of every node depends on it: the forms and their checks are redone for all
+ * nodes in that call.  The ranges are forgotten by a refit of either kind that succeeds and by vhr_update_geometry.
+ * vhr_get_refit_statistics / vhr_get_refit_times describe the last refit of either kind: after a dirty pass out[1] and out[2] are the dirty
+ * records and the dirty nodes, out[7] the upward launches made. */
+#define VHR_REFIT_FORCE_PARTIAL 1u
+int vhr_refit_geometry_partial(vhr_context *ctx, uint32_t flags);
+/* out[0] = calls since the last build that took the dirty path and succeeded; of the last call: out[1] = dirty records, out[2] = dirty nodes
+ * (ancestors included), out[3] = nodes whose derived forms were rewritten, out[4] = what it ran as (0 = the dirty path, 1 = whole tree: first
+ * refit since the build, 2 = whole tree: over the threshold), out[5] = 1 if the scene centre's bits changed and all forms were redone,
+ * out[6] = vertex ranges used, out[7] = primitive ranges used. */
+int vhr_get_partial_refit_statistics(vhr_context *ctx, uint64_t out[8]);
 /* The surface-area cost of the tree -- the sum over the inner nodes of child box area x (1 for an inner child, the triangle count for a
  * leaf), over the root's area, on the padded boxes the walkers test: out[0] = as built, out[1] = as it is now.  The number to watch when
  * deciding to rebuild.  One reduction, computed when asked (waits for the context's streams). */

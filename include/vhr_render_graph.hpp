@@ -169,6 +169,11 @@ public:
         check(context.handle, vhr_update_primitive_transforms(context.handle, first_primitive, count, transforms), "UpdatePrimitiveTransforms");
     }
     void RefitGeometry() { check(context.handle, vhr_refit_geometry(context.handle), "RefitGeometry"); }
+    // ... or, when little moved (one character, a door): only the subtrees the updated ranges touch, the same arrays bit for bit.  The library
+    // runs the whole-tree refit itself where that is cheaper (first refit since the build, a large dirty share) unless force_partial is set.
+    void RefitUpdatedGeometry(bool force_partial = false) {
+        check(context.handle, vhr_refit_geometry_partial(context.handle, force_partial ? VHR_REFIT_FORCE_PARTIAL : 0u), "RefitUpdatedGeometry");
+    }
     DeviceContext &context;
 };
 

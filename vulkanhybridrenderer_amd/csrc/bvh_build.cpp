@@ -385,7 +385,7 @@ inline int32_t leaf_link(uint32_t first, uint32_t count) { return ~int32_t((firs
 
 }  // namespace
 
-void derive_node_forms(HostBvh &out, unsigned hw);
+void derive_node_forms(HostBvh &out, unsigned hw, const std::vector<uint8_t> *only = nullptr);
 
 void build_bvh(const vhr_vertex *vertices, const uint32_t *indices, const vhr_primitive *primitives,
                uint32_t primitive_count, HostBvh &out, int leaf_tris, int threads, int presplit_percent, int frame_mode) {
@@ -633,14 +633,16 @@ void build_bvh(const vhr_vertex *vertices, const uint32_t *indices, const vhr_pr
     lap("derived node forms");
 }
 
-// The scene centre and the derived node forms of out.nodes (centre / half extent, 48-byte, half precision): the last stage of a build and of a refit
-void derive_node_forms(HostBvh &out, unsigned hw) {
+// The scene centre and the derived node forms of out.nodes (centre / half extent, 48-byte, half precision): the last stage of a build and of a refit.
+// `only` (a partial refit whose scene centre kept its bits): the forms of the flagged nodes with out.centre as it stands
+void derive_node_forms(HostBvh &out, unsigned hw, const std::vector<uint8_t> *only) {
     const float inf = std::numeric_limits<float>::infinity();
     // centre / half-extent twin of every node (BvhNodeCH): c +- h must contain [lo, hi] in exact arithmetic
     auto finalize_ch = [&]() {
         out.nodes_ch.resize(out.nodes.size());
         parallel_for(out.nodes.size(), hw, [&](size_t k0, size_t k1) {
         for (size_t k = k0; k < k1; ++k) {
+            if (only && !(*only)[k]) continue;
             const BvhNode &nd = out.nodes[k];
             BvhNodeCH c{};
             for (int which = 0; which < 2; ++which) {
@@ -675,6 +677,7 @@ void derive_node_forms(HostBvh &out, unsigned hw) {
         out.nodes48.resize(out.nodes_ch.size());
         parallel_for(out.nodes_ch.size(), hw, [&](size_t k0, size_t k1) {
         for (size_t k = k0; k < k1; ++k) {
+            if (only && !(*only)[k]) continue;
             const BvhNodeCH &c = out.nodes_ch[k];
             BvhNode48 n{};
             for (int w = 0; w < 2; ++w) { n.cx[w] = c.cx[w]; n.cy[w] = c.cy[w]; n.cz[w] = c.cz[w]; }
@@ -692,16 +695,19 @@ void derive_node_forms(HostBvh &out, unsigned hw) {
     auto finalize16 = [&]() {
         finalize_ch();
         float lo[3] = { inf, inf, inf }, hi[3] = { -inf, -inf, -inf };
-        for (const BvhNode &nd : out.nodes)
+        for (size_t k = 0; k < (only ? 0 : out.nodes.size()); ++k) {
+            const BvhNode &nd = out.nodes[k];
             for (int a = 0; a < 3; ++a) {
                 if (nd.box0[2 * a] <= nd.box0[2 * a + 1]) { lo[a] = std::min(lo[a], nd.box0[2 * a]); hi[a] = std::max(hi[a], nd.box0[2 * a + 1]); }
                 if (nd.box1[2 * a] <= nd.box1[2 * a + 1]) { lo[a] = std::min(lo[a], nd.box1[2 * a]); hi[a] = std::max(hi[a], nd.box1[2 * a + 1]); }
             }
-        for (int a = 0; a < 3; ++a) out.centre[a] = (lo[a] <= hi[a]) ? 0.5f * (lo[a] + hi[a]) : 0.0f;
+        }
+        if (!only) for (int a = 0; a < 3; ++a) out.centre[a] = (lo[a] <= hi[a]) ? 0.5f * (lo[a] + hi[a]) : 0.0f;
         out.nodes16.resize(out.nodes.size());
         std::atomic<uint32_t> overflow{ 0 };
         parallel_for(out.nodes.size(), hw, [&](size_t k0, size_t k1) {
         for (size_t k = k0; k < k1; ++k) {
+            if (only && !(*only)[k]) continue;
             const BvhNode &nd = out.nodes[k];
             BvhNode16 c{};
             for (int which = 0; which < 2; ++which) {
@@ -719,7 +725,9 @@ void derive_node_forms(HostBvh &out, unsigned hw) {
             out.nodes16[k] = c;
         }
         });
-        out.nodes16_valid = overflow == 0 && out.nodes.size() * sizeof(BvhNode16) < (size_t(1) << 31);
+        // (`only`: the nodes left alone count too -- an overflow leaves a centre or a half extent with the exponent of inf, which is what
+        // nodes16_in_range looks for; nothing else this function writes is out of the walkers' range)
+        out.nodes16_valid = only ? nodes16_in_range(out) : overflow == 0 && out.nodes.size() * sizeof(BvhNode16) < (size_t(1) << 31);
     };
     finalize16();
 }
@@ -843,6 +851,8 @@ inline void record_box(const HostBvh &bvh, const BvhTri &t, Box &bx) {
 inline bool absent_child1(const HostBvh &bvh, const BvhNode &nd) { return bvh.nodes.size() == 1 && nd.child1 == nd.child0; }     // (a one-leaf scene)
 }  // namespace
 
+void refit_check_pass(const HostBvh &bvh, uint64_t counts[3], unsigned hw);
+
 bool refit_bvh(const vhr_vertex *vertices, const uint32_t *indices, const vhr_primitive *primitives, uint32_t primitive_count, HostBvh &bvh, uint64_t counts[3], int threads) {
     counts[0] = counts[1] = counts[2] = 0;
     const size_t n_nodes = bvh.nodes.size(), n_tris = bvh.tris.size();
@@ -911,7 +921,26 @@ bool refit_bvh(const vhr_vertex *vertices, const uint32_t *indices, const vhr_pr
     }
     // 4. the scene centre and the derived forms
     derive_node_forms(bvh, hw);
-    // the check pass: exact comparisons of what the walkers will meet
+    // what a partial refit starts from: the unpadded boxes, every node's parent, every record's leaf node
+    bvh.self_box.resize(n_nodes * 6);
+    bvh.parent.assign(n_nodes, 0xffffffffu);
+    bvh.owner.assign(n_tris, 0u);
+    for (size_t k = 0; k < n_nodes; ++k) {
+        for (int a = 0; a < 3; ++a) { bvh.self_box[6 * k + a] = self[k].lo[a]; bvh.self_box[6 * k + 3 + a] = self[k].hi[a]; }
+        const int32_t links[2] = { bvh.nodes[k].child0, bvh.nodes[k].child1 };
+        for (int32_t link : links) {
+            if (link >= 0) { bvh.parent[size_t(link)] = uint32_t(k); continue; }
+            const uint32_t v = ~uint32_t(link), first = v >> 2, count = (v & 3u) + 1u;
+            for (uint32_t i = 0; i < count; ++i) bvh.owner[first + i] = uint32_t(k);
+        }
+    }
+    refit_check_pass(bvh, counts, hw);
+    return true;
+}
+
+// the check pass: exact comparisons of what the walkers will meet
+void refit_check_pass(const HostBvh &bvh, uint64_t counts[3], unsigned hw) {
+    const size_t n_nodes = bvh.nodes.size();
     std::atomic<uint64_t> records_outside{ 0 }, children_outside{ 0 };
     parallel_for(n_nodes, hw, [&](size_t k0, size_t k1) {
         uint64_t bad_records = 0, bad_children = 0;
@@ -947,6 +976,89 @@ bool refit_bvh(const vhr_vertex *vertices, const uint32_t *indices, const vhr_pr
     });
     counts[0] = records_outside;
     counts[1] = children_outside;
+}
+
+// the partial refit's host twin (k0_refit_mark_kernel, the level kernels with their one-bit test, the forms restricted to the dirty nodes).  The
+// two check passes stay whole-tree here: the host is not the hot path, and their totals are what a dirty pass has to reproduce anyway.
+bool refit_bvh_partial(const vhr_vertex *vertices, const uint32_t *indices, const vhr_primitive *primitives, uint32_t primitive_count, HostBvh &bvh,
+                       const RefitDirty &dirty, uint64_t counts[3], uint64_t out[4], int threads) {
+    counts[0] = counts[1] = counts[2] = 0;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    const size_t n_nodes = bvh.nodes.size(), n_tris = bvh.tris.size();
+    if (!n_nodes || !n_tris || bvh.self_box.size() != n_nodes * 6 || bvh.parent.size() != n_nodes || bvh.owner.size() != n_tris) return false;
+    for (const BvhTri &t : bvh.tris)
+        if (t.prim >= primitive_count || t.tri >= primitives[t.prim].index_count / 3) return false;
+    const unsigned hw = host_threads(threads);
+    // 1. mark, and the dirty records
+    std::vector<uint8_t> mark(n_nodes, 0);
+    for (size_t i = 0; i < n_tris; ++i) {
+        BvhTri &tri = bvh.tris[i];
+        const vhr_primitive &pr = primitives[tri.prim];
+        uint32_t vi[3];
+        for (int c = 0; c < 3; ++c) vi[c] = pr.vertex_offset + indices[pr.index_offset + 3 * tri.tri + c];
+        if (!(dirty.primitives.holds(tri.prim) || dirty.vertices.holds(vi[0]) || dirty.vertices.holds(vi[1]) || dirty.vertices.holds(vi[2]))) continue;
+        const float *m = pr.transform;
+        float w[3][3];
+        for (int c = 0; c < 3; ++c) {
+            const float *v = vertices[vi[c]].pos;
+            w[c][0] = ((m[0] * v[0] + m[4] * v[1]) + m[8] * v[2]) + m[12];
+            w[c][1] = ((m[1] * v[0] + m[5] * v[1]) + m[9] * v[2]) + m[13];
+            w[c][2] = ((m[2] * v[0] + m[6] * v[1]) + m[10] * v[2]) + m[14];
+        }
+        for (int a = 0; a < 3; ++a) {
+            tri.v0[a] = w[0][a];
+            tri.e1[a] = w[1][a] - w[0][a];
+            tri.e2[a] = w[2][a] - w[0][a];
+            counts[2] += uint64_t(!std::isfinite(tri.v0[a])) + uint64_t(!std::isfinite(tri.e1[a])) + uint64_t(!std::isfinite(tri.e2[a]));
+        }
+        ++out[0];
+        for (uint32_t node = bvh.owner[i]; node != 0xffffffffu && !mark[node]; node = bvh.parent[node]) { mark[node] = 1; ++out[1]; }
+    }
+    // 2. + 3. the dirty nodes' boxes, bottom-up, from the boxes the clean ones keep
+    auto self_of = [&](size_t k) { Box b; for (int a = 0; a < 3; ++a) { b.lo[a] = bvh.self_box[6 * k + a]; b.hi[a] = bvh.self_box[6 * k + 3 + a]; } return b; };
+    auto child_box = [&](int32_t link) {
+        if (link >= 0) return self_of(size_t(link));
+        const uint32_t v = ~uint32_t(link), first = v >> 2, count = (v & 3u) + 1u;
+        Box bx, one;
+        bx.reset();
+        for (uint32_t i = 0; i < count; ++i) { record_box(bvh, bvh.tris[first + i], one); bx.grow(one); }
+        return bx;
+    };
+    auto put = [](float *dst, const Box &bx) {
+        float lo[3], hi[3];
+        padded(bx, lo, hi);
+        for (int a = 0; a < 3; ++a) { dst[2 * a] = lo[a]; dst[2 * a + 1] = hi[a]; }
+    };
+    for (size_t k = n_nodes; k-- > 0;) {
+        if (!mark[k]) continue;
+        BvhNode &nd = bvh.nodes[k];
+        Box mine = child_box(nd.child0);
+        put(nd.box0, mine);
+        if (!absent_child1(bvh, nd)) {
+            const Box b1 = child_box(nd.child1);
+            put(nd.box1, b1);
+            mine.grow(b1);
+        }
+        for (int a = 0; a < 3; ++a) { bvh.self_box[6 * k + a] = mine.lo[a]; bvh.self_box[6 * k + 3 + a] = mine.hi[a]; }
+    }
+    // 4. the scene centre from the root's two slots (every other slot lies inside them: the containment the check pass counts violations of)
+    const float inf = std::numeric_limits<float>::infinity();
+    float centre[3];
+    const BvhNode &root = bvh.nodes[0];
+    for (int a = 0; a < 3; ++a) {
+        float lo = inf, hi = -inf;
+        if (root.box0[2 * a] <= root.box0[2 * a + 1]) { lo = std::min(lo, root.box0[2 * a]); hi = std::max(hi, root.box0[2 * a + 1]); }
+        if (root.box1[2 * a] <= root.box1[2 * a + 1]) { lo = std::min(lo, root.box1[2 * a]); hi = std::max(hi, root.box1[2 * a + 1]); }
+        centre[a] = lo <= hi ? 0.5f * (lo + hi) : 0.0f;
+    }
+    const bool moved = std::memcmp(centre, bvh.centre, sizeof(centre)) != 0;
+    if (moved) derive_node_forms(bvh, hw);               // (the whole-tree reduction: the same centre)
+    else derive_node_forms(bvh, hw, &mark);
+    out[2] = moved ? n_nodes : out[1];
+    out[3] = moved ? 1u : 0u;
+    const uint64_t non_finite = counts[2];
+    refit_check_pass(bvh, counts, hw);
+    counts[2] = non_finite;
     return true;
 }
 

@@ -374,6 +374,10 @@ int vhr_update_geometry(vhr_context *ctx, const vhr_vertex *vertices, uint32_t v
     // a build replaces whatever updates were pending and everything a refit had prepared
     ctx->refit_pending = ctx->sah_cost_built_valid = false;
     for (uint64_t &w : ctx->refit_stats) w = 0;
+    for (uint64_t &w : ctx->partial_stats) w = 0;
+    ctx->refit_dirty = RefitDirty{};
+    ctx->prim_tri_prefix.assign(size_t(primitive_count) + 1u, 0u);
+    for (uint32_t p = 0; p < primitive_count; ++p) ctx->prim_tri_prefix[p + 1u] = ctx->prim_tri_prefix[p] + primitives[p].index_count / 3;
     if (!ctx->host_only) {
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         { const int src_ = ctx->sync_streams(); if (src_ != VHR_OK) return src_; }
@@ -548,6 +552,7 @@ int vhr_update_vertices(vhr_context *ctx, uint32_t first_vertex, uint32_t vertex
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));          // the caller's array is free when the call returns
     }
     ctx->refit_pending = true;
+    ctx->refit_dirty.vertices.add(first_vertex, vertex_count);
     return VHR_OK;
 }
 
@@ -578,27 +583,49 @@ int vhr_update_primitive_transforms(vhr_context *ctx, uint32_t first_primitive, 
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     ctx->refit_pending = true;
+    ctx->refit_dirty.primitives.add(first_primitive, count);
     return VHR_OK;
 }
 
-int vhr_refit_geometry(vhr_context *ctx) {
-    if (!ctx) return VHR_ERROR_INVALID_ARGUMENT;
-    { const int rc = refit_state_checks(ctx, "vhr_refit_geometry"); if (rc != VHR_OK) return rc; }
-    if (ctx->recording || ctx->cur_pass) return ctx->fail(VHR_ERROR_GRAPH, "vhr_refit_geometry: called from inside a pass");
+// the share of the scene the pending ranges touch, from what the host knows: the triangles of the primitive ranges, and the vertex ranges' share of
+// the vertices taken as their share of the triangles (an estimate; it only chooses between two routes to the same arrays).  The two shares
+// are added, so a range reported both ways counts twice; clamped to 1
+static double dirty_share(const vhr_context *ctx) {
+    uint64_t tris = 0;
+    const DirtyRanges &pr = ctx->refit_dirty.primitives;
+    for (uint32_t i = 0; i < pr.count; ++i) tris += ctx->prim_tri_prefix[pr.hi[i]] - ctx->prim_tri_prefix[pr.lo[i]];
+    const double total = double(ctx->prim_tri_prefix.empty() ? 0u : ctx->prim_tri_prefix.back());
+    return std::min(1.0, (total > 0.0 ? double(tris) / total : 1.0) + (ctx->vertex_count ? double(ctx->refit_dirty.vertices.covered()) / double(ctx->vertex_count) : 1.0));
+}
+
+// vhr_refit_geometry (partial == false) and vhr_refit_geometry_partial: the same preconditions, refusals and synchronisation
+static int refit_geometry(vhr_context *ctx, const char *who, bool partial, bool force) {
+    { const int rc = refit_state_checks(ctx, who); if (rc != VHR_OK) return rc; }
+    if (ctx->recording || ctx->cur_pass) return ctx->fail(VHR_ERROR_GRAPH, std::string(who) + ": called from inside a pass");
     if (!ctx->refit_pending) return VHR_OK;              // nothing changed: nothing is launched
     const auto t0 = std::chrono::steady_clock::now();
+    uint64_t ran_as = kRanDirty;
+    const bool asked_partial = partial;
+    // the first refit since the build has no per-node boxes to start from: whole tree, whatever the flags and the share (this reason is the one reported)
+    if (partial && !(ctx->host_only ? !ctx->h_bvh.self_box.empty() : device_refit_boxes_valid(ctx))) { partial = false; ran_as = kRanWholeFirst; }
+    if (partial && !force && dirty_share(ctx) > kPartialRefitMaxShare) { partial = false; ran_as = kRanWholeThreshold; }
     if (ctx->host_only) {
         if (!ctx->sah_cost_built_valid) { ctx->sah_cost_built = bvh_sah_cost(ctx->h_bvh); ctx->sah_cost_built_valid = true; }
-        uint64_t counts[3];
-        if (!refit_bvh(ctx->h_vertices.data(), ctx->h_indices.data(), ctx->h_primitives.data(), ctx->primitive_count, ctx->h_bvh, counts, ctx->bvh_build_threads))
-            return ctx->fail(VHR_ERROR_GRAPH, "vhr_refit_geometry: the tree's nodes are not numbered parents before children");
+        uint64_t counts[3], dirty_counts[4] = { ctx->h_bvh.tris.size(), ctx->h_bvh.nodes.size(), ctx->h_bvh.nodes.size(), 0 };
+        const bool walked = partial ? refit_bvh_partial(ctx->h_vertices.data(), ctx->h_indices.data(), ctx->h_primitives.data(), ctx->primitive_count, ctx->h_bvh,
+                                                        ctx->refit_dirty, counts, dirty_counts, ctx->bvh_build_threads)
+                                    : refit_bvh(ctx->h_vertices.data(), ctx->h_indices.data(), ctx->h_primitives.data(), ctx->primitive_count, ctx->h_bvh, counts, ctx->bvh_build_threads);
+        if (!walked)
+            return ctx->fail(VHR_ERROR_GRAPH, std::string(who) + (partial ? ": the tree or its per-node boxes are not what a dirty pass can walk (a record outside its primitive's triangles)"
+                                                                          : ": the tree's nodes are not numbered parents before children"));
         check_node_forms(ctx->h_bvh, ctx->bvh_form_checks, ctx->bvh_build_threads);
         ctx->nodes16_valid = ctx->h_bvh.nodes16_valid && ctx->bvh_form_checks[3] == 0;
         ctx->bvh_fingerprint = bvh_fingerprint(ctx->h_bvh);
         ctx->bvh_tree_fingerprint = bvh_tree_fingerprint(ctx->h_bvh);
         ctx->bvh_fingerprint_valid = true;
-        ctx->refit_stats[kRefitRecords] = ctx->h_bvh.tris.size();
-        ctx->refit_stats[kRefitNodes] = ctx->h_bvh.nodes.size();
+        ctx->refit_stats[kRefitRecords] = dirty_counts[0];
+        ctx->refit_stats[kRefitNodes] = dirty_counts[1];
+        if (asked_partial) { ctx->partial_stats[kPartialForms] = dirty_counts[2]; ctx->partial_stats[kPartialCentreMoved] = dirty_counts[3]; }
         ctx->refit_stats[kRefitRecordsOutside] = counts[0];
         ctx->refit_stats[kRefitChildrenOutside] = counts[1];
         ctx->refit_stats[kRefitNonFinite] = counts[2];
@@ -607,16 +634,45 @@ int vhr_refit_geometry(vhr_context *ctx) {
     } else {
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         { const int src_ = ctx->sync_streams(); if (src_ != VHR_OK) return src_; }
-        const int rc = device_refit_bvh(ctx);
+        bool ran_whole = false;
+        const int rc = partial ? device_refit_bvh_partial(ctx, &ran_whole) : device_refit_bvh(ctx);
         if (rc != VHR_OK) return rc;
+        if (ran_whole) ran_as = kRanWholeFirst;
         ctx->bvh_fingerprint_valid = false;              // the hashes describe the refitted arrays: taken again when somebody asks
     }
     ctx->refit_times_ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (asked_partial) {                                 // what the last partial call did, whether it succeeds or not
+        ctx->partial_stats[kPartialRecords] = ctx->refit_stats[kRefitRecords];
+        ctx->partial_stats[kPartialNodes] = ctx->refit_stats[kRefitNodes];
+        if (ran_as != kRanDirty) { ctx->partial_stats[kPartialForms] = ctx->refit_stats[kRefitNodes]; ctx->partial_stats[kPartialCentreMoved] = 0; }
+        ctx->partial_stats[kPartialRanAs] = ran_as;
+        ctx->partial_stats[kPartialVertexRanges] = ctx->refit_dirty.vertices.count;
+        ctx->partial_stats[kPartialPrimitiveRanges] = ctx->refit_dirty.primitives.count;
+    }
     if (ctx->refit_stats[kRefitNonFinite])               // (updates stay pending: nothing may trace these arrays; not counted as a refit)
-        return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_refit_geometry: " + std::to_string(ctx->refit_stats[kRefitNonFinite]) +
+        return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, std::string(who) + ": " + std::to_string(ctx->refit_stats[kRefitNonFinite]) +
                          " non-finite coordinates in the triangle records: the tree's arrays are not valid; update the vertices / transforms and refit again, or rebuild");
     ++ctx->refit_stats[kRefitCount];
+    if (asked_partial && ran_as == kRanDirty) ++ctx->partial_stats[kPartialCount];
     ctx->refit_pending = false;
+    ctx->refit_dirty = RefitDirty{};
+    return VHR_OK;
+}
+
+int vhr_refit_geometry(vhr_context *ctx) {
+    if (!ctx) return VHR_ERROR_INVALID_ARGUMENT;
+    return refit_geometry(ctx, "vhr_refit_geometry", false, false);
+}
+
+int vhr_refit_geometry_partial(vhr_context *ctx, uint32_t flags) {
+    if (!ctx) return VHR_ERROR_INVALID_ARGUMENT;
+    if (flags & ~uint32_t(VHR_REFIT_FORCE_PARTIAL)) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_refit_geometry_partial: unknown flag bits " + std::to_string(flags));
+    return refit_geometry(ctx, "vhr_refit_geometry_partial", true, (flags & VHR_REFIT_FORCE_PARTIAL) != 0);
+}
+
+int vhr_get_partial_refit_statistics(vhr_context *ctx, uint64_t out[8]) {
+    if (!ctx || !out) return VHR_ERROR_INVALID_ARGUMENT;
+    for (int i = 0; i < kPartialStatWords; ++i) out[i] = ctx->partial_stats[i];
     return VHR_OK;
 }
 

@@ -177,15 +177,17 @@ __global__ __launch_bounds__(256) void k0_kept_flags_kernel(const uint32_t *__re
 }
 
 // ---- 3. the derived node forms, with the host's formulas (bvh_build.cpp finalize_ch / finalize16) ----
+// A partial refit runs the per-node kernels below on the nodes whose bit is set in `dirty` (one word per 32 nodes); nullptr = every node.
+__device__ __forceinline__ bool node_selected(const uint32_t *dirty, uint32_t k) { return !dirty || ((dirty[k >> 5] >> (k & 31u)) & 1u) != 0u; }
 __device__ __forceinline__ uint32_t upper16(float h) {
     uint32_t bits = __float_as_uint(h);
     if (h > 0.0f && (bits & 0xffffu)) bits += 0x10000u;
     return bits >> 16;
 }
 __global__ __launch_bounds__(256) void k0_forms_kernel(const BvhNode *__restrict__ nodes, uint32_t count, float cx, float cy, float cz, BvhNodeCH *__restrict__ nodes_ch,
-                                                       BvhNode48 *__restrict__ nodes48, BvhNode16 *__restrict__ nodes16) {
+                                                       BvhNode48 *__restrict__ nodes48, BvhNode16 *__restrict__ nodes16, const uint32_t *__restrict__ dirty) {
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
-    if (k >= count) return;
+    if (k >= count || !node_selected(dirty, k)) return;
     const BvhNode nd = nodes[k];
     const float centre[3] = { cx, cy, cz };
     BvhNodeCH c{};
@@ -254,10 +256,11 @@ __device__ __forceinline__ double half_value_d(uint32_t h) {
 }
 __global__ __launch_bounds__(256) void k0_check_forms_kernel(const BvhNode *__restrict__ nodes, const BvhNodeCH *__restrict__ nodes_ch, const BvhNode48 *__restrict__ nodes48,
                                                              const BvhNode16 *__restrict__ nodes16, uint32_t count, float cx, float cy, float cz,
-                                                             unsigned long long *__restrict__ out) {
+                                                             unsigned long long *__restrict__ out, const uint32_t *__restrict__ dirty, uint16_t *__restrict__ status) {
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
     uint32_t bad[5] = { 0u, 0u, 0u, 0u, 0u };
-    if (k < count) {
+    uint32_t old = 0u;                                   // what this node added to out[1..4] at its last check, four bits each (at most 7)
+    if (k < count && node_selected(dirty, k)) {
         const BvhNode nd = nodes[k];
         const BvhNodeCH ch = nodes_ch[k];
         const BvhNode48 n48 = nodes48[k];
@@ -295,12 +298,16 @@ __global__ __launch_bounds__(256) void k0_check_forms_kernel(const BvhNode *__re
         if (n48.child0 != as48(nd.child0) || n48.child1 != as48(nd.child1) || ch.child0 != nd.child0 || ch.child1 != nd.child1) ++bad[2];
         auto as16 = [](int32_t link) { return link >= 0 ? link * int32_t(sizeof(BvhNode16)) : link; };
         if (n16.child0 != as16(nd.child0) || n16.child1 != as16(nd.child1)) ++bad[3];
+        if (status) {                                    // (a dirty pass: the counters get new - old, the host adds that to its totals)
+            if (dirty) old = status[k];
+            status[k] = uint16_t(bad[1] | (bad[2] << 4) | (bad[3] << 8) | (bad[4] << 12));
+        }
     }
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
-        uint32_t v = bad[i];
-        for (int off = 32; off > 0; off >>= 1) v += uint32_t(__shfl_xor(int(v), off));
-        if ((threadIdx.x & 63u) == 0u && v) atomicAdd(&out[i], (unsigned long long)v);
+        int v = int(bad[i]) - (i ? int((old >> (4 * (i - 1))) & 15u) : 0);
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        if ((threadIdx.x & 63u) == 0u && v) atomicAdd(&out[i], (unsigned long long)(long long)v);
     }
 }
 
@@ -848,6 +855,31 @@ struct RefitFrame { float r[9]; uint32_t on; };
 struct RefitCounters { unsigned long long non_finite, records_outside, children_outside, pad; };
 // the leaf pass: record k re-derived in its slot from (prim, tri) with k0_triangles_kernel's arithmetic; three 16-byte loads' worth of gather
 // per corner, three 16-byte stores
+// one record from its primitive's transform and its three vertices (absolute indices `vi`): the one place a refit of either kind derives a
+// record; returns the non-finite coordinates met
+__device__ __forceinline__ uint32_t refit_write_record(float4 *slot, const float4 &q2, const vhr_primitive &pr, const vhr_vertex *__restrict__ vertices, const uint32_t vi[3]) {
+    const float *m = pr.transform;
+    float w[3][3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float *v = vertices[vi[c]].pos;
+        w[c][0] = ((m[0] * v[0] + m[4] * v[1]) + m[8] * v[2]) + m[12];
+        w[c][1] = ((m[1] * v[0] + m[5] * v[1]) + m[9] * v[2]) + m[13];
+        w[c][2] = ((m[2] * v[0] + m[6] * v[1]) + m[10] * v[2]) + m[14];
+    }
+    float e1[3], e2[3];
+    uint32_t bad = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        e1[a] = w[1][a] - w[0][a];
+        e2[a] = w[2][a] - w[0][a];
+        bad += uint32_t(!isfinite(w[0][a])) + uint32_t(!isfinite(e1[a])) + uint32_t(!isfinite(e2[a]));
+    }
+    slot[0] = float4{ w[0][0], w[0][1], w[0][2], e1[0] };
+    slot[1] = float4{ e1[1], e1[2], e2[0], e2[1] };
+    slot[2] = float4{ e2[2], q2.y, q2.z, q2.w };
+    return bad;
+}
 __global__ __launch_bounds__(256) void k0_refit_records_kernel(const vhr_vertex *__restrict__ vertices, const uint32_t *__restrict__ indices,
                                                                const vhr_primitive *__restrict__ primitives, uint32_t primitive_count, uint32_t n,
                                                                BvhTri *__restrict__ tris, RefitCounters *__restrict__ counters) {
@@ -859,31 +891,60 @@ __global__ __launch_bounds__(256) void k0_refit_records_kernel(const vhr_vertex 
         const uint32_t p = __float_as_uint(q2.y), local = __float_as_uint(q2.z);
         if (p < primitive_count) {
             const vhr_primitive &pr = primitives[p];
-            const float *m = pr.transform;
-            float w[3][3];
+            uint32_t vi[3];
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float *v = vertices[pr.vertex_offset + indices[pr.index_offset + 3u * local + uint32_t(c)]].pos;
-                w[c][0] = ((m[0] * v[0] + m[4] * v[1]) + m[8] * v[2]) + m[12];
-                w[c][1] = ((m[1] * v[0] + m[5] * v[1]) + m[9] * v[2]) + m[13];
-                w[c][2] = ((m[2] * v[0] + m[6] * v[1]) + m[10] * v[2]) + m[14];
-            }
-            float e1[3], e2[3];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                e1[a] = w[1][a] - w[0][a];
-                e2[a] = w[2][a] - w[0][a];
-                bad += uint32_t(!isfinite(w[0][a])) + uint32_t(!isfinite(e1[a])) + uint32_t(!isfinite(e2[a]));
-            }
-            slot[0] = float4{ w[0][0], w[0][1], w[0][2], e1[0] };
-            slot[1] = float4{ e1[1], e1[2], e2[0], e2[1] };
-            slot[2] = float4{ e2[2], q2.y, q2.z, q2.w };
+            for (int c = 0; c < 3; ++c) vi[c] = pr.vertex_offset + indices[pr.index_offset + 3u * local + uint32_t(c)];
+            bad = refit_write_record(slot, q2, pr, vertices, vi);
         } else {
             bad = 1u;                                                // (not a record of this scene: cannot happen, never dereferenced)
         }
     }
     for (int off = 32; off > 0; off >>= 1) bad += uint32_t(__shfl_xor(int(bad), off));
     if ((threadIdx.x & 63u) == 0u && bad) atomicAdd(&counters->non_finite, (unsigned long long)bad);
+}
+// The partial refit's mark and leaf pass, one thread per record: a record with its primitive in a primitive range or one of its three absolute
+// vertex indices in a vertex range is dirty -- re-derived as above, and its leaf's node and that node's ancestors get their dirty bit (one
+// vector atomicOr per step; the climb ends at the first bit somebody else has set, so every node is counted once).  A clean record costs its
+// (prim, tri) words and three index reads, and no store.
+constexpr uint32_t kNoParent = 0xffffffffu;
+struct PartialCounters { unsigned long long dirty_records, dirty_nodes; };
+__global__ __launch_bounds__(256) void k0_refit_mark_kernel(const vhr_vertex *__restrict__ vertices, const uint32_t *__restrict__ indices,
+                                                            const vhr_primitive *__restrict__ primitives, uint32_t primitive_count, uint32_t n,
+                                                            BvhTri *__restrict__ tris, const uint32_t *__restrict__ owner, const uint32_t *__restrict__ parent,
+                                                            uint32_t *__restrict__ dirty, RefitDirty ranges, RefitCounters *__restrict__ counters,
+                                                            PartialCounters *__restrict__ partial) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    uint32_t bad = 0, records = 0, nodes = 0;
+    if (k < n) {
+        float4 *slot = reinterpret_cast<float4 *>(tris + k);
+        const float4 q2 = slot[2];                                   // (e2.z, prim, tri, flat)
+        const uint32_t p = __float_as_uint(q2.y), local = __float_as_uint(q2.z);
+        if (p < primitive_count) {
+            const vhr_primitive &pr = primitives[p];
+            uint32_t vi[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) vi[c] = pr.vertex_offset + indices[pr.index_offset + 3u * local + uint32_t(c)];
+            if (ranges.primitives.holds(p) || ranges.vertices.holds(vi[0]) || ranges.vertices.holds(vi[1]) || ranges.vertices.holds(vi[2])) {
+                bad = refit_write_record(slot, q2, pr, vertices, vi);
+                records = 1u;
+                for (uint32_t node = owner[k]; node != kNoParent; node = parent[node]) {
+                    const uint32_t bit = 1u << (node & 31u);
+                    if (atomicOr(&dirty[node >> 5], bit) & bit) break;
+                    ++nodes;
+                }
+            }
+        } else {
+            bad = 1u;                                                // (not a record of this scene: cannot happen, never dereferenced)
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        bad += uint32_t(__shfl_xor(int(bad), off)); records += uint32_t(__shfl_xor(int(records), off)); nodes += uint32_t(__shfl_xor(int(nodes), off));
+    }
+    if ((threadIdx.x & 63u) == 0u) {
+        if (bad) atomicAdd(&counters->non_finite, (unsigned long long)bad);
+        if (records) atomicAdd(&partial->dirty_records, (unsigned long long)records);
+        if (nodes) atomicAdd(&partial->dirty_nodes, (unsigned long long)nodes);
+    }
 }
 // the unpadded box of a record in the tree's frame: k0_triangles_kernel's (world axes) or k0_frame_boxes_kernel's
 __device__ __forceinline__ Box6 refit_record_box(const BvhTri &t, const RefitFrame &f) {
@@ -928,9 +989,9 @@ __device__ __forceinline__ void refit_node(uint32_t k, BvhNode *nodes, const Bvh
 // the upward pass, design (a): one launch per level, deepest first; nodes [begin, end) are one level (the plan checks that the tree is
 // numbered level by level, as both builders number it)
 __global__ __launch_bounds__(256) void k0_refit_level_kernel(BvhNode *__restrict__ nodes, const BvhTri *__restrict__ tris, Box6 *__restrict__ self_box,
-                                                             uint32_t begin, uint32_t end, RefitFrame f, uint32_t single) {
+                                                             uint32_t begin, uint32_t end, RefitFrame f, uint32_t single, const uint32_t *__restrict__ dirty) {
     const uint32_t i = begin + blockIdx.x * 256u + threadIdx.x;
-    if (i >= end) return;
+    if (i >= end || !node_selected(dirty, i)) return;
     refit_node(i, nodes, tris, self_box, f, single != 0u);
 }
 // ... and the levels at the top, which have fewer nodes than a launch is worth: one workgroup, a barrier between levels
@@ -938,9 +999,10 @@ constexpr int kRefitTopLevels = 16;
 constexpr uint32_t kRefitTopNodes = 1024;          // a level of at most this many nodes belongs to the top
 struct RefitTop { uint32_t begin[kRefitTopLevels + 1]; int levels; };
 __global__ __launch_bounds__(256) void k0_refit_top_kernel(BvhNode *__restrict__ nodes, const BvhTri *__restrict__ tris, Box6 *__restrict__ self_box,
-                                                           RefitTop top, RefitFrame f, uint32_t single) {
+                                                           RefitTop top, RefitFrame f, uint32_t single, const uint32_t *__restrict__ dirty) {
     for (int level = top.levels - 1; level >= 0; --level) {
-        for (uint32_t i = top.begin[level] + threadIdx.x; i < top.begin[level + 1]; i += 256u) refit_node(i, nodes, tris, self_box, f, single != 0u);
+        for (uint32_t i = top.begin[level] + threadIdx.x; i < top.begin[level + 1]; i += 256u)
+            if (node_selected(dirty, i)) refit_node(i, nodes, tris, self_box, f, single != 0u);
         __threadfence_block();
         __syncthreads();
     }
@@ -948,10 +1010,10 @@ __global__ __launch_bounds__(256) void k0_refit_top_kernel(BvhNode *__restrict__
 // the check pass: what the walkers will meet, in exact comparisons -- every record's corners inside its leaf's slot, every inner child's two
 // slots inside the slot its parent holds for it
 __global__ __launch_bounds__(256) void k0_refit_check_kernel(const BvhNode *__restrict__ nodes, const BvhTri *__restrict__ tris, uint32_t count, RefitFrame f,
-                                                             RefitCounters *__restrict__ counters) {
+                                                             RefitCounters *__restrict__ counters, const uint32_t *__restrict__ dirty, uint8_t *__restrict__ status) {
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
-    uint32_t bad_records = 0, bad_children = 0;
-    if (k < count) {
+    int bad_records = 0, bad_children = 0;
+    if (k < count && node_selected(dirty, k)) {
         const BvhNode nd = nodes[k];
         auto inside = [](const float *lo, const float *hi, const float *slot) {
             bool in = true;
@@ -977,11 +1039,17 @@ __global__ __launch_bounds__(256) void k0_refit_check_kernel(const BvhNode *__re
                 }
             }
         }
+        // what this node added to the two counters at its last check (records: at most 8, four bits; children: at most 4): a dirty pass
+        // counts new - old, like k0_check_forms_kernel
+        const uint32_t old = dirty ? status[k] : 0u;
+        status[k] = uint8_t(uint32_t(bad_records) | (uint32_t(bad_children) << 4));
+        bad_records -= int(old & 15u);
+        bad_children -= int(old >> 4);
     }
-    for (int off = 32; off > 0; off >>= 1) { bad_records += uint32_t(__shfl_xor(int(bad_records), off)); bad_children += uint32_t(__shfl_xor(int(bad_children), off)); }
+    for (int off = 32; off > 0; off >>= 1) { bad_records += __shfl_xor(bad_records, off); bad_children += __shfl_xor(bad_children, off); }
     if ((threadIdx.x & 63u) == 0u) {
-        if (bad_records) atomicAdd(&counters->records_outside, (unsigned long long)bad_records);
-        if (bad_children) atomicAdd(&counters->children_outside, (unsigned long long)bad_children);
+        if (bad_records) atomicAdd(&counters->records_outside, (unsigned long long)(long long)bad_records);
+        if (bad_children) atomicAdd(&counters->children_outside, (unsigned long long)(long long)bad_children);
     }
 }
 // vhr_get_bvh_sah_cost: per workgroup the sum over its nodes of child half area x (1 | triangles of the leaf), reduced in a fixed order (the
@@ -1266,13 +1334,13 @@ int device_build_bvh(vhr_context *ctx, const std::vector<uint32_t> &tri_prefix, 
         ctx->bvh_centre[a] = lo <= hi ? 0.5f * (lo + hi) : 0.0f;
     }
     hipLaunchKernelGGL(k0_forms_kernel, grid(n_inner), block, 0, s, ctx->d_nodes, n_inner, ctx->bvh_centre[0], ctx->bvh_centre[1], ctx->bvh_centre[2], ctx->d_nodes_ch,
-                       ctx->d_nodes48, ctx->d_nodes16);
+                       ctx->d_nodes48, ctx->d_nodes16, static_cast<const uint32_t *>(nullptr));
     {   // the self-checks of the node forms, where the nodes are (the host builder's tree is checked on the host)
         unsigned long long *d_checks;
         K0_TRY(tmp.alloc(&d_checks, 5));
         K0_TRY(hipMemsetAsync(d_checks, 0, 5 * sizeof(unsigned long long), s));
         hipLaunchKernelGGL(k0_check_forms_kernel, grid(n_inner), block, 0, s, ctx->d_nodes, ctx->d_nodes_ch, ctx->d_nodes48, ctx->d_nodes16, n_inner,
-                           ctx->bvh_centre[0], ctx->bvh_centre[1], ctx->bvh_centre[2], d_checks);
+                           ctx->bvh_centre[0], ctx->bvh_centre[1], ctx->bvh_centre[2], d_checks, static_cast<const uint32_t *>(nullptr), static_cast<uint16_t *>(nullptr));
         unsigned long long h_checks[5];
         K0_TRY(hipMemcpyAsync(h_checks, d_checks, sizeof(h_checks), hipMemcpyDeviceToHost, s));
         K0_TRY(hipStreamSynchronize(s));
@@ -1294,12 +1362,21 @@ int device_build_bvh(vhr_context *ctx, const std::vector<uint32_t> &tri_prefix, 
 
 // ---- refit on the device ----
 // What a refit needs beyond what a build leaves behind, made at the first refit from the nodes' links (fetched once) and kept until the next
-// build: the level ranges (checked, not assumed: the refit relies on parents-before-children only), the per-node unpadded boxes, counters.
+// build: the level ranges (checked, not assumed: the refit relies on parents-before-children only), the per-node unpadded boxes, counters;
+// for the partial refit every node's parent, every record's leaf node, one dirty bit per node and what each node last added to the checks.
 struct RefitPlan {
     std::vector<uint32_t> level_begin;        // nodes [level_begin[l], level_begin[l + 1]) are level l
     Box6 *d_self_box = nullptr;
-    RefitCounters *d_counters = nullptr;      // + the 5 words of k0_check_forms_kernel + 12 of the scene bounds behind it
+    RefitCounters *d_counters = nullptr;      // + the 5 words of k0_check_forms_kernel + 12 of the scene bounds + PartialCounters behind it
     double *d_partial = nullptr;              // k0_sah_cost_kernel's sums, one per workgroup
+    uint32_t *d_parent = nullptr;             // per node; kNoParent for the root
+    uint32_t *d_owner = nullptr;              // per record: the node whose leaf holds it
+    uint32_t *d_dirty = nullptr;              // one bit per node, all clear between refits
+    uint16_t *d_form_status = nullptr;        // per node: its part of k0_check_forms_kernel's out[1..4] at its last check
+    uint8_t *d_check_status = nullptr;        // per node: its part of k0_refit_check_kernel's two counters
+    bool boxes_valid = false;                 // a whole-tree refit has filled d_self_box and the two status arrays
+    bool dirty_stale = false;                 // a dirty pass ended early (an error after its mark kernel): d_dirty may hold bits
+    unsigned long long totals[6] = { 0, 0, 0, 0, 0, 0 };      // form checks out[1..4], records outside, children outside: over all nodes
     hipEvent_t ev[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
     uint32_t launches = 0;                    // of the upward pass (reporting)
 };
@@ -1307,6 +1384,7 @@ void free_refit_plan(vhr_context *ctx) {
     RefitPlan *p = ctx->refit_plan;
     if (!p) return;
     hipFree(p->d_self_box); hipFree(p->d_counters); hipFree(p->d_partial);
+    hipFree(p->d_parent); hipFree(p->d_owner); hipFree(p->d_dirty); hipFree(p->d_form_status); hipFree(p->d_check_status);
     for (hipEvent_t e : p->ev) if (e) hipEventDestroy(e);
     delete p;
     ctx->refit_plan = nullptr;
@@ -1318,12 +1396,15 @@ void free_refit_plan(vhr_context *ctx) {
         if (e_ != hipSuccess) return ctx->fail(VHR_ERROR_DEVICE, std::string("refit: ") + #expr + ": " + hipGetErrorString(e_)); \
     } while (0)
 
+// the counters of one refit as they lie in device memory
+struct RefitReadback { RefitCounters c; unsigned long long checks[5]; uint32_t bounds[12]; PartialCounters partial; };
+
 static int make_refit_plan(vhr_context *ctx) {
     if (ctx->refit_plan) return VHR_OK;
     const uint32_t n = ctx->node_count;
     std::vector<BvhNode> nodes(n);
     REFIT_TRY(hipMemcpy(nodes.data(), ctx->d_nodes, sizeof(BvhNode) * n, hipMemcpyDeviceToHost));
-    std::vector<uint32_t> depth(n, 0u);
+    std::vector<uint32_t> depth(n, 0u), parent(n, kNoParent), owner(ctx->tri_count, 0u);
     uint32_t levels = 1;
     for (uint32_t k = 0; k < n; ++k) {
         const int32_t links[2] = { nodes[k].child0, nodes[k].child1 };
@@ -1331,10 +1412,12 @@ static int make_refit_plan(vhr_context *ctx) {
             if (link >= 0) {
                 if (uint32_t(link) <= k || uint32_t(link) >= n) return ctx->fail(VHR_ERROR_GRAPH, "vhr_refit_geometry: the tree's nodes are not numbered parents before children");
                 depth[uint32_t(link)] = depth[k] + 1u;
+                parent[uint32_t(link)] = k;
                 levels = std::max(levels, depth[k] + 2u);
             } else {
                 const uint32_t v = ~uint32_t(link), first = v >> 2, count = (v & 3u) + 1u;
                 if (uint64_t(first) + count > ctx->tri_count) return ctx->fail(VHR_ERROR_GRAPH, "vhr_refit_geometry: a leaf lies outside the triangle records");
+                for (uint32_t i = 0; i < count; ++i) owner[first + i] = k;
             }
         }
         // one launch per level needs every level to be a contiguous range of nodes: both builders number breadth first, anything else is refused
@@ -1345,12 +1428,21 @@ static int make_refit_plan(vhr_context *ctx) {
     p->level_begin.assign(levels + 1u, 0u);
     for (uint32_t k = 0; k < n; ++k) ++p->level_begin[depth[k] + 1u];
     for (uint32_t l = 0; l < levels; ++l) p->level_begin[l + 1u] += p->level_begin[l];
+    const size_t dirty_bytes = sizeof(uint32_t) * ((size_t(n) + 31u) / 32u);
     hipError_t e = hipMalloc(reinterpret_cast<void **>(&p->d_self_box), sizeof(Box6) * n);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&p->d_counters), sizeof(RefitCounters) + 5 * sizeof(unsigned long long) + 12 * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&p->d_counters), sizeof(RefitReadback));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&p->d_partial), sizeof(double) * ((n + 255u) / 256u));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&p->d_parent), sizeof(uint32_t) * n);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&p->d_owner), sizeof(uint32_t) * std::max(ctx->tri_count, 1u));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&p->d_dirty), dirty_bytes);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&p->d_form_status), sizeof(uint16_t) * n);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&p->d_check_status), sizeof(uint8_t) * n);
+    if (e == hipSuccess) e = hipMemcpy(p->d_parent, parent.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice);
+    if (e == hipSuccess && ctx->tri_count) e = hipMemcpy(p->d_owner, owner.data(), sizeof(uint32_t) * ctx->tri_count, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(p->d_dirty, 0, dirty_bytes);
     if (e != hipSuccess) {
-        hipFree(p->d_self_box); hipFree(p->d_counters); hipFree(p->d_partial);
-        delete p;
+        ctx->refit_plan = p;
+        free_refit_plan(ctx);
         return ctx->fail(VHR_ERROR_DEVICE, std::string("refit: allocating the plan: ") + hipGetErrorString(e));
     }
     ctx->refit_plan = p;
@@ -1383,6 +1475,79 @@ int device_bvh_sah_cost(vhr_context *ctx, double *cost) {
     return VHR_OK;
 }
 
+static dim3 refit_grid(uint32_t count) { return dim3((count + 255u) / 256u); }
+static RefitFrame refit_frame(const vhr_context *ctx) {
+    RefitFrame f;
+    for (int i = 0; i < 9; ++i) f.r[i] = ctx->bvh_frame[i];
+    f.on = ctx->bvh_frame_on ? 1u : 0u;
+    return f;
+}
+// the upward pass: the boxes, level by level from the deepest; the levels at the top in one launch.  `dirty`: nullptr = every node
+static void refit_upward(vhr_context *ctx, RefitPlan *p, const RefitFrame &f, const uint32_t *dirty) {
+    const uint32_t single = ctx->node_count == 1u ? 1u : 0u;
+    const uint32_t levels = uint32_t(p->level_begin.size()) - 1u;
+    uint32_t top_levels = 0;
+    while (top_levels < levels && top_levels < uint32_t(kRefitTopLevels) && p->level_begin[top_levels + 1u] - p->level_begin[top_levels] <= kRefitTopNodes) ++top_levels;
+    p->launches = 0;
+    for (uint32_t l = levels; l-- > top_levels;) {
+        const uint32_t begin = p->level_begin[l], end = p->level_begin[l + 1u];
+        hipLaunchKernelGGL(k0_refit_level_kernel, refit_grid(end - begin), dim3(256), 0, ctx->stream, ctx->d_nodes, ctx->d_tris, p->d_self_box, begin, end, f, single, dirty);
+        ++p->launches;
+    }
+    if (top_levels) {
+        RefitTop top{};
+        top.levels = int(top_levels);
+        for (uint32_t l = 0; l <= top_levels; ++l) top.begin[l] = p->level_begin[l];
+        hipLaunchKernelGGL(k0_refit_top_kernel, dim3(1), dim3(256), 0, ctx->stream, ctx->d_nodes, ctx->d_tris, p->d_self_box, top, f, single, dirty);
+        ++p->launches;
+    }
+}
+// the derived forms, their containment check and the refit's own, for the nodes of `dirty` (nullptr = every node), with ctx->bvh_centre
+static void refit_forms_and_checks(vhr_context *ctx, RefitPlan *p, const RefitFrame &f, const uint32_t *dirty) {
+    const uint32_t n_nodes = ctx->node_count;
+    RefitReadback *d = reinterpret_cast<RefitReadback *>(p->d_counters);
+    hipStream_t s = ctx->stream;
+    hipLaunchKernelGGL(k0_forms_kernel, refit_grid(n_nodes), dim3(256), 0, s, ctx->d_nodes, n_nodes, ctx->bvh_centre[0], ctx->bvh_centre[1], ctx->bvh_centre[2], ctx->d_nodes_ch,
+                       ctx->d_nodes48, ctx->d_nodes16, dirty);
+    hipLaunchKernelGGL(k0_check_forms_kernel, refit_grid(n_nodes), dim3(256), 0, s, ctx->d_nodes, ctx->d_nodes_ch, ctx->d_nodes48, ctx->d_nodes16, n_nodes,
+                       ctx->bvh_centre[0], ctx->bvh_centre[1], ctx->bvh_centre[2], d->checks, dirty, p->d_form_status);
+    hipLaunchKernelGGL(k0_refit_check_kernel, refit_grid(n_nodes), dim3(256), 0, s, ctx->d_nodes, ctx->d_tris, n_nodes, f, &d->c, dirty, p->d_check_status);
+}
+// the counters of a finished refit into the context: `forms_whole` / `checks_whole` say whether the form checks / the refit's own check ran over
+// every node (their counters are then the totals) or over the dirty nodes (new - old, added to the totals)
+static void refit_publish(vhr_context *ctx, RefitPlan *p, const RefitReadback &got, bool forms_whole, bool checks_whole, uint64_t records, uint64_t nodes, bool timed) {
+    const uint32_t n_nodes = ctx->node_count;
+    for (int i = 0; i < 4; ++i) p->totals[i] = (forms_whole ? 0ull : p->totals[i]) + got.checks[i + 1];      // (two's complement: a negative difference wraps back)
+    p->totals[4] = (checks_whole ? 0ull : p->totals[4]) + got.c.records_outside;
+    p->totals[5] = (checks_whole ? 0ull : p->totals[5]) + got.c.children_outside;
+    const bool in_range = p->totals[3] == 0ull && size_t(n_nodes) * sizeof(BvhNode16) < (size_t(1) << 31);
+    ctx->bvh_form_checks[0] = 2ull * n_nodes;                    // boxes checked: two per node
+    ctx->bvh_form_checks[1] = p->totals[0];
+    ctx->bvh_form_checks[2] = p->totals[1];
+    ctx->bvh_form_checks[3] = in_range ? p->totals[2] : 0ull;
+    ctx->nodes16_valid = in_range && p->totals[2] == 0ull;       // else the walkers stay on the 48-byte nodes, as after a build
+    ctx->refit_stats[kRefitRecords] = records;
+    ctx->refit_stats[kRefitNodes] = nodes;
+    ctx->refit_stats[kRefitRecordsOutside] = p->totals[4];
+    ctx->refit_stats[kRefitChildrenOutside] = p->totals[5];
+    ctx->refit_stats[kRefitNonFinite] = got.c.non_finite;
+    ctx->refit_stats[kRefitHalfNodes] = ctx->nodes16_valid ? 1u : 0u;
+    ctx->refit_stats[7] = p->launches;
+    for (int i = 1; i < 4; ++i) ctx->refit_times_ms[i] = 0.0;
+    if (timed) {                               // kernels only: the scene centre's read-back lies between ev[2] and ev[3]
+        const int pairs[3][2] = { { 0, 1 }, { 1, 2 }, { 3, 4 } };
+        for (int i = 0; i < 3; ++i) {
+            float ms = 0.0f;
+            if (hipEventElapsedTime(&ms, p->ev[pairs[i][0]], p->ev[pairs[i][1]]) == hipSuccess) ctx->refit_times_ms[i + 1] = ms;
+        }
+    }
+}
+static RefitReadback refit_counters_init() {
+    RefitReadback init{};
+    for (int a = 0; a < 3; ++a) { init.bounds[a] = init.bounds[6 + a] = 0xffffffffu; }
+    return init;
+}
+
 // The refit proper; the caller (vhr_refit_geometry) has checked that there is a tree, that it is not a presplit one, and has waited for the
 // context's streams.  Fills ctx->refit_stats / refit_times_ms[1..3] and the context's tree state (centre, form checks, nodes16_valid).
 int device_refit_bvh(vhr_context *ctx) {
@@ -1396,47 +1561,27 @@ int device_refit_bvh(vhr_context *ctx) {
     RefitPlan *p = ctx->refit_plan;
     const uint32_t n_nodes = ctx->node_count, n_tris = ctx->tri_count;
     const dim3 block(256);
-    auto grid = [](uint32_t count) { return dim3((count + 255u) / 256u); };
     const bool timed = (ctx->kernel_timing_mask & (1u << kKernelRefit)) != 0;
     if (timed)
         for (hipEvent_t &e : p->ev) if (!e) REFIT_TRY(hipEventCreate(&e));
-    RefitFrame f;
-    for (int i = 0; i < 9; ++i) f.r[i] = ctx->bvh_frame[i];
-    f.on = ctx->bvh_frame_on ? 1u : 0u;
-    const uint32_t single = n_nodes == 1u ? 1u : 0u;
-    unsigned long long *d_checks = reinterpret_cast<unsigned long long *>(p->d_counters + 1);
-    uint32_t *d_bounds = reinterpret_cast<uint32_t *>(d_checks + 5);
-    struct { RefitCounters c; unsigned long long checks[5]; uint32_t bounds[12]; } init{}, got{};
-    for (int a = 0; a < 3; ++a) { init.bounds[a] = init.bounds[6 + a] = 0xffffffffu; }
+    const RefitFrame f = refit_frame(ctx);
+    RefitReadback *d = reinterpret_cast<RefitReadback *>(p->d_counters);
+    const RefitReadback init = refit_counters_init();
+    RefitReadback got{};
     REFIT_TRY(hipMemcpyAsync(p->d_counters, &init, sizeof(init), hipMemcpyHostToDevice, s));
     if (timed) REFIT_TRY(hipEventRecord(p->ev[0], s));
     // 1. the records
-    hipLaunchKernelGGL(k0_refit_records_kernel, grid(n_tris), block, 0, s, ctx->d_vertices, ctx->d_indices, ctx->d_primitives, ctx->primitive_count, n_tris, ctx->d_tris,
+    hipLaunchKernelGGL(k0_refit_records_kernel, refit_grid(n_tris), block, 0, s, ctx->d_vertices, ctx->d_indices, ctx->d_primitives, ctx->primitive_count, n_tris, ctx->d_tris,
                        p->d_counters);
     if (timed) REFIT_TRY(hipEventRecord(p->ev[1], s));
-    // 2. + 3. the boxes, level by level from the deepest; the levels at the top in one launch
-    const uint32_t levels = uint32_t(p->level_begin.size()) - 1u;
-    uint32_t top_levels = 0;
-    while (top_levels < levels && top_levels < uint32_t(kRefitTopLevels) && p->level_begin[top_levels + 1u] - p->level_begin[top_levels] <= kRefitTopNodes) ++top_levels;
-    p->launches = 0;
-    for (uint32_t l = levels; l-- > top_levels;) {
-        const uint32_t begin = p->level_begin[l], end = p->level_begin[l + 1u];
-        hipLaunchKernelGGL(k0_refit_level_kernel, grid(end - begin), block, 0, s, ctx->d_nodes, ctx->d_tris, p->d_self_box, begin, end, f, single);
-        ++p->launches;
-    }
-    if (top_levels) {
-        RefitTop top{};
-        top.levels = int(top_levels);
-        for (uint32_t l = 0; l <= top_levels; ++l) top.begin[l] = p->level_begin[l];
-        hipLaunchKernelGGL(k0_refit_top_kernel, dim3(1), block, 0, s, ctx->d_nodes, ctx->d_tris, p->d_self_box, top, f, single);
-        ++p->launches;
-    }
+    // 2. + 3. the boxes
+    refit_upward(ctx, p, f, nullptr);
     if (timed) REFIT_TRY(hipEventRecord(p->ev[2], s));
     // 4. the scene centre (one reduction and a read-back of 12 words: k0_forms_kernel takes the centre by value, like the build), the derived
     // forms, their containment check and the refit's own
-    hipLaunchKernelGGL(k0_node_bounds_kernel, grid(n_nodes), block, 0, s, ctx->d_nodes, n_nodes, d_bounds + 6);
+    hipLaunchKernelGGL(k0_node_bounds_kernel, refit_grid(n_nodes), block, 0, s, ctx->d_nodes, n_nodes, d->bounds + 6);
     uint32_t h_bounds[12];
-    REFIT_TRY(hipMemcpyAsync(h_bounds, d_bounds, sizeof(h_bounds), hipMemcpyDeviceToHost, s));
+    REFIT_TRY(hipMemcpyAsync(h_bounds, d->bounds, sizeof(h_bounds), hipMemcpyDeviceToHost, s));
     REFIT_TRY(hipStreamSynchronize(s));
     REFIT_TRY(hipGetLastError());
     for (int a = 0; a < 3; ++a) {
@@ -1444,34 +1589,82 @@ int device_refit_bvh(vhr_context *ctx) {
         ctx->bvh_centre[a] = lo <= hi ? 0.5f * (lo + hi) : 0.0f;
     }
     if (timed) REFIT_TRY(hipEventRecord(p->ev[3], s));
-    hipLaunchKernelGGL(k0_forms_kernel, grid(n_nodes), block, 0, s, ctx->d_nodes, n_nodes, ctx->bvh_centre[0], ctx->bvh_centre[1], ctx->bvh_centre[2], ctx->d_nodes_ch,
-                       ctx->d_nodes48, ctx->d_nodes16);
-    hipLaunchKernelGGL(k0_check_forms_kernel, grid(n_nodes), block, 0, s, ctx->d_nodes, ctx->d_nodes_ch, ctx->d_nodes48, ctx->d_nodes16, n_nodes,
-                       ctx->bvh_centre[0], ctx->bvh_centre[1], ctx->bvh_centre[2], d_checks);
-    hipLaunchKernelGGL(k0_refit_check_kernel, grid(n_nodes), block, 0, s, ctx->d_nodes, ctx->d_tris, n_nodes, f, p->d_counters);
+    refit_forms_and_checks(ctx, p, f, nullptr);
     if (timed) REFIT_TRY(hipEventRecord(p->ev[4], s));
     REFIT_TRY(hipMemcpyAsync(&got, p->d_counters, sizeof(got), hipMemcpyDeviceToHost, s));
     REFIT_TRY(hipStreamSynchronize(s));
     REFIT_TRY(hipGetLastError());
-    const bool in_range = got.checks[4] == 0ull && size_t(n_nodes) * sizeof(BvhNode16) < (size_t(1) << 31);
-    for (int i = 0; i < 3; ++i) ctx->bvh_form_checks[i] = got.checks[i];
-    ctx->bvh_form_checks[3] = in_range ? got.checks[3] : 0ull;
-    ctx->nodes16_valid = in_range && got.checks[3] == 0ull;      // else the walkers stay on the 48-byte nodes, as after a build
-    ctx->refit_stats[kRefitRecords] = n_tris;
-    ctx->refit_stats[kRefitNodes] = n_nodes;
-    ctx->refit_stats[kRefitRecordsOutside] = got.c.records_outside;
-    ctx->refit_stats[kRefitChildrenOutside] = got.c.children_outside;
-    ctx->refit_stats[kRefitNonFinite] = got.c.non_finite;
-    ctx->refit_stats[kRefitHalfNodes] = ctx->nodes16_valid ? 1u : 0u;
-    ctx->refit_stats[7] = p->launches;
-    for (int i = 1; i < 4; ++i) ctx->refit_times_ms[i] = 0.0;
-    if (timed) {                               // kernels only: the scene bounds' reduction and its read-back lie between ev[2] and ev[3]
-        const int pairs[3][2] = { { 0, 1 }, { 1, 2 }, { 3, 4 } };
-        for (int i = 0; i < 3; ++i) {
-            float ms = 0.0f;
-            if (hipEventElapsedTime(&ms, p->ev[pairs[i][0]], p->ev[pairs[i][1]]) == hipSuccess) ctx->refit_times_ms[i + 1] = ms;
-        }
+    p->boxes_valid = true;
+    refit_publish(ctx, p, got, true, true, n_tris, n_nodes, timed);
+    return VHR_OK;
+}
+
+bool device_refit_boxes_valid(const vhr_context *ctx) { return ctx->refit_plan && ctx->refit_plan->boxes_valid; }
+
+// vhr_refit_geometry_partial's dirty path; same contract as device_refit_bvh.  The scene centre comes from the root's two slots: every other
+// slot lies inside them (the containment the check pass counts violations of, which the padding guarantees for finite coordinates), so the
+// whole-tree reduction gives the same bits.
+int device_refit_bvh_partial(vhr_context *ctx, bool *ran_whole) {
+    *ran_whole = false;
+    { const int rc = make_refit_plan(ctx); if (rc != VHR_OK) return rc; }
+    RefitPlan *p = ctx->refit_plan;
+    if (!p->boxes_valid) { *ran_whole = true; return device_refit_bvh(ctx); }
+    hipStream_t s = ctx->stream;
+    const uint32_t n_nodes = ctx->node_count, n_tris = ctx->tri_count;
+    const dim3 block(256);
+    const bool timed = (ctx->kernel_timing_mask & (1u << kKernelRefit)) != 0;
+    if (timed)
+        for (hipEvent_t &e : p->ev) if (!e) REFIT_TRY(hipEventCreate(&e));
+    const RefitFrame f = refit_frame(ctx);
+    RefitReadback *d = reinterpret_cast<RefitReadback *>(p->d_counters);
+    const RefitReadback init = refit_counters_init();
+    RefitReadback got{};
+    REFIT_TRY(hipMemcpyAsync(p->d_counters, &init, sizeof(init), hipMemcpyHostToDevice, s));
+    const size_t dirty_bytes = sizeof(uint32_t) * ((size_t(n_nodes) + 31u) / 32u);
+    if (p->dirty_stale) REFIT_TRY(hipMemsetAsync(p->d_dirty, 0, dirty_bytes, s));      // (the last dirty pass did not reach its own clearing)
+    p->dirty_stale = true;
+    if (timed) REFIT_TRY(hipEventRecord(p->ev[0], s));
+    // 1. mark, and the dirty records
+    hipLaunchKernelGGL(k0_refit_mark_kernel, refit_grid(n_tris), block, 0, s, ctx->d_vertices, ctx->d_indices, ctx->d_primitives, ctx->primitive_count, n_tris, ctx->d_tris,
+                       p->d_owner, p->d_parent, p->d_dirty, ctx->refit_dirty, &d->c, &d->partial);
+    if (timed) REFIT_TRY(hipEventRecord(p->ev[1], s));
+    // 2. + 3. the dirty nodes' boxes: the same launches, a one-bit test per node
+    refit_upward(ctx, p, f, p->d_dirty);
+    if (timed) REFIT_TRY(hipEventRecord(p->ev[2], s));
+    // 4. the scene centre from the root (the first of the two read-backs)
+    BvhNode root;
+    REFIT_TRY(hipMemcpyAsync(&root, ctx->d_nodes, sizeof(root), hipMemcpyDeviceToHost, s));
+    REFIT_TRY(hipStreamSynchronize(s));
+    REFIT_TRY(hipGetLastError());
+    float centre[3];
+    for (int a = 0; a < 3; ++a) {
+        float lo = 3.0e38f, hi = -3.0e38f;                           // k0_node_bounds_kernel's identities and its tests
+        if (root.box0[2 * a] <= root.box0[2 * a + 1]) { lo = fminf(lo, root.box0[2 * a]); hi = fmaxf(hi, root.box0[2 * a + 1]); }
+        if (root.box1[2 * a] <= root.box1[2 * a + 1]) { lo = fminf(lo, root.box1[2 * a]); hi = fmaxf(hi, root.box1[2 * a + 1]); }
+        centre[a] = lo <= hi ? 0.5f * (lo + hi) : 0.0f;
     }
+    const bool centre_moved = std::memcmp(centre, ctx->bvh_centre, sizeof(centre)) != 0;
+    for (int a = 0; a < 3; ++a) ctx->bvh_centre[a] = centre[a];
+    if (timed) REFIT_TRY(hipEventRecord(p->ev[3], s));
+    if (centre_moved) {                        // every node's half-precision form hangs on the centre: all forms and their checks again
+        hipLaunchKernelGGL(k0_forms_kernel, refit_grid(n_nodes), block, 0, s, ctx->d_nodes, n_nodes, centre[0], centre[1], centre[2], ctx->d_nodes_ch, ctx->d_nodes48,
+                           ctx->d_nodes16, static_cast<const uint32_t *>(nullptr));
+        hipLaunchKernelGGL(k0_check_forms_kernel, refit_grid(n_nodes), block, 0, s, ctx->d_nodes, ctx->d_nodes_ch, ctx->d_nodes48, ctx->d_nodes16, n_nodes, centre[0], centre[1],
+                           centre[2], d->checks, static_cast<const uint32_t *>(nullptr), p->d_form_status);
+        hipLaunchKernelGGL(k0_refit_check_kernel, refit_grid(n_nodes), block, 0, s, ctx->d_nodes, ctx->d_tris, n_nodes, f, &d->c, static_cast<const uint32_t *>(p->d_dirty),
+                           p->d_check_status);
+    } else {
+        refit_forms_and_checks(ctx, p, f, p->d_dirty);
+    }
+    if (timed) REFIT_TRY(hipEventRecord(p->ev[4], s));
+    REFIT_TRY(hipMemsetAsync(p->d_dirty, 0, dirty_bytes, s));
+    REFIT_TRY(hipMemcpyAsync(&got, p->d_counters, sizeof(got), hipMemcpyDeviceToHost, s));
+    REFIT_TRY(hipStreamSynchronize(s));
+    REFIT_TRY(hipGetLastError());
+    p->dirty_stale = false;
+    refit_publish(ctx, p, got, centre_moved, false, got.partial.dirty_records, got.partial.dirty_nodes, timed);
+    ctx->partial_stats[kPartialForms] = centre_moved ? n_nodes : got.partial.dirty_nodes;
+    ctx->partial_stats[kPartialCentreMoved] = centre_moved ? 1u : 0u;
     return VHR_OK;
 }
 

@@ -160,7 +160,55 @@ struct HostBvh {
     std::vector<BvhTri> tris;          // one per REFERENCE ("bvh_presplit": a fat triangle is in several leaves)
     uint32_t max_depth = 0;
     int presplit_level = -1;           // the grid level the references were split on, -1 = none were
+    // what a partial refit needs (refit_bvh_partial), left behind by refit_bvh: every node's unpadded box (lo[3], hi[3]), its parent
+    // (0xffffffff: the root) and, per record, the node that holds its leaf.  Empty after a build.
+    std::vector<float> self_box;
+    std::vector<uint32_t> parent, owner;
 };
+
+// ---- partial refit: what moved since the last refit, as the update calls reported it ----
+// Up to kMax half-open ranges [lo, hi), sorted, disjoint and not adjacent.  A seventeenth range is merged with its nearest neighbour: a looser
+// set is always correct, only slower.  Passed to the marking kernel by value.
+struct DirtyRanges {
+    static constexpr uint32_t kMax = 16;
+    uint32_t count = 0;
+    uint32_t lo[kMax] = {}, hi[kMax] = {};
+    void clear() { count = 0; }
+    void add(uint32_t first, uint32_t n) {
+        if (!n) return;
+        uint64_t l[kMax + 1], h[kMax + 1];
+        uint32_t m = 0;
+        uint64_t nl = first, nh = uint64_t(first) + n;
+        bool placed = false;
+        for (uint32_t i = 0; i < count; ++i) {
+            if (hi[i] < nl) { l[m] = lo[i]; h[m] = hi[i]; ++m; continue; }                       // wholly before (touching ranges merge)
+            if (lo[i] > nh) {                                                                       // wholly after: the new range goes first
+                if (!placed) { l[m] = nl; h[m] = nh; ++m; placed = true; }
+                l[m] = lo[i]; h[m] = hi[i]; ++m;
+                continue;
+            }
+            nl = nl < lo[i] ? nl : lo[i];
+            nh = nh > hi[i] ? nh : hi[i];
+        }
+        if (!placed) { l[m] = nl; h[m] = nh; ++m; }
+        if (m > kMax) {                                                                             // overflow: close the smallest gap
+            uint32_t best = 0;
+            for (uint32_t i = 1; i + 1 < m; ++i) if (l[i + 1] - h[i] < l[best + 1] - h[best]) best = i;
+            h[best] = h[best + 1];
+            for (uint32_t i = best + 1; i + 1 < m; ++i) { l[i] = l[i + 1]; h[i] = h[i + 1]; }
+            --m;
+        }
+        count = m;
+        for (uint32_t i = 0; i < m; ++i) { lo[i] = uint32_t(l[i]); hi[i] = uint32_t(h[i]); }      // (hi <= the buffer's length: the callers check their ranges)
+    }
+    __host__ __device__ bool holds(uint32_t x) const {
+        bool in = false;
+        for (uint32_t i = 0; i < count; ++i) in = in || (x >= lo[i] && x < hi[i]);
+        return in;
+    }
+    uint64_t covered() const { uint64_t s = 0; for (uint32_t i = 0; i < count; ++i) s += hi[i] - lo[i]; return s; }
+};
+struct RefitDirty { DirtyRanges vertices, primitives; };
 
 // builds the BVH2 (csrc/bvh_build.cpp)
 void check_node_forms(const HostBvh &bvh, uint64_t out[4], int threads = 0);
@@ -186,6 +234,25 @@ double bvh_sah_cost(const HostBvh &bvh);
 struct RefitPlan;
 void free_refit_plan(vhr_context *ctx);
 int device_refit_bvh(vhr_context *ctx);
+// ---- partial refit (vhr_refit_geometry_partial): the same arrays, bit for bit, at a cost that follows what moved ----
+// vhr_get_partial_refit_statistics' words
+enum PartialStat { kPartialCount = 0, kPartialRecords = 1, kPartialNodes = 2, kPartialForms = 3, kPartialRanAs = 4, kPartialCentreMoved = 5, kPartialVertexRanges = 6,
+                   kPartialPrimitiveRanges = 7, kPartialStatWords = 8 };
+enum PartialRanAs { kRanDirty = 0, kRanWholeFirst = 1, kRanWholeThreshold = 2 };
+// flags == 0: above this share of the scene (triangles of the primitive ranges + the vertex ranges' share of the vertices) the whole-tree refit
+// runs instead.  From profiles/partial_refit_rate.jsonl (tools/partial_refit_rate.py, MI355X): on bistro_proc the dirty path's wall time is about 0.8 x the
+// whole-tree refit's at a share of 0.3, about 0.9 x at 0.4 and just above it at 0.5 -- the crossover lies between 0.4 and 0.5; on sponza_proc it
+// still wins at 0.5 (about 0.8 x).  0.3 is the largest measured share whose gain exceeds the whole-tree refit's own spread between calls (about
+// +-5 %), which the one at 0.4 does not in every run; a wrong value only costs what the whole-tree path costs.
+constexpr double kPartialRefitMaxShare = 0.3;
+// the host twin: records with a vertex or a primitive in `dirty` re-derived, their ancestors' boxes recomputed from bvh.self_box, the derived forms
+// of those nodes (of all nodes if the scene centre's bits changed), then the whole-tree check pass.  Needs what a whole-tree refit_bvh leaves in
+// `bvh` (self_box / parent / owner).  out[0] = dirty records, [1] = dirty nodes, [2] = nodes whose forms were rewritten, [3] = 1 if the centre moved
+bool refit_bvh_partial(const vhr_vertex *vertices, const uint32_t *indices, const vhr_primitive *primitives, uint32_t primitive_count, HostBvh &bvh,
+                       const RefitDirty &dirty, uint64_t counts[3], uint64_t out[4], int threads = 0);
+// the device side: *ran_whole = true if no per-node boxes existed yet (the first refit since the build) and the whole-tree refit ran instead
+int device_refit_bvh_partial(vhr_context *ctx, bool *ran_whole);
+bool device_refit_boxes_valid(const vhr_context *ctx);      // a whole-tree refit since the build has left the per-node boxes a dirty pass starts from
 int device_bvh_sah_cost(vhr_context *ctx, double *cost);
 
 enum class PassKind { Graphics, Raytracing, Compute };
@@ -419,6 +486,10 @@ struct vhr_context {
     double sah_cost_built = 0.0;                 // vhr_get_bvh_sah_cost out[0]: taken before the first refit touches the tree, or when first asked
     bool sah_cost_built_valid = false;
     vhr::RefitPlan *refit_plan = nullptr;        // device contexts: level ranges, per-node boxes, counters (kept until the next build or vhr_destroy)
+    // partial refit: the ranges the update calls reported since the last successful refit (cleared by it and by a build)
+    vhr::RefitDirty refit_dirty;
+    uint64_t partial_stats[vhr::kPartialStatWords] = {};
+    std::vector<uint32_t> prim_tri_prefix;       // triangles before primitive p (primitive_count + 1 entries): the dirty share of a primitive range
     // a host-only context keeps the arrays and the tree of its last build: the refit's host twin works on them
     std::vector<vhr_vertex> h_vertices;
     std::vector<uint32_t> h_indices;

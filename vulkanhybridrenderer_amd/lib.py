@@ -41,7 +41,7 @@ EXPORTS = [
     "vhr_comm_start_frame_exchanges", "vhr_comm_finish_frame_exchanges",
     "vhr_calibration_stream_read", "vhr_ray_query", "vhr_get_ray_query_statistics", "vhr_ray_query_struct_layout",
     "vhr_update_vertices", "vhr_update_primitive_transforms", "vhr_refit_geometry", "vhr_get_refit_statistics", "vhr_get_refit_times",
-    "vhr_get_bvh_sah_cost",
+    "vhr_get_bvh_sah_cost", "vhr_refit_geometry_partial", "vhr_get_partial_refit_statistics",
 ]
 
 PATH_PREFIXES = ("hybrid", "raytraced", "rayquery", "forward_raster")      # vhr_<prefix>_{create,destroy,build,rebuild,last_error}
@@ -308,6 +308,8 @@ def load():
     L.vhr_get_refit_statistics.argtypes = [vp, C.POINTER(u64)]
     L.vhr_get_refit_times.argtypes = [vp, C.POINTER(C.c_double)]
     L.vhr_get_bvh_sah_cost.argtypes = [vp, C.POINTER(C.c_double)]
+    L.vhr_refit_geometry_partial.argtypes = [vp, u32]
+    L.vhr_get_partial_refit_statistics.argtypes = [vp, C.POINTER(u64)]
     L.vhr_set_kernel_timing.argtypes = [vp, i32]
     L.vhr_get_kernel_time.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(u64), i32]
     _lib = L
@@ -335,6 +337,7 @@ SSR_SHADER = "hybrid_render_path/ssr.comp"
 
 ATTACHMENT_IMAGE, SAMPLED_IMAGE, STORAGE_IMAGE = 0, 1, 2
 UPDATE_DEVICE_MEMORY = 2          # vhr_update_vertices: VHR_UPDATE_DEVICE_MEMORY
+REFIT_FORCE_PARTIAL = 1           # vhr_refit_geometry_partial: VHR_REFIT_FORCE_PARTIAL
 
 
 def transient(name, fmt, binding, kind=STORAGE_IMAGE, width=0, height=0, clear=(0, 0, 0, 0)):
@@ -436,6 +439,17 @@ class Context:
 
     def refit_geometry(self):
         self.check(self.L.vhr_refit_geometry(self.handle), "refit_geometry")
+
+    def refit_geometry_partial(self, force=False):
+        """vhr_refit_geometry_partial: only the records the pending updates' ranges touch and their leaves' ancestors; the same arrays as
+        refit_geometry().  force=True: the dirty path whatever the dirty share (the first refit after a build is whole-tree regardless)."""
+        self.check(self.L.vhr_refit_geometry_partial(self.handle, REFIT_FORCE_PARTIAL if force else 0), "refit_geometry_partial")
+
+    def partial_refit_statistics(self):
+        out = (C.c_uint64 * 8)()
+        self.check(self.L.vhr_get_partial_refit_statistics(self.handle, out), "partial_refit_statistics")
+        return dict(partial_refits=int(out[0]), dirty_records=int(out[1]), dirty_nodes=int(out[2]), forms_rewritten=int(out[3]), ran_as=int(out[4]),
+                    centre_moved=int(out[5]), vertex_ranges=int(out[6]), primitive_ranges=int(out[7]))
 
     def refit_statistics(self):
         out = (C.c_uint64 * 8)()
