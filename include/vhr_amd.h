@@ -734,6 +734,13 @@ int vhr_get_bvh_fingerprint(vhr_context *ctx, uint64_t *out);
  * of the order of the triangles inside a leaf.  The host's and the device's build of a scene agree on it ("bvh_builder" 0 / 1: the same
  * algorithm, the same tree; the reference's BLAS / TLAS are the driver's, resource_manager.cpp:593-801). */
 int vhr_get_bvh_tree_fingerprint(vhr_context *ctx, uint64_t *out);
+/* The derived node forms -- what the walkers read -- against the one definition of their arithmetic (csrc/bvh_math.hpp).  out[0] = the hash
+ * (vhr_get_bvh_fingerprint's mixing) of the scene centre and the centre / half-extent, 48-byte and 32-byte nodes as they stand, fetched
+ * from the device if they live there; out[1] = the same hash after the host has derived the forms again from a copy of the (lo, hi) nodes.
+ * out[0] == out[1] for every tree, built or refitted by either builder.  The 32-byte nodes are hashed always, in range or not: a scene
+ * beyond the half range leaves inf in the same halves on both sides (the host's software float -> half conversions round like the
+ * hardware's, overflow included).  VHR_ERROR_GRAPH without a tree. */
+int vhr_get_bvh_forms_fingerprint(vhr_context *ctx, uint64_t out[2]);
 
 /* ---- Refit: geometry that moves without a rebuild (an extension; what Vulkan calls VK_BUILD_ACCELERATION_STRUCTURE_MODE_UPDATE_KHR) ----
  * The tree of the last vhr_update_geometry keeps its topology; its triangle records and boxes are recomputed from the current vertices and

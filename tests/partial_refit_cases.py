@@ -37,6 +37,44 @@ def updates(scene, seed=11):
     }
 
 
+def form_scenes():
+    """name -> (scene, "bvh_frame") for the checks of the derived node forms against csrc/bvh_math.hpp (bvh_forms_fingerprint): the tiny scene, a
+    triangle soup with and without the frame search, the tiny scene far from the origin with very small and very large triangles, and the
+    tiny scene wider than the half range (no usable 32-byte form: its halves hold inf)."""
+    import dataclasses
+    from tests.test_gpu_fuzz import soup
+    tiny = scenes.tiny_scene()
+    rng = np.random.default_rng(7)
+    v = tiny.vertices.copy()
+    v["pos"] = v["pos"] * rng.choice(np.array([1e-4, 1.0, 3e3], np.float32), size=(len(v), 1)).astype(np.float32) + np.float32(12345.678)
+    w = tiny.vertices.copy()
+    w["pos"][:3] *= np.float32(5e4)
+    return {"tiny": (tiny, 1), "soup3 world axes": (soup(3, 2000, 8), 0), "soup3 frame search": (soup(3, 2000, 8), 1),
+            "far": (dataclasses.replace(tiny, name="tiny_far", vertices=v), 1), "wide": (dataclasses.replace(tiny, name="tiny_wide", vertices=w), 1)}
+
+
+def check_forms_through_refits(ctx, scene, name):
+    """out[0] == out[1] of bvh_forms_fingerprint as `ctx` stands (just built), after a whole-tree refit of every vertex displaced by a few
+    centimetres (the scene centre is computed again) and after a partial refit of the last primitive's block."""
+    def check(stage):
+        as_is, derived_again = ctx.bvh_forms_fingerprint()
+        assert as_is == derived_again and as_is != 0, (name, stage)
+    check("build")
+    rng = np.random.default_rng(5)
+    v = scene.vertices.copy()
+    v["pos"] += rng.normal(scale=0.05, size=v["pos"].shape).astype(np.float32)
+    ctx.update_vertices(v)
+    ctx.refit_geometry()
+    check("refit")
+    first, end = vertex_blocks(scene)[-1]
+    block = v[first:end].copy()
+    block["pos"] += rng.normal(scale=0.3, size=block["pos"].shape).astype(np.float32)
+    ctx.update_vertices(block, first_vertex=first)
+    ctx.refit_geometry_partial(force=True)
+    assert ctx.partial_refit_statistics()["ran_as"] == 0, name
+    check("partial refit")
+
+
 def apply(ctx, calls):
     for kind, first, data in calls:
         if kind == "v":

@@ -4,6 +4,7 @@ the tile sizes, axis-parallel rays (zero direction components), the BASELINE ao_
 import numpy as np
 import pytest
 
+from tests import partial_refit_cases as cases
 from tests.helpers import GpuHybrid, assert_reflections_identical, f16, oracle_frames
 from vulkanhybridrenderer_amd import abi, camera, lib, scenes
 
@@ -365,6 +366,26 @@ def test_every_node_form_contains_its_box():
             assert seen[0] == seen[1]
         finally:
             c.close()
+
+
+@pytest.mark.parametrize("name", sorted(cases.form_scenes()))
+def test_device_forms_are_what_the_host_derives_from_the_same_nodes(name):
+    """The device builder's and the device refits' derived forms against the host's run of the same csrc/bvh_math.hpp: the forms as they stand
+    in device memory hash like the forms the host derives from the fetched (lo, hi) nodes -- scene centre included, so the centre a device
+    refit computes is the host's -- after a build, a whole-tree refit and a partial refit.  The wide scene has no usable 32-byte form; its
+    32-byte nodes are hashed all the same (the inf of an overflow is the same bits on both sides)."""
+    scene, frame = cases.form_scenes()[name]
+    c = lib.Context(64, 64)
+    try:
+        c.set_option("bvh_builder", 1)
+        c.set_option("bvh_frame", frame)
+        c.upload_scene(scene)
+        assert c.bvh_builder_used() == 1
+        cases.check_forms_through_refits(c, scene, name)
+        assert c.refit_statistics()["half_nodes"] == (0 if name == "wide" else 1)
+        assert c.bvh_form_checks()[1:] == (0, 0, 0)
+    finally:
+        c.close()
 
 
 def test_scene_far_from_the_origin_with_mixed_scales(oracle):

@@ -53,8 +53,11 @@ def test_partial_refit_equals_the_whole_tree_refit_and_the_host_twin(oracle, bui
             assert (st["records"], st["nodes"]) == (ps["dirty_records"], ps["dirty_nodes"]) and 1 <= st["upward_launches"] <= whole_launches, (name, st)
             if len(ups[name]) == 1:
                 assert ps["dirty_records"] == cases.expected_dirty_records(scene, ups[name][0]), (name, ps)
+            forms = [c.bvh_forms_fingerprint() for c in (a, b)]
+            assert forms[0] == forms[1] and forms[0][0] == forms[0][1], (name, forms)
             if h:
                 h.refit_geometry_partial(force=True)
+                assert h.bvh_forms_fingerprint() == forms[0], name
                 hp = h.partial_refit_statistics()
                 assert h.bvh_fingerprint() == sa["fingerprint"] and h.bvh_tree_fingerprint() == sa["tree"], name
                 assert (hp["dirty_records"], hp["dirty_nodes"], hp["centre_moved"]) == (ps["dirty_records"], ps["dirty_nodes"], ps["centre_moved"]), (name, hp, ps)

@@ -76,10 +76,12 @@ def test_identity_refit_keeps_the_device_tree_bit_for_bit(oracle):
             ctx.set_option("bvh_builder", builder)
             ctx.upload_scene(scene)
             built = (ctx.bvh_fingerprint(), ctx.bvh_tree_fingerprint(), ctx.bvh_form_checks())
+            forms = ctx.bvh_forms_fingerprint()
             ctx.update_vertices(scene.vertices)
             ctx.refit_geometry()
             _clean(ctx)
             assert (ctx.bvh_fingerprint(), ctx.bvh_tree_fingerprint(), ctx.bvh_form_checks()) == built, builder
+            assert ctx.bvh_forms_fingerprint() == forms and forms[0] == forms[1], (builder, forms)
             cost = ctx.bvh_sah_cost()
             assert cost[0] == cost[1] > 0
     finally:

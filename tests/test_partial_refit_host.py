@@ -73,6 +73,23 @@ def test_partial_refit_equals_the_whole_tree_refit(vhr, name, frame, update):
         b.close()
 
 
+@pytest.mark.parametrize("name", sorted(cases.form_scenes()))
+def test_forms_are_what_the_host_derives_again(vhr, name):
+    """bvh_forms_fingerprint on host-only contexts (true by construction there: the same function both times; the GPU twin of this test is
+    where it bites) after a build, a refit and a partial refit; and the getter refuses without a tree."""
+    scene, frame = cases.form_scenes()[name]
+    c = lib.Context(64, 64, host_only=True)
+    try:
+        with pytest.raises(lib.VhrError, match="no geometry yet"):
+            c.bvh_forms_fingerprint()
+        c.set_option("bvh_frame", frame)
+        c.update_geometry(scene.vertices, scene.indices, scene.primitives)
+        cases.check_forms_through_refits(c, scene, name)
+        assert c.refit_statistics()["half_nodes"] == (0 if name == "wide" else 1)
+    finally:
+        c.close()
+
+
 def test_two_primitives_sharing_one_vertex_block(vhr):
     """Two primitives with the same vertex_offset (one mesh instanced twice): an update of that block dirties the records of both."""
     scene = soup(1, 60, 3)

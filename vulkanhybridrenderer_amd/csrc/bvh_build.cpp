@@ -28,6 +28,7 @@
 #include "vhr_internal.hpp"
 #include "presplit.hpp"
 #include "bvh_frame.hpp"
+#include "bvh_math.hpp"
 
 namespace vhr {
 namespace {
@@ -296,96 +297,7 @@ struct Builder {
     }
 };
 
-inline void padded(const Box &b, float lo[3], float hi[3]) {
-    // Conservative padding: box culling must never change which triangles are accepted.
-    for (int a = 0; a < 3; ++a) {
-        float pad = 1e-3f + 1e-5f * std::max(std::fabs(b.lo[a]), std::fabs(b.hi[a]));
-        lo[a] = b.lo[a] - pad;
-        hi[a] = b.hi[a] + pad;
-    }
-}
-
-// value of a half bit pattern (exact)
-inline double half_value(uint16_t h) {
-    const int e = (h >> 10) & 31, m = h & 1023;
-    const double v = e == 0 ? std::ldexp(double(m), -24) : (e == 31 ? (m ? std::nan("") : HUGE_VAL) : std::ldexp(double(1024 + m), e - 25));
-    return (h & 0x8000) ? -v : v;
-}
-
-uint16_t half_directed(float x, bool down);
-
-// One axis of one child box of the 32-byte node form (BvhNode16): centre (relative to `origin`) and half extent as halves such that
-// origin + c +- h contains [lo, hi] in exact arithmetic with a few fp32 ulp to spare (the walker rounds o - origin and the FMAs).
-// Neither half is subnormal.  An absent child (lo > hi) gets c = 0, h = -1.  false: the half range does not reach (the form is unusable).
-inline bool half_centre_extent(float lo, float hi, float origin, uint16_t &c16, uint16_t &h16) {
-    if (!(lo <= hi)) { c16 = 0; h16 = 0xbc00; return true; }
-    const double mid = 0.5 * double(lo) + 0.5 * double(hi) - double(origin);
-    // nearest half of the centre: directed conversion both ways, the closer one (ties: either is fine)
-    const uint16_t dn = half_directed(float(mid), true), up = half_directed(float(mid), false);
-    c16 = std::fabs(half_value(dn) - mid) <= std::fabs(half_value(up) - mid) ? dn : up;
-    if (((c16 >> 10) & 31) == 0) c16 = 0;                                 // subnormal centre: 0 (h below absorbs the difference)
-    if (((c16 >> 10) & 31) == 31) return false;
-    const double c = double(origin) + half_value(c16);
-    double need = std::max(double(hi) - c, c - double(lo));
-    need += (std::fabs(double(origin)) + std::fabs(half_value(c16)) + need) * 4.8e-7 + 1e-30;
-    float nf = float(need);
-    if (double(nf) < need) nf = std::nextafter(nf, std::numeric_limits<float>::infinity());
-    h16 = half_directed(nf, false);
-    if (((h16 >> 10) & 31) == 0) h16 = 0x0400;                            // smallest normal half
-    if (((h16 >> 10) & 31) == 31) return false;
-    return true;
-}
-
-// float -> half bits, rounded toward -inf (down = true) or +inf; |x| beyond the half range saturates outward to +-inf
-inline uint16_t half_directed(float x, bool down) {
-    if (std::isnan(x)) return 0x7e00;
-    if (std::isinf(x)) return x < 0 ? 0xfc00 : 0x7c00;
-    // nearest-even conversion first, then step one ulp outward if it landed on the wrong side
-    uint32_t u;
-    std::memcpy(&u, &x, 4);
-    const uint32_t sign = (u >> 16) & 0x8000u;
-    const float ax = std::fabs(x);
-    uint16_t h;
-    if (ax >= 65520.0f) h = uint16_t(sign | 0x7c00u);
-    else if (ax < 5.9604645e-8f * 0.5f) h = uint16_t(sign);
-    else {
-        int e;
-        const float m = std::frexp(ax, &e);                 // ax = m * 2^e, m in [0.5, 1)
-        int he = e + 14;                                     // half exponent field for normals
-        if (he <= 0) {                                       // subnormal half: units of 2^-24
-            const uint32_t q = uint32_t(std::nearbyint(std::ldexp(ax, 24)));
-            h = uint16_t(sign | q);
-        } else {
-            uint32_t q = uint32_t(std::nearbyint(std::ldexp(m, 11)));   // 11-bit significand incl. implicit bit
-            if (q == 2048u) { q = 1024u; ++he; }
-            h = (he >= 31) ? uint16_t(sign | 0x7c00u) : uint16_t(sign | (uint32_t(he) << 10) | (q & 0x3ffu));
-        }
-    }
-    auto value = [](uint16_t hb) -> float {
-        const uint32_t s2 = hb & 0x8000u, ex = (hb >> 10) & 0x1fu, ma = hb & 0x3ffu;
-        float v;
-        if (ex == 0) v = std::ldexp(float(ma), -24);
-        else if (ex == 31) v = ma ? NAN : INFINITY;
-        else v = std::ldexp(float(ma | 0x400u), int(ex) - 25);
-        return s2 ? -v : v;
-    };
-    auto step = [](uint16_t hb, bool up) -> uint16_t {     // next representable half toward +inf (up) or -inf
-        if ((hb & 0x7fffu) == 0) return up ? uint16_t(0x0001) : uint16_t(0x8001);
-        const bool neg = hb & 0x8000u;
-        return (neg == up) ? uint16_t(hb - 1) : uint16_t(hb + 1);
-    };
-    const float v = value(h);
-    if (down && v > x) h = step(h, false);
-    if (!down && v < x) h = step(h, true);
-    return h;
-}
-
-inline int32_t leaf_link(uint32_t first, uint32_t count) { return ~int32_t((first << 2) | (count - 1)); }
-
-
 }  // namespace
-
-void derive_node_forms(HostBvh &out, unsigned hw, const std::vector<uint8_t> *only = nullptr);
 
 void build_bvh(const vhr_vertex *vertices, const uint32_t *indices, const vhr_primitive *primitives,
                uint32_t primitive_count, HostBvh &out, int leaf_tris, int threads, int presplit_percent, int frame_mode) {
@@ -398,22 +310,11 @@ void build_bvh(const vhr_vertex *vertices, const uint32_t *indices, const vhr_pr
     b.tris.reserve(total);
     for (uint32_t p = 0; p < primitive_count; ++p) {
         const vhr_primitive &pr = primitives[p];
-        const float *m = pr.transform;
         for (uint32_t t = 0; t < pr.index_count / 3; ++t) {
-            float w[3][3];
-            for (int c = 0; c < 3; ++c) {
-                const float *v = vertices[pr.vertex_offset + indices[pr.index_offset + 3 * t + c]].pos;
-                // transform * vec4(pos, 1), columns accumulated left to right, no contraction
-                w[c][0] = ((m[0] * v[0] + m[4] * v[1]) + m[8] * v[2]) + m[12];
-                w[c][1] = ((m[1] * v[0] + m[5] * v[1]) + m[9] * v[2]) + m[13];
-                w[c][2] = ((m[2] * v[0] + m[6] * v[1]) + m[10] * v[2]) + m[14];
-            }
+            const uint32_t *vi = indices + pr.index_offset + 3 * t;
             BvhTri tri;
-            for (int a = 0; a < 3; ++a) {
-                tri.v0[a] = w[0][a];
-                tri.e1[a] = w[1][a] - w[0][a];
-                tri.e2[a] = w[2][a] - w[0][a];
-            }
+            bvh_math::world_record(pr.transform, vertices[pr.vertex_offset + vi[0]].pos, vertices[pr.vertex_offset + vi[1]].pos, vertices[pr.vertex_offset + vi[2]].pos, tri.v0,
+                                   tri.e1, tri.e2);
             tri.prim = p;
             tri.tri = t;
             tri.flat = uint32_t(b.tris.size());
@@ -458,16 +359,7 @@ void build_bvh(const vhr_vertex *vertices, const uint32_t *indices, const vhr_pr
     for (size_t i = i0; i < i1; ++i) {
         const BvhTri &t = b.tris[i];
         Box bx;
-        bx.reset();
-        if (framed) {
-            bvh_frame::box_in_frame(out.frame, t, bx.lo, bx.hi);
-        } else {
-            float p1[3], p2[3];
-            for (int a = 0; a < 3; ++a) { p1[a] = t.v0[a] + t.e1[a]; p2[a] = t.v0[a] + t.e2[a]; }
-            bx.grow(t.v0);
-            bx.grow(p1);
-            bx.grow(p2);
-        }
+        bvh_math::record_box(t, out.frame, framed, bx.lo, bx.hi);
         b.tri_box[i] = bx;
         for (int a = 0; a < 3; ++a) b.centroid[size_t(i) * 3 + a] = 0.5f * (bx.lo[a] + bx.hi[a]);
         b.order[i] = uint32_t(i);
@@ -586,21 +478,18 @@ void build_bvh(const vhr_vertex *vertices, const uint32_t *indices, const vhr_pr
 
     const float inf = std::numeric_limits<float>::infinity();
     auto set_child = [&](BvhNode &node, int which, const TmpNode &child, int32_t link) {
-        float lo[3], hi[3];
-        padded(child.box, lo, hi);
-        float *dst = which == 0 ? node.box0 : node.box1;
-        for (int a = 0; a < 3; ++a) { dst[2 * a] = lo[a]; dst[2 * a + 1] = hi[a]; }
+        bvh_math::pad_slot(child.box.lo, child.box.hi, which == 0 ? node.box0 : node.box1);
         (which == 0 ? node.child0 : node.child1) = link;
     };
 
     const TmpNode &root = b.nodes[0];
     if (root.left < 0) {                       // whole scene fits one leaf
         BvhNode node{};
-        set_child(node, 0, root, leaf_link(leaf_pos[0], root.count));
+        set_child(node, 0, root, bvh_math::leaf_link(leaf_pos[0], root.count));
         for (int a = 0; a < 3; ++a) { node.box1[2 * a] = inf; node.box1[2 * a + 1] = -inf; }
         node.child1 = node.child0;
         out.nodes.push_back(node);
-        derive_node_forms(out, hw);
+        derive_node_forms(out, threads);
         return;
     }
     // breadth-first numbering of the inner nodes
@@ -623,127 +512,68 @@ void build_bvh(const vhr_vertex *vertices, const uint32_t *indices, const vhr_pr
         const TmpNode &t = b.nodes[bfs_order[k]];
         BvhNode node{};
         const TmpNode &l = b.nodes[t.left], &r = b.nodes[t.right];
-        set_child(node, 0, l, l.left >= 0 ? bfs_index[t.left] : leaf_link(leaf_pos[t.left], l.count));
-        set_child(node, 1, r, r.left >= 0 ? bfs_index[t.right] : leaf_link(leaf_pos[t.right], r.count));
+        set_child(node, 0, l, l.left >= 0 ? bfs_index[t.left] : bvh_math::leaf_link(leaf_pos[t.left], l.count));
+        set_child(node, 1, r, r.left >= 0 ? bfs_index[t.right] : bvh_math::leaf_link(leaf_pos[t.right], r.count));
         out.nodes[k] = node;
     }
     });
     lap("numbering + (lo, hi) nodes");
-    derive_node_forms(out, hw);
+    derive_node_forms(out, threads);
     lap("derived node forms");
 }
 
-// The scene centre and the derived node forms of out.nodes (centre / half extent, 48-byte, half precision): the last stage of a build and of a refit.
-// `only` (a partial refit whose scene centre kept its bits): the forms of the flagged nodes with out.centre as it stands
-void derive_node_forms(HostBvh &out, unsigned hw, const std::vector<uint8_t> *only) {
-    const float inf = std::numeric_limits<float>::infinity();
-    // centre / half-extent twin of every node (BvhNodeCH): c +- h must contain [lo, hi] in exact arithmetic
-    auto finalize_ch = [&]() {
-        out.nodes_ch.resize(out.nodes.size());
-        parallel_for(out.nodes.size(), hw, [&](size_t k0, size_t k1) {
-        for (size_t k = k0; k < k1; ++k) {
-            if (only && !(*only)[k]) continue;
-            const BvhNode &nd = out.nodes[k];
-            BvhNodeCH c{};
-            for (int which = 0; which < 2; ++which) {
-                const float *box = which == 0 ? nd.box0 : nd.box1;
-                float *hdst = which == 0 ? c.h0 : c.h1;
-                for (int a = 0; a < 3; ++a) {
-                    const float lo = box[2 * a], hi = box[2 * a + 1];
-                    float cc = 0.0f, hh = -1.0f;                   // absent child: never entered
-                    if (lo <= hi) {
-                        cc = 0.5f * lo + 0.5f * hi;
-                        hh = std::max(hi - cc, cc - lo);
-                        hh += (std::fabs(cc) + hh) * 2.4e-7f;      // 4 ulp of the magnitudes involved
-                        while (double(cc) - double(hh) > double(lo) || double(cc) + double(hh) < double(hi)) hh = std::nextafter(hh, inf);
-                    }
-                    (a == 0 ? c.cx : a == 1 ? c.cy : c.cz)[which] = cc;
-                    hdst[a] = hh;
-                }
-            }
-            c.child0 = nd.child0;
-            c.child1 = nd.child1;
-            out.nodes_ch[k] = c;
-        }
-        });
-        // the 48-byte form: half extents as the upper half of their fp32 pattern, rounded up (away from zero for the -1 of an
-        // absent child, which is exact anyway)
-        auto upper16 = [](float h) -> uint32_t {
-            uint32_t bits;
-            std::memcpy(&bits, &h, 4);
-            if (h > 0.0f && (bits & 0xffffu)) bits += 0x10000u;      // next value with 16 zero bits below (an overflow would give +inf: no finite h gets there)
-            return bits >> 16;
-        };
-        out.nodes48.resize(out.nodes_ch.size());
-        parallel_for(out.nodes_ch.size(), hw, [&](size_t k0, size_t k1) {
-        for (size_t k = k0; k < k1; ++k) {
-            if (only && !(*only)[k]) continue;
-            const BvhNodeCH &c = out.nodes_ch[k];
-            BvhNode48 n{};
-            for (int w = 0; w < 2; ++w) { n.cx[w] = c.cx[w]; n.cy[w] = c.cy[w]; n.cz[w] = c.cz[w]; }
-            n.hp[0] = (upper16(c.h0[0]) << 16) | upper16(c.h0[1]);
-            n.hp[1] = (upper16(c.h0[2]) << 16) | upper16(c.h1[0]);
-            n.hp[2] = (upper16(c.h1[1]) << 16) | upper16(c.h1[2]);
-            // inner links as BYTE offsets (index * 48): the walkers add them to the base address as they are
-            n.child0 = c.child0 >= 0 ? c.child0 * int32_t(sizeof(BvhNode48)) : c.child0;
-            n.child1 = c.child1 >= 0 ? c.child1 * int32_t(sizeof(BvhNode48)) : c.child1;
-            out.nodes48[k] = n;
-        }
-        });
-    };
-
-    auto finalize16 = [&]() {
-        finalize_ch();
-        float lo[3] = { inf, inf, inf }, hi[3] = { -inf, -inf, -inf };
-        for (size_t k = 0; k < (only ? 0 : out.nodes.size()); ++k) {
-            const BvhNode &nd = out.nodes[k];
-            for (int a = 0; a < 3; ++a) {
-                if (nd.box0[2 * a] <= nd.box0[2 * a + 1]) { lo[a] = std::min(lo[a], nd.box0[2 * a]); hi[a] = std::max(hi[a], nd.box0[2 * a + 1]); }
-                if (nd.box1[2 * a] <= nd.box1[2 * a + 1]) { lo[a] = std::min(lo[a], nd.box1[2 * a]); hi[a] = std::max(hi[a], nd.box1[2 * a + 1]); }
-            }
-        }
-        if (!only) for (int a = 0; a < 3; ++a) out.centre[a] = (lo[a] <= hi[a]) ? 0.5f * (lo[a] + hi[a]) : 0.0f;
-        out.nodes16.resize(out.nodes.size());
-        std::atomic<uint32_t> overflow{ 0 };
-        parallel_for(out.nodes.size(), hw, [&](size_t k0, size_t k1) {
-        for (size_t k = k0; k < k1; ++k) {
-            if (only && !(*only)[k]) continue;
-            const BvhNode &nd = out.nodes[k];
-            BvhNode16 c{};
-            for (int which = 0; which < 2; ++which) {
-                const float *box = which == 0 ? nd.box0 : nd.box1;
-                for (int a = 0; a < 3; ++a) {
-                    uint16_t c16, h16;
-                    if (!half_centre_extent(box[2 * a], box[2 * a + 1], out.centre[a], c16, h16)) overflow = 1;
-                    c.c[2 * a + which] = c16;
-                    c.h[2 * a + which] = h16;
-                }
-            }
-            // inner links as BYTE offsets (index * 32), like the 48-byte nodes'
-            c.child0 = nd.child0 >= 0 ? nd.child0 * int32_t(sizeof(BvhNode16)) : nd.child0;
-            c.child1 = nd.child1 >= 0 ? nd.child1 * int32_t(sizeof(BvhNode16)) : nd.child1;
-            out.nodes16[k] = c;
-        }
-        });
-        // (`only`: the nodes left alone count too -- an overflow leaves a centre or a half extent with the exponent of inf, which is what
-        // nodes16_in_range looks for; nothing else this function writes is out of the walkers' range)
-        out.nodes16_valid = only ? nodes16_in_range(out) : overflow == 0 && out.nodes.size() * sizeof(BvhNode16) < (size_t(1) << 31);
-    };
-    finalize16();
+// The scene centre and the derived node forms of out.nodes (centre / half extent, 48-byte, half precision; bvh_math::forms_of): the last stage of a
+// build and of a refit.  `only` (a partial refit whose scene centre kept its bits): the forms of the flagged nodes with out.centre as it stands
+void derive_node_forms(HostBvh &out, int threads, const std::vector<uint8_t> *only) {
+    const unsigned hw = host_threads(threads);
+    const size_t n = out.nodes.size();
+    if (!only) {
+        float lo[3], hi[3];
+        bvh_math::no_bounds(lo, hi);
+        for (const BvhNode &nd : out.nodes) bvh_math::bounds_of_node(nd, lo, hi);
+        bvh_math::centre_of(lo, hi, out.centre);
+    }
+    out.nodes_ch.resize(n);
+    out.nodes48.resize(n);
+    out.nodes16.resize(n);
+    parallel_for(n, hw, [&](size_t k0, size_t k1) {
+        for (size_t k = k0; k < k1; ++k)
+            if (!only || (*only)[k]) bvh_math::forms_of(out.nodes[k], out.centre, out.nodes_ch[k], out.nodes48[k], out.nodes16[k]);
+    });
+    // (`only`: the nodes left alone count too -- an overflow leaves a centre or a half extent with the exponent of inf, which is what
+    // nodes16_in_range looks for; nothing else forms_of writes is out of the walkers' range)
+    out.nodes16_valid = nodes16_in_range(out);
 }
 
 // A 64-bit multiplicative hash over the (lo, hi) nodes and the leaf triangles in their final order, eight bytes at a time: the
 // identity of a build (tests: the tree must not depend on the number of build threads)
-uint64_t bvh_fingerprint(const HostBvh &bvh) {
+namespace {
+struct WordHash {
     uint64_t h = 1469598103934665603ull;
-    auto eat = [&](const void *p, size_t bytes) {
-        const unsigned char *b = static_cast<const unsigned char *>(p);
-        for (size_t i = 0; i + 8 <= bytes; i += 8) { uint64_t w; std::memcpy(&w, b + i, 8); h = (h ^ w) * 1099511628211ull; h ^= h >> 29; }
-    };
-    static_assert(sizeof(BvhNode) % 8 == 0 && sizeof(BvhTri) % 8 == 0, "whole words");
-    eat(bvh.nodes.data(), bvh.nodes.size() * sizeof(BvhNode));
-    eat(bvh.tris.data(), bvh.tris.size() * sizeof(BvhTri));
-    return h;
+    template <typename T>
+    void eat(const T *p, size_t count) {
+        static_assert(sizeof(T) % 8 == 0, "whole words");
+        const unsigned char *b = reinterpret_cast<const unsigned char *>(p);
+        for (size_t i = 0; i + 8 <= count * sizeof(T); i += 8) { uint64_t w; std::memcpy(&w, b + i, 8); h = (h ^ w) * 1099511628211ull; h ^= h >> 29; }
+    }
+};
+}  // namespace
+uint64_t bvh_fingerprint(const HostBvh &bvh) {
+    WordHash hash;
+    hash.eat(bvh.nodes.data(), bvh.nodes.size());
+    hash.eat(bvh.tris.data(), bvh.tris.size());
+    return hash.h;
+}
+// ... and the same hash over what the walkers read instead: the scene centre and the three derived forms, the 32-byte form whether it is in
+// range or not (a scene beyond the half range leaves the same inf in it with either builder)
+uint64_t bvh_forms_fingerprint(const HostBvh &bvh) {
+    WordHash hash;
+    const struct { float c[4]; } centre = { { bvh.centre[0], bvh.centre[1], bvh.centre[2], 0.0f } };
+    hash.eat(&centre, 1);
+    hash.eat(bvh.nodes_ch.data(), bvh.nodes_ch.size());
+    hash.eat(bvh.nodes48.data(), bvh.nodes48.size());
+    hash.eat(bvh.nodes16.data(), bvh.nodes16.size());
+    return hash.h;
 }
 
 // A hash of the TREE rather than of its arrays: per inner node the bits of its two child boxes and its children's hashes (left, right),
@@ -753,7 +583,7 @@ uint64_t bvh_fingerprint(const HostBvh &bvh) {
 uint64_t bvh_tree_fingerprint(const HostBvh &bvh) {
     auto mix = [](uint64_t h, uint64_t w) { h = (h ^ w) * 1099511628211ull; return h ^ (h >> 29); };
     auto leaf_hash = [&](int32_t link) {
-        const uint32_t v = ~uint32_t(link), first = v >> 2, count = (v & 3u) + 1u;
+        const uint32_t first = bvh_math::leaf_first(link), count = bvh_math::leaf_count(link);
         uint32_t ids[4] = { 0, 0, 0, 0 };
         for (uint32_t i = 0; i < count; ++i) ids[i] = bvh.tris[first + i].flat;
         std::sort(ids, ids + count);
@@ -778,47 +608,17 @@ uint64_t bvh_tree_fingerprint(const HostBvh &bvh) {
 // rests on (boxes only cull).  out: boxes checked, centre / half-extent boxes that do not contain theirs, 48-byte boxes that do not
 // contain the centre / half-extent box, half-precision 32-byte (compact) boxes that do not contain theirs.  (vhr_get_bvh_form_checks)
 void check_node_forms(const HostBvh &bvh, uint64_t out[4], int threads) {
-    auto upper = [](uint32_t w16) -> double { const uint32_t bits = w16 << 16; float f; std::memcpy(&f, &bits, 4); return double(f); };
-    out[0] = out[1] = out[2] = out[3] = 0;
     std::atomic<uint64_t> total[4];
     for (auto &t : total) t = 0;
     parallel_for(bvh.nodes.size(), host_threads(threads), [&](size_t k0, size_t k1) {
-    uint64_t out[4] = { 0, 0, 0, 0 };                  // this thread's counts
-    for (size_t k = k0; k < k1; ++k) {
-        const BvhNode &nd = bvh.nodes[k];
-        const BvhNodeCH &ch = bvh.nodes_ch[k];
-        const BvhNode48 &n48 = bvh.nodes48[k];
-        const BvhNode16 &n16 = bvh.nodes16[k];
-        const double h48[6] = { upper(n48.hp[0] >> 16), upper(n48.hp[0] & 0xffffu), upper(n48.hp[1] >> 16), upper(n48.hp[1] & 0xffffu), upper(n48.hp[2] >> 16), upper(n48.hp[2] & 0xffffu) };
-        for (int which = 0; which < 2; ++which) {
-            const float *box = which == 0 ? nd.box0 : nd.box1;
-            const float *hh = which == 0 ? ch.h0 : ch.h1;
-            ++out[0];
-            for (int a = 0; a < 3; ++a) {
-                const double lo = box[2 * a], hi = box[2 * a + 1];
-                const double c = (a == 0 ? ch.cx : a == 1 ? ch.cy : ch.cz)[which], h = hh[a];
-                const double c48 = (a == 0 ? n48.cx : a == 1 ? n48.cy : n48.cz)[which], hw = h48[3 * which + a];
-                // the 32-byte form: centre + c16 +- h16 in exact arithmetic, no subnormal / inf / NaN half (checked only when the form is in use)
-                const uint16_t cb = n16.c[2 * a + which], hb = n16.h[2 * a + which];
-                const double c16 = double(bvh.centre[a]) + half_value(cb), h16 = half_value(hb);
-                const bool normal16 = (cb == 0 || (((cb >> 10) & 31) != 0 && ((cb >> 10) & 31) != 31)) && ((hb >> 10) & 31) != 0 && ((hb >> 10) & 31) != 31;
-                if (!(lo <= hi)) {                           // an absent child: never entered in any form
-                    if (!(h < 0.0)) ++out[1];
-                    if (!(hw < 0.0)) ++out[2];
-                    if (bvh.nodes16_valid && !(h16 < 0.0)) ++out[3];
-                    continue;
-                }
-                if (c - h > lo || c + h < hi) ++out[1];
-                if (c48 != c || hw < h) ++out[2];
-                if (bvh.nodes16_valid && (!normal16 || !(c16 - h16 <= lo) || !(c16 + h16 >= hi))) ++out[3];
-            }
+        uint64_t mine[4] = { 0, 0, 0, 0 };                 // this thread's counts
+        for (size_t k = k0; k < k1; ++k) {
+            uint32_t bad[5] = { 0, 0, 0, 0, 0 };
+            bvh_math::check_forms(bvh.nodes[k], bvh.nodes_ch[k], bvh.nodes48[k], bvh.nodes16[k], bvh.centre, bad);
+            for (int i = 0; i < 3; ++i) mine[i] += bad[i];
+            if (bvh.nodes16_valid) mine[3] += bad[3];      // (the 32-byte form is checked only where it is in use)
         }
-        auto as48 = [](int32_t link) { return link >= 0 ? link * int32_t(sizeof(BvhNode48)) : link; };
-        if (n48.child0 != as48(nd.child0) || n48.child1 != as48(nd.child1) || ch.child0 != nd.child0 || ch.child1 != nd.child1) ++out[2];
-        auto as16 = [](int32_t link) { return link >= 0 ? link * int32_t(sizeof(BvhNode16)) : link; };
-        if (bvh.nodes16_valid && (n16.child0 != as16(nd.child0) || n16.child1 != as16(nd.child1))) ++out[3];
-    }
-    for (int i = 0; i < 4; ++i) total[i] += out[i];
+        for (int i = 0; i < 4; ++i) total[i] += mine[i];
     });
     for (int i = 0; i < 4; ++i) out[i] = total[i];
 }
@@ -826,29 +626,33 @@ void check_node_forms(const HostBvh &bvh, uint64_t out[4], int threads) {
 bool nodes16_in_range(const HostBvh &bvh) {
     if (bvh.nodes16.size() != bvh.nodes.size() || bvh.nodes16.size() * sizeof(BvhNode16) >= (size_t(1) << 31)) return false;
     for (const BvhNode16 &n : bvh.nodes16)
-        for (int i = 0; i < 6; ++i) {
-            const int ec = (n.c[i] >> 10) & 31, eh = (n.h[i] >> 10) & 31;
-            if (ec == 31 || (ec == 0 && n.c[i] != 0) || eh == 31 || eh == 0) return false;
-        }
+        if (!bvh_math::half16_in_range(n)) return false;
     return true;
 }
 
-// ---- refit: the host twin of csrc/kernels_bvh.hip's k0_refit_* kernels ----
+// ---- refit: the host side of csrc/kernels_bvh.hip's k0_refit_* kernels (the arithmetic of both: bvh_math.hpp) ----
 namespace {
-// the box of one leaf record in the tree's frame: build_bvh's "triangles + boxes" stage
-inline void record_box(const HostBvh &bvh, const BvhTri &t, Box &bx) {
-    bx.reset();
-    if (bvh.frame_on) {
-        bvh_frame::box_in_frame(bvh.frame, t, bx.lo, bx.hi);
-    } else {
-        float p1[3], p2[3];
-        for (int a = 0; a < 3; ++a) { p1[a] = t.v0[a] + t.e1[a]; p2[a] = t.v0[a] + t.e2[a]; }
-        bx.grow(t.v0);
-        bx.grow(p1);
-        bx.grow(p2);
+// the walk of both refits relies on this and on nothing else: links in range, children numbered after their parents, records of this scene
+bool refit_can_walk(const HostBvh &bvh, const vhr_primitive *primitives, uint32_t primitive_count, bool links) {
+    const size_t n_nodes = bvh.nodes.size(), n_tris = bvh.tris.size();
+    for (size_t k = 0; links && k < n_nodes; ++k) {
+        const int32_t both[2] = { bvh.nodes[k].child0, bvh.nodes[k].child1 };
+        for (int32_t link : both) {
+            if (link >= 0) { if (size_t(link) <= k || size_t(link) >= n_nodes) return false; continue; }
+            if (size_t(bvh_math::leaf_first(link)) + bvh_math::leaf_count(link) > n_tris) return false;
+        }
     }
+    for (const BvhTri &t : bvh.tris)
+        if (t.prim >= primitive_count || t.tri >= primitives[t.prim].index_count / 3) return false;
+    return true;
 }
-inline bool absent_child1(const HostBvh &bvh, const BvhNode &nd) { return bvh.nodes.size() == 1 && nd.child1 == nd.child0; }     // (a one-leaf scene)
+// record `tri` re-derived in its slot from (prim, tri); returns the non-finite coordinates met
+uint32_t refit_record(BvhTri &tri, const vhr_vertex *vertices, const uint32_t vi[3], const vhr_primitive &pr) {
+    return bvh_math::world_record(pr.transform, vertices[vi[0]].pos, vertices[vi[1]].pos, vertices[vi[2]].pos, tri.v0, tri.e1, tri.e2);
+}
+void record_corners(const BvhTri &tri, const uint32_t *indices, const vhr_primitive &pr, uint32_t vi[3]) {
+    for (int c = 0; c < 3; ++c) vi[c] = pr.vertex_offset + indices[pr.index_offset + 3 * tri.tri + c];
+}
 }  // namespace
 
 void refit_check_pass(const HostBvh &bvh, uint64_t counts[3], unsigned hw);
@@ -856,84 +660,37 @@ void refit_check_pass(const HostBvh &bvh, uint64_t counts[3], unsigned hw);
 bool refit_bvh(const vhr_vertex *vertices, const uint32_t *indices, const vhr_primitive *primitives, uint32_t primitive_count, HostBvh &bvh, uint64_t counts[3], int threads) {
     counts[0] = counts[1] = counts[2] = 0;
     const size_t n_nodes = bvh.nodes.size(), n_tris = bvh.tris.size();
-    if (!n_nodes || !n_tris) return false;
-    for (size_t k = 0; k < n_nodes; ++k) {                 // the walk below relies on this and on nothing else
-        const int32_t links[2] = { bvh.nodes[k].child0, bvh.nodes[k].child1 };
-        for (int32_t link : links) {
-            if (link >= 0) { if (size_t(link) <= k || size_t(link) >= n_nodes) return false; continue; }
-            const uint32_t v = ~uint32_t(link), first = v >> 2, count = (v & 3u) + 1u;
-            if (size_t(first) + count > n_tris) return false;
-        }
-    }
-    for (const BvhTri &t : bvh.tris)
-        if (t.prim >= primitive_count || t.tri >= primitives[t.prim].index_count / 3) return false;
+    if (!n_nodes || !n_tris || !refit_can_walk(bvh, primitives, primitive_count, true)) return false;
     const unsigned hw = host_threads(threads);
-    // 1. the records, each in its slot (build_bvh's first loop: the same expressions in the same order)
+    // 1. the records, each in its slot
     std::atomic<uint64_t> non_finite{ 0 };
     parallel_for(n_tris, hw, [&](size_t i0, size_t i1) {
         uint64_t bad = 0;
         for (size_t i = i0; i < i1; ++i) {
-            BvhTri &tri = bvh.tris[i];
-            const vhr_primitive &pr = primitives[tri.prim];
-            const float *m = pr.transform;
-            float w[3][3];
-            for (int c = 0; c < 3; ++c) {
-                const float *v = vertices[pr.vertex_offset + indices[pr.index_offset + 3 * tri.tri + c]].pos;
-                w[c][0] = ((m[0] * v[0] + m[4] * v[1]) + m[8] * v[2]) + m[12];
-                w[c][1] = ((m[1] * v[0] + m[5] * v[1]) + m[9] * v[2]) + m[13];
-                w[c][2] = ((m[2] * v[0] + m[6] * v[1]) + m[10] * v[2]) + m[14];
-            }
-            for (int a = 0; a < 3; ++a) {
-                tri.v0[a] = w[0][a];
-                tri.e1[a] = w[1][a] - w[0][a];
-                tri.e2[a] = w[2][a] - w[0][a];
-                bad += uint64_t(!std::isfinite(tri.v0[a])) + uint64_t(!std::isfinite(tri.e1[a])) + uint64_t(!std::isfinite(tri.e2[a]));
-            }
+            const vhr_primitive &pr = primitives[bvh.tris[i].prim];
+            uint32_t vi[3];
+            record_corners(bvh.tris[i], indices, pr, vi);
+            bad += refit_record(bvh.tris[i], vertices, vi, pr);
         }
         non_finite += bad;
     });
     counts[2] = non_finite;
-    // 2. + 3. the boxes bottom-up (children have larger indices than their parents), padded into the parents' slots
-    std::vector<Box> self(n_nodes);
-    auto child_box = [&](int32_t link) {
-        if (link >= 0) return self[size_t(link)];
-        const uint32_t v = ~uint32_t(link), first = v >> 2, count = (v & 3u) + 1u;
-        Box bx, one;
-        bx.reset();
-        for (uint32_t i = 0; i < count; ++i) { record_box(bvh, bvh.tris[first + i], one); bx.grow(one); }
-        return bx;
-    };
-    auto put = [](float *dst, const Box &bx) {
-        float lo[3], hi[3];
-        padded(bx, lo, hi);
-        for (int a = 0; a < 3; ++a) { dst[2 * a] = lo[a]; dst[2 * a + 1] = hi[a]; }
-    };
-    for (size_t k = n_nodes; k-- > 0;) {
-        BvhNode &nd = bvh.nodes[k];
-        const Box b0 = child_box(nd.child0);
-        put(nd.box0, b0);
-        self[k] = b0;
-        if (!absent_child1(bvh, nd)) {
-            const Box b1 = child_box(nd.child1);
-            put(nd.box1, b1);
-            self[k].grow(b1);
-        }
-    }
-    // 4. the scene centre and the derived forms
-    derive_node_forms(bvh, hw);
-    // what a partial refit starts from: the unpadded boxes, every node's parent, every record's leaf node
+    // 2. + 3. the boxes bottom-up (children have larger indices than their parents), padded into the parents' slots; and what a partial refit
+    // starts from: the unpadded boxes, every node's parent, every record's leaf node
     bvh.self_box.resize(n_nodes * 6);
     bvh.parent.assign(n_nodes, 0xffffffffu);
     bvh.owner.assign(n_tris, 0u);
-    for (size_t k = 0; k < n_nodes; ++k) {
-        for (int a = 0; a < 3; ++a) { bvh.self_box[6 * k + a] = self[k].lo[a]; bvh.self_box[6 * k + 3 + a] = self[k].hi[a]; }
-        const int32_t links[2] = { bvh.nodes[k].child0, bvh.nodes[k].child1 };
-        for (int32_t link : links) {
+    for (size_t k = n_nodes; k-- > 0;) {
+        BvhNode &nd = bvh.nodes[k];
+        bvh_math::refit_slots(nd, n_nodes == 1, bvh.tris.data(), bvh.self_box.data(), bvh.frame, bvh.frame_on, &bvh.self_box[6 * k], &bvh.self_box[6 * k + 3]);
+        const int32_t both[2] = { nd.child0, nd.child1 };
+        for (int32_t link : both) {
             if (link >= 0) { bvh.parent[size_t(link)] = uint32_t(k); continue; }
-            const uint32_t v = ~uint32_t(link), first = v >> 2, count = (v & 3u) + 1u;
-            for (uint32_t i = 0; i < count; ++i) bvh.owner[first + i] = uint32_t(k);
+            for (uint32_t i = 0; i < bvh_math::leaf_count(link); ++i) bvh.owner[bvh_math::leaf_first(link) + i] = uint32_t(k);
         }
     }
+    // 4. the scene centre and the derived forms
+    derive_node_forms(bvh, threads);
     refit_check_pass(bvh, counts, hw);
     return true;
 }
@@ -943,36 +700,11 @@ void refit_check_pass(const HostBvh &bvh, uint64_t counts[3], unsigned hw) {
     const size_t n_nodes = bvh.nodes.size();
     std::atomic<uint64_t> records_outside{ 0 }, children_outside{ 0 };
     parallel_for(n_nodes, hw, [&](size_t k0, size_t k1) {
-        uint64_t bad_records = 0, bad_children = 0;
-        auto inside = [](const float *lo, const float *hi, const float *slot) {
-            for (int a = 0; a < 3; ++a) if (!(lo[a] >= slot[2 * a] && hi[a] <= slot[2 * a + 1])) return false;
-            return true;
-        };
-        for (size_t k = k0; k < k1; ++k) {
-            const BvhNode &nd = bvh.nodes[k];
-            for (int which = 0; which < 2; ++which) {
-                if (which == 1 && absent_child1(bvh, nd)) continue;
-                const float *slot = which == 0 ? nd.box0 : nd.box1;
-                const int32_t link = which == 0 ? nd.child0 : nd.child1;
-                if (link >= 0) {
-                    const BvhNode &c = bvh.nodes[size_t(link)];
-                    for (int w = 0; w < 2; ++w) {
-                        const float *cb = w == 0 ? c.box0 : c.box1;
-                        const float lo[3] = { cb[0], cb[2], cb[4] }, hi[3] = { cb[1], cb[3], cb[5] };
-                        if (!inside(lo, hi, slot)) ++bad_children;
-                    }
-                } else {
-                    const uint32_t v = ~uint32_t(link), first = v >> 2, count = (v & 3u) + 1u;
-                    for (uint32_t i = 0; i < count; ++i) {
-                        Box one;
-                        record_box(bvh, bvh.tris[first + i], one);
-                        if (!inside(one.lo, one.hi, slot)) ++bad_records;
-                    }
-                }
-            }
-        }
-        records_outside += bad_records;
-        children_outside += bad_children;
+        int bad_records = 0, bad_children = 0;
+        for (size_t k = k0; k < k1; ++k)
+            bvh_math::refit_check(bvh.nodes[k], n_nodes == 1, bvh.nodes.data(), bvh.tris.data(), bvh.frame, bvh.frame_on, bad_records, bad_children);
+        records_outside += uint64_t(bad_records);
+        children_outside += uint64_t(bad_children);
     });
     counts[0] = records_outside;
     counts[1] = children_outside;
@@ -986,8 +718,7 @@ bool refit_bvh_partial(const vhr_vertex *vertices, const uint32_t *indices, cons
     out[0] = out[1] = out[2] = out[3] = 0;
     const size_t n_nodes = bvh.nodes.size(), n_tris = bvh.tris.size();
     if (!n_nodes || !n_tris || bvh.self_box.size() != n_nodes * 6 || bvh.parent.size() != n_nodes || bvh.owner.size() != n_tris) return false;
-    for (const BvhTri &t : bvh.tris)
-        if (t.prim >= primitive_count || t.tri >= primitives[t.prim].index_count / 3) return false;
+    if (!refit_can_walk(bvh, primitives, primitive_count, false)) return false;
     const unsigned hw = host_threads(threads);
     // 1. mark, and the dirty records
     std::vector<uint8_t> mark(n_nodes, 0);
@@ -995,65 +726,21 @@ bool refit_bvh_partial(const vhr_vertex *vertices, const uint32_t *indices, cons
         BvhTri &tri = bvh.tris[i];
         const vhr_primitive &pr = primitives[tri.prim];
         uint32_t vi[3];
-        for (int c = 0; c < 3; ++c) vi[c] = pr.vertex_offset + indices[pr.index_offset + 3 * tri.tri + c];
+        record_corners(tri, indices, pr, vi);
         if (!(dirty.primitives.holds(tri.prim) || dirty.vertices.holds(vi[0]) || dirty.vertices.holds(vi[1]) || dirty.vertices.holds(vi[2]))) continue;
-        const float *m = pr.transform;
-        float w[3][3];
-        for (int c = 0; c < 3; ++c) {
-            const float *v = vertices[vi[c]].pos;
-            w[c][0] = ((m[0] * v[0] + m[4] * v[1]) + m[8] * v[2]) + m[12];
-            w[c][1] = ((m[1] * v[0] + m[5] * v[1]) + m[9] * v[2]) + m[13];
-            w[c][2] = ((m[2] * v[0] + m[6] * v[1]) + m[10] * v[2]) + m[14];
-        }
-        for (int a = 0; a < 3; ++a) {
-            tri.v0[a] = w[0][a];
-            tri.e1[a] = w[1][a] - w[0][a];
-            tri.e2[a] = w[2][a] - w[0][a];
-            counts[2] += uint64_t(!std::isfinite(tri.v0[a])) + uint64_t(!std::isfinite(tri.e1[a])) + uint64_t(!std::isfinite(tri.e2[a]));
-        }
+        counts[2] += refit_record(tri, vertices, vi, pr);
         ++out[0];
         for (uint32_t node = bvh.owner[i]; node != 0xffffffffu && !mark[node]; node = bvh.parent[node]) { mark[node] = 1; ++out[1]; }
     }
     // 2. + 3. the dirty nodes' boxes, bottom-up, from the boxes the clean ones keep
-    auto self_of = [&](size_t k) { Box b; for (int a = 0; a < 3; ++a) { b.lo[a] = bvh.self_box[6 * k + a]; b.hi[a] = bvh.self_box[6 * k + 3 + a]; } return b; };
-    auto child_box = [&](int32_t link) {
-        if (link >= 0) return self_of(size_t(link));
-        const uint32_t v = ~uint32_t(link), first = v >> 2, count = (v & 3u) + 1u;
-        Box bx, one;
-        bx.reset();
-        for (uint32_t i = 0; i < count; ++i) { record_box(bvh, bvh.tris[first + i], one); bx.grow(one); }
-        return bx;
-    };
-    auto put = [](float *dst, const Box &bx) {
-        float lo[3], hi[3];
-        padded(bx, lo, hi);
-        for (int a = 0; a < 3; ++a) { dst[2 * a] = lo[a]; dst[2 * a + 1] = hi[a]; }
-    };
-    for (size_t k = n_nodes; k-- > 0;) {
-        if (!mark[k]) continue;
-        BvhNode &nd = bvh.nodes[k];
-        Box mine = child_box(nd.child0);
-        put(nd.box0, mine);
-        if (!absent_child1(bvh, nd)) {
-            const Box b1 = child_box(nd.child1);
-            put(nd.box1, b1);
-            mine.grow(b1);
-        }
-        for (int a = 0; a < 3; ++a) { bvh.self_box[6 * k + a] = mine.lo[a]; bvh.self_box[6 * k + 3 + a] = mine.hi[a]; }
-    }
-    // 4. the scene centre from the root's two slots (every other slot lies inside them: the containment the check pass counts violations of)
-    const float inf = std::numeric_limits<float>::infinity();
+    for (size_t k = n_nodes; k-- > 0;)
+        if (mark[k]) bvh_math::refit_slots(bvh.nodes[k], n_nodes == 1, bvh.tris.data(), bvh.self_box.data(), bvh.frame, bvh.frame_on, &bvh.self_box[6 * k], &bvh.self_box[6 * k + 3]);
+    // 4. the scene centre from the root's two slots
     float centre[3];
-    const BvhNode &root = bvh.nodes[0];
-    for (int a = 0; a < 3; ++a) {
-        float lo = inf, hi = -inf;
-        if (root.box0[2 * a] <= root.box0[2 * a + 1]) { lo = std::min(lo, root.box0[2 * a]); hi = std::max(hi, root.box0[2 * a + 1]); }
-        if (root.box1[2 * a] <= root.box1[2 * a + 1]) { lo = std::min(lo, root.box1[2 * a]); hi = std::max(hi, root.box1[2 * a + 1]); }
-        centre[a] = lo <= hi ? 0.5f * (lo + hi) : 0.0f;
-    }
+    bvh_math::centre_of_root(bvh.nodes[0], centre);
     const bool moved = std::memcmp(centre, bvh.centre, sizeof(centre)) != 0;
-    if (moved) derive_node_forms(bvh, hw);               // (the whole-tree reduction: the same centre)
-    else derive_node_forms(bvh, hw, &mark);
+    if (moved) derive_node_forms(bvh, threads);          // (the whole-tree reduction: the same centre)
+    else derive_node_forms(bvh, threads, &mark);
     out[2] = moved ? n_nodes : out[1];
     out[3] = moved ? 1u : 0u;
     const uint64_t non_finite = counts[2];
@@ -1064,23 +751,13 @@ bool refit_bvh_partial(const vhr_vertex *vertices, const uint32_t *indices, cons
 
 double bvh_sah_cost(const HostBvh &bvh) {
     if (bvh.nodes.empty()) return 0.0;
-    auto half_area = [](const float *b) {
-        const double dx = double(b[1]) - double(b[0]), dy = double(b[3]) - double(b[2]), dz = double(b[5]) - double(b[4]);
-        return dx * dy + dy * dz + dz * dx;
-    };
-    auto weight = [](int32_t link) { return link >= 0 ? 1.0 : double((~uint32_t(link) & 3u) + 1u); };
+    const bool single = bvh.nodes.size() == 1;
     double sum = 0.0;
     for (const BvhNode &nd : bvh.nodes) {
-        sum += half_area(nd.box0) * weight(nd.child0);
-        if (!absent_child1(bvh, nd)) sum += half_area(nd.box1) * weight(nd.child1);
+        sum += bvh_math::sah_term(nd.box0, nd.child0);
+        if (!bvh_math::absent_child1(nd, single)) sum += bvh_math::sah_term(nd.box1, nd.child1);
     }
-    const BvhNode &r = bvh.nodes[0];
-    float root[6];
-    for (int i = 0; i < 6; ++i) root[i] = r.box0[i];
-    if (!absent_child1(bvh, r))
-        for (int a = 0; a < 3; ++a) { root[2 * a] = std::min(root[2 * a], r.box1[2 * a]); root[2 * a + 1] = std::max(root[2 * a + 1], r.box1[2 * a + 1]); }
-    const double area = half_area(root);
-    return area > 0.0 ? sum / area : 0.0;
+    return bvh_math::sah_cost(sum, bvh.nodes[0], single);
 }
 
 }  // namespace vhr

@@ -1101,7 +1101,26 @@ int vhr_get_bvh_tree_fingerprint(vhr_context *ctx, uint64_t *out) {
     *out = ctx->bvh_tree_fingerprint;
     return VHR_OK;
 }
-
+// The forms as they stand against the forms the host derives from the same (lo, hi) nodes: equal hashes say that the builder that made the
+// tree (or refitted it) and the host run the same bvh_math.hpp, conversions included.
+int vhr_get_bvh_forms_fingerprint(vhr_context *ctx, uint64_t out[2]) {
+    if (!ctx || !out) return VHR_ERROR_INVALID_ARGUMENT;
+    if (ctx->host_only ? ctx->h_bvh.nodes.empty() : (!ctx->d_nodes || !ctx->node_count))
+        return ctx->fail(VHR_ERROR_GRAPH, "vhr_get_bvh_forms_fingerprint: no geometry yet (vhr_update_geometry first)");
+    HostBvh fetched, again;
+    if (!ctx->host_only) {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        { const int src_ = ctx->sync_streams(); if (src_ != VHR_OK) return src_; }
+        const int frc = fetch_device_tree(ctx, fetched);
+        if (frc != VHR_OK) return frc;
+    }
+    const HostBvh &tree = ctx->host_only ? ctx->h_bvh : fetched;
+    out[0] = bvh_forms_fingerprint(tree);
+    again.nodes = tree.nodes;
+    derive_node_forms(again, ctx->bvh_build_threads);
+    out[1] = bvh_forms_fingerprint(again);
+    return VHR_OK;
+}
 
 int vhr_get_bvh_form_checks(vhr_context *ctx, uint64_t out[4]) {
     if (!ctx || !out) return VHR_ERROR_INVALID_ARGUMENT;

@@ -41,6 +41,7 @@
 #include "vhr_internal.hpp"
 #include "presplit.hpp"
 #include "bvh_frame.hpp"
+#include "bvh_math.hpp"
 
 namespace vhr {
 namespace {
@@ -58,7 +59,7 @@ __host__ __device__ inline float unordered(uint32_t u) {
     return f;
 }
 
-// ---- 1. triangles: world-space records (bvh_build.cpp:359-381) + boxes + the bounds of the box centres ----
+// ---- 1. triangles: world-space records + boxes (bvh_math.hpp) + the bounds of the box centres ----
 // min / max into a word many waves aim at: look first (most values no longer move it), then the atomic
 __device__ __forceinline__ void atomic_min_checked(uint32_t *p, uint32_t v) {
     if (v < __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(p, v);
@@ -77,28 +78,14 @@ __global__ __launch_bounds__(256) void k0_triangles_kernel(const vhr_vertex *__r
         while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (tri_prefix[mid] <= t) lo = mid; else hi = mid; }
         const uint32_t p = lo, local = t - tri_prefix[p];
         const vhr_primitive &pr = primitives[p];
-        const float *m = pr.transform;
-        float w[3][3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float *v = vertices[pr.vertex_offset + indices[pr.index_offset + 3u * local + uint32_t(k)]].pos;
-            // transform * vec4(pos, 1), columns accumulated left to right, no contraction
-            w[k][0] = ((m[0] * v[0] + m[4] * v[1]) + m[8] * v[2]) + m[12];
-            w[k][1] = ((m[1] * v[0] + m[5] * v[1]) + m[9] * v[2]) + m[13];
-            w[k][2] = ((m[2] * v[0] + m[6] * v[1]) + m[10] * v[2]) + m[14];
-        }
+        const uint32_t *vi = indices + pr.index_offset + 3u * local;
         BvhTri tri;
         Box6 b;
+        bvh_math::world_record(pr.transform, vertices[pr.vertex_offset + vi[0]].pos, vertices[pr.vertex_offset + vi[1]].pos, vertices[pr.vertex_offset + vi[2]].pos, tri.v0, tri.e1,
+                               tri.e2);
+        bvh_math::record_box(tri, nullptr, false, b.lo, b.hi);                       // (world axes: a frame's boxes come from k0_frame_boxes_kernel)
 #pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            tri.v0[a] = w[0][a];
-            tri.e1[a] = w[1][a] - w[0][a];
-            tri.e2[a] = w[2][a] - w[0][a];
-            const float p1 = tri.v0[a] + tri.e1[a], p2 = tri.v0[a] + tri.e2[a];      // the box of what the walkers intersect (bvh_build.cpp:402)
-            b.lo[a] = fminf(fminf(tri.v0[a], p1), p2);
-            b.hi[a] = fmaxf(fmaxf(tri.v0[a], p1), p2);
-            c[a] = 0.5f * (b.lo[a] + b.hi[a]);
-        }
+        for (int a = 0; a < 3; ++a) c[a] = 0.5f * (b.lo[a] + b.hi[a]);
         tri.prim = p;
         tri.tri = local;
         tri.flat = t;
@@ -145,16 +132,6 @@ __device__ __forceinline__ uint32_t first_triangle(const int2 *node_children, co
     while (node >= n) node = uint32_t(node_children[node].x);
     return position[node];
 }
-__device__ __forceinline__ void set_child(BvhNode &node, int which, const Box6 &b, int32_t link) {
-    float *dst = which == 0 ? node.box0 : node.box1;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float pad = 1e-3f + 1e-5f * fmaxf(fabsf(b.lo[a]), fabsf(b.hi[a]));       // bvh_build.cpp:292-299
-        dst[2 * a] = b.lo[a] - pad;
-        dst[2 * a + 1] = b.hi[a] + pad;
-    }
-    (which == 0 ? node.child0 : node.child1) = link;
-}
 __global__ __launch_bounds__(256) void k0_emit_kernel(const int2 *__restrict__ node_children, const Box6 *__restrict__ node_box, const uint32_t *__restrict__ node_size,
                                                       const uint32_t *__restrict__ kept_rank, const uint32_t *__restrict__ position, uint32_t n, uint32_t total_nodes,
                                                       uint32_t leaf_tris, BvhNode *__restrict__ nodes) {
@@ -164,11 +141,14 @@ __global__ __launch_bounds__(256) void k0_emit_kernel(const int2 *__restrict__ n
     auto link_of = [&](uint32_t c) -> int32_t {
         const uint32_t size = node_size[c];
         if (size > leaf_tris) return int32_t(kept_rank[c - n]);
-        return ~int32_t((first_triangle(node_children, position, n, c) << 2) | (size - 1u));
+        return bvh_math::leaf_link(first_triangle(node_children, position, n, c), size);
     };
     BvhNode out{};
-    set_child(out, 0, node_box[uint32_t(ch.x)], link_of(uint32_t(ch.x)));
-    set_child(out, 1, node_box[uint32_t(ch.y)], link_of(uint32_t(ch.y)));
+    const Box6 b0 = node_box[uint32_t(ch.x)], b1 = node_box[uint32_t(ch.y)];
+    bvh_math::pad_slot(b0.lo, b0.hi, out.box0);
+    bvh_math::pad_slot(b1.lo, b1.hi, out.box1);
+    out.child0 = link_of(uint32_t(ch.x));
+    out.child1 = link_of(uint32_t(ch.y));
     nodes[kept_rank[node - n]] = out;
 }
 __global__ __launch_bounds__(256) void k0_kept_flags_kernel(const uint32_t *__restrict__ node_size, uint32_t n, uint32_t total_nodes, uint32_t leaf_tris, uint32_t *__restrict__ flags) {
@@ -176,84 +156,26 @@ __global__ __launch_bounds__(256) void k0_kept_flags_kernel(const uint32_t *__re
     if (n + k < total_nodes) flags[k] = node_size[n + k] > leaf_tris ? 1u : 0u;
 }
 
-// ---- 3. the derived node forms, with the host's formulas (bvh_build.cpp finalize_ch / finalize16) ----
+// ---- 3. the derived node forms (bvh_math::forms_of) and their self-checks (bvh_math::check_forms) ----
 // A partial refit runs the per-node kernels below on the nodes whose bit is set in `dirty` (one word per 32 nodes); nullptr = every node.
 __device__ __forceinline__ bool node_selected(const uint32_t *dirty, uint32_t k) { return !dirty || ((dirty[k >> 5] >> (k & 31u)) & 1u) != 0u; }
-__device__ __forceinline__ uint32_t upper16(float h) {
-    uint32_t bits = __float_as_uint(h);
-    if (h > 0.0f && (bits & 0xffffu)) bits += 0x10000u;
-    return bits >> 16;
-}
 __global__ __launch_bounds__(256) void k0_forms_kernel(const BvhNode *__restrict__ nodes, uint32_t count, float cx, float cy, float cz, BvhNodeCH *__restrict__ nodes_ch,
                                                        BvhNode48 *__restrict__ nodes48, BvhNode16 *__restrict__ nodes16, const uint32_t *__restrict__ dirty) {
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
     if (k >= count || !node_selected(dirty, k)) return;
     const BvhNode nd = nodes[k];
     const float centre[3] = { cx, cy, cz };
-    BvhNodeCH c{};
-    BvhNode16 h16{};
-    const float inf = __builtin_inff();
-#pragma unroll
-    for (int which = 0; which < 2; ++which) {
-        const float *box = which == 0 ? nd.box0 : nd.box1;
-        float *hdst = which == 0 ? c.h0 : c.h1;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float lo = box[2 * a], hi = box[2 * a + 1];
-            float cc = 0.0f, hh = -1.0f;
-            if (lo <= hi) {
-                cc = 0.5f * lo + 0.5f * hi;
-                hh = fmaxf(hi - cc, cc - lo);
-                hh += (fabsf(cc) + hh) * 2.4e-7f;
-                while (double(cc) - double(hh) > double(lo) || double(cc) + double(hh) < double(hi)) hh = nextafterf(hh, inf);
-            }
-            (a == 0 ? c.cx : a == 1 ? c.cy : c.cz)[which] = cc;
-            hdst[a] = hh;
-            // the 32-byte form (BvhNode16): centre relative to the scene centre and half extent as halves, no subnormals; centre + c +- h
-            // contains [lo, hi] in exact arithmetic with a few fp32 ulp to spare (the host's half_centre_extent; an overflow leaves inf,
-            // which the host sees in the downloaded nodes and then keeps the walkers on the 48-byte form)
-            uint16_t cb = 0, hb = 0xbc00;
-            if (lo <= hi) {
-                const double mid = 0.5 * double(lo) + 0.5 * double(hi) - double(centre[a]);
-                cb = __half_as_ushort(__float2half_rn(float(mid)));
-                if (((cb >> 10) & 31) == 0) cb = 0;
-                const double cv = double(centre[a]) + double(__half2float(__ushort_as_half(cb)));
-                double need = fmax(double(hi) - cv, cv - double(lo));
-                need += (fabs(double(centre[a])) + fabs(cv - double(centre[a])) + need) * 4.8e-7 + 1e-30;
-                float nf = float(need);
-                if (double(nf) < need) nf = nextafterf(nf, inf);
-                hb = __half_as_ushort(__float2half_ru(nf));
-                if (((hb >> 10) & 31) == 0) hb = 0x0400;
-            }
-            h16.c[2 * a + which] = cb;
-            h16.h[2 * a + which] = hb;
-        }
-    }
-    c.child0 = nd.child0; c.child1 = nd.child1;
-    h16.child0 = nd.child0 >= 0 ? nd.child0 * int32_t(sizeof(BvhNode16)) : nd.child0;
-    h16.child1 = nd.child1 >= 0 ? nd.child1 * int32_t(sizeof(BvhNode16)) : nd.child1;
+    BvhNodeCH c;
+    BvhNode48 n48;
+    BvhNode16 h16;
+    bvh_math::forms_of(nd, centre, c, n48, h16);
     nodes_ch[k] = c;
     nodes16[k] = h16;
-    BvhNode48 n48{};
-    n48.cx[0] = c.cx[0]; n48.cx[1] = c.cx[1]; n48.cy[0] = c.cy[0]; n48.cy[1] = c.cy[1]; n48.cz[0] = c.cz[0]; n48.cz[1] = c.cz[1];
-    n48.hp[0] = (upper16(c.h0[0]) << 16) | upper16(c.h0[1]);
-    n48.hp[1] = (upper16(c.h0[2]) << 16) | upper16(c.h1[0]);
-    n48.hp[2] = (upper16(c.h1[1]) << 16) | upper16(c.h1[2]);
-    n48.child0 = c.child0 >= 0 ? c.child0 * int32_t(sizeof(BvhNode48)) : c.child0;
-    n48.child1 = c.child1 >= 0 ? c.child1 * int32_t(sizeof(BvhNode48)) : c.child1;
     nodes48[k] = n48;
 }
 
-// The host's self-checks of the derived node forms (bvh_build.cpp check_node_forms + nodes16_in_range), on the device: every form must CONTAIN
-// the (lo, hi) boxes in exact arithmetic (doubles hold every value involved exactly).  out[0] boxes checked, out[1] centre / half-extent boxes
-// that do not contain theirs, out[2] 48-byte boxes that do not contain the centre / half-extent box (or links that differ), out[3] 32-byte
-// boxes that do not contain theirs (or links that differ), out[4] halves of the 32-byte form outside the range its walker reads (inf / NaN /
-// subnormal): the caller keeps out[3] only if out[4] == 0, like the host, which checks the 32-byte form only where it is in use.
-__device__ __forceinline__ double half_value_d(uint32_t h) {
-    const int e = int((h >> 10) & 31u), m = int(h & 1023u);
-    const double v = e == 0 ? ldexp(double(m), -24) : (e == 31 ? (m ? __builtin_nan("") : __builtin_inf()) : ldexp(double(1024 + m), e - 25));
-    return (h & 0x8000u) ? -v : v;
-}
+// The five counters of check_forms summed over the nodes; the caller keeps out[3] only if out[4] == 0 (the 32-byte form is checked only where
+// it is in use).
 __global__ __launch_bounds__(256) void k0_check_forms_kernel(const BvhNode *__restrict__ nodes, const BvhNodeCH *__restrict__ nodes_ch, const BvhNode48 *__restrict__ nodes48,
                                                              const BvhNode16 *__restrict__ nodes16, uint32_t count, float cx, float cy, float cz,
                                                              unsigned long long *__restrict__ out, const uint32_t *__restrict__ dirty, uint16_t *__restrict__ status) {
@@ -265,39 +187,8 @@ __global__ __launch_bounds__(256) void k0_check_forms_kernel(const BvhNode *__re
         const BvhNodeCH ch = nodes_ch[k];
         const BvhNode48 n48 = nodes48[k];
         const BvhNode16 n16 = nodes16[k];
-        const double centre[3] = { double(cx), double(cy), double(cz) };
-        auto upper = [](uint32_t w16) { return double(__uint_as_float(w16 << 16)); };
-        const double h48[6] = { upper(n48.hp[0] >> 16), upper(n48.hp[0] & 0xffffu), upper(n48.hp[1] >> 16), upper(n48.hp[1] & 0xffffu), upper(n48.hp[2] >> 16), upper(n48.hp[2] & 0xffffu) };
-        for (int i = 0; i < 6; ++i) {
-            const uint32_t ec = (n16.c[i] >> 10) & 31u, eh = (n16.h[i] >> 10) & 31u;
-            if (ec == 31u || (ec == 0u && n16.c[i] != 0) || eh == 31u || eh == 0u) ++bad[4];
-        }
-        for (int which = 0; which < 2; ++which) {
-            const float *box = which == 0 ? nd.box0 : nd.box1;
-            const float *hh = which == 0 ? ch.h0 : ch.h1;
-            ++bad[0];
-            for (int a = 0; a < 3; ++a) {
-                const double lo = box[2 * a], hi = box[2 * a + 1];
-                const double c = (a == 0 ? ch.cx : a == 1 ? ch.cy : ch.cz)[which], h = hh[a];
-                const double c48 = (a == 0 ? n48.cx : a == 1 ? n48.cy : n48.cz)[which], hw = h48[3 * which + a];
-                const uint32_t cb = n16.c[2 * a + which], hb = n16.h[2 * a + which];
-                const double c16 = centre[a] + half_value_d(cb), h16 = half_value_d(hb);
-                const bool normal16 = (cb == 0u || (((cb >> 10) & 31u) != 0u && ((cb >> 10) & 31u) != 31u)) && ((hb >> 10) & 31u) != 0u && ((hb >> 10) & 31u) != 31u;
-                if (!(lo <= hi)) {                           // an absent child: never entered in any form
-                    if (!(h < 0.0)) ++bad[1];
-                    if (!(hw < 0.0)) ++bad[2];
-                    if (!(h16 < 0.0)) ++bad[3];
-                    continue;
-                }
-                if (c - h > lo || c + h < hi) ++bad[1];
-                if (c48 != c || hw < h) ++bad[2];
-                if (!normal16 || !(c16 - h16 <= lo) || !(c16 + h16 >= hi)) ++bad[3];
-            }
-        }
-        auto as48 = [](int32_t link) { return link >= 0 ? link * int32_t(sizeof(BvhNode48)) : link; };
-        if (n48.child0 != as48(nd.child0) || n48.child1 != as48(nd.child1) || ch.child0 != nd.child0 || ch.child1 != nd.child1) ++bad[2];
-        auto as16 = [](int32_t link) { return link >= 0 ? link * int32_t(sizeof(BvhNode16)) : link; };
-        if (n16.child0 != as16(nd.child0) || n16.child1 != as16(nd.child1)) ++bad[3];
+        const float centre[3] = { cx, cy, cz };
+        bvh_math::check_forms(nd, ch, n48, n16, centre, bad);
         if (status) {                                    // (a dirty pass: the counters get new - old, the host adds that to its totals)
             if (dirty) old = status[k];
             status[k] = uint16_t(bad[1] | (bad[2] << 4) | (bad[3] << 8) | (bad[4] << 12));
@@ -314,15 +205,9 @@ __global__ __launch_bounds__(256) void k0_check_forms_kernel(const BvhNode *__re
 // bounds of all child boxes (the scene centre of the half-precision form): one reduction over the nodes
 __global__ __launch_bounds__(256) void k0_node_bounds_kernel(const BvhNode *__restrict__ nodes, uint32_t count, uint32_t *__restrict__ bounds) {
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
-    float mn[3] = { 3.0e38f, 3.0e38f, 3.0e38f }, mx[3] = { -3.0e38f, -3.0e38f, -3.0e38f };
-    if (k < count) {
-        const BvhNode nd = nodes[k];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            if (nd.box0[2 * a] <= nd.box0[2 * a + 1]) { mn[a] = fminf(mn[a], nd.box0[2 * a]); mx[a] = fmaxf(mx[a], nd.box0[2 * a + 1]); }
-            if (nd.box1[2 * a] <= nd.box1[2 * a + 1]) { mn[a] = fminf(mn[a], nd.box1[2 * a]); mx[a] = fmaxf(mx[a], nd.box1[2 * a + 1]); }
-        }
-    }
+    float mn[3], mx[3];
+    bvh_math::no_bounds(mn, mx);
+    if (k < count) bvh_math::bounds_of_node(nodes[k], mn, mx);
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         for (int off = 32; off > 0; off >>= 1) { mn[a] = fminf(mn[a], __shfl_xor(mn[a], off)); mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], off)); }
@@ -421,7 +306,7 @@ __global__ __launch_bounds__(256) void k0_sah_bin_kernel(const Box6 *__restrict_
         else if (v != 0u) atomic_max_checked(dst, v);
     }
 }
-// the sweep over one node's bins (bvh_build.cpp:136-171): best (axis, bin) by strict <, axes and bins in ascending order
+// the sweep over one node's bins (the host Builder's): best (axis, bin) by strict <, axes and bins in ascending order
 struct SahChoice { int axis, bin; uint32_t n_left; float lo[2][3], hi[2][3], clo[2][3], chi[2][3]; };
 __device__ __forceinline__ SahChoice sah_sweep(const uint32_t *bins, const float *node_clo, const float *node_chi) {
     SahChoice best;
@@ -853,29 +738,14 @@ __global__ __launch_bounds__(256) void k0_iota_kernel(uint32_t *__restrict__ ord
 // ---- refit (vhr_refit_geometry): the topology stays, the records and the boxes follow the vertices and the transforms ----
 struct RefitFrame { float r[9]; uint32_t on; };
 struct RefitCounters { unsigned long long non_finite, records_outside, children_outside, pad; };
-// the leaf pass: record k re-derived in its slot from (prim, tri) with k0_triangles_kernel's arithmetic; three 16-byte loads' worth of gather
-// per corner, three 16-byte stores
+// the leaf pass: record k re-derived in its slot from (prim, tri) with bvh_math::world_record; three 16-byte loads' worth of gather per corner,
+// three 16-byte stores
 // one record from its primitive's transform and its three vertices (absolute indices `vi`): the one place a refit of either kind derives a
 // record; returns the non-finite coordinates met
 __device__ __forceinline__ uint32_t refit_write_record(float4 *slot, const float4 &q2, const vhr_primitive &pr, const vhr_vertex *__restrict__ vertices, const uint32_t vi[3]) {
-    const float *m = pr.transform;
-    float w[3][3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float *v = vertices[vi[c]].pos;
-        w[c][0] = ((m[0] * v[0] + m[4] * v[1]) + m[8] * v[2]) + m[12];
-        w[c][1] = ((m[1] * v[0] + m[5] * v[1]) + m[9] * v[2]) + m[13];
-        w[c][2] = ((m[2] * v[0] + m[6] * v[1]) + m[10] * v[2]) + m[14];
-    }
-    float e1[3], e2[3];
-    uint32_t bad = 0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        e1[a] = w[1][a] - w[0][a];
-        e2[a] = w[2][a] - w[0][a];
-        bad += uint32_t(!isfinite(w[0][a])) + uint32_t(!isfinite(e1[a])) + uint32_t(!isfinite(e2[a]));
-    }
-    slot[0] = float4{ w[0][0], w[0][1], w[0][2], e1[0] };
+    float v0[3], e1[3], e2[3];
+    const uint32_t bad = bvh_math::world_record(pr.transform, vertices[vi[0]].pos, vertices[vi[1]].pos, vertices[vi[2]].pos, v0, e1, e2);
+    slot[0] = float4{ v0[0], v0[1], v0[2], e1[0] };
     slot[1] = float4{ e1[1], e1[2], e2[0], e2[1] };
     slot[2] = float4{ e2[2], q2.y, q2.z, q2.w };
     return bad;
@@ -946,43 +816,11 @@ __global__ __launch_bounds__(256) void k0_refit_mark_kernel(const vhr_vertex *__
         if (nodes) atomicAdd(&partial->dirty_nodes, (unsigned long long)nodes);
     }
 }
-// the unpadded box of a record in the tree's frame: k0_triangles_kernel's (world axes) or k0_frame_boxes_kernel's
-__device__ __forceinline__ Box6 refit_record_box(const BvhTri &t, const RefitFrame &f) {
-    Box6 b;
-    if (f.on) {
-        bvh_frame::box_in_frame(f.r, t, b.lo, b.hi);
-    } else {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float p1 = t.v0[a] + t.e1[a], p2 = t.v0[a] + t.e2[a];
-            b.lo[a] = fminf(fminf(t.v0[a], p1), p2);
-            b.hi[a] = fmaxf(fmaxf(t.v0[a], p1), p2);
-        }
-    }
-    return b;
-}
-__device__ __forceinline__ void refit_grow(Box6 &b, const Box6 &o) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { b.lo[a] = fminf(b.lo[a], o.lo[a]); b.hi[a] = fmaxf(b.hi[a], o.hi[a]); }
-}
-__device__ __forceinline__ Box6 refit_child_box(int32_t link, const BvhTri *tris, const Box6 *self_box, const RefitFrame &f) {
-    if (link >= 0) return self_box[link];
-    const uint32_t v = ~uint32_t(link), first = v >> 2, count = (v & 3u) + 1u;
-    Box6 b = refit_record_box(tris[first], f);
-    for (uint32_t i = 1; i < count; ++i) refit_grow(b, refit_record_box(tris[first + i], f));
-    return b;
-}
-// one node: its children's unpadded boxes (a leaf's from its records, an inner child's from the level below), padded into its two slots with
-// set_child; its own unpadded box for its parent.  Links are read, never written.
+// one node (bvh_math::refit_slots): its two slots from its children's unpadded boxes, its own unpadded box for its parent
 __device__ __forceinline__ void refit_node(uint32_t k, BvhNode *nodes, const BvhTri *tris, Box6 *self_box, const RefitFrame &f, bool single) {
     BvhNode nd = nodes[k];
-    Box6 mine = refit_child_box(nd.child0, tris, self_box, f);
-    set_child(nd, 0, mine, nd.child0);
-    if (!(single && nd.child1 == nd.child0)) {                     // (a one-leaf scene: child 1 is absent, its inverted box stays)
-        const Box6 other = refit_child_box(nd.child1, tris, self_box, f);
-        set_child(nd, 1, other, nd.child1);
-        refit_grow(mine, other);
-    }
+    Box6 mine;
+    bvh_math::refit_slots(nd, single, tris, reinterpret_cast<const float *>(self_box), f.r, f.on != 0u, mine.lo, mine.hi);
     nodes[k] = nd;
     self_box[k] = mine;
 }
@@ -1015,30 +853,7 @@ __global__ __launch_bounds__(256) void k0_refit_check_kernel(const BvhNode *__re
     int bad_records = 0, bad_children = 0;
     if (k < count && node_selected(dirty, k)) {
         const BvhNode nd = nodes[k];
-        auto inside = [](const float *lo, const float *hi, const float *slot) {
-            bool in = true;
-            for (int a = 0; a < 3; ++a) in = in && lo[a] >= slot[2 * a] && hi[a] <= slot[2 * a + 1];
-            return in;
-        };
-        for (int which = 0; which < 2; ++which) {
-            if (which == 1 && count == 1u && nd.child1 == nd.child0) continue;
-            const float *slot = which == 0 ? nd.box0 : nd.box1;
-            const int32_t link = which == 0 ? nd.child0 : nd.child1;
-            if (link >= 0) {
-                const BvhNode c = nodes[link];
-                for (int w = 0; w < 2; ++w) {
-                    const float *cb = w == 0 ? c.box0 : c.box1;
-                    const float lo[3] = { cb[0], cb[2], cb[4] }, hi[3] = { cb[1], cb[3], cb[5] };
-                    if (!inside(lo, hi, slot)) ++bad_children;
-                }
-            } else {
-                const uint32_t v = ~uint32_t(link), first = v >> 2, n = (v & 3u) + 1u;
-                for (uint32_t i = 0; i < n; ++i) {
-                    const Box6 b = refit_record_box(tris[first + i], f);
-                    if (!inside(b.lo, b.hi, slot)) ++bad_records;
-                }
-            }
-        }
+        bvh_math::refit_check(nd, count == 1u, nodes, tris, f.r, f.on != 0u, bad_records, bad_children);
         // what this node added to the two counters at its last check (records: at most 8, four bits; children: at most 4): a dirty pass
         // counts new - old, like k0_check_forms_kernel
         const uint32_t old = dirty ? status[k] : 0u;
@@ -1060,17 +875,20 @@ __global__ __launch_bounds__(256) void k0_sah_cost_kernel(const BvhNode *__restr
     double sum = 0.0;
     if (k < count) {
         const BvhNode nd = nodes[k];
-        auto term = [](const float *b, int32_t link) {
-            const double dx = double(b[1]) - double(b[0]), dy = double(b[3]) - double(b[2]), dz = double(b[5]) - double(b[4]);
-            return (dx * dy + dy * dz + dz * dx) * (link >= 0 ? 1.0 : double((~uint32_t(link) & 3u) + 1u));
-        };
-        sum = term(nd.box0, nd.child0);
-        if (!(count == 1u && nd.child1 == nd.child0)) sum += term(nd.box1, nd.child1);
+        sum = bvh_math::sah_term(nd.box0, nd.child0);
+        if (!bvh_math::absent_child1(nd, count == 1u)) sum += bvh_math::sah_term(nd.box1, nd.child1);
     }
     for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
     if ((threadIdx.x & 63u) == 0u) s_wave[threadIdx.x >> 6] = sum;
     __syncthreads();
     if (threadIdx.x == 0u) partial[blockIdx.x] = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
+}
+
+// the scene centre from what k0_node_bounds_kernel left (lo[3], hi[3] as ordered uints)
+void centre_from_bounds(const uint32_t bounds[6], float centre[3]) {
+    float lo[3], hi[3];
+    for (int a = 0; a < 3; ++a) { lo[a] = unordered(bounds[a]); hi[a] = unordered(bounds[3 + a]); }
+    bvh_math::centre_of(lo, hi, centre);
 }
 
 struct Scratch {            // device allocations of one build, freed together
@@ -1329,10 +1147,7 @@ int device_build_bvh(vhr_context *ctx, const std::vector<uint32_t> &tri_prefix, 
     K0_TRY(hipMemcpyAsync(h_bounds, d_bounds, sizeof(h_bounds), hipMemcpyDeviceToHost, s));
     K0_TRY(hipStreamSynchronize(s));
     K0_TRY(hipGetLastError());
-    for (int a = 0; a < 3; ++a) {
-        const float lo = unordered(h_bounds[6 + a]), hi = unordered(h_bounds[9 + a]);
-        ctx->bvh_centre[a] = lo <= hi ? 0.5f * (lo + hi) : 0.0f;
-    }
+    centre_from_bounds(h_bounds + 6, ctx->bvh_centre);
     hipLaunchKernelGGL(k0_forms_kernel, grid(n_inner), block, 0, s, ctx->d_nodes, n_inner, ctx->bvh_centre[0], ctx->bvh_centre[1], ctx->bvh_centre[2], ctx->d_nodes_ch,
                        ctx->d_nodes48, ctx->d_nodes16, static_cast<const uint32_t *>(nullptr));
     {   // the self-checks of the node forms, where the nodes are (the host builder's tree is checked on the host)
@@ -1415,7 +1230,7 @@ static int make_refit_plan(vhr_context *ctx) {
                 parent[uint32_t(link)] = k;
                 levels = std::max(levels, depth[k] + 2u);
             } else {
-                const uint32_t v = ~uint32_t(link), first = v >> 2, count = (v & 3u) + 1u;
+                const uint32_t first = bvh_math::leaf_first(link), count = bvh_math::leaf_count(link);
                 if (uint64_t(first) + count > ctx->tri_count) return ctx->fail(VHR_ERROR_GRAPH, "vhr_refit_geometry: a leaf lies outside the triangle records");
                 for (uint32_t i = 0; i < count; ++i) owner[first + i] = k;
             }
@@ -1465,13 +1280,7 @@ int device_bvh_sah_cost(vhr_context *ctx, double *cost) {
     REFIT_TRY(hipGetLastError());
     double sum = 0.0;
     for (double v : partial) sum += v;
-    float box[6];
-    for (int i = 0; i < 6; ++i) box[i] = root.box0[i];
-    if (!(n == 1u && root.child1 == root.child0))
-        for (int a = 0; a < 3; ++a) { box[2 * a] = std::min(box[2 * a], root.box1[2 * a]); box[2 * a + 1] = std::max(box[2 * a + 1], root.box1[2 * a + 1]); }
-    const double dx = double(box[1]) - double(box[0]), dy = double(box[3]) - double(box[2]), dz = double(box[5]) - double(box[4]);
-    const double area = dx * dy + dy * dz + dz * dx;
-    *cost = area > 0.0 ? sum / area : 0.0;
+    *cost = bvh_math::sah_cost(sum, root, n == 1u);
     return VHR_OK;
 }
 
@@ -1584,10 +1393,7 @@ int device_refit_bvh(vhr_context *ctx) {
     REFIT_TRY(hipMemcpyAsync(h_bounds, d->bounds, sizeof(h_bounds), hipMemcpyDeviceToHost, s));
     REFIT_TRY(hipStreamSynchronize(s));
     REFIT_TRY(hipGetLastError());
-    for (int a = 0; a < 3; ++a) {
-        const float lo = unordered(h_bounds[6 + a]), hi = unordered(h_bounds[9 + a]);
-        ctx->bvh_centre[a] = lo <= hi ? 0.5f * (lo + hi) : 0.0f;
-    }
+    centre_from_bounds(h_bounds + 6, ctx->bvh_centre);
     if (timed) REFIT_TRY(hipEventRecord(p->ev[3], s));
     refit_forms_and_checks(ctx, p, f, nullptr);
     if (timed) REFIT_TRY(hipEventRecord(p->ev[4], s));
@@ -1637,12 +1443,7 @@ int device_refit_bvh_partial(vhr_context *ctx, bool *ran_whole) {
     REFIT_TRY(hipStreamSynchronize(s));
     REFIT_TRY(hipGetLastError());
     float centre[3];
-    for (int a = 0; a < 3; ++a) {
-        float lo = 3.0e38f, hi = -3.0e38f;                           // k0_node_bounds_kernel's identities and its tests
-        if (root.box0[2 * a] <= root.box0[2 * a + 1]) { lo = fminf(lo, root.box0[2 * a]); hi = fmaxf(hi, root.box0[2 * a + 1]); }
-        if (root.box1[2 * a] <= root.box1[2 * a + 1]) { lo = fminf(lo, root.box1[2 * a]); hi = fmaxf(hi, root.box1[2 * a + 1]); }
-        centre[a] = lo <= hi ? 0.5f * (lo + hi) : 0.0f;
-    }
+    bvh_math::centre_of_root(root, centre);
     const bool centre_moved = std::memcmp(centre, ctx->bvh_centre, sizeof(centre)) != 0;
     for (int a = 0; a < 3; ++a) ctx->bvh_centre[a] = centre[a];
     if (timed) REFIT_TRY(hipEventRecord(p->ev[3], s));

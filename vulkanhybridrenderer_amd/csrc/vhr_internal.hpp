@@ -214,6 +214,9 @@ struct RefitDirty { DirtyRanges vertices, primitives; };
 void check_node_forms(const HostBvh &bvh, uint64_t out[4], int threads = 0);
 bool nodes16_in_range(const HostBvh &bvh);      // no inf / NaN / subnormal half in the 32-byte form (a device-built tree: the host decides)
 uint64_t bvh_fingerprint(const HostBvh &bvh);
+uint64_t bvh_forms_fingerprint(const HostBvh &bvh);     // of the scene centre and the derived forms (vhr_get_bvh_forms_fingerprint)
+// the scene centre and nodes_ch / nodes48 / nodes16 from `nodes` (the last stage of a build and of a refit); `only`: the flagged nodes, with the centre as it stands
+void derive_node_forms(HostBvh &bvh, int threads = 0, const std::vector<uint8_t> *only = nullptr);
 uint64_t bvh_tree_fingerprint(const HostBvh &bvh);      // of the tree, not of its arrays: equal for the host's and the device's build of a scene
 void build_bvh(const vhr_vertex *vertices, const uint32_t *indices, const vhr_primitive *primitives,
                uint32_t primitive_count, HostBvh &out, int leaf_tris = kMaxLeafTris, int threads = 0, int presplit_percent = 0, int frame_mode = 0);

@@ -35,7 +35,7 @@ EXPORTS = [
     "vhr_raytraced_last_error", "vhr_standin_rayquery_forward", "vhr_rayquery_create", "vhr_rayquery_destroy", "vhr_rayquery_build",
     "vhr_rayquery_rebuild", "vhr_rayquery_last_error", "vhr_standin_forward_raster", "vhr_forward_raster_create", "vhr_forward_raster_destroy",
     "vhr_forward_raster_build", "vhr_forward_raster_rebuild", "vhr_forward_raster_last_error", "vhr_get_transient_image_samples",
-    "vhr_set_ray_statistics", "vhr_get_ray_statistics", "vhr_get_bvh_statistics", "vhr_get_current_stream", "vhr_get_bvh_builder", "vhr_get_bvh_presplit_level", "vhr_get_bvh_frame", "vhr_get_bvh_form_checks", "vhr_get_bvh_fingerprint", "vhr_get_bvh_tree_fingerprint", "vhr_set_kernel_timing",
+    "vhr_set_ray_statistics", "vhr_get_ray_statistics", "vhr_get_bvh_statistics", "vhr_get_current_stream", "vhr_get_bvh_builder", "vhr_get_bvh_presplit_level", "vhr_get_bvh_frame", "vhr_get_bvh_form_checks", "vhr_get_bvh_fingerprint", "vhr_get_bvh_tree_fingerprint", "vhr_get_bvh_forms_fingerprint", "vhr_set_kernel_timing",
     "vhr_get_kernel_time", "vhr_set_option", "vhr_get_option", "vhr_option_count", "vhr_option_info", "vhr_get_traversal_statistics", "vhr_source_fingerprint", "vhr_debug_wave_lifetimes", "vhr_get_reflection_statistics", "vhr_get_binary64_statistics", "vhr_debug_ray_triangle", "vhr_get_traversal_cycles", "vhr_get_drain_statistics", "vhr_get_build_times", "vhr_atrous_overlap", "vhr_atrous_output_extent", "vhr_strip_plan_make",
     "vhr_strip_plan_exchanges", "vhr_tile_grid_choose", "vhr_tile_plan_make", "vhr_tile_plan_make_weighted", "vhr_get_tile_cost_map", "vhr_tile_plan_exchanges", "vhr_tile_plan_replan", "vhr_comm_replan", "vhr_comm_get_unique_id", "vhr_comm_use_library", "vhr_comm_library", "vhr_comm_create", "vhr_comm_create_tiled", "vhr_comm_destroy", "vhr_comm_last_error", "vhr_comm_exchange_raytraced",
     "vhr_comm_start_frame_exchanges", "vhr_comm_finish_frame_exchanges",
@@ -261,6 +261,7 @@ def load():
     L.vhr_get_bvh_frame.argtypes = [vp, C.POINTER(C.c_float)]
     L.vhr_get_bvh_fingerprint.argtypes = [vp, C.POINTER(u64)]
     L.vhr_get_bvh_tree_fingerprint.argtypes = [vp, C.POINTER(u64)]
+    L.vhr_get_bvh_forms_fingerprint.argtypes = [vp, C.POINTER(u64)]
     L.vhr_set_option.argtypes = [vp, C.c_char_p, i32]
     L.vhr_get_traversal_statistics.argtypes = [vp, C.POINTER(u64)]
     L.vhr_get_traversal_cycles.argtypes = [vp, C.POINTER(u64)]
@@ -771,6 +772,13 @@ class Context:
         out = C.c_uint64()
         self.check(self.L.vhr_get_bvh_tree_fingerprint(self.handle, C.byref(out)), "bvh_tree_fingerprint")
         return int(out.value)
+
+    def bvh_forms_fingerprint(self):
+        """(hash of the scene centre and the derived node forms as they stand, the same after the host derives them again from the
+        (lo, hi) nodes): equal for any tree, whichever builder made or refitted it."""
+        out = (C.c_uint64 * 2)()
+        self.check(self.L.vhr_get_bvh_forms_fingerprint(self.handle, out), "bvh_forms_fingerprint")
+        return int(out[0]), int(out[1])
 
     def build_times_ms(self):
         """K0: (host BVH build, upload of scene + tree) of the last upload_scene, milliseconds."""
