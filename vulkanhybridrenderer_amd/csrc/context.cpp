@@ -11,7 +11,16 @@
 #include "fingerprint.h"      // build/fingerprint.h, written by the Makefile
 
 namespace vhr {
-int upload_srgb_lut(const float *lut);
+// Every ray-tracing unit's copy of the sRGB decode table (SrgbLutCopy, vhr_internal.hpp).  The head is constant-initialised, so it is there before
+// the first unit's constructor runs, in whatever order the units are initialised.
+static SrgbLutCopy *g_srgb_lut_copies = nullptr;
+SrgbLutCopy::SrgbLutCopy(int (*copy_fn)(const float *)) : copy(copy_fn), next(g_srgb_lut_copies) { g_srgb_lut_copies = this; }
+int upload_srgb_lut(const float *lut) {
+    if (!g_srgb_lut_copies) return -1;
+    for (const SrgbLutCopy *c = g_srgb_lut_copies; c; c = c->next)
+        if (c->copy(lut) != 0) return -1;
+    return 0;
+}
 
 uint32_t format_stride(int32_t format) {      // VkUtils::FormatStride, vulkan_utils.h:128-148
     switch (format) {

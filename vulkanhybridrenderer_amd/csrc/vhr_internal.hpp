@@ -341,7 +341,7 @@ struct SvgfCmd {
     const void *src_base; void *dst_base;                          // Copy: the images' base pointers (hazard checks)
 };
 
-// vhr_ray_query's counters (csrc/kernels_trace.hip): rays the binary64 launch walked again (= entries of the redo list), waves whose stack
+// vhr_ray_query's counters (csrc/kernels_ray_query.hip): rays the binary64 launch walked again (= entries of the redo list), waves whose stack
 // overflowed, rays with a hit.  A buffer of the query's own: no frame reads or writes it.
 struct RayQueryCounters { uint32_t redo_count, overflows; unsigned long long hits; };
 // ... and the list of rays decision (vi) hands to the binary64 launch; one set per stream queries were enqueued on, so that queries in flight
@@ -572,7 +572,7 @@ struct vhr_context {
     vhr_context() { for (int i = 0; i < vhr::kOptCount; ++i) options[i] = vhr::kOptionInfo[i].def; }
     int cu_count = 256;
     uint32_t *d_tile_counter = nullptr;
-    // "raygen_cost_order" (csrc/kernels_trace.hip): ray-tracing launch f leaves its waves' lifetimes in cost[f & 1], and its FIRST block, before it
+    // "raygen_cost_order" (csrc/trace_queue.hpp): ray-tracing launch f leaves its waves' lifetimes in cost[f & 1], and its FIRST block, before it
     // turns to its own tile, sorts the blocks of launch f - 1 by the lifetimes in cost[(f - 1) & 1] into order[(f + 1) & 1] -- the order launch
     // f + 1 starts its blocks in.  Everything happens inside the launches the frame has anyway: no kernel, stream or event of its own.  One set for
     // the shadow / AO queue kernel, one for the mirror-ray queue kernel, one for the raytraced path's (launches of different shapes).
@@ -639,7 +639,17 @@ inline void launch(vhr_context *ctx, K kernel, dim3 grid, dim3 block, size_t lds
 
 uint32_t format_stride(int32_t format);   // VkUtils::FormatStride (vulkan_utils.h:128-148)
 
-// kernel launchers (csrc/kernels_trace.hip, csrc/kernels_svgf.hip).  All enqueue on ctx->stream.
+// The sRGB decode table of the texture fetch (csrc/trace_device.hpp) exists once per ray-tracing unit: a unit that includes that header owns a
+// SrgbLutCopy, whose constructor links it into the list upload_srgb_lut() walks -- every unit's table is filled, or the call fails (csrc/context.cpp).
+struct SrgbLutCopy {
+    int (*copy)(const float *lut);       // 256 floats to this unit's table; 0 = done
+    SrgbLutCopy *next;
+    explicit SrgbLutCopy(int (*copy_fn)(const float *));
+};
+int upload_srgb_lut(const float *lut);
+
+// kernel launchers (csrc/kernels_trace.hip and the units split from it -- kernels_raytraced.hip, kernels_forward.hip, kernels_standin.hip,
+// kernels_ray_query.hip -- and csrc/kernels_svgf.hip).  All enqueue on ctx->stream.
 struct ImageView { void *ptr; uint32_t width, height; };
 int launch_raygen(vhr_context *ctx, const vhr_per_frame_data &pfd, uint32_t width, uint32_t height,
                   const Image &normals, const Image &depth, Image &shadow_ao, Image *reflections);
