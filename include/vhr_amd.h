@@ -250,7 +250,8 @@ const char *vhr_hybrid_last_error(vhr_hybrid_render_path *path);
  * what Renderer::Render's function-static carries --, then the images in the order integrated[0], integrated[1], previous normals, history,
  * moments history, each as the path's NEXT frame will see it (the moments double buffer's current side; the ping-pong pair in its
  * frame-start order), so a blob loads into any path of the same extent whatever pool indices that path was given.  A context restored
- * from a blob continues bit-identically (tests/test_gpu_svgf.py).  `last_frame` may be NULL. */
+ * from a blob continues bit-identically (tests/test_gpu_svgf.py).  `last_frame` may be NULL.  Options are no part of the blob -- "alpha_test_rays"
+ * included: a restored renderer sets it again if it had it on. */
 int  vhr_hybrid_state_size(vhr_hybrid_render_path *path, uint64_t *bytes);
 int  vhr_hybrid_save_state(vhr_hybrid_render_path *path, void *blob, uint64_t bytes);
 int  vhr_hybrid_load_state(vhr_hybrid_render_path *path, const void *blob, uint64_t bytes, vhr_per_frame_data *last_frame);
@@ -641,7 +642,20 @@ int vhr_get_ray_statistics(vhr_context *ctx, uint64_t out[4]);
  *  of the triangles' boxes, if that beats the world axes by 5 % -- a scene whose dominant orientation is not the world's walks up to twice as
  *  fast for it, a scene along the world axes keeps them and its tree, bit for bit (the search costs such a scene ~1.5 ms of K0) --, 0 = the world
  *  axes whatever the scene; the walkers rotate a ray once for the box tests and intersect triangles in world space as ever: images
- *  bit-identical, both builders, the same tree (vhr_get_bvh_frame tells which frame the current tree uses; "bvh_presplit" is not combined with a rotated frame). */
+ *  bit-identical, both builders, the same tree (vhr_get_bvh_frame tells which frame the current tree uses; "bvh_presplit" is not combined with a rotated frame).
+ *  Not in the table either, because it CHANGES IMAGES (the table's entries are result-neutral), and read at every launch: "alpha_test_rays"
+ *  0 (default) = every triangle is opaque to the hybrid path's shadow, AO and mirror rays, as in the reference's hybrid path
+ *  (raygen.rgen:32-65); 1 = a candidate hit that gbuf.frag:20-32, evaluated at the hit, would discard does not exist for those rays, both
+ *  bounces of the two-bounce extension included -- uv0 interpolated at the hit, albedo = base_color without a base-colour texture, else the
+ *  texture through its own sampler at LOD 0; discarded iff (alpha_mask == 1 && albedo.a < alpha_cutoff) || albedo.a == 0 -- so that a ray
+ *  sees what the raster pass drew: a fence's shadow, occlusion and mirror image have the fence's holes.  An ignored candidate is skipped
+ *  before anything else sees it: it ends no any-hit ray, shrinks no closest t and takes no part in the (t, flat index) tie-break; decision
+ *  (vi) comes first, the binary64 re-decision or its deferral included.  This is the G-buffer's rule, not shadow_anyhit.rahit's, which the
+ *  raytraced render path keeps.  vhr_update_geometry looks once whether any primitive CAN discard (alpha_mask == 1, a base-colour texture,
+ *  or untextured with base_color[3] == 0; a texture's alpha bytes are not scanned): where none can, 1 launches exactly the kernels 0
+ *  launches.  Where one can, "fuse_temporal" does not fuse (the epilogue has no alpha form: the SVGF pass runs its own dispatch) and the
+ *  launches cost what profiles/alpha_rays_rate.jsonl reports.  vhr_get_option returns this key (not the bvh_* keys); a host-only context
+ *  accepts it; it is no part of vhr_hybrid_save_state's blob, of vhr_hybrid_settings or of vhr_trace_params. */
 int vhr_set_option(vhr_context *ctx, const char *key, int32_t value);
 int vhr_get_option(vhr_context *ctx, const char *key, int32_t *value);
 int32_t vhr_option_count(void);
@@ -688,7 +702,8 @@ int vhr_get_traversal_statistics(vhr_context *ctx, uint64_t out[4]);
 int vhr_get_reflection_statistics(vhr_context *ctx, uint64_t out[10]);
 /* Decision (vi)'s binary64 half in the work-queue kernels of the last vhr_trace_rays (statistics enabled).  A candidate whose fp32 solution contradicts
  * itself is decided again in binary64 -- in the per-pixel kernels in place, in the queue kernels outside their loops: the pixel is marked and computed
- * again by the per-pixel code when its tile is done.  out[0] = such pixels of the shadow / AO launch, out[1] = of the mirror ray's launch, out[2..3] = 0. */
+ * again by the per-pixel code when its tile is done.  out[0] = such pixels of the shadow / AO launch, out[1] = of the mirror ray's launch, out[2] =
+ * the launches of the last vhr_trace_rays that ran an "alpha_test_rays" instantiation (0, 1 or 2; counted with or without statistics), out[3] = 0. */
 int vhr_get_binary64_statistics(vhr_context *ctx, uint64_t out[4]);
 
 /* Where the waves of the last work-queue raygen launch spent their time (statistics enabled; s_memtime ticks summed
@@ -746,7 +761,8 @@ int vhr_get_bvh_forms_fingerprint(vhr_context *ctx, uint64_t out[2]);
  * The tree of the last vhr_update_geometry keeps its topology; its triangle records and boxes are recomputed from the current vertices and
  * primitive transforms.  Per frame: vhr_update_vertices / vhr_update_primitive_transforms (any number), vhr_refit_geometry,
  * vhr_update_per_frame_ubo, vhr_graph_execute.  Results do not depend on the tree, so a refitted tree publishes exactly the images and ray
- * query answers a rebuild from the same arrays publishes; what degrades is speed (watch vhr_get_bvh_sah_cost and rebuild when it has grown).
+ * query answers a rebuild from the same arrays publishes ("alpha_test_rays" and VHR_RAY_QUERY_ALPHA_TEST included: what a ray sees is decided
+ * per candidate from the primitive's material and the current vertices' uv0, never from the tree); what degrades is speed (watch vhr_get_bvh_sah_cost and rebuild when it has grown).
  *   - While updates are pending (an update call without a vhr_refit_geometry after it) vhr_graph_execute, vhr_ray_query and the vhr_standin_*
  *     calls fail with VHR_ERROR_GRAPH and a message that names vhr_refit_geometry: a stale tree is never traced silently.
  *   - Refused, with a message in vhr_last_error: no geometry yet (VHR_ERROR_GRAPH); a tree built with "bvh_presplit" whose references were
@@ -811,7 +827,7 @@ int vhr_get_partial_refit_statistics(vhr_context *ctx, uint64_t out[8]);
  * deciding to rebuild.  One reduction, computed when asked (waits for the context's streams). */
 int vhr_get_bvh_sah_cost(vhr_context *ctx, double out[2]);
 
-/* ---- Batched ray queries on the scene's BVH (rayQueryEXT with an opaque TLAS, cull mask 0xFF) ----
+/* ---- Batched ray queries on the scene's BVH (rayQueryEXT with an opaque TLAS, cull mask 0xFF; VHR_RAY_QUERY_ALPHA_TEST: a non-opaque one) ----
  * Traces `count` caller-made rays against the geometry of the last vhr_update_geometry.  The flags of rayQueryInitializeEXT this
  * stands for are gl_RayFlagsTerminateOnFirstHitEXT (VHR_RAY_QUERY_TERMINATE_ON_FIRST_HIT) or none; the mask is 0xFF.
  *   - All geometry is opaque and two-sided; a triangle is hit iff tmin < t < tmax (decision (vi): fp32 Moeller-Trumbore, a candidate whose
@@ -819,6 +835,11 @@ int vhr_get_bvh_sah_cost(vhr_context *ctx, double out[2]);
  *   - Without the flag: results = vhr_ray_hit[count], the hit of smallest t, ties broken by the smaller flat triangle index (primitive-major
  *     order of vhr_update_geometry); a miss is geometry_index = primitive_index = 0xFFFFFFFF, t = u = v = 0.  With it: results =
  *     uint8_t[count], 1 = some triangle is hit (which one ends the walk depends on the tree; the boolean does not).
+ *   - VHR_RAY_QUERY_ALPHA_TEST (16; combines with both other flags; 4 and 8 are no flags): geometry the G-buffer pass cuts holes into is no longer
+ *     opaque -- a candidate hit that gbuf.frag:20-32 would discard at the hit (the rule spelled out at "alpha_test_rays" above) does not
+ *     exist for the ray, as if a rayQueryEXT loop had not confirmed it: it ends no any-hit ray and is no closest hit.  Otherwise the
+ *     contract is unchanged: closest = min t, then the smaller flat index, among the candidates that exist.  Independent of
+ *     "alpha_test_rays"; on a scene none of whose primitives can discard the flag launches the plain kernels.
  *   - Degenerate rays are not rejected: a zero or NaN direction or tmin >= tmax misses, an infinite tmax is an unbounded ray.
  *   - Device path (no VHR_RAY_QUERY_HOST_MEMORY): `rays` and `results` are device pointers.  The work is enqueued on the stream
  *     vhr_get_current_stream reports at the time of the call (after a vhr_update_geometry made earlier on it) and the call returns

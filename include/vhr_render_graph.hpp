@@ -155,7 +155,8 @@ public:
         check(context.handle, vhr_update_per_frame_ubo(context.handle, resource_idx, &per_frame_data), "UpdatePerFrameUBO");
     }
     // Extension: rayQueryEXT against the TLAS this manager owns (vhr_ray_query).  `flags` = VHR_RAY_QUERY_TERMINATE_ON_FIRST_HIT and / or
-    // VHR_RAY_QUERY_HOST_MEMORY; results = vhr_ray_hit[count], or uint8_t[count] with the first.  Device pointers: enqueued on the context's
+    // VHR_RAY_QUERY_HOST_MEMORY and / or VHR_RAY_QUERY_ALPHA_TEST (a hit the G-buffer pass would discard -- alpha mask, alpha 0 -- does not
+    // exist for the ray); results = vhr_ray_hit[count], or uint8_t[count] with the first.  Device pointers: enqueued on the context's
     // current stream, no synchronisation.
     void QueryRays(const vhr_ray *rays, uint32_t count, uint32_t flags, void *results) {
         check(context.handle, vhr_ray_query(context.handle, rays, count, flags, results), "QueryRays");

@@ -123,7 +123,8 @@ typedef struct vhr_ray_hit {
 
 enum {
     VHR_RAY_QUERY_TERMINATE_ON_FIRST_HIT = 1,   /* gl_RayFlagsTerminateOnFirstHitEXT: results = uint8_t[count], 1 = occluded, 0 = not */
-    VHR_RAY_QUERY_HOST_MEMORY = 2               /* rays and results are host memory: staged, and the call returns with the results in place */
+    VHR_RAY_QUERY_HOST_MEMORY = 2,              /* rays and results are host memory: staged, and the call returns with the results in place */
+    VHR_RAY_QUERY_ALPHA_TEST = 16               /* a candidate hit gbuf.frag:20-32 would discard does not exist for the ray (4 and 8 stay unknown flags) */
 };
 
 /* VkFormat values (passed through unchanged from reference-side code) */

@@ -56,6 +56,7 @@ ray_dtype = np.dtype([("origin", "<f4", 3), ("tmin", "<f4"), ("direction", "<f4"
 ray_hit_dtype = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("geometry_index", "<u4"), ("primitive_index", "<u4"),
                           ("reserved", "<u4")])
 RAY_QUERY_TERMINATE_ON_FIRST_HIT, RAY_QUERY_HOST_MEMORY = 1, 2
+RAY_QUERY_ALPHA_TEST = 16         # a candidate hit the G-buffer pass would discard does not exist for the ray (4 and 8 are no flags)
 RAY_MISS = 0xFFFFFFFF              # vhr_ray_hit.geometry_index / primitive_index of a miss
 
 assert vertex_dtype.itemsize == 56

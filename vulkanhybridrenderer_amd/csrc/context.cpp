@@ -380,6 +380,13 @@ int vhr_update_geometry(vhr_context *ctx, const vhr_vertex *vertices, uint32_t v
             return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "UpdateGeometry: vertex " + std::to_string(v) + " has a non-finite position");
     if (total_triangles >= (1ull << 29))            // a leaf link packs (first triangle << 2 | count - 1) into 31 bits
         return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "UpdateGeometry: 2^29 triangles or more");
+    // "alpha_test_rays" / VHR_RAY_QUERY_ALPHA_TEST: can gbuf.frag:20-32 discard a fragment of any primitive?  (A texture's alpha bytes are not
+    // scanned: a base-colour texture counts as able to.)
+    ctx->scene_can_discard = false;
+    for (uint32_t p = 0; p < primitive_count; ++p) {
+        const vhr_material &m = primitives[p].material;
+        if (m.alpha_mask == 1 || m.base_color_texture != -1 || m.base_color[3] == 0.0f) ctx->scene_can_discard = true;
+    }
     // a build replaces whatever updates were pending and everything a refit had prepared
     ctx->refit_pending = ctx->sah_cost_built_valid = false;
     for (uint64_t &w : ctx->refit_stats) w = 0;
@@ -870,6 +877,11 @@ int vhr_set_option(vhr_context *ctx, const char *key, int32_t value) {
         ctx->bvh_build_threads = value;
         return VHR_OK;
     }
+    if (!std::strcmp(key, "alpha_test_rays")) {              // read at every launch of the hybrid path's rays
+        if (value < 0 || value > 1) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "alpha_test_rays must be 0 (every triangle is opaque to the hybrid path's rays) or 1 (they skip what the G-buffer pass discards)");
+        ctx->alpha_test_rays = value;
+        return VHR_OK;
+    }
     for (int i = 0; i < vhr::kOptCount; ++i) {
         const vhr::OptionInfo &o = vhr::kOptionInfo[i];
         if (std::strcmp(key, o.name)) continue;
@@ -895,6 +907,7 @@ int vhr_option_info(int32_t index, const char **name, int32_t *default_value, in
 
 int vhr_get_option(vhr_context *ctx, const char *key, int32_t *value) {
     if (!ctx || !key || !value) return VHR_ERROR_INVALID_ARGUMENT;
+    if (!std::strcmp(key, "alpha_test_rays")) { *value = ctx->alpha_test_rays; return VHR_OK; }
     for (int i = 0; i < vhr::kOptCount; ++i)
         if (!std::strcmp(key, vhr::kOptionInfo[i].name)) { *value = ctx->options[i]; return VHR_OK; }
     return ctx->fail(VHR_ERROR_NOT_FOUND, std::string("unknown option '") + key + "'");
@@ -945,7 +958,7 @@ int vhr_get_reflection_statistics(vhr_context *ctx, uint64_t out[10]) {
 int vhr_get_binary64_statistics(vhr_context *ctx, uint64_t out[4]) {
     if (!ctx || !out) return VHR_ERROR_INVALID_ARGUMENT;
     if (!ctx->host_only) { const int src_ = ctx->sync_streams(); if (src_ != VHR_OK) return src_; }
-    out[0] = ctx->h_ray_stats.pending_rays; out[1] = ctx->h_refl_stats.pending_rays; out[2] = 0; out[3] = 0;
+    out[0] = ctx->h_ray_stats.pending_rays; out[1] = ctx->h_refl_stats.pending_rays; out[2] = ctx->alpha_launches; out[3] = 0;
     return VHR_OK;
 }
 
@@ -969,7 +982,7 @@ int vhr_get_drain_statistics(vhr_context *ctx, uint64_t out[4]) {
 int vhr_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, uint32_t flags, void *results) {
     if (!ctx) return VHR_ERROR_INVALID_ARGUMENT;
     // the arguments first (the same answer on every context), then the device
-    if (flags & ~uint32_t(VHR_RAY_QUERY_TERMINATE_ON_FIRST_HIT | VHR_RAY_QUERY_HOST_MEMORY))
+    if (flags & ~uint32_t(VHR_RAY_QUERY_TERMINATE_ON_FIRST_HIT | VHR_RAY_QUERY_HOST_MEMORY | VHR_RAY_QUERY_ALPHA_TEST))
         return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_ray_query: unknown flag bits " + std::to_string(flags));
     if (count > 0 && (!rays || !results)) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_ray_query: rays and results must not be NULL when count > 0");
     if (count > 0 && reinterpret_cast<uintptr_t>(rays) % 16u) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_ray_query: rays must be 16-byte aligned");
@@ -978,10 +991,10 @@ int vhr_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, uint32_
     { const int stale = ctx->refuse_if_stale("vhr_ray_query"); if (stale != VHR_OK) return stale; }
     if (count == 0) return VHR_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const bool any_hit = (flags & VHR_RAY_QUERY_TERMINATE_ON_FIRST_HIT) != 0;
+    const bool any_hit = (flags & VHR_RAY_QUERY_TERMINATE_ON_FIRST_HIT) != 0, alpha_test = (flags & VHR_RAY_QUERY_ALPHA_TEST) != 0;
     const uint64_t ray_bytes = uint64_t(count) * sizeof(vhr_ray), result_bytes = uint64_t(count) * (any_hit ? 1u : sizeof(vhr_ray_hit));
     ctx->rq_rays = count;
-    if (!(flags & VHR_RAY_QUERY_HOST_MEMORY)) return vhr::launch_ray_query(ctx, rays, count, any_hit, results);
+    if (!(flags & VHR_RAY_QUERY_HOST_MEMORY)) return vhr::launch_ray_query(ctx, rays, count, any_hit, alpha_test, results);
     // host memory: staged through the context's own buffer (rays, then the results at the next 256-byte boundary)
     const uint64_t result_offset = (ray_bytes + 255u) & ~uint64_t(255u), staging = result_offset + result_bytes;
     if (ctx->rq_staging_bytes < staging) {
@@ -993,7 +1006,7 @@ int vhr_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, uint32_
     }
     char *const d = static_cast<char *>(ctx->d_rq_staging);
     HIP_TRY(ctx, hipMemcpyAsync(d, rays, ray_bytes, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = vhr::launch_ray_query(ctx, reinterpret_cast<const vhr_ray *>(d), count, any_hit, d + result_offset);
+    const int rc = vhr::launch_ray_query(ctx, reinterpret_cast<const vhr_ray *>(d), count, any_hit, alpha_test, d + result_offset);
     if (rc != VHR_OK) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(results, d + result_offset, result_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

@@ -1,7 +1,7 @@
 // The batched ray query (vhr_ray_query) and the debug kernel that runs the walkers' triangle test on explicit pairs
 // (vhr_debug_ray_triangle).  (Split from the end of kernels_trace.hip; built with the same flags.)
 #define VHR_TRACE_UNIT unit_ray_query      // names this unit's copy of the sRGB decode table (trace_device.hpp), which comes with the header:
-                                           // nothing here samples a texture, the copy is filled and never read
+                                           // gbuf_discarded (VHR_RAY_QUERY_ALPHA_TEST) samples base-colour textures here
 #include "trace_queue.hpp"
 
 namespace vhr {
@@ -73,7 +73,8 @@ __device__ __forceinline__ void ray_query_store(const RayQueryArgs &a, const uin
     r[3] = hit ? prim : kNoHit; r[4] = hit ? tri : kNoHit; r[5] = 0u;
 }
 
-template <bool SPILL>
+// ALPHA (VHR_RAY_QUERY_ALPHA_TEST): a candidate gbuf_discarded names does not exist -- the walk's Reject, behind decision (vi) as ever.
+template <bool SPILL, bool ALPHA = false>
 __global__ __launch_bounds__(kQueueBlock * 2) void ray_query_kernel(const RayQueryArgs a, const uint32_t stack_levels, const uint32_t refill_threshold,
                                                                     const uint32_t early_exit, const Stamps st) {
     vhr_stamp(st);
@@ -108,7 +109,7 @@ __global__ __launch_bounds__(kQueueBlock * 2) void ray_query_kernel(const RayQue
                 flagged = false;
             }
         }, nullptr,
-        [&](uint32_t) { flagged = true; });
+        [&](uint32_t) { flagged = true; }, alpha_reject<ALPHA>(a.scene));
     for (int off = 32; off > 0; off >>= 1) hits += uint32_t(__shfl_xor(int(hits), off));
     const bool wave_overflow = __any(overflow != 0u);
     if (lane == 0) {
@@ -118,6 +119,7 @@ __global__ __launch_bounds__(kQueueBlock * 2) void ray_query_kernel(const RayQue
 }
 
 // Decision (vi), second half, for the rays launch 1 listed: the per-pixel walker with the binary64 redo inside its leaf test.
+template <bool ALPHA = false>
 __global__ __launch_bounds__(kTraceBlock) void ray_query_redo_kernel(const RayQueryArgs a, const Stamps st) {
     vhr_stamp(st);
     __shared__ int s_stack[kTraceStack * kTraceBlock];
@@ -134,10 +136,10 @@ __global__ __launch_bounds__(kTraceBlock) void ray_query_redo_kernel(const RayQu
         bool hit, was;
         if (any_hit) {
             was = static_cast<const uint8_t *>(a.results)[ray] != 0u;
-            hit = traverse<true>(a.scene, o, d, p.w, q.w, s_stack + threadIdx.x, best, overflow);
+            hit = traverse<true>(a.scene, o, d, p.w, q.w, s_stack + threadIdx.x, best, overflow, alpha_reject<ALPHA>(a.scene));
         } else {
             was = static_cast<const uint32_t *>(a.results)[size_t(ray) * 6u + 3u] != kNoHit;
-            hit = traverse<false>(a.scene, o, d, p.w, q.w, s_stack + threadIdx.x, best, overflow);
+            hit = traverse<false>(a.scene, o, d, p.w, q.w, s_stack + threadIdx.x, best, overflow, alpha_reject<ALPHA>(a.scene));
         }
         ray_query_store(a, ray, any_hit, hit, best.t, best.u, best.v, hit && !any_hit ? a.scene.tris[best.tri_index].prim : 0u,
                         hit && !any_hit ? a.scene.tris[best.tri_index].tri : 0u);
@@ -147,7 +149,7 @@ __global__ __launch_bounds__(kTraceBlock) void ray_query_redo_kernel(const RayQu
     if (overflow) atomicAdd(&a.counters->overflows, 1u);
 }
 
-int launch_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, bool any_hit, void *results) {
+int launch_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, bool any_hit, bool alpha_test, void *results) {
     if (count == 0) return VHR_OK;
     RayQueryScratch *q = nullptr;                  // this stream's counters and list
     for (RayQueryScratch &e : ctx->rq_scratch) if (e.stream == ctx->stream) q = &e;
@@ -182,10 +184,14 @@ int launch_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, bool
     const QueueLaunch ql = queue_launch(ctx, kOptLdsStackLevels, kOptEarlyExit, 2u);
     const dim3 grid(uint32_t((uint64_t(count) + 2u * kQueryWaveRays - 1u) / (2u * kQueryWaveRays)));
     ctx->time_begin(kKernelRayQuery);
-    with_bool(ql.spill, [&](auto sp) { launch(ctx, ray_query_kernel<decltype(sp)::value>, grid, dim3(kQueueBlock * 2), ql.lds_bytes, a, ql.levels, ql.threshold, ql.early_exit); });
+    // the flag on a scene none of whose primitives can discard asks for nothing: the plain kernels
+    const bool alpha = alpha_test && ctx->scene_can_discard;
+    with_bool(ql.spill, [&](auto sp) { with_bool(alpha, [&](auto al) {
+        launch(ctx, ray_query_kernel<decltype(sp)::value, decltype(al)::value>, grid, dim3(kQueueBlock * 2), ql.lds_bytes, a, ql.levels, ql.threshold, ql.early_exit);
+    }); });
     if (a.scene.node_count != 0) {
         const uint32_t redo_blocks = std::min<uint32_t>((count + kTraceBlock - 1u) / kTraceBlock, uint32_t(ctx->cu_count) * 4u);
-        launch(ctx, ray_query_redo_kernel, dim3(redo_blocks), dim3(kTraceBlock), 0, a);
+        with_bool(alpha, [&](auto al) { launch(ctx, ray_query_redo_kernel<decltype(al)::value>, dim3(redo_blocks), dim3(kTraceBlock), 0, a); });
     }
     ctx->time_end(kKernelRayQuery);
     if (hipGetLastError() != hipSuccess) return ctx->fail(VHR_ERROR_DEVICE, "vhr_ray_query: kernel launch failed");

@@ -51,7 +51,8 @@ struct RaygenArgs {
 
 // raygen.rgen:26-55 for one covered pixel: its shadow ray and its AO rays one after another (the walker with the whole of decision (vi): traverse<> ->
 // ray_triangle).  STRIDE: the stack's (kTraceBlock: the per-pixel kernels' LDS columns; 1: a private array).
-template <int STRIDE>
+// ALPHA ("alpha_test_rays" on a scene that can discard, in every kernel of this file): a candidate gbuf_discarded names does not exist for the ray.
+template <int STRIDE, bool ALPHA = false>
 __device__ __forceinline__ void pixel_visibility(const RaygenArgs &a, const uint32_t x, const uint32_t y, const float depth, int *stack, uint32_t &overflow,
                                                  f3 &P, f3 &N, f3 &origin, float &shadow_payload, float &ao_payload) {
     const uint32_t W = a.width, H = a.height;
@@ -73,7 +74,7 @@ __device__ __forceinline__ void pixel_visibility(const RaygenArgs &a, const uint
         const f3 cone_dir = normalize3(uniform_sample_cone(rnd1, rnd2, a.tp.cone_cos_max));   // rgen:34
         const f3 dir = onb_transform(L, cone_dir);                                       // rgen:35,40
         // rgen:37-41 issues this trace four times with identical arguments; once is equivalent
-        const bool occluded = traverse<true, false, STRIDE>(a.scene, origin, dir, a.tp.tmin, a.tp.tmax, stack, hit, overflow);
+        const bool occluded = traverse<true, false, STRIDE>(a.scene, origin, dir, a.tp.tmin, a.tp.tmax, stack, hit, overflow, alpha_reject<ALPHA>(a.scene));
         shadow_payload = occluded ? 0.0f : 1.0f;                                         // miss.rmiss:7
     }
     ao_payload = 0.0f;                                                                   // rgen:44-55
@@ -82,7 +83,7 @@ __device__ __forceinline__ void pixel_visibility(const RaygenArgs &a, const uint
         rnd2 = random01(rng);
         const f3 rnd_dir = cosine_hemisphere(rnd1, rnd2);
         const f3 dir = onb_transform(N, rnd_dir);
-        const bool occluded = traverse<true, false, STRIDE>(a.scene, origin, dir, a.tp.tmin, a.tp.ao_tmax, stack, hit, overflow);
+        const bool occluded = traverse<true, false, STRIDE>(a.scene, origin, dir, a.tp.tmin, a.tp.ao_tmax, stack, hit, overflow, alpha_reject<ALPHA>(a.scene));
         ao_payload += occluded ? 0.0f : 1.0f;
     }
     if (a.tp.ao_spp) ao_payload /= float(a.tp.ao_spp); else ao_payload = 1.0f;
@@ -93,16 +94,18 @@ __device__ __forceinline__ void pixel_visibility(const RaygenArgs &a, const uint
 // test the binary64 arithmetic cost the kernel 13 registers = a wave per SIMD, 1.3-1.5 % of the frame: profiles/r6_decision_vi_cost.txt).  `a` points at
 // the launch's arguments where they lie in memory (the address of a by-value argument would copy all of it to every lane's scratch).  At 1080p:
 // none to three pixels of a frame on the BASELINE stand-ins, up to ~70 on sponza_hard_rot (profiles/r6_decision_vi_cost.txt).
+template <bool ALPHA = false>
 __device__ VHR_REDO_INLINE float2 redo_pixel_visibility(const RaygenArgs *a, const uint32_t x, const uint32_t y) {
     int st[kTraceStack];
     uint32_t overflow = 0;
     f3 P, N, origin;
     float shadow_payload, ao_payload;
-    pixel_visibility<1>(*a, x, y, a->depth[size_t(y) * a->width + x], st, overflow, P, N, origin, shadow_payload, ao_payload);
+    pixel_visibility<1, ALPHA>(*a, x, y, a->depth[size_t(y) * a->width + x], st, overflow, P, N, origin, shadow_payload, ao_payload);
     return float2{ shadow_payload, ao_payload };
 }
 
 // raygen.rgen:14-66 for one pixel
+template <bool ALPHA = false>
 __device__ __forceinline__ void raygen_pixel(const RaygenArgs &a, const uint32_t x, const uint32_t y, int *stack, uint32_t &overflow, bool &covered, bool &second_ray) {
     const uint32_t W = a.width;
     const float depth = a.depth[size_t(y) * W + x];                                      // rgen:19
@@ -114,7 +117,7 @@ __device__ __forceinline__ void raygen_pixel(const RaygenArgs &a, const uint32_t
     covered = true;
     f3 P, N, origin;
     float shadow_payload, ao_payload;
-    pixel_visibility<kTraceBlock>(a, x, y, depth, stack, overflow, P, N, origin, shadow_payload, ao_payload);
+    pixel_visibility<kTraceBlock, ALPHA>(a, x, y, depth, stack, overflow, P, N, origin, shadow_payload, ao_payload);
     store_rg16f(a.shadow_ao, W, x, y, shadow_payload, ao_payload);                       // rgen:57
 
     if (a.reflections) {
@@ -124,12 +127,13 @@ __device__ __forceinline__ void raygen_pixel(const RaygenArgs &a, const uint32_t
             const f3 I = normalize3(P - cam);
             const float ni2 = 2.0f * dot3(N, I);
             const f3 rdir = I - N * ni2;                                                 // reflect(I, N)
-            payload = trace_reflection(a.scene, a.pfd, a.tp, origin, rdir, stack, overflow, second_ray);
+            payload = trace_reflection<kTraceBlock, ALPHA>(a.scene, a.pfd, a.tp, origin, rdir, stack, overflow, second_ray);
         }
         store_rgba16f(a.reflections, W, x, y, payload.x, payload.y, payload.z, payload.w);
     }
 }
 
+template <bool ALPHA = false>
 __global__ __launch_bounds__(kTraceBlock) void raygen_kernel(const RaygenArgs a, const Stamps st) {
     vhr_stamp(st);
     __shared__ int s_stack[kTraceStack * kTraceBlock];
@@ -138,7 +142,7 @@ __global__ __launch_bounds__(kTraceBlock) void raygen_kernel(const RaygenArgs a,
     pixel_of_thread(x, y, a.row_begin);
     uint32_t overflow = 0;
     bool covered = false, second_ray = false;
-    if (x < a.width && y < a.row_end) raygen_pixel(a, x, y, stack, overflow, covered, second_ray);
+    if (x < a.width && y < a.row_end) raygen_pixel<ALPHA>(a, x, y, stack, overflow, covered, second_ray);
     if (a.stats) {
         const unsigned long long cov = __ballot(covered), ovf = __ballot(overflow != 0), sec = __ballot(second_ray);
         if ((threadIdx.x & 63u) == 0) {
@@ -170,7 +174,8 @@ __global__ __launch_bounds__(kTraceBlock) void raygen_kernel(const RaygenArgs a,
 // live in scratch.  STATS: in-kernel counters and timers (vhr_set_ray_statistics).  Per covered pixel the wave keeps 5 words in LDS -- the ray
 // origin and the G-buffer normal as the halves it is -- and recomputes the pixel's seed and the ray's direction at refill with raygen.rgen's
 // exact arithmetic.
-template <int WAVES, bool COMPACT, bool SPILL, bool STATS, bool FUSE = false>
+// ALPHA ("alpha_test_rays"): the leaf test asks gbuf_discarded about every consistent candidate before it ends the ray.
+template <int WAVES, bool COMPACT, bool SPILL, bool STATS, bool FUSE = false, bool ALPHA = false>
 __global__ __launch_bounds__(kQueueBlock *WAVES) __attribute__((amdgpu_waves_per_eu(VHR_K1_WAVES_MIN, 8))) void raygen_queue_kernel(const RaygenArgs a, const uint32_t stack_levels, const uint32_t refill_threshold,
                                                                           const uint32_t block_tiles_x, const uint32_t early_exit, const uint32_t tile_rows, const uint32_t steal_threshold, const Stamps st) {
     vhr_stamp(st);
@@ -441,6 +446,7 @@ __global__ __launch_bounds__(kQueueBlock *WAVES) __attribute__((amdgpu_waves_per
                 // (the consistency test behind the candidates only: few tests get this far, and a wave whose lanes all failed skips it)
                 if (mt_candidate(ro, rd, v0, e1, e2, tmin, tmax, ct, cu, cv)) {
                     if (solution_consistent(ro, rd, v0, e1, e2, ct, cu, cv)) {
+                        if constexpr (ALPHA) { if (gbuf_discarded(a.scene, first + i, cu, cv)) continue; }      // a hole: the candidate does not exist
                         found = true;
                         break;
                     }
@@ -502,7 +508,7 @@ __global__ __launch_bounds__(kQueueBlock *WAVES) __attribute__((amdgpu_waves_per
         if (a.tp.ao_spp) ao_payload = float(a.scene.node_count == 0 ? a.tp.ao_spp : (kind_bits ? a.tp.ao_spp - uint32_t(__popc(vis >> 1)) : (vis >> 8))) / float(a.tp.ao_spp);   // rgen:55: the AO rays that escaped
         if (vis & kRedoPixel) {                           // decision (vi): one of this pixel's rays met a candidate that contradicts itself
             static_assert(offsetof(RaygenArgs, scene) == 0, "the launch's arguments start with `a`");
-            const float2 again = redo_pixel_visibility(reinterpret_cast<const RaygenArgs *>((const void *)__builtin_amdgcn_kernarg_segment_ptr()), x, y);
+            const float2 again = redo_pixel_visibility<ALPHA>(reinterpret_cast<const RaygenArgs *>((const void *)__builtin_amdgcn_kernarg_segment_ptr()), x, y);
             shadow_payload = again.x; ao_payload = again.y;
             n_redo = 1;
         }
@@ -556,7 +562,7 @@ __global__ __launch_bounds__(kQueueBlock *WAVES) __attribute__((amdgpu_waves_per
 }
 
 // Mirror ray of raygen.rgen:59-65 (closest hit, reflection_hit.rchit / reflection_miss.rmiss) for one pixel of the image
-template <int STRIDE>
+template <int STRIDE, bool ALPHA = false>
 __device__ __forceinline__ f4 reflection_payload(const RaygenArgs &a, const uint32_t x, const uint32_t y, int *stack, bool &second_ray) {
     const uint32_t W = a.width, H = a.height;
     f4 payload = f4{ 0.0f, 0.0f, 0.0f, 0.0f };
@@ -572,12 +578,13 @@ __device__ __forceinline__ f4 reflection_payload(const RaygenArgs &a, const uint
         const float ni2 = 2.0f * dot3(N, I);
         const f3 rdir = I - N * ni2;
         uint32_t overflow = 0;
-        payload = trace_reflection<STRIDE>(a.scene, a.pfd, a.tp, origin, rdir, stack, overflow, second_ray);
+        payload = trace_reflection<STRIDE, ALPHA>(a.scene, a.pfd, a.tp, origin, rdir, stack, overflow, second_ray);
     }
     return payload;
 }
+template <bool ALPHA = false>
 __device__ __forceinline__ void reflection_pixel(const RaygenArgs &a, const uint32_t x, const uint32_t y, int *stack, bool &second_ray) {
-    const f4 payload = reflection_payload<kTraceBlock>(a, x, y, stack, second_ray);
+    const f4 payload = reflection_payload<kTraceBlock, ALPHA>(a, x, y, stack, second_ray);
     store_rgba16f(a.reflections, a.width, x, y, payload.x, payload.y, payload.z, payload.w);
 }
 
@@ -589,14 +596,16 @@ __device__ __forceinline__ void reflection_pixel(const RaygenArgs &a, const uint
 // the waves the scratch ring then had room for).  About one pixel of a 1080p frame on the BASELINE stand-ins, ~70-100 on sponza_hard_rot.  `second`: a second-bounce ray was
 // traced (the launch's ray count).
 struct RedoReflection { f4 payload; uint32_t second; };
+template <bool ALPHA = false>
 __device__ __attribute__((noinline)) RedoReflection redo_pixel_reflection(const RaygenArgs *a, const uint32_t x, const uint32_t y) {
     int st[kTraceStack];
     bool second_ray = false;
-    const f4 payload = reflection_payload<1>(*a, x, y, st, second_ray);
+    const f4 payload = reflection_payload<1, ALPHA>(*a, x, y, st, second_ray);
     return RedoReflection{ payload, second_ray ? 1u : 0u };
 }
 
 // ... one pixel per thread
+template <bool ALPHA = false>
 __global__ __launch_bounds__(kTraceBlock) void reflection_kernel(const RaygenArgs a, const Stamps st) {
     vhr_stamp(st);
     __shared__ int s_refl_stack[kTraceStack * kTraceBlock];
@@ -604,7 +613,7 @@ __global__ __launch_bounds__(kTraceBlock) void reflection_kernel(const RaygenArg
     uint32_t x, y;
     pixel_of_thread(x, y, a.row_begin);
     bool second_ray = false;
-    if (x < a.width && y < a.row_end) reflection_pixel(a, x, y, stack, second_ray);
+    if (x < a.width && y < a.row_end) reflection_pixel<ALPHA>(a, x, y, stack, second_ray);
     if (a.stats) {
         const unsigned long long sec = __ballot(second_ray);
         if ((threadIdx.x & 63u) == 0 && sec) atomicAdd(&a.stats->second_bounce_rays, (unsigned long long)__popcll(sec));
@@ -636,7 +645,8 @@ __device__ __forceinline__ void mirror_ray_of_pixel(const RaygenArgs &a, f3 cam,
     rdir = I - N * ni2;                                                                      // rgen:61 reflect(I, N)
 }
 
-template <bool SPILL, int BOUNCES, bool STATS = false>
+// ALPHA ("alpha_test_rays"): the walk's Reject is GbufDiscard, behind decision (vi) as ever; phase 3's redo applies it as well.
+template <bool SPILL, int BOUNCES, bool STATS = false, bool ALPHA = false>
 __global__ __launch_bounds__(kQueueBlock * 2) __attribute__((amdgpu_waves_per_eu(7, 7))) void reflection_queue_kernel(
     const RaygenArgs a, const uint32_t stack_levels, const uint32_t refill_threshold, const uint32_t tiles_x, const uint32_t tiles_total,
     const uint32_t early_exit, const Stamps st) {
@@ -727,7 +737,8 @@ __global__ __launch_bounds__(kQueueBlock * 2) __attribute__((amdgpu_waves_per_eu
         [&](uint32_t pix, uint32_t tri, float u, float v) {                                  // the hit record replaces the ray's origin
             s_ray[orow][pix] = __uint_as_float(tri); s_ray[orow + 1][pix] = u; s_ray[orow + 2][pix] = v;
         }, &wc,
-        [&](uint32_t pix) { atomicOr(&s_redo[pix >> 5], 1u << (pix & 31u)); });                   // decision (vi): the pixel is computed again in phase 3
+        [&](uint32_t pix) { atomicOr(&s_redo[pix >> 5], 1u << (pix & 31u)); },                    // decision (vi): the pixel is computed again in phase 3
+        alpha_reject<ALPHA>(a.scene));
     wave_lds_sync();
     if (STATS) t_walk += __builtin_readcyclecounter() - tw0;
     if constexpr (BOUNCES > 1) if (bounce == 0) {
@@ -775,7 +786,7 @@ __global__ __launch_bounds__(kQueueBlock * 2) __attribute__((amdgpu_waves_per_eu
         const uint32_t tri = traced ? __float_as_uint(s_ray[0][p]) : kNoHit;
         if (traced && ((s_redo[p >> 5] >> (p & 31u)) & 1u)) {                                // decision (vi): this pixel's ray asked for binary64
             static_assert(offsetof(RaygenArgs, scene) == 0, "the launch's arguments start with `a`");
-            const RedoReflection again = redo_pixel_reflection(reinterpret_cast<const RaygenArgs *>((const void *)__builtin_amdgcn_kernarg_segment_ptr()), x, y);
+            const RedoReflection again = redo_pixel_reflection<ALPHA>(reinterpret_cast<const RaygenArgs *>((const void *)__builtin_amdgcn_kernarg_segment_ptr()), x, y);
             payload = again.payload;
             ++n_redo;
             if (BOUNCES > 1) redo_second += int(again.second) - int(tri != kNoHit);          // (the launch's count of second-bounce rays)
@@ -828,14 +839,20 @@ __global__ __launch_bounds__(kQueueBlock * 2) __attribute__((amdgpu_waves_per_eu
     if (a.co.wave_cost && lane == 0) a.co.wave_cost[tile] = uint32_t(min(__builtin_readcyclecounter() - t_cost0, 0xffffffffull));
 }
 
-// The shadow / AO launch itself, by the options in force (everything launch_raygen decided is in `a`).
-static void issue_raygen(vhr_context *ctx, const RaygenArgs &a_in, const uint32_t width, const uint32_t height) {
+// "alpha_test_rays", read at every launch: the alpha instantiations run only where the switch is on AND some primitive of the scene can discard
+// (vhr_update_geometry looked); everywhere else the launches are the ones they were before the switch existed.
+static bool alpha_rays(const vhr_context *ctx) { return ctx->alpha_test_rays != 0 && ctx->scene_can_discard; }
+
+// The shadow / AO launch itself, by the options in force (everything launch_raygen decided is in `a`).  `alpha`: alpha_rays() as launch_raygen
+// saw it (a launch held back for "fuse_temporal" never has it).
+static void issue_raygen(vhr_context *ctx, const RaygenArgs &a_in, const uint32_t width, const uint32_t height, const bool alpha = false) {
     RaygenArgs a = a_in;
     a.co = CostOrderArgs{};
     (void)height;
     ctx->time_begin(kKernelRaygen);
+    if (alpha) ++ctx->alpha_launches;
     if (ctx->options[kOptRaygenVariant] == 0) {
-        launch(ctx, raygen_kernel, dim3((width + 15) / 16, (a.row_end - a.row_begin + 15) / 16), dim3(kTraceBlock), 0, a);
+        with_bool(alpha, [&](auto al) { launch(ctx, raygen_kernel<decltype(al)::value>, dim3((width + 15) / 16, (a.row_end - a.row_begin + 15) / 16), dim3(kTraceBlock), 0, a); });
     } else {
         const uint32_t rows_traced = a.row_end - a.row_begin;
         // rows of a wave's tile: 8, or ("raygen_tile_rows" 0 = auto, the default) 6 for a launch whose 8x8 tiles would fill less than 70 % of the
@@ -863,12 +880,14 @@ static void issue_raygen(vhr_context *ctx, const RaygenArgs &a_in, const uint32_
             constexpr int WV = decltype(waves_c)::value;
             with_bool(q.spill, [&](auto sp) {
                 constexpr bool SP = decltype(sp)::value;
-                if (a.fuse_temporal && compact && !a.stats) {   // "fuse_temporal": svgf.comp in the tiles' epilogues (the default node form only)
+                if (a.fuse_temporal && compact && !a.stats && !alpha) {   // "fuse_temporal": svgf.comp in the tiles' epilogues (the default node form only)
                     go(raygen_queue_kernel<WV, true, SP, false, true>);
                     return;
                 }
                 with_bool(compact, [&](auto co) {
-                    with_bool(a.stats != nullptr, [&](auto st) { go(raygen_queue_kernel<WV, decltype(co)::value, SP, decltype(st)::value>); });
+                    with_bool(a.stats != nullptr, [&](auto st) { with_bool(alpha, [&](auto al) {
+                        go(raygen_queue_kernel<WV, decltype(co)::value, SP, decltype(st)::value, false, decltype(al)::value>);
+                    }); });
                 });
             });
         };
@@ -939,6 +958,7 @@ int launch_raygen(vhr_context *ctx, const vhr_per_frame_data &pfd, uint32_t widt
     a.col_end = owned_col_end;
     a.stats = ctx->ray_stats_enabled ? ctx->d_ray_stats : nullptr;
     ctx->raytraced_pixels = 0;                 // ray statistics are the hybrid path's again
+    ctx->alpha_launches = 0;
     if (a.row_end <= a.row_begin || a.col_end <= a.col_begin) return VHR_OK;
     if (ctx->options[kOptTraceOverlap]) {      // strips / tiles: trace the margin the denoiser recomputes too (no exchange of raw visibility)
         a.row_begin = owned_begin > ctx->overlap ? owned_begin - ctx->overlap : 0u;
@@ -950,12 +970,14 @@ int launch_raygen(vhr_context *ctx, const vhr_per_frame_data &pfd, uint32_t widt
     // "fuse_temporal" (opt-in): hold the launch back until the next pass shows its first command -- if that is svgf.comp on this launch's
     // images, the queue kernel runs it in its tiles' epilogues (flush_deferred_raygen).  Only the default kernel has that epilogue, only
     // whole-image work on one stream qualifies, and only a pass nobody hooked an epilogue to (its owner expects the image when it runs).
+    // With "alpha_test_rays" in force the launch is not held back: the epilogue has no alpha instantiation, the SVGF pass runs its own dispatch.
+    const bool alpha = alpha_rays(ctx);
     {
         // (the epilogue exists in the queue kernel on the 32-byte nodes only: issue_raygen)
         const bool default_kernel = ctx->options[kOptRaygenVariant] != 0 && ctx->options[kOptCompactNodes] != 0 && ctx->nodes16_valid;
         const bool whole = a.row_begin == 0 && a.row_end == height && a.col_begin == 0 && a.col_end == width;
         const bool mirror = a.reflections && a.tp.reflections;
-        if (ctx->options[kOptFuseTemporal] && ctx->may_defer_raygen && default_kernel && whole && !mirror && !a.stats && ctx->frames_in_flight == 1 &&
+        if (ctx->options[kOptFuseTemporal] && !alpha && ctx->may_defer_raygen && default_kernel && whole && !mirror && !a.stats && ctx->frames_in_flight == 1 &&
             (ctx->in_kernel_stamps() || !ctx->options[kOptPassTimestamps]) && a.scene.node_count != 0) {
             a.fuse_temporal = 0u;
             DeferredRaygen d;
@@ -968,7 +990,7 @@ int launch_raygen(vhr_context *ctx, const vhr_per_frame_data &pfd, uint32_t widt
             return VHR_OK;
         }
     }
-    issue_raygen(ctx, a, width, height);
+    issue_raygen(ctx, a, width, height, alpha);
     // The mirror ray's launch (raygen.rgen:59-65): not denoised, so owned rows (and columns) only.  It runs BEHIND the shadow / AO launch: beside it
     // (a second stream) the two take as long as one after the other, and with walk and shading in two launches the walk is no faster
     // (profiles/r4_reflection_concurrent.txt, r4d/r4e logs in profiles/r4_reflection_split.txt).
@@ -1000,6 +1022,7 @@ int launch_raygen(vhr_context *ctx, const vhr_per_frame_data &pfd, uint32_t widt
             }
         }
         ctx->time_begin(kKernelReflection);
+        if (alpha) ++ctx->alpha_launches;
         if (m.tp.reflections <= 2 && ctx->options[kOptReflectionVariant] != 0) {
             const QueueLaunch q = queue_launch(ctx, kOptReflectionLdsStackLevels, kOptReflectionEarlyExit, 2u);
             const TileGrid g = tile_grid(m.col_end - m.col_begin, owned_end - owned_begin, 8u);      // (reflection_queue_kernel: 8 x 8 pixels per wave)
@@ -1009,11 +1032,14 @@ int launch_raygen(vhr_context *ctx, const vhr_per_frame_data &pfd, uint32_t widt
                                    (g.tiles_x * 2654435761u) ^ (g.tiles_total * 40503u) ^ (uint32_t(m.tp.reflections) << 28) ^ (m.row_begin * 97u) ^ (m.col_begin * 193u), m.co,
                                    { g.tiles_x, g.tiles_x, 1u, 8u, 8u, m.col_begin, m.row_begin });
             with_bool(q.spill, [&](auto sp) { with_bool(m.tp.reflections == 2, [&](auto two) { with_bool(m.stats != nullptr, [&](auto st) {
-                launch(ctx, reflection_queue_kernel<decltype(sp)::value, decltype(two)::value ? 2 : 1, decltype(st)::value>, g.grid, g.block, q.lds_bytes, m, q.levels, q.threshold,
-                       g.tiles_x, g.tiles_total, q.early_exit);
+                constexpr bool SP = decltype(sp)::value, ST = decltype(st)::value;
+                constexpr int B = decltype(two)::value ? 2 : 1;
+                with_bool(alpha, [&](auto al) {
+                    launch(ctx, reflection_queue_kernel<SP, B, ST, decltype(al)::value>, g.grid, g.block, q.lds_bytes, m, q.levels, q.threshold, g.tiles_x, g.tiles_total, q.early_exit);
+                });
             }); }); });
         } else {
-            launch(ctx, reflection_kernel, dim3((width + 15) / 16, (owned_end - owned_begin + 15) / 16), dim3(kTraceBlock), 0, m);
+            with_bool(alpha, [&](auto al) { launch(ctx, reflection_kernel<decltype(al)::value>, dim3((width + 15) / 16, (owned_end - owned_begin + 15) / 16), dim3(kTraceBlock), 0, m); });
         }
         ctx->time_end(kKernelReflection);
         if (on_own_stream) {

@@ -11,6 +11,8 @@
 // device_math.hpp so visibility results are bit-reproducible.
 #pragma once
 
+#include <type_traits>
+
 #include "device_math.hpp"
 #include "vhr_internal.hpp"
 
@@ -252,6 +254,26 @@ __device__ bool alpha_ignored(const DeviceScene &sc, uint32_t tri_index, float u
     return albedo.w < prim.material.alpha_cutoff;                                        // rahit:24-26
 }
 
+// gbuf.frag:20-32 evaluated at a candidate hit: true = the G-buffer pass would discard the fragment, so the surface has a hole there and the
+// candidate does not exist for a ray that is to see what the raster pass drew ("alpha_test_rays", VHR_RAY_QUERY_ALPHA_TEST).  uv0 is
+// interpolated as shadow_anyhit.rahit:19-20 does; an untextured primitive's albedo is its base colour (the rahit reads textures[-1] there and
+// has no `a == 0` clause: alpha_ignored above keeps that rule for the raytraced path).  A pure function of (triangle, u, v).
+__device__ bool gbuf_discarded(const DeviceScene &sc, uint32_t tri_index, float u, float v) {
+    const BvhTri &bt = sc.tris[tri_index];
+    const vhr_primitive &prim = sc.primitives[bt.prim];
+    float alpha = prim.material.base_color[3];                                           // gbuf.frag:19-26
+    if (prim.material.base_color_texture != -1) {
+        const vhr_vertex &a = sc.vertices[prim.vertex_offset + sc.indices[prim.index_offset + 3 * bt.tri + 0]];
+        const vhr_vertex &b = sc.vertices[prim.vertex_offset + sc.indices[prim.index_offset + 3 * bt.tri + 1]];
+        const vhr_vertex &c = sc.vertices[prim.vertex_offset + sc.indices[prim.index_offset + 3 * bt.tri + 2]];
+        const float bx = 1.0f - u - v, by = u, bz = v;                                   // rahit:19
+        const float uvx = a.uv0[0] * bx + b.uv0[0] * by + c.uv0[0] * bz;                 // rahit:20
+        const float uvy = a.uv0[1] * bx + b.uv0[1] * by + c.uv0[1] * bz;
+        alpha = sample_texture(sc, prim.material.base_color_texture, uvx, uvy).w;
+    }
+    return (prim.material.alpha_mask == 1 && alpha < prim.material.alpha_cutoff) || alpha == 0.0f;   // gbuf.frag:27-32
+}
+
 // Per-lane BVH2 walk with the traversal stack in LDS (stack[level * kTraceBlock + thread]: conflict free; STRIDE 1: a private array).
 // ANY_HIT: gl_RayFlagsTerminateOnFirstHitEXT | SkipClosestHitShader (raygen.rgen:39,51) -- returns at the
 // first accepted triangle; the boolean result does not depend on the visiting order.
@@ -266,6 +288,22 @@ struct NoReject {
     __device__ __forceinline__ bool operator()(uint32_t) const { return false; }
     __device__ __forceinline__ bool operator()(uint32_t, uint32_t) const { return false; }
 };
+// GbufDiscard: the hybrid path's rays and the ray query with their alpha test on -- gbuf_discarded at the candidate.  A Reject with kAtHit is
+// handed the candidate's barycentrics as well: reject(triangle, u, v), in wave_queue_walk reject(ray id, triangle, u, v).
+struct GbufDiscard {
+    static constexpr bool kActive = true;
+    static constexpr bool kAtHit = true;
+    const DeviceScene *sc;
+    __device__ __forceinline__ bool operator()(uint32_t tri, float u, float v) const { return gbuf_discarded(*sc, tri, u, v); }
+    __device__ __forceinline__ bool operator()(uint32_t, uint32_t tri, float u, float v) const { return gbuf_discarded(*sc, tri, u, v); }
+};
+template <typename R, typename = void> struct reject_at_hit : std::false_type {};
+template <typename R> struct reject_at_hit<R, std::void_t<decltype(R::kAtHit)>> : std::true_type {};
+// the hybrid path's and the ray query's walkers by their alpha switch: GbufDiscard or nothing
+template <bool ALPHA> using AlphaReject = std::conditional_t<ALPHA, GbufDiscard, NoReject>;
+template <bool ALPHA> __device__ __forceinline__ AlphaReject<ALPHA> alpha_reject(const DeviceScene &sc) {
+    if constexpr (ALPHA) return GbufDiscard{ &sc }; else return NoReject{};
+}
 
 template <bool ANY_HIT, bool ALPHA = false, int STRIDE = kTraceBlock, typename Reject = NoReject>
 __device__ __forceinline__ bool traverse(const DeviceScene &sc, f3 o, f3 d, float tmin, float tmax, int *stack, Hit &best,
@@ -305,7 +343,8 @@ __device__ __forceinline__ bool traverse(const DeviceScene &sc, f3 o, f3 d, floa
                 float t, u, w;
                 if (ray_triangle(o, d, f3{ a.x, a.y, a.z }, f3{ a.w, b.x, b.y }, f3{ b.z, b.w, c.x }, tmin, tmax, t, u, w)) {
                     if (ALPHA && alpha_ignored(sc, first + i, u, w)) continue;
-                    if constexpr (Reject::kActive) { if (reject(first + i)) continue; }
+                    if constexpr (reject_at_hit<Reject>::value) { if (reject(first + i, u, w)) continue; }
+                    else if constexpr (Reject::kActive) { if (reject(first + i)) continue; }
                     if (ANY_HIT) return true;
                     const uint32_t flat = __float_as_uint(c.w);
                     if (!found || t < best.t || (t == best.t && flat < best.flat)) {
@@ -430,12 +469,13 @@ __device__ __forceinline__ void hit_position_normal(const DeviceScene &sc, const
 
 // The mirror ray of raygen.rgen:59-65 with the optional second bounce: a mirror ray from the first hit about the shader's N
 // (normalised, facing the incoming ray), origin biased like raygen.rgen:29, shaded by reflection_hit.rchit without recursion.
-template <int STRIDE = kTraceBlock>
+// ALPHA ("alpha_test_rays"): both bounces skip the candidates gbuf_discarded names.
+template <int STRIDE = kTraceBlock, bool ALPHA = false>
 __device__ __forceinline__ f4 trace_reflection(const DeviceScene &sc, const vhr_per_frame_data &pfd, const vhr_trace_params &tp, f3 origin,
                                                f3 rdir, int *stack, uint32_t &overflow, bool &second_ray) {
     Hit hit;
     second_ray = false;
-    if (!traverse<false, false, STRIDE>(sc, origin, rdir, tp.tmin, tp.tmax, stack, hit, overflow)) return f4{ 0.0f, 0.0f, 0.0f, 0.0f };   // reflection_miss.rmiss:7
+    if (!traverse<false, false, STRIDE>(sc, origin, rdir, tp.tmin, tp.tmax, stack, hit, overflow, alpha_reject<ALPHA>(sc))) return f4{ 0.0f, 0.0f, 0.0f, 0.0f };   // reflection_miss.rmiss:7
     if (tp.reflections < 2) return shade_reflection_hit(sc, pfd, hit);
     f3 hp, hn;
     (void)shade_reflection_hit(sc, pfd, hit, nullptr, &hp, &hn);
@@ -447,7 +487,7 @@ __device__ __forceinline__ f4 trace_reflection(const DeviceScene &sc, const vhr_
     second_ray = true;
     Hit hit2;
     f4 second = f4{ 0.0f, 0.0f, 0.0f, 0.0f };
-    if (traverse<false, false, STRIDE>(sc, o2, d2, tp.tmin, tp.tmax, stack, hit2, overflow)) second = shade_reflection_hit(sc, pfd, hit2);
+    if (traverse<false, false, STRIDE>(sc, o2, d2, tp.tmin, tp.tmax, stack, hit2, overflow, alpha_reject<ALPHA>(sc))) second = shade_reflection_hit(sc, pfd, hit2);
     return shade_reflection_hit(sc, pfd, hit, &second);
 }
 

@@ -513,7 +513,8 @@ struct CostOrderArgs {
 // decision vi), early exit of the node loop, LDS stack + scratch spill.  Leaves: every triangle, Moeller-Trumbore against the
 // full [tmin, tmax] interval, closest = min t then smaller flat index; with `any_hit` (wave-uniform) the first accepted
 // triangle ends the ray (gl_RayFlagsTerminateOnFirstHitEXT -- the boolean does not depend on the order).  ALPHA: every
-// candidate first runs shadow_anyhit.rahit (alpha_ignored); Reject: then reject(pix, triangle) (forward_raster_queue_kernel).  PER_RAY (the batched ray query, ray_query_kernel): every ray brings
+// candidate first runs shadow_anyhit.rahit (alpha_ignored); Reject: then reject(pix, triangle) (forward_raster_queue_kernel) or, for a Reject
+// with kAtHit (GbufDiscard: the hybrid path's mirror ray and the ray query with their alpha test on), reject(pix, triangle, u, v).  PER_RAY (the batched ray query, ray_query_kernel): every ray brings
 // its own interval -- fetch(r, pix, origin, direction, tmin, tmax), the ray's tmax seeds the cull -- and commit(pix, triangle, u, v, t)
 // is also told the hit's t; `tmin` / `tmax` are then unused.
 // ---------------------------------------------------------------------------------------------
@@ -618,7 +619,8 @@ __device__ __forceinline__ void wave_queue_walk(const DeviceScene &sc, int *stac
                         if (!mt_binary64(ro, rd, v0, e1, e2, ray_tmin, ray_tmax, t, uu, ww)) continue;
                     }
                     if (ALPHA && alpha_ignored(sc, first + i, uu, ww)) continue;
-                    if constexpr (Reject::kActive) { if (reject(pix, first + i)) continue; }
+                    if constexpr (reject_at_hit<Reject>::value) { if (reject(pix, first + i, uu, ww)) continue; }
+                    else if constexpr (Reject::kActive) { if (reject(pix, first + i)) continue; }
                     const uint32_t flat = __float_as_uint(tc.w);
                     if (best_tri == kNoHit || t < tbest || (t == tbest && flat < best_flat)) {
                         tbest = t; best_tri = first + i; best_flat = flat; best_u = uu; best_v = ww;

@@ -464,6 +464,13 @@ struct vhr_context {
     uint64_t bvh_fingerprint = 0;                   // bvh_fingerprint() of the last build (vhr_get_bvh_fingerprint)
     uint64_t bvh_tree_fingerprint = 0;              // bvh_tree_fingerprint() of the last build (vhr_get_bvh_tree_fingerprint)
     bool bvh_fingerprint_valid = false;             // a device-built tree is hashed when somebody asks (it would have to be fetched first)
+    // "alpha_test_rays" (vhr_set_option, beside the bvh_* keys: it changes images, so it is no entry of VHR_OPTION_TABLE): 1 = the hybrid path's
+    // shadow, AO and mirror rays skip what gbuf.frag:20-32 discards (gbuf_discarded, trace_device.hpp).  Read at every launch.
+    int alpha_test_rays = 0;
+    // some primitive of the current scene CAN discard (alpha_mask == 1, a base-colour texture, or untextured with base_color[3] == 0): looked up
+    // once per vhr_update_geometry; without one the switch and VHR_RAY_QUERY_ALPHA_TEST launch the plain kernels
+    bool scene_can_discard = false;
+    uint32_t alpha_launches = 0;                 // launches of the last TraceRays that ran an alpha instantiation (vhr_get_binary64_statistics out[2])
     int bvh_host_checks = 0;                        // "bvh_host_checks" 1: a device-built tree is fetched and the host's self-checks repeated on it
     uint64_t bvh_form_checks[4] = { 0, 0, 0, 0 };   // check_node_forms of the last build (vhr_get_bvh_form_checks)
     float bvh_centre[3] = { 0, 0, 0 };
@@ -681,6 +688,6 @@ int flush_recorded(vhr_context *ctx);          // issue the commands a compute p
 int launch_calibration_read(vhr_context *ctx, const Image &img, uint32_t bytes_per_lane, uint32_t *sink);
 int launch_ray_triangle_pairs(vhr_context *ctx, const float *pairs, uint32_t n, uint32_t *hit, float *tuv);
 // vhr_ray_query's device path: `rays` (count x vhr_ray) and `results` (vhr_ray_hit or uint8_t per ray) are device memory; enqueued on ctx->stream
-int launch_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, bool any_hit, void *results);
+int launch_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, bool any_hit, bool alpha_test, void *results);
 
 }  // namespace vhr

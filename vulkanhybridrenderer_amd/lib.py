@@ -715,6 +715,13 @@ class Context:
         self.check(self.L.vhr_get_binary64_statistics(self.handle, out), "binary64_statistics")
         return dict(pixels_again=int(out[0]), mirror_pixels_again=int(out[1]))
 
+    def alpha_launches(self):
+        """Launches of the last vhr_trace_rays that ran an "alpha_test_rays" instantiation (0 with the switch off, and on a scene none of
+        whose primitives can discard): 1 = the shadow / AO launch, 2 = that and the mirror ray's."""
+        out = (C.c_uint64 * 4)()
+        self.check(self.L.vhr_get_binary64_statistics(self.handle, out), "binary64_statistics")
+        return int(out[2])
+
     def wave_lifetimes(self, capacity=1 << 20):
         """Lifetimes (shader clock ticks) of the last ray-tracing launch's waves (what raygen_cost_order sorts by)."""
         import numpy as np
@@ -826,20 +833,21 @@ class Context:
             a = aligned
         return a
 
-    def ray_query(self, rays, any_hit=False):
+    def ray_query(self, rays, any_hit=False, alpha_test=False):
         """vhr_ray_query on host arrays: rays (n, 8) float32 or abi.ray_dtype.  Returns abi.ray_hit_dtype[n] (closest hit; a miss has
-        geometry_index = primitive_index = abi.RAY_MISS) or, with any_hit, bool[n] (occluded)."""
+        geometry_index = primitive_index = abi.RAY_MISS) or, with any_hit, bool[n] (occluded).  alpha_test: a candidate hit the G-buffer
+        pass would discard (alpha mask, alpha 0) does not exist for the ray."""
         r = self._rays_array(rays)
         n = len(r)
         out = np.zeros(n, np.uint8) if any_hit else np.zeros(n, abi.ray_hit_dtype)
-        flags = abi.RAY_QUERY_HOST_MEMORY | (abi.RAY_QUERY_TERMINATE_ON_FIRST_HIT if any_hit else 0)
+        flags = abi.RAY_QUERY_HOST_MEMORY | (abi.RAY_QUERY_TERMINATE_ON_FIRST_HIT if any_hit else 0) | (abi.RAY_QUERY_ALPHA_TEST if alpha_test else 0)
         self.check(self.L.vhr_ray_query(self.handle, r.ctypes.data if n else None, n, flags, out.ctypes.data if n else None), "ray_query")
         return out.astype(bool) if any_hit else out
 
-    def ray_query_device(self, rays_ptr, count, results_ptr, any_hit=False):
+    def ray_query_device(self, rays_ptr, count, results_ptr, any_hit=False, alpha_test=False):
         """vhr_ray_query on device memory (e.g. torch tensors' data_ptr()): `count` vhr_ray records at rays_ptr (16-byte aligned), results
         (vhr_ray_hit, or one uint8 per ray with any_hit) at results_ptr.  Enqueued on current_stream(); returns without synchronising."""
-        flags = abi.RAY_QUERY_TERMINATE_ON_FIRST_HIT if any_hit else 0
+        flags = (abi.RAY_QUERY_TERMINATE_ON_FIRST_HIT if any_hit else 0) | (abi.RAY_QUERY_ALPHA_TEST if alpha_test else 0)
         self.check(self.L.vhr_ray_query(self.handle, rays_ptr or None, int(count), flags, results_ptr or None), "ray_query_device")
 
     def ray_query_statistics(self):

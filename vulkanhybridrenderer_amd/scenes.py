@@ -386,6 +386,32 @@ def _procedural_texture(k, size=512):
     return img
 
 
+def alpha_masked(scene, percent, texture_size=64, n_textures=3):
+    """A copy of `scene` in which `percent` % of the primitives, evenly spread over the list, are alpha-masked cut-outs: each gets one of
+    `n_textures` procedural textures (appended to the scene's) whose alpha channel is the texture's own checker -- 255 / 0 in cells of an
+    eighth, a quarter and half of the texture -- as its base colour, alpha_mask 1 and alpha_cutoff 0.5.  What the G-buffer pass then
+    discards, rays traced with "alpha_test_rays" skip (tools/alpha_rays_rate.py; 0 % returns the scene's arrays unchanged)."""
+    prims = scene.primitives.copy()
+    n = len(prims)
+    count = int(round(n * percent / 100.0))
+    textures = list(scene.textures)
+    if count:
+        first = len(textures)
+        for t in range(n_textures):
+            img = _procedural_texture(t, texture_size)
+            cell = max(1, texture_size // (8 >> (t % 3)))
+            y, x = np.mgrid[0:texture_size, 0:texture_size]
+            img[..., 3] = np.where(((x // cell) + (y // cell)) & 1, 255, 0)
+            textures.append(dict(rgba8=img, format=abi.FORMAT_R8G8B8A8_SRGB, mag=abi.FILTER_LINEAR, min=abi.FILTER_LINEAR,
+                                 address_u=abi.ADDRESS_REPEAT, address_v=abi.ADDRESS_REPEAT))
+        chosen = np.unique((np.arange(count) * n) // count)
+        m = prims["material"]
+        m["base_color_texture"][chosen] = first + np.arange(len(chosen)) % n_textures
+        m["alpha_mask"][chosen] = 1
+        m["alpha_cutoff"][chosen] = 0.5
+    return Scene(f"{scene.name}_alpha{percent:g}", scene.vertices, scene.indices, prims, textures, scene.camera, scene.light)
+
+
 def bistro_proc(detail=1.0, n_primitives=3000, n_textures=64, texture_size=512):
     """Street canyon: ground, two facades and thousands of ledges, awnings, posts and props.
 
