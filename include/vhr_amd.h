@@ -655,7 +655,9 @@ int vhr_get_ray_statistics(vhr_context *ctx, uint64_t out[4]);
  *  or untextured with base_color[3] == 0; a texture's alpha bytes are not scanned): where none can, 1 launches exactly the kernels 0
  *  launches.  Where one can, "fuse_temporal" does not fuse (the epilogue has no alpha form: the SVGF pass runs its own dispatch) and the
  *  launches cost what profiles/alpha_rays_rate.jsonl reports.  vhr_get_option returns this key (not the bvh_* keys); a host-only context
- *  accepts it; it is no part of vhr_hybrid_save_state's blob, of vhr_hybrid_settings or of vhr_trace_params. */
+ *  accepts it; it is no part of vhr_hybrid_save_state's blob, of vhr_hybrid_settings or of vhr_trace_params.
+ *  "object_motion_vectors" is the third key of that kind (it changes the motion image; not in the table; vhr_get_option returns it; every
+ *  context accepts it; refused inside a pass): 0 (default) / 1, described at "Object motion vectors" below the refit calls. */
 int vhr_set_option(vhr_context *ctx, const char *key, int32_t value);
 int vhr_get_option(vhr_context *ctx, const char *key, int32_t *value);
 int32_t vhr_option_count(void);
@@ -688,6 +690,12 @@ int vhr_debug_wave_lifetimes(vhr_context *ctx, uint32_t *out, uint32_t capacity,
  * itself decided again in binary64; the reference leaves this to the driver's traceRayEXT, raygen.rgen:39,51,64) -- on explicit pairs, for parity tests:
  * pairs = count x 17 floats (o[3], d[3], v0[3], e1[3], e2[3], tmin, tmax), HOST memory; hit[count] = 0 / 1, tuv[count x 3] = (t, u, v) of a hit, else 0. */
 int vhr_debug_ray_triangle(vhr_context *ctx, const float *pairs, uint32_t count, uint32_t *hit, float *tuv);
+/* Diagnostics: the leaf records, nine floats per triangle (v0, e1, e2), to HOST memory in flat triangle order (primitive-major, as the
+ * arrays of vhr_update_geometry list them), so the result does not depend on the tree.  previous = 0: the current records; 1: the previous
+ * ones (VHR_ERROR_GRAPH with "object_motion_vectors" off).  *count = the scene's triangles, also when capacity_triangles is too small
+ * (VHR_ERROR_INVALID_ARGUMENT).  A "bvh_presplit" tree with split references has several records per triangle: VHR_ERROR_UNSUPPORTED.
+ * Waits for the context's streams; works on a host-only context. */
+int vhr_debug_triangle_records(vhr_context *ctx, int32_t previous, float *out, uint32_t capacity_triangles, uint32_t *count);
 /* What the last frame's rays cost, where: those lifetimes -- the any-hit launch's and the mirror ray's -- summed into a map of 8 x 8-pixel cells,
  * out[cy * cols + cx], cols >= ceil(width / 8), rows >= ceil(height / 8).  The cost map vhr_tile_plan_make_weighted cuts a grid by (cell = 8).
  * VHR_ERROR_NOT_FOUND when no queue kernel has left lifetimes ("raygen_cost_order" 0, or 1 on launches below 2 048 workgroups: set it to 2). */
@@ -769,8 +777,8 @@ int vhr_get_bvh_forms_fingerprint(vhr_context *ctx, uint64_t out[2]);
  *     split (vhr_get_bvh_presplit_level >= 0: VHR_ERROR_UNSUPPORTED, rebuild instead); a range outside the buffer, a NULL array with a
  *     non-zero count, an unknown flag, non-finite host data (VHR_ERROR_INVALID_ARGUMENT).  Argument checks come first, on every context.
  *   - Topology changes (triangles or primitives added or removed) need vhr_update_geometry.  Frame state is left alone: the SVGF history,
- *     cost orders, statistics.  Motion vectors stay what the G-buffer pass makes them (camera motion only), so moving geometry ghosts in the
- *     SVGF history exactly as it would in the reference.
+ *     cost orders, statistics.  By default motion vectors stay what the G-buffer pass makes them (camera motion only), so moving geometry ghosts
+ *     in the SVGF history; "object_motion_vectors" 1 (below) makes the stand-in G-buffer follow the geometry the refits moved.
  *   - A host-only context supports all of it on the host (the same arithmetic): it keeps the arrays and the tree of its last build.
  *   - vhr_resize keeps the refitted tree; vhr_update_geometry discards pending updates and everything a refit prepared. */
 #define VHR_UPDATE_DEVICE_MEMORY 2u   /* vhr_update_vertices: `vertices` is device memory (the counterpart of VHR_RAY_QUERY_HOST_MEMORY's default) */
@@ -822,6 +830,27 @@ int vhr_refit_geometry_partial(vhr_context *ctx, uint32_t flags);
  * refit since the build, 2 = whole tree: over the threshold), out[5] = 1 if the scene centre's bits changed and all forms were redone,
  * out[6] = vertex ranges used, out[7] = primitive ranges used. */
 int vhr_get_partial_refit_statistics(vhr_context *ctx, uint64_t out[8]);
+/* ---- Object motion vectors: the refits keep last frame's triangle records ("object_motion_vectors", vhr_set_option; default 0) ----
+ * A leaf record (v0, e1, e2 in world space, the primitive's transform baked in) keeps its slot through a refit, and a visible point is affine
+ * in its hit's barycentrics, P = v0 + u e1 + v e2.  With the option on the library keeps, per record, the record the slot held before the
+ * last refit; the stand-in G-buffer (vhr_standin_gbuffer) reprojects a hit through P + d, d = (pv0 - v0) + u (pe1 - e1) + v (pe2 - e2), in
+ * place of P, so motion.xy follows vertices and transforms alike.  Nothing else of the G-buffer changes, a record that did not move gives d
+ * = 0 exactly and its texel's bits stay, and while no record differs from its previous one the plain kernel is launched.
+ *   The contract.  Let S0 be the records after the build, or after the option was switched on.  Let Si be the records after the i-th call of
+ *   vhr_refit_geometry / vhr_refit_geometry_partial that SUCCEEDS with the option on; a call with nothing pending counts and leaves Si =
+ *   Si-1 (it launches one settle pass if the call before it left differing records, else nothing).  After that call the previous record of
+ *   every slot k is Si-1(k), bit for bit.  A refit that fails (non-finite coordinates) does not count: once a later one succeeds, previous
+ *   is still the state before the failed attempt.  Hence ONE refit call per frame -- also in a frame without updates -- makes previous "last
+ *   frame"; two refits between two frames make the motion relative to the state between them.
+ * Turning the option on waits for the context's streams, allocates the arrays (52 bytes per record) and sets previous = current; turning it
+ * off frees them.  vhr_update_geometry sets previous = current for the new tree; vhr_resize keeps everything.  The arrays take no part in the
+ * fingerprints or the form checks, and vhr_hybrid_save_state's blob does not carry them: the first frame after a load has no object motion.
+ * The rayquery, forward raster and raytraced paths write no motion image and ignore the option; an integrator whose G-buffer comes from its own
+ * raster pass writes object motion itself.  Costs: profiles/object_motion_rate.jsonl (tools/object_motion_rate.py).
+ * out[0] = 1 if the option is on and the arrays exist, out[1] = records whose previous differs from current (any of the nine words) after the
+ * last successful refit (0 after a build, after switching on and after a settle), out[2] = G-buffer launches since vhr_create that ran the
+ * motion instantiation, out[3] = 0. */
+int vhr_get_object_motion_statistics(vhr_context *ctx, uint64_t out[4]);
 /* The surface-area cost of the tree -- the sum over the inner nodes of child box area x (1 for an inner child, the triangle count for a
  * leaf), over the root's area, on the padded boxes the walkers test: out[0] = as built, out[1] = as it is now.  The number to watch when
  * deciding to rebuild.  One reduction, computed when asked (waits for the context's streams). */

@@ -653,28 +653,50 @@ uint32_t refit_record(BvhTri &tri, const vhr_vertex *vertices, const uint32_t vi
 void record_corners(const BvhTri &tri, const uint32_t *indices, const vhr_primitive &pr, uint32_t vi[3]) {
     for (int c = 0; c < 3; ++c) vi[c] = pr.vertex_offset + indices[pr.index_offset + 3 * tri.tri + c];
 }
+// "object_motion_vectors", the bookkeeping of k0_refit_records_kernel<true> / k0_refit_mark_kernel<true> (vhr_context::d_prev_saved has the rules):
+// before record i is rewritten by refit `epoch` ...
+void motion_save(HostBvh &bvh, size_t i, uint32_t epoch) {
+    if (bvh.prev_saved[i] == epoch) return;              // saved by a failed attempt of this refit: the record holds that attempt's values
+    bvh.prev_tris[i] = bvh.tris[i];
+    bvh.prev_saved[i] = epoch;
+}
+// ... a record the refit leaves as it is ...
+void motion_settle(HostBvh &bvh, size_t i, uint32_t epoch) {
+    if (bvh.prev_saved[i] == epoch - 1u) bvh.prev_tris[i] = bvh.tris[i];
+}
+// ... and whether the two differ in any of the nine words afterwards
+uint64_t motion_differs(const HostBvh &bvh, size_t i) {
+    const BvhTri &p = bvh.prev_tris[i], &c = bvh.tris[i];
+    return (std::memcmp(p.v0, c.v0, sizeof(c.v0)) || std::memcmp(p.e1, c.e1, sizeof(c.e1)) || std::memcmp(p.e2, c.e2, sizeof(c.e2))) ? 1u : 0u;
+}
 }  // namespace
 
 void refit_check_pass(const HostBvh &bvh, uint64_t counts[3], unsigned hw);
 
-bool refit_bvh(const vhr_vertex *vertices, const uint32_t *indices, const vhr_primitive *primitives, uint32_t primitive_count, HostBvh &bvh, uint64_t counts[3], int threads) {
+bool refit_bvh(const vhr_vertex *vertices, const uint32_t *indices, const vhr_primitive *primitives, uint32_t primitive_count, HostBvh &bvh, uint64_t counts[3], int threads,
+               uint32_t motion_epoch) {
     counts[0] = counts[1] = counts[2] = 0;
     const size_t n_nodes = bvh.nodes.size(), n_tris = bvh.tris.size();
     if (!n_nodes || !n_tris || !refit_can_walk(bvh, primitives, primitive_count, true)) return false;
+    const bool motion = motion_epoch != 0 && bvh.prev_tris.size() == n_tris && bvh.prev_saved.size() == n_tris;
     const unsigned hw = host_threads(threads);
     // 1. the records, each in its slot
-    std::atomic<uint64_t> non_finite{ 0 };
+    std::atomic<uint64_t> non_finite{ 0 }, differing{ 0 };
     parallel_for(n_tris, hw, [&](size_t i0, size_t i1) {
-        uint64_t bad = 0;
+        uint64_t bad = 0, differs = 0;
         for (size_t i = i0; i < i1; ++i) {
             const vhr_primitive &pr = primitives[bvh.tris[i].prim];
             uint32_t vi[3];
             record_corners(bvh.tris[i], indices, pr, vi);
+            if (motion) motion_save(bvh, i, motion_epoch);
             bad += refit_record(bvh.tris[i], vertices, vi, pr);
+            if (motion) differs += motion_differs(bvh, i);
         }
         non_finite += bad;
+        differing += differs;
     });
     counts[2] = non_finite;
+    bvh.prev_differing = differing;
     // 2. + 3. the boxes bottom-up (children have larger indices than their parents), padded into the parents' slots; and what a partial refit
     // starts from: the unpadded boxes, every node's parent, every record's leaf node
     bvh.self_box.resize(n_nodes * 6);
@@ -713,12 +735,14 @@ void refit_check_pass(const HostBvh &bvh, uint64_t counts[3], unsigned hw) {
 // the partial refit's host twin (k0_refit_mark_kernel, the level kernels with their one-bit test, the forms restricted to the dirty nodes).  The
 // two check passes stay whole-tree here: the host is not the hot path, and their totals are what a dirty pass has to reproduce anyway.
 bool refit_bvh_partial(const vhr_vertex *vertices, const uint32_t *indices, const vhr_primitive *primitives, uint32_t primitive_count, HostBvh &bvh,
-                       const RefitDirty &dirty, uint64_t counts[3], uint64_t out[4], int threads) {
+                       const RefitDirty &dirty, uint64_t counts[3], uint64_t out[4], int threads, uint32_t motion_epoch) {
     counts[0] = counts[1] = counts[2] = 0;
     out[0] = out[1] = out[2] = out[3] = 0;
     const size_t n_nodes = bvh.nodes.size(), n_tris = bvh.tris.size();
     if (!n_nodes || !n_tris || bvh.self_box.size() != n_nodes * 6 || bvh.parent.size() != n_nodes || bvh.owner.size() != n_tris) return false;
     if (!refit_can_walk(bvh, primitives, primitive_count, false)) return false;
+    const bool motion = motion_epoch != 0 && bvh.prev_tris.size() == n_tris && bvh.prev_saved.size() == n_tris;
+    bvh.prev_differing = 0;
     const unsigned hw = host_threads(threads);
     // 1. mark, and the dirty records
     std::vector<uint8_t> mark(n_nodes, 0);
@@ -727,8 +751,14 @@ bool refit_bvh_partial(const vhr_vertex *vertices, const uint32_t *indices, cons
         const vhr_primitive &pr = primitives[tri.prim];
         uint32_t vi[3];
         record_corners(tri, indices, pr, vi);
-        if (!(dirty.primitives.holds(tri.prim) || dirty.vertices.holds(vi[0]) || dirty.vertices.holds(vi[1]) || dirty.vertices.holds(vi[2]))) continue;
+        if (!(dirty.primitives.holds(tri.prim) || dirty.vertices.holds(vi[0]) || dirty.vertices.holds(vi[1]) || dirty.vertices.holds(vi[2]))) {
+            // (a clean record saved by a failed attempt of this refit -- a whole-tree one -- keeps its previous; it is counted like a rewritten one)
+            if (motion) { motion_settle(bvh, i, motion_epoch); if (bvh.prev_saved[i] == motion_epoch) bvh.prev_differing += motion_differs(bvh, i); }
+            continue;
+        }
+        if (motion) motion_save(bvh, i, motion_epoch);
         counts[2] += refit_record(tri, vertices, vi, pr);
+        if (motion) bvh.prev_differing += motion_differs(bvh, i);
         ++out[0];
         for (uint32_t node = bvh.owner[i]; node != 0xffffffffu && !mark[node]; node = bvh.parent[node]) { mark[node] = 1; ++out[1]; }
     }

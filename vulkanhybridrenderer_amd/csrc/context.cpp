@@ -257,8 +257,38 @@ int vhr_create(const vhr_create_info *info, vhr_context **out) {
     return VHR_OK;
 }
 
+// "object_motion_vectors": the previous records and their bookkeeping
+static void free_motion(vhr_context *ctx) {
+    if (!ctx->host_only) { hipFree(ctx->d_prev_tris); hipFree(ctx->d_prev_saved); }
+    ctx->d_prev_tris = nullptr; ctx->d_prev_saved = nullptr;
+    ctx->h_bvh.prev_tris.clear(); ctx->h_bvh.prev_saved.clear();
+    ctx->h_bvh.prev_differing = 0;
+    ctx->motion_epoch = 1;
+    ctx->motion_differing = ctx->motion_refit_differing = 0;
+}
+// previous = current for the tree the context holds (none yet: nothing to keep); the caller has waited for the context's streams
+static int reset_motion(vhr_context *ctx) {
+    free_motion(ctx);
+    if (!ctx->object_motion_vectors || !ctx->tri_count) return VHR_OK;
+    if (ctx->host_only) {
+        ctx->h_bvh.prev_tris = ctx->h_bvh.tris;
+        ctx->h_bvh.prev_saved.assign(ctx->h_bvh.tris.size(), 0u);
+        return VHR_OK;
+    }
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&ctx->d_prev_tris), sizeof(BvhTri) * ctx->tri_count);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&ctx->d_prev_saved), sizeof(uint32_t) * ctx->tri_count);
+    if (e == hipSuccess) e = hipMemcpy(ctx->d_prev_tris, ctx->d_tris, sizeof(BvhTri) * ctx->tri_count, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipMemset(ctx->d_prev_saved, 0, sizeof(uint32_t) * ctx->tri_count);
+    if (e != hipSuccess) {
+        free_motion(ctx);
+        return ctx->fail(VHR_ERROR_DEVICE, std::string("object_motion_vectors: allocating the previous records: ") + hipGetErrorString(e));
+    }
+    return VHR_OK;
+}
+
 static void free_scene(vhr_context *ctx) {
     vhr::free_refit_plan(ctx);
+    free_motion(ctx);
     hipFree(ctx->d_vertices); hipFree(ctx->d_indices); hipFree(ctx->d_primitives); hipFree(ctx->d_normal_matrices);
     hipFree(ctx->d_nodes); hipFree(ctx->d_nodes16); hipFree(ctx->d_nodes_ch); hipFree(ctx->d_nodes48); hipFree(ctx->d_tris);
     ctx->d_vertices = nullptr; ctx->d_indices = nullptr; ctx->d_primitives = nullptr; ctx->d_normal_matrices = nullptr;
@@ -482,7 +512,7 @@ int vhr_update_geometry(vhr_context *ctx, const vhr_vertex *vertices, uint32_t v
         ctx->vertex_count = vertex_count;
         ctx->index_count = index_count;
         ctx->primitive_count = primitive_count;
-        return VHR_OK;
+        return reset_motion(ctx);
     }
     if (!device_built) {
         const auto t_upload0 = std::chrono::steady_clock::now();
@@ -501,7 +531,7 @@ int vhr_update_geometry(vhr_context *ctx, const vhr_vertex *vertices, uint32_t v
     ctx->index_count = index_count;
     ctx->primitive_count = primitive_count;
     ctx->geometry_upload_ms = upload_ms;
-    return VHR_OK;
+    return reset_motion(ctx);                 // "object_motion_vectors": previous = current for the new tree
 }
 
 int vhr_get_bvh_builder(vhr_context *ctx, int32_t *used) {
@@ -618,7 +648,22 @@ static double dirty_share(const vhr_context *ctx) {
 static int refit_geometry(vhr_context *ctx, const char *who, bool partial, bool force) {
     { const int rc = refit_state_checks(ctx, who); if (rc != VHR_OK) return rc; }
     if (ctx->recording || ctx->cur_pass) return ctx->fail(VHR_ERROR_GRAPH, std::string(who) + ": called from inside a pass");
-    if (!ctx->refit_pending) return VHR_OK;              // nothing changed: nothing is launched
+    if (!ctx->refit_pending) {                           // nothing changed: nothing is launched ...
+        if (!ctx->motion_valid() || ctx->motion_differing == 0) return VHR_OK;
+        // ... but "object_motion_vectors" counts the call as a refit: what the last one moved has stopped (one settle pass)
+        if (ctx->host_only) {
+            HostBvh &b = ctx->h_bvh;
+            for (size_t i = 0; i < b.tris.size(); ++i) if (b.prev_saved[i] == ctx->motion_epoch) b.prev_tris[i] = b.tris[i];
+        } else {
+            HIP_TRY(ctx, hipSetDevice(ctx->device));
+            { const int src_ = ctx->sync_streams(); if (src_ != VHR_OK) return src_; }
+            const int rc = device_motion_settle(ctx);
+            if (rc != VHR_OK) return rc;
+        }
+        ++ctx->motion_epoch;
+        ctx->motion_differing = 0;
+        return VHR_OK;
+    }
     const auto t0 = std::chrono::steady_clock::now();
     uint64_t ran_as = kRanDirty;
     const bool asked_partial = partial;
@@ -628,9 +673,11 @@ static int refit_geometry(vhr_context *ctx, const char *who, bool partial, bool 
     if (ctx->host_only) {
         if (!ctx->sah_cost_built_valid) { ctx->sah_cost_built = bvh_sah_cost(ctx->h_bvh); ctx->sah_cost_built_valid = true; }
         uint64_t counts[3], dirty_counts[4] = { ctx->h_bvh.tris.size(), ctx->h_bvh.nodes.size(), ctx->h_bvh.nodes.size(), 0 };
+        const uint32_t motion_epoch = ctx->motion_valid() ? ctx->motion_epoch + 1u : 0u;
         const bool walked = partial ? refit_bvh_partial(ctx->h_vertices.data(), ctx->h_indices.data(), ctx->h_primitives.data(), ctx->primitive_count, ctx->h_bvh,
-                                                        ctx->refit_dirty, counts, dirty_counts, ctx->bvh_build_threads)
-                                    : refit_bvh(ctx->h_vertices.data(), ctx->h_indices.data(), ctx->h_primitives.data(), ctx->primitive_count, ctx->h_bvh, counts, ctx->bvh_build_threads);
+                                                        ctx->refit_dirty, counts, dirty_counts, ctx->bvh_build_threads, motion_epoch)
+                                    : refit_bvh(ctx->h_vertices.data(), ctx->h_indices.data(), ctx->h_primitives.data(), ctx->primitive_count, ctx->h_bvh, counts, ctx->bvh_build_threads,
+                                                motion_epoch);
         if (!walked)
             return ctx->fail(VHR_ERROR_GRAPH, std::string(who) + (partial ? ": the tree or its per-node boxes are not what a dirty pass can walk (a record outside its primitive's triangles)"
                                                                           : ": the tree's nodes are not numbered parents before children"));
@@ -646,6 +693,7 @@ static int refit_geometry(vhr_context *ctx, const char *who, bool partial, bool 
         ctx->refit_stats[kRefitChildrenOutside] = counts[1];
         ctx->refit_stats[kRefitNonFinite] = counts[2];
         ctx->refit_stats[kRefitHalfNodes] = ctx->nodes16_valid ? 1u : 0u;
+        ctx->motion_refit_differing = ctx->h_bvh.prev_differing;
         for (int i = 1; i < 4; ++i) ctx->refit_times_ms[i] = 0.0;
     } else {
         HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -670,6 +718,7 @@ static int refit_geometry(vhr_context *ctx, const char *who, bool partial, bool 
                          " non-finite coordinates in the triangle records: the tree's arrays are not valid; update the vertices / transforms and refit again, or rebuild");
     ++ctx->refit_stats[kRefitCount];
     if (asked_partial && ran_as == kRanDirty) ++ctx->partial_stats[kPartialCount];
+    if (ctx->motion_valid()) { ++ctx->motion_epoch; ctx->motion_differing = ctx->motion_refit_differing; }      // (a failed attempt leaves both: its retry has the same number)
     ctx->refit_pending = false;
     ctx->refit_dirty = RefitDirty{};
     return VHR_OK;
@@ -882,6 +931,20 @@ int vhr_set_option(vhr_context *ctx, const char *key, int32_t value) {
         ctx->alpha_test_rays = value;
         return VHR_OK;
     }
+    if (!std::strcmp(key, "object_motion_vectors")) {        // the refits keep last frame's triangle records; the stand-in G-buffer reprojects through them
+        if (value < 0 || value > 1)
+            return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "object_motion_vectors must be 0 (motion vectors follow the camera only) or 1 (and the geometry the refits moved)");
+        if (ctx->recording || ctx->cur_pass) return ctx->fail(VHR_ERROR_GRAPH, "object_motion_vectors: set from inside a pass");
+        if (value == ctx->object_motion_vectors) return VHR_OK;
+        if (!ctx->host_only) {                               // frames in flight read the arrays that are about to be made or freed
+            HIP_TRY(ctx, hipSetDevice(ctx->device));
+            const int src_ = ctx->sync_streams(); if (src_ != VHR_OK) return src_;
+        }
+        ctx->object_motion_vectors = value;
+        const int rc = reset_motion(ctx);
+        if (rc != VHR_OK) ctx->object_motion_vectors = 0;
+        return rc;
+    }
     for (int i = 0; i < vhr::kOptCount; ++i) {
         const vhr::OptionInfo &o = vhr::kOptionInfo[i];
         if (std::strcmp(key, o.name)) continue;
@@ -908,6 +971,7 @@ int vhr_option_info(int32_t index, const char **name, int32_t *default_value, in
 int vhr_get_option(vhr_context *ctx, const char *key, int32_t *value) {
     if (!ctx || !key || !value) return VHR_ERROR_INVALID_ARGUMENT;
     if (!std::strcmp(key, "alpha_test_rays")) { *value = ctx->alpha_test_rays; return VHR_OK; }
+    if (!std::strcmp(key, "object_motion_vectors")) { *value = ctx->object_motion_vectors; return VHR_OK; }
     for (int i = 0; i < vhr::kOptCount; ++i)
         if (!std::strcmp(key, vhr::kOptionInfo[i].name)) { *value = ctx->options[i]; return VHR_OK; }
     return ctx->fail(VHR_ERROR_NOT_FOUND, std::string("unknown option '") + key + "'");
@@ -1043,6 +1107,45 @@ int vhr_debug_ray_triangle(vhr_context *ctx, const float *pairs, uint32_t count,
     if (!ctx || (count && (!pairs || !hit || !tuv))) return ctx ? ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_debug_ray_triangle: null argument") : VHR_ERROR_INVALID_ARGUMENT;
     if (ctx->host_only) return ctx->fail(VHR_ERROR_DEVICE, "vhr_debug_ray_triangle: host-only context");
     return launch_ray_triangle_pairs(ctx, pairs, count, hit, tuv);
+}
+
+int vhr_debug_triangle_records(vhr_context *ctx, int32_t previous, float *out, uint32_t capacity_triangles, uint32_t *count) {
+    if (!ctx || !count || (previous != 0 && previous != 1)) return ctx ? ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_debug_triangle_records: null count, or previous is neither 0 nor 1") : VHR_ERROR_INVALID_ARGUMENT;
+    *count = 0;
+    if (ctx->host_only ? ctx->h_bvh.nodes.empty() : (ctx->d_nodes == nullptr || ctx->node_count == 0))
+        return ctx->fail(VHR_ERROR_GRAPH, "vhr_debug_triangle_records: no geometry yet (vhr_update_geometry first)");
+    if (ctx->bvh_presplit_level >= 0)
+        return ctx->fail(VHR_ERROR_UNSUPPORTED, "vhr_debug_triangle_records: the tree was built with \"bvh_presplit\" and has several records per triangle: there is no record per flat triangle to report");
+    if (previous && !ctx->motion_valid())
+        return ctx->fail(VHR_ERROR_GRAPH, "vhr_debug_triangle_records: no previous records (vhr_set_option \"object_motion_vectors\" 1 first)");
+    *count = ctx->tri_count;
+    if (capacity_triangles < ctx->tri_count || !out)
+        return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_debug_triangle_records: room for " + std::to_string(capacity_triangles) + " triangles, the scene has " + std::to_string(ctx->tri_count));
+    std::vector<BvhTri> fetched;
+    const BvhTri *records = previous ? ctx->h_bvh.prev_tris.data() : ctx->h_bvh.tris.data();
+    if (!ctx->host_only) {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        { const int src_ = ctx->sync_streams(); if (src_ != VHR_OK) return src_; }
+        fetched.resize(ctx->tri_count);
+        HIP_TRY(ctx, hipMemcpy(fetched.data(), previous ? ctx->d_prev_tris : ctx->d_tris, sizeof(BvhTri) * ctx->tri_count, hipMemcpyDeviceToHost));
+        records = fetched.data();
+    }
+    for (uint32_t k = 0; k < ctx->tri_count; ++k) {          // flat triangle order: independent of the tree
+        const BvhTri &t = records[k];
+        if (t.flat >= ctx->tri_count) return ctx->fail(VHR_ERROR_GRAPH, "vhr_debug_triangle_records: a record's flat index lies outside the scene's triangles");
+        float *o = out + size_t(t.flat) * 9;
+        for (int c = 0; c < 3; ++c) { o[c] = t.v0[c]; o[3 + c] = t.e1[c]; o[6 + c] = t.e2[c]; }
+    }
+    return VHR_OK;
+}
+
+int vhr_get_object_motion_statistics(vhr_context *ctx, uint64_t out[4]) {
+    if (!ctx || !out) return VHR_ERROR_INVALID_ARGUMENT;
+    out[0] = ctx->motion_valid() ? 1u : 0u;
+    out[1] = ctx->motion_valid() ? ctx->motion_differing : 0u;
+    out[2] = ctx->motion_launches;
+    out[3] = 0;
+    return VHR_OK;
 }
 
 int vhr_get_bvh_statistics(vhr_context *ctx, uint64_t out[5]) {

@@ -737,24 +737,50 @@ __global__ __launch_bounds__(256) void k0_iota_kernel(uint32_t *__restrict__ ord
 
 // ---- refit (vhr_refit_geometry): the topology stays, the records and the boxes follow the vertices and the transforms ----
 struct RefitFrame { float r[9]; uint32_t on; };
-struct RefitCounters { unsigned long long non_finite, records_outside, children_outside, pad; };
+struct RefitCounters { unsigned long long non_finite, records_outside, children_outside, differing; };      // differing: "object_motion_vectors" only
 // the leaf pass: record k re-derived in its slot from (prim, tri) with bvh_math::world_record; three 16-byte loads' worth of gather per corner,
 // three 16-byte stores
 // one record from its primitive's transform and its three vertices (absolute indices `vi`): the one place a refit of either kind derives a
-// record; returns the non-finite coordinates met
-__device__ __forceinline__ uint32_t refit_write_record(float4 *slot, const float4 &q2, const vhr_primitive &pr, const vhr_vertex *__restrict__ vertices, const uint32_t vi[3]) {
+// record; `now`: what it stored; returns the non-finite coordinates met
+__device__ __forceinline__ uint32_t refit_write_record(float4 *slot, const float4 &q2, const vhr_primitive &pr, const vhr_vertex *__restrict__ vertices, const uint32_t vi[3],
+                                                       float4 now[3]) {
     float v0[3], e1[3], e2[3];
     const uint32_t bad = bvh_math::world_record(pr.transform, vertices[vi[0]].pos, vertices[vi[1]].pos, vertices[vi[2]].pos, v0, e1, e2);
-    slot[0] = float4{ v0[0], v0[1], v0[2], e1[0] };
-    slot[1] = float4{ e1[1], e1[2], e2[0], e2[1] };
-    slot[2] = float4{ e2[2], q2.y, q2.z, q2.w };
+    now[0] = float4{ v0[0], v0[1], v0[2], e1[0] };
+    now[1] = float4{ e1[1], e1[2], e2[0], e2[1] };
+    now[2] = float4{ e2[2], q2.y, q2.z, q2.w };
+    slot[0] = now[0]; slot[1] = now[1]; slot[2] = now[2];
     return bad;
 }
+// "object_motion_vectors" (the MOTION instantiations; vhr_context::d_prev_saved has the rules): per record its state before the last successful
+// refit, the whole 48 bytes in the same slot, and the number of the refit that last saved it.  `epoch`: the number of the refit that is running.
+struct RefitMotion { BvhTri *prev; uint32_t *saved; uint32_t epoch; };
+__device__ __forceinline__ uint32_t motion_differs(const float4 a[3], const float4 b[3]) {      // in any of the nine words, as bits
+    uint32_t x = (__float_as_uint(a[0].x) ^ __float_as_uint(b[0].x)) | (__float_as_uint(a[0].y) ^ __float_as_uint(b[0].y)) | (__float_as_uint(a[0].z) ^ __float_as_uint(b[0].z)) |
+                 (__float_as_uint(a[0].w) ^ __float_as_uint(b[0].w));
+    x |= (__float_as_uint(a[1].x) ^ __float_as_uint(b[1].x)) | (__float_as_uint(a[1].y) ^ __float_as_uint(b[1].y)) | (__float_as_uint(a[1].z) ^ __float_as_uint(b[1].z)) |
+         (__float_as_uint(a[1].w) ^ __float_as_uint(b[1].w));
+    x |= __float_as_uint(a[2].x) ^ __float_as_uint(b[2].x);
+    return x != 0u ? 1u : 0u;
+}
+// record k is about to be rewritten (`slot` still holds its old words, q2 the third of them): its previous state into `was`, saved first unless a
+// failed attempt of this refit has saved it already (the slot then holds that attempt's values, the previous array the state to keep)
+__device__ __forceinline__ void motion_save(const RefitMotion &m, uint32_t k, const float4 *slot, const float4 &q2, float4 was[3]) {
+    float4 *pslot = reinterpret_cast<float4 *>(m.prev + k);
+    if (m.saved[k] != m.epoch) {
+        was[0] = slot[0]; was[1] = slot[1]; was[2] = q2;
+        pslot[0] = was[0]; pslot[1] = was[1]; pslot[2] = was[2];
+        m.saved[k] = m.epoch;
+    } else {
+        was[0] = pslot[0]; was[1] = pslot[1]; was[2] = pslot[2];
+    }
+}
+template <bool MOTION>
 __global__ __launch_bounds__(256) void k0_refit_records_kernel(const vhr_vertex *__restrict__ vertices, const uint32_t *__restrict__ indices,
                                                                const vhr_primitive *__restrict__ primitives, uint32_t primitive_count, uint32_t n,
-                                                               BvhTri *__restrict__ tris, RefitCounters *__restrict__ counters) {
+                                                               BvhTri *__restrict__ tris, RefitCounters *__restrict__ counters, const RefitMotion motion) {
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
-    uint32_t bad = 0;
+    uint32_t bad = 0, differs = 0;
     if (k < n) {
         float4 *slot = reinterpret_cast<float4 *>(tris + k);
         const float4 q2 = slot[2];                                   // (e2.z, prim, tri, flat)
@@ -764,27 +790,39 @@ __global__ __launch_bounds__(256) void k0_refit_records_kernel(const vhr_vertex 
             uint32_t vi[3];
 #pragma unroll
             for (int c = 0; c < 3; ++c) vi[c] = pr.vertex_offset + indices[pr.index_offset + 3u * local + uint32_t(c)];
-            bad = refit_write_record(slot, q2, pr, vertices, vi);
+            float4 was[3], now[3];
+            if constexpr (MOTION) motion_save(motion, k, slot, q2, was);
+            bad = refit_write_record(slot, q2, pr, vertices, vi, now);
+            if constexpr (MOTION) differs = motion_differs(was, now);
         } else {
             bad = 1u;                                                // (not a record of this scene: cannot happen, never dereferenced)
         }
     }
     for (int off = 32; off > 0; off >>= 1) bad += uint32_t(__shfl_xor(int(bad), off));
     if ((threadIdx.x & 63u) == 0u && bad) atomicAdd(&counters->non_finite, (unsigned long long)bad);
+    if constexpr (MOTION) {
+        for (int off = 32; off > 0; off >>= 1) differs += uint32_t(__shfl_xor(int(differs), off));
+        if ((threadIdx.x & 63u) == 0u && differs) atomicAdd(&counters->differing, (unsigned long long)differs);
+    }
 }
 // The partial refit's mark and leaf pass, one thread per record: a record with its primitive in a primitive range or one of its three absolute
 // vertex indices in a vertex range is dirty -- re-derived as above, and its leaf's node and that node's ancestors get their dirty bit (one
 // vector atomicOr per step; the climb ends at the first bit somebody else has set, so every node is counted once).  A clean record costs its
-// (prim, tri) words and three index reads, and no store.
+// (prim, tri) words and three index reads, and no store.  MOTION: a clean record also costs its `saved` word; one the refit before this one
+// saved has stopped and is settled (previous = current), one a failed whole-tree attempt of this refit saved keeps its previous and is compared.
+// A pass that then FAILS (non-finite coordinates) has settled those records all the same: until the retry succeeds the context's differing count
+// (vhr_get_object_motion_statistics out[1]) is the last successful refit's and no longer describes the arrays -- which nothing may trace meanwhile.
+// The contract holds after the retry: the dirty set only grows, and a settled record it reaches is saved again from its unchanged slot.
 constexpr uint32_t kNoParent = 0xffffffffu;
 struct PartialCounters { unsigned long long dirty_records, dirty_nodes; };
+template <bool MOTION>
 __global__ __launch_bounds__(256) void k0_refit_mark_kernel(const vhr_vertex *__restrict__ vertices, const uint32_t *__restrict__ indices,
                                                             const vhr_primitive *__restrict__ primitives, uint32_t primitive_count, uint32_t n,
                                                             BvhTri *__restrict__ tris, const uint32_t *__restrict__ owner, const uint32_t *__restrict__ parent,
                                                             uint32_t *__restrict__ dirty, RefitDirty ranges, RefitCounters *__restrict__ counters,
-                                                            PartialCounters *__restrict__ partial) {
+                                                            PartialCounters *__restrict__ partial, const RefitMotion motion) {
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
-    uint32_t bad = 0, records = 0, nodes = 0;
+    uint32_t bad = 0, records = 0, nodes = 0, differs = 0;
     if (k < n) {
         float4 *slot = reinterpret_cast<float4 *>(tris + k);
         const float4 q2 = slot[2];                                   // (e2.z, prim, tri, flat)
@@ -795,12 +833,24 @@ __global__ __launch_bounds__(256) void k0_refit_mark_kernel(const vhr_vertex *__
 #pragma unroll
             for (int c = 0; c < 3; ++c) vi[c] = pr.vertex_offset + indices[pr.index_offset + 3u * local + uint32_t(c)];
             if (ranges.primitives.holds(p) || ranges.vertices.holds(vi[0]) || ranges.vertices.holds(vi[1]) || ranges.vertices.holds(vi[2])) {
-                bad = refit_write_record(slot, q2, pr, vertices, vi);
+                float4 was[3], now[3];
+                if constexpr (MOTION) motion_save(motion, k, slot, q2, was);
+                bad = refit_write_record(slot, q2, pr, vertices, vi, now);
+                if constexpr (MOTION) differs = motion_differs(was, now);
                 records = 1u;
                 for (uint32_t node = owner[k]; node != kNoParent; node = parent[node]) {
                     const uint32_t bit = 1u << (node & 31u);
                     if (atomicOr(&dirty[node >> 5], bit) & bit) break;
                     ++nodes;
+                }
+            } else if constexpr (MOTION) {
+                const uint32_t saved = motion.saved[k];
+                float4 *pslot = reinterpret_cast<float4 *>(motion.prev + k);
+                if (saved == motion.epoch - 1u) {
+                    pslot[0] = slot[0]; pslot[1] = slot[1]; pslot[2] = q2;
+                } else if (saved == motion.epoch) {
+                    const float4 was[3] = { pslot[0], pslot[1], pslot[2] }, now[3] = { slot[0], slot[1], q2 };
+                    differs = motion_differs(was, now);
                 }
             }
         } else {
@@ -815,6 +865,18 @@ __global__ __launch_bounds__(256) void k0_refit_mark_kernel(const vhr_vertex *__
         if (records) atomicAdd(&partial->dirty_records, (unsigned long long)records);
         if (nodes) atomicAdd(&partial->dirty_nodes, (unsigned long long)nodes);
     }
+    if constexpr (MOTION) {
+        for (int off = 32; off > 0; off >>= 1) differs += uint32_t(__shfl_xor(int(differs), off));
+        if ((threadIdx.x & 63u) == 0u && differs) atomicAdd(&counters->differing, (unsigned long long)differs);
+    }
+}
+// the settle pass of a refit call with nothing pending (number `epoch`): what refit epoch - 1 saved has stopped
+__global__ __launch_bounds__(256) void k0_motion_settle_kernel(const BvhTri *__restrict__ tris, uint32_t n, const RefitMotion motion) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k >= n || motion.saved[k] != motion.epoch - 1u) return;
+    const float4 *slot = reinterpret_cast<const float4 *>(tris + k);
+    float4 *pslot = reinterpret_cast<float4 *>(motion.prev + k);
+    pslot[0] = slot[0]; pslot[1] = slot[1]; pslot[2] = slot[2];
 }
 // one node (bvh_math::refit_slots): its two slots from its children's unpadded boxes, its own unpadded box for its parent
 __device__ __forceinline__ void refit_node(uint32_t k, BvhNode *nodes, const BvhTri *tris, Box6 *self_box, const RefitFrame &f, bool single) {
@@ -1340,6 +1402,7 @@ static void refit_publish(vhr_context *ctx, RefitPlan *p, const RefitReadback &g
     ctx->refit_stats[kRefitRecordsOutside] = p->totals[4];
     ctx->refit_stats[kRefitChildrenOutside] = p->totals[5];
     ctx->refit_stats[kRefitNonFinite] = got.c.non_finite;
+    ctx->motion_refit_differing = got.c.differing;
     ctx->refit_stats[kRefitHalfNodes] = ctx->nodes16_valid ? 1u : 0u;
     ctx->refit_stats[7] = p->launches;
     for (int i = 1; i < 4; ++i) ctx->refit_times_ms[i] = 0.0;
@@ -1350,6 +1413,11 @@ static void refit_publish(vhr_context *ctx, RefitPlan *p, const RefitReadback &g
             if (hipEventElapsedTime(&ms, p->ev[pairs[i][0]], p->ev[pairs[i][1]]) == hipSuccess) ctx->refit_times_ms[i + 1] = ms;
         }
     }
+}
+// "object_motion_vectors": what the leaf pass of the refit that is about to run needs (prev == nullptr: the option is off, the plain kernels run)
+static RefitMotion refit_motion(const vhr_context *ctx) {
+    const bool on = ctx->object_motion_vectors && ctx->d_prev_tris && ctx->d_prev_saved;
+    return RefitMotion{ on ? ctx->d_prev_tris : nullptr, on ? ctx->d_prev_saved : nullptr, ctx->motion_epoch + 1u };
 }
 static RefitReadback refit_counters_init() {
     RefitReadback init{};
@@ -1380,8 +1448,13 @@ int device_refit_bvh(vhr_context *ctx) {
     REFIT_TRY(hipMemcpyAsync(p->d_counters, &init, sizeof(init), hipMemcpyHostToDevice, s));
     if (timed) REFIT_TRY(hipEventRecord(p->ev[0], s));
     // 1. the records
-    hipLaunchKernelGGL(k0_refit_records_kernel, refit_grid(n_tris), block, 0, s, ctx->d_vertices, ctx->d_indices, ctx->d_primitives, ctx->primitive_count, n_tris, ctx->d_tris,
-                       p->d_counters);
+    const RefitMotion motion = refit_motion(ctx);
+    if (motion.prev)
+        hipLaunchKernelGGL(k0_refit_records_kernel<true>, refit_grid(n_tris), block, 0, s, ctx->d_vertices, ctx->d_indices, ctx->d_primitives, ctx->primitive_count, n_tris, ctx->d_tris,
+                           p->d_counters, motion);
+    else
+        hipLaunchKernelGGL(k0_refit_records_kernel<false>, refit_grid(n_tris), block, 0, s, ctx->d_vertices, ctx->d_indices, ctx->d_primitives, ctx->primitive_count, n_tris, ctx->d_tris,
+                           p->d_counters, motion);
     if (timed) REFIT_TRY(hipEventRecord(p->ev[1], s));
     // 2. + 3. the boxes
     refit_upward(ctx, p, f, nullptr);
@@ -1431,8 +1504,13 @@ int device_refit_bvh_partial(vhr_context *ctx, bool *ran_whole) {
     p->dirty_stale = true;
     if (timed) REFIT_TRY(hipEventRecord(p->ev[0], s));
     // 1. mark, and the dirty records
-    hipLaunchKernelGGL(k0_refit_mark_kernel, refit_grid(n_tris), block, 0, s, ctx->d_vertices, ctx->d_indices, ctx->d_primitives, ctx->primitive_count, n_tris, ctx->d_tris,
-                       p->d_owner, p->d_parent, p->d_dirty, ctx->refit_dirty, &d->c, &d->partial);
+    const RefitMotion motion = refit_motion(ctx);
+    if (motion.prev)
+        hipLaunchKernelGGL(k0_refit_mark_kernel<true>, refit_grid(n_tris), block, 0, s, ctx->d_vertices, ctx->d_indices, ctx->d_primitives, ctx->primitive_count, n_tris, ctx->d_tris,
+                           p->d_owner, p->d_parent, p->d_dirty, ctx->refit_dirty, &d->c, &d->partial, motion);
+    else
+        hipLaunchKernelGGL(k0_refit_mark_kernel<false>, refit_grid(n_tris), block, 0, s, ctx->d_vertices, ctx->d_indices, ctx->d_primitives, ctx->primitive_count, n_tris, ctx->d_tris,
+                           p->d_owner, p->d_parent, p->d_dirty, ctx->refit_dirty, &d->c, &d->partial, motion);
     if (timed) REFIT_TRY(hipEventRecord(p->ev[1], s));
     // 2. + 3. the dirty nodes' boxes: the same launches, a one-bit test per node
     refit_upward(ctx, p, f, p->d_dirty);
@@ -1466,6 +1544,17 @@ int device_refit_bvh_partial(vhr_context *ctx, bool *ran_whole) {
     refit_publish(ctx, p, got, centre_moved, false, got.partial.dirty_records, got.partial.dirty_nodes, timed);
     ctx->partial_stats[kPartialForms] = centre_moved ? n_nodes : got.partial.dirty_nodes;
     ctx->partial_stats[kPartialCentreMoved] = centre_moved ? 1u : 0u;
+    return VHR_OK;
+}
+
+// A refit call with nothing pending while the last refit left records that differ from their previous ones: those objects have stopped.  The
+// caller has waited for the context's streams (frames in flight read the previous array) and counts the call as a refit.
+int device_motion_settle(vhr_context *ctx) {
+    const RefitMotion motion = refit_motion(ctx);
+    if (!motion.prev || !ctx->tri_count) return VHR_OK;
+    hipLaunchKernelGGL(k0_motion_settle_kernel, refit_grid(ctx->tri_count), dim3(256), 0, ctx->stream, ctx->d_tris, ctx->tri_count, motion);
+    REFIT_TRY(hipStreamSynchronize(ctx->stream));
+    REFIT_TRY(hipGetLastError());
     return VHR_OK;
 }
 

@@ -16,10 +16,16 @@ struct GbufferArgs {
     float *depth;
     uchar4 *albedo;          // B8G8R8A8_UNORM, optional
     uint32_t width, height;
+    const BvhTri *prev_tris; // "object_motion_vectors": every record's state before the last refit, slot for slot (the MOTION instantiation only)
 };
 
 constexpr int kGbufferMaxLayers = 32;      // discarded surfaces a primary ray may step through
 
+// MOTION ("object_motion_vectors", launched only while the last refit's records differ from their previous ones): the visible point is affine in the
+// hit's barycentrics, P = v0 + u e1 + v e2, so the record the slot held before the refit gives where that surface point was.  The reprojection
+// goes through P + d with d = (pv0 - v0) + u (pe1 - e1) + v (pe2 - e2): the difference form is exactly 0 for a record that did not move, so
+// its texel keeps the plain kernel's bits.  Nothing but motion.xy differs between the two instantiations.
+template <bool MOTION>
 __global__ __launch_bounds__(kTraceBlock) void gbuffer_kernel(const GbufferArgs a, const Stamps st) {
     vhr_stamp(st);
     __shared__ int s_stack[kTraceStack * kTraceBlock];
@@ -82,7 +88,15 @@ __global__ __launch_bounds__(kTraceBlock) void gbuffer_kernel(const GbufferArgs 
     store_rgba16f(a.normals, W, x, y, wn.x, wn.y, wn.z, float(bt.prim));
     const float cx = (float(x) + 0.5f) * a.pfd.display_size_inverse[0];                      // gbuf.frag:46
     const float cy = (float(y) + 0.5f) * a.pfd.display_size_inverse[1];
-    const f4 rp = mat4_mul(a.prev_projview, f4{ P.x, P.y, P.z, 1.0f });
+    f3 Pp = P;
+    if constexpr (MOTION) {
+        const float4 *c = reinterpret_cast<const float4 *>(a.scene.tris + h.tri_index), *p = reinterpret_cast<const float4 *>(a.prev_tris + h.tri_index);
+        const float4 c0 = c[0], c1 = c[1], c2 = c[2], p0 = p[0], p1 = p[1], p2 = p[2];       // (v0.xyz, e1.x) (e1.yz, e2.xy) (e2.z, ...)
+        const f3 d = f3{ (p0.x - c0.x) + h.u * (p0.w - c0.w) + h.v * (p1.z - c1.z), (p0.y - c0.y) + h.u * (p1.x - c1.x) + h.v * (p1.w - c1.w),
+                         (p0.z - c0.z) + h.u * (p1.y - c1.y) + h.v * (p2.x - c2.x) };
+        Pp = P + d;
+    }
+    const f4 rp = mat4_mul(a.prev_projview, f4{ Pp.x, Pp.y, Pp.z, 1.0f });
     const float px = (rp.x / rp.w) * 0.5f + 0.5f, py = (rp.y / rp.w) * 0.5f + 0.5f;          // gbuf.frag:47
     float metallic = prim.material.metallic_factor, roughness = prim.material.roughness_factor;
     if (prim.material.metallic_roughness_texture != -1) {                                    // gbuf.frag:50-56
@@ -111,8 +125,12 @@ int launch_standin_gbuffer(vhr_context *ctx, const vhr_per_frame_data &pfd, Imag
     a.albedo = albedo ? static_cast<uchar4 *>(albedo->ptr) : nullptr;
     a.width = depth.width;
     a.height = depth.height;
+    // the previous records matter only while some record differs from its previous one: else the plain kernel (the "alpha_test_rays" precedent)
+    const bool object_motion = ctx->object_motion_vectors && ctx->d_prev_tris && ctx->motion_differing != 0;
+    a.prev_tris = object_motion ? ctx->d_prev_tris : nullptr;
     const dim3 grid((a.width + 15) / 16, (a.height + 15) / 16);
-    launch(ctx, gbuffer_kernel, grid, dim3(kTraceBlock), 0, a);
+    if (object_motion) { launch(ctx, gbuffer_kernel<true>, grid, dim3(kTraceBlock), 0, a); ++ctx->motion_launches; }
+    else launch(ctx, gbuffer_kernel<false>, grid, dim3(kTraceBlock), 0, a);
     if (hipGetLastError() != hipSuccess) return ctx->fail(VHR_ERROR_DEVICE, "gbuffer kernel launch failed");
     return VHR_OK;
 }

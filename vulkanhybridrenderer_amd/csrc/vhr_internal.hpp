@@ -164,6 +164,11 @@ struct HostBvh {
     // (0xffffffff: the root) and, per record, the node that holds its leaf.  Empty after a build.
     std::vector<float> self_box;
     std::vector<uint32_t> parent, owner;
+    // "object_motion_vectors" on a host-only context (the twin of vhr_context::d_prev_tris / d_prev_saved): per record, last refit's record and the
+    // refit that last saved it; both empty with the option off.  prev_differing: records whose previous differs from current after the last walk
+    std::vector<BvhTri> prev_tris;
+    std::vector<uint32_t> prev_saved;
+    uint64_t prev_differing = 0;
 };
 
 // ---- partial refit: what moved since the last refit, as the update calls reported it ----
@@ -230,7 +235,9 @@ enum RefitStat { kRefitCount = 0, kRefitRecords = 1, kRefitNodes = 2, kRefitReco
 // the host twin (csrc/bvh_build.cpp; the arithmetic of build_bvh): every leaf record re-derived in its slot, the boxes bottom-up in the tree's
 // frame, the derived forms; counts[0] = records outside their leaf's box, [1] = child boxes outside their parent's slot, [2] = non-finite
 // coordinates met.  false: `bvh` is not a tree a refit can walk (links out of range, children numbered before their parents)
-bool refit_bvh(const vhr_vertex *vertices, const uint32_t *indices, const vhr_primitive *primitives, uint32_t primitive_count, HostBvh &bvh, uint64_t counts[3], int threads = 0);
+// motion_epoch != 0 ("object_motion_vectors"): the number of this refit; bvh.prev_tris / prev_saved / prev_differing are kept as the kernels keep theirs
+bool refit_bvh(const vhr_vertex *vertices, const uint32_t *indices, const vhr_primitive *primitives, uint32_t primitive_count, HostBvh &bvh, uint64_t counts[3], int threads = 0,
+               uint32_t motion_epoch = 0);
 // surface-area cost of the tree: sum over the inner nodes of child area x (1 for an inner child, the triangle count for a leaf), over the root's area
 double bvh_sah_cost(const HostBvh &bvh);
 // the device side (csrc/kernels_bvh.hip): what a refit needs beyond what a build leaves behind, prepared at the first refit
@@ -252,11 +259,13 @@ constexpr double kPartialRefitMaxShare = 0.3;
 // of those nodes (of all nodes if the scene centre's bits changed), then the whole-tree check pass.  Needs what a whole-tree refit_bvh leaves in
 // `bvh` (self_box / parent / owner).  out[0] = dirty records, [1] = dirty nodes, [2] = nodes whose forms were rewritten, [3] = 1 if the centre moved
 bool refit_bvh_partial(const vhr_vertex *vertices, const uint32_t *indices, const vhr_primitive *primitives, uint32_t primitive_count, HostBvh &bvh,
-                       const RefitDirty &dirty, uint64_t counts[3], uint64_t out[4], int threads = 0);
+                       const RefitDirty &dirty, uint64_t counts[3], uint64_t out[4], int threads = 0, uint32_t motion_epoch = 0);
 // the device side: *ran_whole = true if no per-node boxes existed yet (the first refit since the build) and the whole-tree refit ran instead
 int device_refit_bvh_partial(vhr_context *ctx, bool *ran_whole);
 bool device_refit_boxes_valid(const vhr_context *ctx);      // a whole-tree refit since the build has left the per-node boxes a dirty pass starts from
 int device_bvh_sah_cost(vhr_context *ctx, double *cost);
+// "object_motion_vectors": the settle pass of a refit call with nothing pending -- every record the last refit saved gets previous = current
+int device_motion_settle(vhr_context *ctx);
 
 enum class PassKind { Graphics, Raytracing, Compute };
 
@@ -471,6 +480,20 @@ struct vhr_context {
     // once per vhr_update_geometry; without one the switch and VHR_RAY_QUERY_ALPHA_TEST launch the plain kernels
     bool scene_can_discard = false;
     uint32_t alpha_launches = 0;                 // launches of the last TraceRays that ran an alpha instantiation (vhr_get_binary64_statistics out[2])
+    // "object_motion_vectors" (vhr_set_option; like "alpha_test_rays" no entry of VHR_OPTION_TABLE): 1 = the refits keep every leaf record's state
+    // before the last successful refit, and the stand-in G-buffer reprojects a moved surface through it.  Per record k: d_prev_tris[k] (the whole
+    // 48 bytes, in the same slot) and d_prev_saved[k], the number of the refit that last saved it.  Refit number E = motion_epoch + 1 saves a
+    // record it rewrites unless d_prev_saved[k] == E already (a retry after a failed attempt: the record then holds the attempt's garbage, the
+    // previous array the state to keep), and settles a clean record saved by refit E - 1 (previous = current: it has stopped).  Invariant
+    // between refits: d_prev_saved[k] < motion_epoch implies previous == current.  A host-only context keeps the same in h_bvh.prev_*.
+    int object_motion_vectors = 0;
+    vhr::BvhTri *d_prev_tris = nullptr;
+    uint32_t *d_prev_saved = nullptr;
+    uint32_t motion_epoch = 1;                   // successful refits (settle calls included) since the arrays were reset, + 1
+    uint64_t motion_differing = 0;               // records whose previous differs from current after the last successful refit
+    uint64_t motion_refit_differing = 0;         // ... as the last refit attempt counted them (taken over when it succeeds)
+    uint64_t motion_launches = 0;                // G-buffer launches that ran the motion instantiation
+    bool motion_valid() const { return object_motion_vectors && (host_only ? !h_bvh.prev_tris.empty() : d_prev_tris != nullptr); }
     int bvh_host_checks = 0;                        // "bvh_host_checks" 1: a device-built tree is fetched and the host's self-checks repeated on it
     uint64_t bvh_form_checks[4] = { 0, 0, 0, 0 };   // check_node_forms of the last build (vhr_get_bvh_form_checks)
     float bvh_centre[3] = { 0, 0, 0 };

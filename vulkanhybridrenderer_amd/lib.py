@@ -42,6 +42,7 @@ EXPORTS = [
     "vhr_calibration_stream_read", "vhr_ray_query", "vhr_get_ray_query_statistics", "vhr_ray_query_struct_layout",
     "vhr_update_vertices", "vhr_update_primitive_transforms", "vhr_refit_geometry", "vhr_get_refit_statistics", "vhr_get_refit_times",
     "vhr_get_bvh_sah_cost", "vhr_refit_geometry_partial", "vhr_get_partial_refit_statistics",
+    "vhr_get_object_motion_statistics", "vhr_debug_triangle_records",
 ]
 
 PATH_PREFIXES = ("hybrid", "raytraced", "rayquery", "forward_raster")      # vhr_<prefix>_{create,destroy,build,rebuild,last_error}
@@ -311,6 +312,8 @@ def load():
     L.vhr_get_bvh_sah_cost.argtypes = [vp, C.POINTER(C.c_double)]
     L.vhr_refit_geometry_partial.argtypes = [vp, u32]
     L.vhr_get_partial_refit_statistics.argtypes = [vp, C.POINTER(u64)]
+    L.vhr_get_object_motion_statistics.argtypes = [vp, C.POINTER(u64)]
+    L.vhr_debug_triangle_records.argtypes = [vp, i32, C.c_void_p, u32, C.POINTER(u32)]
     L.vhr_set_kernel_timing.argtypes = [vp, i32]
     L.vhr_get_kernel_time.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(u64), i32]
     _lib = L
@@ -451,6 +454,25 @@ class Context:
         self.check(self.L.vhr_get_partial_refit_statistics(self.handle, out), "partial_refit_statistics")
         return dict(partial_refits=int(out[0]), dirty_records=int(out[1]), dirty_nodes=int(out[2]), forms_rewritten=int(out[3]), ran_as=int(out[4]),
                     centre_moved=int(out[5]), vertex_ranges=int(out[6]), primitive_ranges=int(out[7]))
+
+    def object_motion_statistics(self):
+        """"object_motion_vectors": whether the previous records exist, how many differ from the current ones after the last successful refit,
+        and the G-buffer launches that ran the motion instantiation since the context was created."""
+        out = (C.c_uint64 * 4)()
+        self.check(self.L.vhr_get_object_motion_statistics(self.handle, out), "object_motion_statistics")
+        return dict(active=int(out[0]), differing_records=int(out[1]), motion_launches=int(out[2]))
+
+    def triangle_records(self, previous=False):
+        """vhr_debug_triangle_records: (n, 9) float32, (v0, e1, e2) of every triangle in flat (primitive-major) order; previous=True: the
+        records before the last refit ("object_motion_vectors" 1)."""
+        import numpy as np
+        n = C.c_uint32(0)
+        rc = self.L.vhr_debug_triangle_records(self.handle, 1 if previous else 0, None, 0, C.byref(n))  # the count: "too small" unless the scene is empty
+        if rc != -1 or n.value == 0:                      # a refusal (no geometry, a presplit tree, no previous records) surfaces here
+            self.check(rc, "triangle_records")
+        out = np.zeros((n.value, 9), np.float32)
+        self.check(self.L.vhr_debug_triangle_records(self.handle, 1 if previous else 0, out.ctypes.data, n.value, C.byref(n)), "triangle_records")
+        return out
 
     def refit_statistics(self):
         out = (C.c_uint64 * 8)()
