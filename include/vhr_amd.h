@@ -657,7 +657,15 @@ int vhr_get_ray_statistics(vhr_context *ctx, uint64_t out[4]);
  *  launches cost what profiles/alpha_rays_rate.jsonl reports.  vhr_get_option returns this key (not the bvh_* keys); a host-only context
  *  accepts it; it is no part of vhr_hybrid_save_state's blob, of vhr_hybrid_settings or of vhr_trace_params.
  *  "object_motion_vectors" is the third key of that kind (it changes the motion image; not in the table; vhr_get_option returns it; every
- *  context accepts it; refused inside a pass): 0 (default) / 1, described at "Object motion vectors" below the refit calls. */
+ *  context accepts it; refused inside a pass): 0 (default) / 1, described at "Object motion vectors" below the refit calls.
+ *  "shadow_ray_mask", "ao_ray_mask", "reflection_ray_mask" (0..255, default 255; they change images, so not in the table; vhr_get_option
+ *  returns them; every context accepts them; read at every launch of the hybrid path's rays): the cull mask traceRayEXT is given for that
+ *  class of rays (raygen.rgen:39-40,51-52,64 pass 0xFF) -- a candidate hit on primitive p does not exist for the ray iff
+ *  (masks[p] & mask) == 0 (vhr_set_primitive_masks, "Ray cull masks" below); the reflection mask holds for both bounces.  A launch none of
+ *  whose masks ACTS on the masks the primitives carry is exactly the launch it was without them; where the shadow or AO mask acts,
+ *  "fuse_temporal" does not fuse (the epilogue form has no filter, as with alpha).  No part of vhr_trace_params, vhr_hybrid_settings or
+ *  vhr_hybrid_save_state's blob.  The rayquery, forward-raster and raytraced render paths ignore these keys and the primitives' masks, as
+ *  they ignore "alpha_test_rays". */
 int vhr_set_option(vhr_context *ctx, const char *key, int32_t value);
 int vhr_get_option(vhr_context *ctx, const char *key, int32_t *value);
 int32_t vhr_option_count(void);
@@ -856,9 +864,10 @@ int vhr_get_object_motion_statistics(vhr_context *ctx, uint64_t out[4]);
  * deciding to rebuild.  One reduction, computed when asked (waits for the context's streams). */
 int vhr_get_bvh_sah_cost(vhr_context *ctx, double out[2]);
 
-/* ---- Batched ray queries on the scene's BVH (rayQueryEXT with an opaque TLAS, cull mask 0xFF; VHR_RAY_QUERY_ALPHA_TEST: a non-opaque one) ----
+/* ---- Batched ray queries on the scene's BVH (rayQueryEXT with an opaque TLAS, cull mask 0xFF -- vhr_ray_query_masked below takes the cull mask;
+ *      VHR_RAY_QUERY_ALPHA_TEST: a non-opaque one) ----
  * Traces `count` caller-made rays against the geometry of the last vhr_update_geometry.  The flags of rayQueryInitializeEXT this
- * stands for are gl_RayFlagsTerminateOnFirstHitEXT (VHR_RAY_QUERY_TERMINATE_ON_FIRST_HIT) or none; the mask is 0xFF.
+ * stands for are gl_RayFlagsTerminateOnFirstHitEXT (VHR_RAY_QUERY_TERMINATE_ON_FIRST_HIT) or none; the mask is 0xFF (any other: vhr_ray_query_masked).
  *   - All geometry is opaque and two-sided; a triangle is hit iff tmin < t < tmax (decision (vi): fp32 Moeller-Trumbore, a candidate whose
  *     solution contradicts itself decided again in binary64 -- the same test, bit for bit, as every walker of the library and the oracle).
  *   - Without the flag: results = vhr_ray_hit[count], the hit of smallest t, ties broken by the smaller flat triangle index (primitive-major
@@ -881,13 +890,42 @@ int vhr_get_bvh_sah_cost(vhr_context *ctx, double out[2]);
  *     aligned or `results` not 4-byte aligned -- checked first, on every context.  Then VHR_ERROR_NO_DEVICE on a host-only context.
  *     count == 0 returns VHR_OK and launches nothing; a context without geometry makes every ray miss. */
 int vhr_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, uint32_t flags, void *results);
-/* The last vhr_ray_query (waits for the device): out[0] = rays, out[1] = rays with a hit, out[2] = rays decided again in binary64 by the
+/* vhr_ray_query with rayQueryInitializeEXT's cull mask: the same contract, flags, validation order and error codes, and ray i's mask is
+ * `cull_mask` if ray_masks == NULL, else ray_masks[i] & cull_mask.  A candidate hit on primitive p does not exist for a ray of mask m iff
+ * (masks[p] & m) == 0 (vhr_set_primitive_masks): it ends no any-hit ray, shrinks no closest t and takes no part in the (t, flat index)
+ * tie-break; decision (vi) comes first, its binary64 re-decision included, and with VHR_RAY_QUERY_ALPHA_TEST the mask test precedes the
+ * alpha rule.  A ray of mask 0 misses everything.  `ray_masks` lives where `rays` live (device memory, or host memory with
+ * VHR_RAY_QUERY_HOST_MEMORY: staged) and needs no alignment.  cull_mask > 0xFF: VHR_ERROR_INVALID_ARGUMENT, with the other argument checks.
+ * Where the cull mask does not act on the masks the primitives carry and ray_masks is NULL, the launches are vhr_ray_query's own.
+ * vhr_ray_query itself is the (0xFF, NULL) case. */
+int vhr_ray_query_masked(vhr_context *ctx, const vhr_ray *rays, uint32_t count, uint32_t flags, uint32_t cull_mask, const uint8_t *ray_masks, void *results);
+/* The last vhr_ray_query or vhr_ray_query_masked (waits for the device): out[0] = rays, out[1] = rays with a hit, out[2] = rays decided again in binary64 by the
  * second launch, out[3] = waves whose traversal stack overflowed (must be 0).  All 0 before the first query. */
 int vhr_get_ray_query_statistics(vhr_context *ctx, uint64_t out[4]);
 /* The layouts this library was built with, for bindings: out[0] = sizeof(vhr_ray), out[1] = offsetof(vhr_ray, tmin), out[2] =
  * offsetof(vhr_ray, direction), out[3] = offsetof(vhr_ray, tmax), out[4] = sizeof(vhr_ray_hit), out[5] = offsetof(vhr_ray_hit,
  * geometry_index), out[6] = offsetof(vhr_ray_hit, primitive_index), out[7] = offsetof(vhr_ray_hit, reserved).  Returns 8. */
 int vhr_ray_query_struct_layout(uint32_t out[8]);
+
+/* ---- Ray cull masks: per-primitive visibility for rays and ray queries (VkAccelerationStructureInstanceKHR::mask against cullMask) ----
+ * Every primitive has an 8-bit mask, 0xFF after vhr_update_geometry (resource_manager.cpp:704-717 builds its instance with one); every ray
+ * has one: the hybrid path's by class ("shadow_ray_mask", "ao_ray_mask", "reflection_ray_mask" of vhr_set_option), a query's from
+ * vhr_ray_query_masked.  A candidate hit on a triangle of primitive p does not exist for a ray of mask m iff (masks[p] & m) == 0: this object
+ * casts no shadow, that proxy is seen by AO rays only, this batch of queries sees colliders only.  Results never depend on the tree: a ray of
+ * mask m sees, bit for bit, what the plain ray sees on the scene made of the primitives with masks[p] & m != 0.
+ *   - vhr_set_primitive_masks takes host memory.  It is no update in the refit sense: nothing becomes pending, no refit is needed.  It waits
+ *     for the context's streams before it overwrites and takes effect at the next launch.  vhr_update_geometry resets every mask to 0xFF;
+ *     vhr_resize and both refits keep them.  The masks are no part of vhr_hybrid_save_state's blob or of any fingerprint.  The device array
+ *     is made by the first call that stores a value other than 0xFF: a context that never does pays nothing.
+ *   - Refused: NULL with count > 0 (VHR_ERROR_INVALID_ARGUMENT, checked first), no geometry yet or called from inside a pass
+ *     (VHR_ERROR_GRAPH), a range outside the primitives (VHR_ERROR_INVALID_ARGUMENT).  count == 0 does nothing.  A host-only context keeps
+ *     the masks (vhr_get_primitive_masks reads them back).
+ *   - The rayquery, forward-raster and raytraced render paths ignore masks. */
+int vhr_set_primitive_masks(vhr_context *ctx, uint32_t first_primitive, uint32_t count, const uint8_t *masks);
+int vhr_get_primitive_masks(vhr_context *ctx, uint32_t first_primitive, uint32_t count, uint8_t *out);
+/* out[0] = primitives whose mask is not 0xFF, out[1] = launches of the last vhr_trace_rays that ran a mask instantiation (0, 1 or 2; 1 at
+ * most with "raygen_variant" 0), out[2] = 1 if the last ray query ran one, out[3] = 0. */
+int vhr_get_ray_mask_statistics(vhr_context *ctx, uint64_t out[4]);
 
 #ifdef __cplusplus
 }

@@ -161,6 +161,15 @@ public:
     void QueryRays(const vhr_ray *rays, uint32_t count, uint32_t flags, void *results) {
         check(context.handle, vhr_ray_query(context.handle, rays, count, flags, results), "QueryRays");
     }
+    // ... with rayQueryInitializeEXT's cull mask (vhr_ray_query_masked): ray i's mask is cull_mask, ANDed with ray_masks[i] where ray_masks (one
+    // byte per ray, in the memory `rays` are in) is not null; a candidate on a primitive whose mask shares no bit with it does not exist.
+    void QueryRays(const vhr_ray *rays, uint32_t count, uint32_t flags, uint32_t cull_mask, const uint8_t *ray_masks, void *results) {
+        check(context.handle, vhr_ray_query_masked(context.handle, rays, count, flags, cull_mask, ray_masks, results), "QueryRays");
+    }
+    // Extension: per-primitive ray cull masks (VkAccelerationStructureInstanceKHR::mask, per geometry; 0xFF after UpdateGeometry).  No refit needed.
+    void SetPrimitiveMasks(uint32_t first_primitive, const std::vector<uint8_t> &masks) {
+        check(context.handle, vhr_set_primitive_masks(context.handle, first_primitive, uint32_t(masks.size()), masks.data()), "SetPrimitiveMasks");
+    }
     // Extension: geometry that moves without a rebuild (vhr_update_vertices, vhr_update_primitive_transforms, vhr_refit_geometry).  Per frame:
     // UpdateVertices / UpdatePrimitiveTransforms ... RefitGeometry ... UpdatePerFrameUBO ... RenderGraph::Execute.
     void UpdateVertices(uint32_t first_vertex, const std::vector<Vertex> &vertices) {

@@ -104,7 +104,7 @@ typedef struct vhr_trace_params {
     float    tmax;            /* 10000.0 */
 } vhr_trace_params;
 
-/* One ray of vhr_ray_query (include/vhr_amd.h): the arguments of rayQueryInitializeEXT after the TLAS, the cull mask and the flags.
+/* One ray of vhr_ray_query (include/vhr_amd.h): the arguments of rayQueryInitializeEXT after the TLAS, the cull mask (vhr_ray_query_masked takes it) and the flags.
  * 32 bytes; an array of them must start at a 16-byte boundary (the kernel reads a ray as two 16-byte loads). */
 typedef struct vhr_ray {
     float origin[3];

@@ -46,6 +46,16 @@ static thread_local std::string g_create_error;     // vhr_create has no context
         if (e_ != hipSuccess) return (ctx)->fail(VHR_ERROR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
+// the primitives' ray cull masks on the device, for a launch that filters (vhr_set_primitive_masks below)
+int vhr::ensure_device_prim_masks(vhr_context *ctx) {
+    if (ctx->d_prim_masks || ctx->primitive_count == 0) return VHR_OK;
+    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->d_prim_masks), ctx->primitive_count));
+    if (ctx->h_prim_masks.empty()) HIP_TRY(ctx, hipMemsetAsync(ctx->d_prim_masks, 0xFF, ctx->primitive_count, ctx->stream));
+    else HIP_TRY(ctx, hipMemcpyAsync(ctx->d_prim_masks, ctx->h_prim_masks.data(), ctx->primitive_count, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));          // (once per scene; launches on the context's other streams may read it next)
+    return VHR_OK;
+}
+
 vhr::DeviceScene vhr_context::device_scene() const {
     DeviceScene s;
     s.nodes = d_nodes;
@@ -291,6 +301,7 @@ static void free_scene(vhr_context *ctx) {
     free_motion(ctx);
     hipFree(ctx->d_vertices); hipFree(ctx->d_indices); hipFree(ctx->d_primitives); hipFree(ctx->d_normal_matrices);
     hipFree(ctx->d_nodes); hipFree(ctx->d_nodes16); hipFree(ctx->d_nodes_ch); hipFree(ctx->d_nodes48); hipFree(ctx->d_tris);
+    hipFree(ctx->d_prim_masks); ctx->d_prim_masks = nullptr;
     ctx->d_vertices = nullptr; ctx->d_indices = nullptr; ctx->d_primitives = nullptr; ctx->d_normal_matrices = nullptr;
     ctx->d_nodes = nullptr; ctx->d_nodes16 = nullptr; ctx->d_nodes_ch = nullptr; ctx->d_nodes48 = nullptr; ctx->d_tris = nullptr;
     ctx->vertex_count = ctx->index_count = ctx->primitive_count = ctx->node_count = ctx->tri_count = 0;
@@ -417,6 +428,10 @@ int vhr_update_geometry(vhr_context *ctx, const vhr_vertex *vertices, uint32_t v
         const vhr_material &m = primitives[p].material;
         if (m.alpha_mask == 1 || m.base_color_texture != -1 || m.base_color[3] == 0.0f) ctx->scene_can_discard = true;
     }
+    // ... and every primitive's ray cull mask is 0xFF again (the device array goes with the scene's, below)
+    ctx->h_prim_masks.clear();
+    ctx->mask_present[0] = ctx->mask_present[1] = ctx->mask_present[2] = 0; ctx->mask_present[3] = 1ull << 63;
+    ctx->masks_not_ff = 0;
     // a build replaces whatever updates were pending and everything a refit had prepared
     ctx->refit_pending = ctx->sah_cost_built_valid = false;
     for (uint64_t &w : ctx->refit_stats) w = 0;
@@ -630,6 +645,60 @@ int vhr_update_primitive_transforms(vhr_context *ctx, uint32_t first_primitive, 
     }
     ctx->refit_pending = true;
     ctx->refit_dirty.primitives.add(first_primitive, count);
+    return VHR_OK;
+}
+
+// ---- ray cull masks: one byte per primitive, tested against the ray's mask at every candidate (the tree does not depend on them) ----
+static int mask_state_checks(vhr_context *ctx, const char *who, uint32_t first_primitive, uint32_t count, bool writes) {
+    const bool has = ctx->host_only ? !ctx->h_bvh.nodes.empty() : (ctx->d_nodes != nullptr && ctx->node_count != 0);
+    if (!has) return ctx->fail(VHR_ERROR_GRAPH, std::string(who) + ": no geometry yet (vhr_update_geometry first)");
+    if (writes && (ctx->recording || ctx->cur_pass || ctx->in_execute)) return ctx->fail(VHR_ERROR_GRAPH, std::string(who) + ": called from inside a pass");
+    if (uint64_t(first_primitive) + count > ctx->primitive_count)
+        return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, std::string(who) + ": range [" + std::to_string(first_primitive) + ", +" + std::to_string(count) + ") exceeds the primitives (" + std::to_string(ctx->primitive_count) + ")");
+    return VHR_OK;
+}
+
+int vhr_set_primitive_masks(vhr_context *ctx, uint32_t first_primitive, uint32_t count, const uint8_t *masks) {
+    if (!ctx) return VHR_ERROR_INVALID_ARGUMENT;
+    if (count > 0 && !masks) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_set_primitive_masks: masks must not be NULL when count > 0");
+    { const int rc = mask_state_checks(ctx, "vhr_set_primitive_masks", first_primitive, count, true); if (rc != VHR_OK) return rc; }
+    if (count == 0) return VHR_OK;
+    if (ctx->h_prim_masks.empty()) {
+        bool all_ff = true;
+        for (uint32_t p = 0; p < count; ++p) all_ff = all_ff && masks[p] == 0xFFu;
+        if (all_ff) return VHR_OK;                             // nothing to store: every mask is 0xFF already
+        ctx->h_prim_masks.assign(ctx->primitive_count, uint8_t(0xFF));
+    }
+    std::memcpy(ctx->h_prim_masks.data() + first_primitive, masks, count);
+    for (uint64_t &w : ctx->mask_present) w = 0;
+    ctx->masks_not_ff = 0;
+    for (const uint8_t v : ctx->h_prim_masks) {
+        ctx->mask_present[v >> 6] |= 1ull << (v & 63u);
+        if (v != 0xFFu) ++ctx->masks_not_ff;
+    }
+    if (ctx->host_only) return VHR_OK;
+    // frames and queries in flight read the array that is about to be overwritten: wait for them (not an update in the refit sense: nothing is pending)
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    { const int src_ = ctx->sync_streams(); if (src_ != VHR_OK) return src_; }
+    if (!ctx->d_prim_masks) return vhr::ensure_device_prim_masks(ctx);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_prim_masks + first_primitive, masks, count, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));          // the caller's array is free when the call returns
+    return VHR_OK;
+}
+
+int vhr_get_primitive_masks(vhr_context *ctx, uint32_t first_primitive, uint32_t count, uint8_t *out) {
+    if (!ctx) return VHR_ERROR_INVALID_ARGUMENT;
+    if (count > 0 && !out) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_get_primitive_masks: out must not be NULL when count > 0");
+    { const int rc = mask_state_checks(ctx, "vhr_get_primitive_masks", first_primitive, count, false); if (rc != VHR_OK) return rc; }
+    if (count == 0) return VHR_OK;
+    if (ctx->h_prim_masks.empty()) std::memset(out, 0xFF, count);
+    else std::memcpy(out, ctx->h_prim_masks.data() + first_primitive, count);
+    return VHR_OK;
+}
+
+int vhr_get_ray_mask_statistics(vhr_context *ctx, uint64_t out[4]) {
+    if (!ctx || !out) return VHR_ERROR_INVALID_ARGUMENT;
+    out[0] = ctx->masks_not_ff; out[1] = ctx->mask_launches; out[2] = ctx->rq_mask_ran; out[3] = 0;
     return VHR_OK;
 }
 
@@ -931,6 +1000,15 @@ int vhr_set_option(vhr_context *ctx, const char *key, int32_t value) {
         ctx->alpha_test_rays = value;
         return VHR_OK;
     }
+    {   // the hybrid path's ray-class cull masks: read at every launch of its rays, like "alpha_test_rays"
+        int *const slot = !std::strcmp(key, "shadow_ray_mask") ? &ctx->shadow_ray_mask : !std::strcmp(key, "ao_ray_mask") ? &ctx->ao_ray_mask :
+                          !std::strcmp(key, "reflection_ray_mask") ? &ctx->reflection_ray_mask : nullptr;
+        if (slot) {
+            if (value < 0 || value > 255) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, std::string(key) + " must be 0..255 (a primitive whose mask shares no bit with it does not exist for that class of rays)");
+            *slot = value;
+            return VHR_OK;
+        }
+    }
     if (!std::strcmp(key, "object_motion_vectors")) {        // the refits keep last frame's triangle records; the stand-in G-buffer reprojects through them
         if (value < 0 || value > 1)
             return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "object_motion_vectors must be 0 (motion vectors follow the camera only) or 1 (and the geometry the refits moved)");
@@ -972,6 +1050,9 @@ int vhr_get_option(vhr_context *ctx, const char *key, int32_t *value) {
     if (!ctx || !key || !value) return VHR_ERROR_INVALID_ARGUMENT;
     if (!std::strcmp(key, "alpha_test_rays")) { *value = ctx->alpha_test_rays; return VHR_OK; }
     if (!std::strcmp(key, "object_motion_vectors")) { *value = ctx->object_motion_vectors; return VHR_OK; }
+    if (!std::strcmp(key, "shadow_ray_mask")) { *value = ctx->shadow_ray_mask; return VHR_OK; }
+    if (!std::strcmp(key, "ao_ray_mask")) { *value = ctx->ao_ray_mask; return VHR_OK; }
+    if (!std::strcmp(key, "reflection_ray_mask")) { *value = ctx->reflection_ray_mask; return VHR_OK; }
     for (int i = 0; i < vhr::kOptCount; ++i)
         if (!std::strcmp(key, vhr::kOptionInfo[i].name)) { *value = ctx->options[i]; return VHR_OK; }
     return ctx->fail(VHR_ERROR_NOT_FOUND, std::string("unknown option '") + key + "'");
@@ -1043,24 +1124,32 @@ int vhr_get_drain_statistics(vhr_context *ctx, uint64_t out[4]) {
     return VHR_OK;
 }
 
-int vhr_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, uint32_t flags, void *results) {
+// vhr_ray_query and vhr_ray_query_masked: one body.  `who` names the entry point in messages; `masked` = the second (cull_mask checked, the
+// filtering kernels where the mask acts or per-ray masks are given).
+static int ray_query_impl(vhr_context *ctx, const char *who_, const bool masked, const vhr_ray *rays, uint32_t count, uint32_t flags, uint32_t cull_mask,
+                          const uint8_t *ray_masks, void *results) {
     if (!ctx) return VHR_ERROR_INVALID_ARGUMENT;
+    const std::string who(who_);
     // the arguments first (the same answer on every context), then the device
     if (flags & ~uint32_t(VHR_RAY_QUERY_TERMINATE_ON_FIRST_HIT | VHR_RAY_QUERY_HOST_MEMORY | VHR_RAY_QUERY_ALPHA_TEST))
-        return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_ray_query: unknown flag bits " + std::to_string(flags));
-    if (count > 0 && (!rays || !results)) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_ray_query: rays and results must not be NULL when count > 0");
-    if (count > 0 && reinterpret_cast<uintptr_t>(rays) % 16u) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_ray_query: rays must be 16-byte aligned");
-    if (count > 0 && reinterpret_cast<uintptr_t>(results) % 4u) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_ray_query: results must be 4-byte aligned");
-    if (ctx->host_only) return ctx->fail(VHR_ERROR_NO_DEVICE, "vhr_ray_query: host-only context: no device work");
-    { const int stale = ctx->refuse_if_stale("vhr_ray_query"); if (stale != VHR_OK) return stale; }
+        return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": unknown flag bits " + std::to_string(flags));
+    if (count > 0 && (!rays || !results)) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": rays and results must not be NULL when count > 0");
+    if (count > 0 && reinterpret_cast<uintptr_t>(rays) % 16u) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": rays must be 16-byte aligned");
+    if (count > 0 && reinterpret_cast<uintptr_t>(results) % 4u) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": results must be 4-byte aligned");
+    if (masked && cull_mask > 0xFFu) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": cull_mask " + std::to_string(cull_mask) + " exceeds 0xFF");
+    if (ctx->host_only) return ctx->fail(VHR_ERROR_NO_DEVICE, who + ": host-only context: no device work");
+    { const int stale = ctx->refuse_if_stale(who_); if (stale != VHR_OK) return stale; }
     if (count == 0) return VHR_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const bool any_hit = (flags & VHR_RAY_QUERY_TERMINATE_ON_FIRST_HIT) != 0, alpha_test = (flags & VHR_RAY_QUERY_ALPHA_TEST) != 0;
     const uint64_t ray_bytes = uint64_t(count) * sizeof(vhr_ray), result_bytes = uint64_t(count) * (any_hit ? 1u : sizeof(vhr_ray_hit));
     ctx->rq_rays = count;
-    if (!(flags & VHR_RAY_QUERY_HOST_MEMORY)) return vhr::launch_ray_query(ctx, rays, count, any_hit, alpha_test, results);
+    if (!masked) { cull_mask = 0xFFu; ray_masks = nullptr; }
+    if (!(flags & VHR_RAY_QUERY_HOST_MEMORY)) return vhr::launch_ray_query(ctx, rays, count, any_hit, alpha_test, results, cull_mask, ray_masks);
     // host memory: staged through the context's own buffer (rays, then the results at the next 256-byte boundary)
-    const uint64_t result_offset = (ray_bytes + 255u) & ~uint64_t(255u), staging = result_offset + result_bytes;
+    // (vhr_ray_query_masked's per-ray masks, one byte each, behind the results at the next 256-byte boundary)
+    const uint64_t result_offset = (ray_bytes + 255u) & ~uint64_t(255u), mask_offset = (result_offset + result_bytes + 255u) & ~uint64_t(255u);
+    const uint64_t staging = ray_masks ? mask_offset + count : result_offset + result_bytes;
     if (ctx->rq_staging_bytes < staging) {
         (void)hipFree(ctx->d_rq_staging);
         ctx->d_rq_staging = nullptr;
@@ -1070,11 +1159,21 @@ int vhr_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, uint32_
     }
     char *const d = static_cast<char *>(ctx->d_rq_staging);
     HIP_TRY(ctx, hipMemcpyAsync(d, rays, ray_bytes, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = vhr::launch_ray_query(ctx, reinterpret_cast<const vhr_ray *>(d), count, any_hit, alpha_test, d + result_offset);
+    if (ray_masks) HIP_TRY(ctx, hipMemcpyAsync(d + mask_offset, ray_masks, count, hipMemcpyHostToDevice, ctx->stream));
+    const int rc = vhr::launch_ray_query(ctx, reinterpret_cast<const vhr_ray *>(d), count, any_hit, alpha_test, d + result_offset, cull_mask,
+                                         ray_masks ? reinterpret_cast<const uint8_t *>(d + mask_offset) : nullptr);
     if (rc != VHR_OK) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(results, d + result_offset, result_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return VHR_OK;
+}
+
+int vhr_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, uint32_t flags, void *results) {
+    return ray_query_impl(ctx, "vhr_ray_query", false, rays, count, flags, 0xFFu, nullptr, results);
+}
+
+int vhr_ray_query_masked(vhr_context *ctx, const vhr_ray *rays, uint32_t count, uint32_t flags, uint32_t cull_mask, const uint8_t *ray_masks, void *results) {
+    return ray_query_impl(ctx, "vhr_ray_query_masked", true, rays, count, flags, cull_mask, ray_masks, results);
 }
 
 int vhr_get_ray_query_statistics(vhr_context *ctx, uint64_t out[4]) {

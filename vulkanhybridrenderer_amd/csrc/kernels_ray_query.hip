@@ -62,6 +62,8 @@ struct RayQueryArgs {
     uint32_t *redo_list;                  // capacity count
     RayQueryCounters *counters;
     uint32_t count, any_hit;
+    RayMaskArgs masks;                    // vhr_ray_query_masked (the kFilterMask instantiations): masks.shadow = its cull_mask
+    const uint8_t *ray_masks;             // one byte per ray, ANDed with the cull mask, or null
 };
 static_assert(sizeof(vhr_ray) == 2 * sizeof(float4), "vhr_ray is two float4");
 
@@ -73,8 +75,9 @@ __device__ __forceinline__ void ray_query_store(const RayQueryArgs &a, const uin
     r[3] = hit ? prim : kNoHit; r[4] = hit ? tri : kNoHit; r[5] = 0u;
 }
 
-// ALPHA (VHR_RAY_QUERY_ALPHA_TEST): a candidate gbuf_discarded names does not exist -- the walk's Reject, behind decision (vi) as ever.
-template <bool SPILL, bool ALPHA = false>
+// FILTER: kFilterAlpha (VHR_RAY_QUERY_ALPHA_TEST) -- a candidate gbuf_discarded names does not exist; kFilterMask (vhr_ray_query_masked) -- nor does
+// one whose primitive's mask shares no bit with the ray's mask, read at the candidate by ray id.  The walk's Reject, behind decision (vi) as ever.
+template <bool SPILL, int FILTER = kFilterNone>
 __global__ __launch_bounds__(kQueueBlock * 2) void ray_query_kernel(const RayQueryArgs a, const uint32_t stack_levels, const uint32_t refill_threshold,
                                                                     const uint32_t early_exit, const Stamps st) {
     vhr_stamp(st);
@@ -109,7 +112,7 @@ __global__ __launch_bounds__(kQueueBlock * 2) void ray_query_kernel(const RayQue
                 flagged = false;
             }
         }, nullptr,
-        [&](uint32_t) { flagged = true; }, alpha_reject<ALPHA>(a.scene));
+        [&](uint32_t) { flagged = true; }, ray_filter<FILTER>(a.scene, a.masks, a.masks.shadow, a.ray_masks));
     for (int off = 32; off > 0; off >>= 1) hits += uint32_t(__shfl_xor(int(hits), off));
     const bool wave_overflow = __any(overflow != 0u);
     if (lane == 0) {
@@ -119,7 +122,7 @@ __global__ __launch_bounds__(kQueueBlock * 2) void ray_query_kernel(const RayQue
 }
 
 // Decision (vi), second half, for the rays launch 1 listed: the per-pixel walker with the binary64 redo inside its leaf test.
-template <bool ALPHA = false>
+template <int FILTER = kFilterNone>
 __global__ __launch_bounds__(kTraceBlock) void ray_query_redo_kernel(const RayQueryArgs a, const Stamps st) {
     vhr_stamp(st);
     __shared__ int s_stack[kTraceStack * kTraceBlock];
@@ -134,12 +137,14 @@ __global__ __launch_bounds__(kTraceBlock) void ray_query_redo_kernel(const RayQu
         Hit best;
         best.t = best.u = best.v = 0.0f; best.tri_index = 0; best.flat = 0;
         bool hit, was;
+        uint32_t ray_mask = a.masks.shadow;
+        if constexpr (FILTER == kFilterMask) { if (a.ray_masks) ray_mask &= uint32_t(a.ray_masks[ray]); }
         if (any_hit) {
             was = static_cast<const uint8_t *>(a.results)[ray] != 0u;
-            hit = traverse<true>(a.scene, o, d, p.w, q.w, s_stack + threadIdx.x, best, overflow, alpha_reject<ALPHA>(a.scene));
+            hit = traverse<true>(a.scene, o, d, p.w, q.w, s_stack + threadIdx.x, best, overflow, ray_filter<FILTER>(a.scene, a.masks, ray_mask));
         } else {
             was = static_cast<const uint32_t *>(a.results)[size_t(ray) * 6u + 3u] != kNoHit;
-            hit = traverse<false>(a.scene, o, d, p.w, q.w, s_stack + threadIdx.x, best, overflow, alpha_reject<ALPHA>(a.scene));
+            hit = traverse<false>(a.scene, o, d, p.w, q.w, s_stack + threadIdx.x, best, overflow, ray_filter<FILTER>(a.scene, a.masks, ray_mask));
         }
         ray_query_store(a, ray, any_hit, hit, best.t, best.u, best.v, hit && !any_hit ? a.scene.tris[best.tri_index].prim : 0u,
                         hit && !any_hit ? a.scene.tris[best.tri_index].tri : 0u);
@@ -149,7 +154,9 @@ __global__ __launch_bounds__(kTraceBlock) void ray_query_redo_kernel(const RayQu
     if (overflow) atomicAdd(&a.counters->overflows, 1u);
 }
 
-int launch_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, bool any_hit, bool alpha_test, void *results) {
+int launch_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, bool any_hit, bool alpha_test, void *results, uint32_t cull_mask,
+                     const uint8_t *ray_masks) {
+    ctx->rq_mask_ran = 0;
     if (count == 0) return VHR_OK;
     RayQueryScratch *q = nullptr;                  // this stream's counters and list
     for (RayQueryScratch &e : ctx->rq_scratch) if (e.stream == ctx->stream) q = &e;
@@ -183,15 +190,25 @@ int launch_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, bool
         return ctx->fail(VHR_ERROR_DEVICE, "vhr_ray_query: hipMemsetAsync failed");
     const QueueLaunch ql = queue_launch(ctx, kOptLdsStackLevels, kOptEarlyExit, 2u);
     const dim3 grid(uint32_t((uint64_t(count) + 2u * kQueryWaveRays - 1u) / (2u * kQueryWaveRays)));
-    ctx->time_begin(kKernelRayQuery);
     // the flag on a scene none of whose primitives can discard asks for nothing: the plain kernels
     const bool alpha = alpha_test && ctx->scene_can_discard;
-    with_bool(ql.spill, [&](auto sp) { with_bool(alpha, [&](auto al) {
+    // the mask likewise: the filtering kernels only where the cull mask acts on the masks the primitives carry, or with per-ray masks (one may be 0)
+    const bool mask_acts = ray_masks != nullptr || ctx->ray_mask_acts(cull_mask);
+    a.masks = RayMaskArgs{ nullptr, cull_mask, cull_mask, cull_mask, alpha ? 1u : 0u };
+    a.ray_masks = ray_masks;
+    if (mask_acts) {
+        if (const int rc = ensure_device_prim_masks(ctx)) return rc;
+        a.masks.prim_masks = ctx->d_prim_masks;
+        ctx->rq_mask_ran = 1;
+    }
+    const int filter = launch_filter(mask_acts, alpha);
+    ctx->time_begin(kKernelRayQuery);
+    with_bool(ql.spill, [&](auto sp) { with_filter(filter, [&](auto al) {
         launch(ctx, ray_query_kernel<decltype(sp)::value, decltype(al)::value>, grid, dim3(kQueueBlock * 2), ql.lds_bytes, a, ql.levels, ql.threshold, ql.early_exit);
     }); });
     if (a.scene.node_count != 0) {
         const uint32_t redo_blocks = std::min<uint32_t>((count + kTraceBlock - 1u) / kTraceBlock, uint32_t(ctx->cu_count) * 4u);
-        with_bool(alpha, [&](auto al) { launch(ctx, ray_query_redo_kernel<decltype(al)::value>, dim3(redo_blocks), dim3(kTraceBlock), 0, a); });
+        with_filter(filter, [&](auto al) { launch(ctx, ray_query_redo_kernel<decltype(al)::value>, dim3(redo_blocks), dim3(kTraceBlock), 0, a); });
     }
     ctx->time_end(kKernelRayQuery);
     if (hipGetLastError() != hipSuccess) return ctx->fail(VHR_ERROR_DEVICE, "vhr_ray_query: kernel launch failed");

@@ -47,12 +47,15 @@ struct RaygenArgs {
     uint32_t fuse_temporal;  // 0 = off
     TemporalArgs temporal;
     CostOrderArgs co;        // "raygen_cost_order" (the default queue kernel, the mirror-ray queue kernel)
+    RayMaskArgs masks;       // ray cull masks: read by the kFilterMask instantiations only (last, so that no other argument moves)
 };
 
 // raygen.rgen:26-55 for one covered pixel: its shadow ray and its AO rays one after another (the walker with the whole of decision (vi): traverse<> ->
 // ray_triangle).  STRIDE: the stack's (kTraceBlock: the per-pixel kernels' LDS columns; 1: a private array).
-// ALPHA ("alpha_test_rays" on a scene that can discard, in every kernel of this file): a candidate gbuf_discarded names does not exist for the ray.
-template <int STRIDE, bool ALPHA = false>
+// FILTER (in every kernel of this file): kFilterAlpha ("alpha_test_rays" on a scene that can discard) -- a candidate gbuf_discarded names does not exist
+// for the ray; kFilterMask (a ray-class mask that acts: vhr_context::ray_mask_acts) -- a candidate whose primitive's mask shares no bit with the ray's class mask
+// does not exist, and by a.masks.alpha the alpha rule applies behind it.
+template <int STRIDE, int FILTER = kFilterNone>
 __device__ __forceinline__ void pixel_visibility(const RaygenArgs &a, const uint32_t x, const uint32_t y, const float depth, int *stack, uint32_t &overflow,
                                                  f3 &P, f3 &N, f3 &origin, float &shadow_payload, float &ao_payload) {
     const uint32_t W = a.width, H = a.height;
@@ -74,7 +77,7 @@ __device__ __forceinline__ void pixel_visibility(const RaygenArgs &a, const uint
         const f3 cone_dir = normalize3(uniform_sample_cone(rnd1, rnd2, a.tp.cone_cos_max));   // rgen:34
         const f3 dir = onb_transform(L, cone_dir);                                       // rgen:35,40
         // rgen:37-41 issues this trace four times with identical arguments; once is equivalent
-        const bool occluded = traverse<true, false, STRIDE>(a.scene, origin, dir, a.tp.tmin, a.tp.tmax, stack, hit, overflow, alpha_reject<ALPHA>(a.scene));
+        const bool occluded = traverse<true, false, STRIDE>(a.scene, origin, dir, a.tp.tmin, a.tp.tmax, stack, hit, overflow, ray_filter<FILTER>(a.scene, a.masks, a.masks.shadow));
         shadow_payload = occluded ? 0.0f : 1.0f;                                         // miss.rmiss:7
     }
     ao_payload = 0.0f;                                                                   // rgen:44-55
@@ -83,7 +86,7 @@ __device__ __forceinline__ void pixel_visibility(const RaygenArgs &a, const uint
         rnd2 = random01(rng);
         const f3 rnd_dir = cosine_hemisphere(rnd1, rnd2);
         const f3 dir = onb_transform(N, rnd_dir);
-        const bool occluded = traverse<true, false, STRIDE>(a.scene, origin, dir, a.tp.tmin, a.tp.ao_tmax, stack, hit, overflow, alpha_reject<ALPHA>(a.scene));
+        const bool occluded = traverse<true, false, STRIDE>(a.scene, origin, dir, a.tp.tmin, a.tp.ao_tmax, stack, hit, overflow, ray_filter<FILTER>(a.scene, a.masks, a.masks.ao));
         ao_payload += occluded ? 0.0f : 1.0f;
     }
     if (a.tp.ao_spp) ao_payload /= float(a.tp.ao_spp); else ao_payload = 1.0f;
@@ -94,18 +97,18 @@ __device__ __forceinline__ void pixel_visibility(const RaygenArgs &a, const uint
 // test the binary64 arithmetic cost the kernel 13 registers = a wave per SIMD, 1.3-1.5 % of the frame: profiles/r6_decision_vi_cost.txt).  `a` points at
 // the launch's arguments where they lie in memory (the address of a by-value argument would copy all of it to every lane's scratch).  At 1080p:
 // none to three pixels of a frame on the BASELINE stand-ins, up to ~70 on sponza_hard_rot (profiles/r6_decision_vi_cost.txt).
-template <bool ALPHA = false>
+template <int FILTER = kFilterNone>
 __device__ VHR_REDO_INLINE float2 redo_pixel_visibility(const RaygenArgs *a, const uint32_t x, const uint32_t y) {
     int st[kTraceStack];
     uint32_t overflow = 0;
     f3 P, N, origin;
     float shadow_payload, ao_payload;
-    pixel_visibility<1, ALPHA>(*a, x, y, a->depth[size_t(y) * a->width + x], st, overflow, P, N, origin, shadow_payload, ao_payload);
+    pixel_visibility<1, FILTER>(*a, x, y, a->depth[size_t(y) * a->width + x], st, overflow, P, N, origin, shadow_payload, ao_payload);
     return float2{ shadow_payload, ao_payload };
 }
 
 // raygen.rgen:14-66 for one pixel
-template <bool ALPHA = false>
+template <int FILTER = kFilterNone>
 __device__ __forceinline__ void raygen_pixel(const RaygenArgs &a, const uint32_t x, const uint32_t y, int *stack, uint32_t &overflow, bool &covered, bool &second_ray) {
     const uint32_t W = a.width;
     const float depth = a.depth[size_t(y) * W + x];                                      // rgen:19
@@ -117,7 +120,7 @@ __device__ __forceinline__ void raygen_pixel(const RaygenArgs &a, const uint32_t
     covered = true;
     f3 P, N, origin;
     float shadow_payload, ao_payload;
-    pixel_visibility<kTraceBlock, ALPHA>(a, x, y, depth, stack, overflow, P, N, origin, shadow_payload, ao_payload);
+    pixel_visibility<kTraceBlock, FILTER>(a, x, y, depth, stack, overflow, P, N, origin, shadow_payload, ao_payload);
     store_rg16f(a.shadow_ao, W, x, y, shadow_payload, ao_payload);                       // rgen:57
 
     if (a.reflections) {
@@ -127,13 +130,13 @@ __device__ __forceinline__ void raygen_pixel(const RaygenArgs &a, const uint32_t
             const f3 I = normalize3(P - cam);
             const float ni2 = 2.0f * dot3(N, I);
             const f3 rdir = I - N * ni2;                                                 // reflect(I, N)
-            payload = trace_reflection<kTraceBlock, ALPHA>(a.scene, a.pfd, a.tp, origin, rdir, stack, overflow, second_ray);
+            payload = trace_reflection<kTraceBlock>(a.scene, a.pfd, a.tp, origin, rdir, stack, overflow, second_ray, ray_filter<FILTER>(a.scene, a.masks, a.masks.reflection));
         }
         store_rgba16f(a.reflections, W, x, y, payload.x, payload.y, payload.z, payload.w);
     }
 }
 
-template <bool ALPHA = false>
+template <int FILTER = kFilterNone>
 __global__ __launch_bounds__(kTraceBlock) void raygen_kernel(const RaygenArgs a, const Stamps st) {
     vhr_stamp(st);
     __shared__ int s_stack[kTraceStack * kTraceBlock];
@@ -142,7 +145,7 @@ __global__ __launch_bounds__(kTraceBlock) void raygen_kernel(const RaygenArgs a,
     pixel_of_thread(x, y, a.row_begin);
     uint32_t overflow = 0;
     bool covered = false, second_ray = false;
-    if (x < a.width && y < a.row_end) raygen_pixel<ALPHA>(a, x, y, stack, overflow, covered, second_ray);
+    if (x < a.width && y < a.row_end) raygen_pixel<FILTER>(a, x, y, stack, overflow, covered, second_ray);
     if (a.stats) {
         const unsigned long long cov = __ballot(covered), ovf = __ballot(overflow != 0), sec = __ballot(second_ray);
         if ((threadIdx.x & 63u) == 0) {
@@ -174,8 +177,9 @@ __global__ __launch_bounds__(kTraceBlock) void raygen_kernel(const RaygenArgs a,
 // live in scratch.  STATS: in-kernel counters and timers (vhr_set_ray_statistics).  Per covered pixel the wave keeps 5 words in LDS -- the ray
 // origin and the G-buffer normal as the halves it is -- and recomputes the pixel's seed and the ray's direction at refill with raygen.rgen's
 // exact arithmetic.
-// ALPHA ("alpha_test_rays"): the leaf test asks gbuf_discarded about every consistent candidate before it ends the ray.
-template <int WAVES, bool COMPACT, bool SPILL, bool STATS, bool FUSE = false, bool ALPHA = false>
+// FILTER: kFilterAlpha ("alpha_test_rays"): the leaf test asks gbuf_discarded about every consistent candidate before it ends the ray (DESIGN.md
+// section 4b); kFilterMask: it first tests the primitive's mask byte against the class mask of the lane's ray kind.
+template <int WAVES, bool COMPACT, bool SPILL, bool STATS, bool FUSE = false, int FILTER = kFilterNone>
 __global__ __launch_bounds__(kQueueBlock *WAVES) __attribute__((amdgpu_waves_per_eu(VHR_K1_WAVES_MIN, 8))) void raygen_queue_kernel(const RaygenArgs a, const uint32_t stack_levels, const uint32_t refill_threshold,
                                                                           const uint32_t block_tiles_x, const uint32_t early_exit, const uint32_t tile_rows, const uint32_t steal_threshold, const Stamps st) {
     vhr_stamp(st);
@@ -446,7 +450,11 @@ __global__ __launch_bounds__(kQueueBlock *WAVES) __attribute__((amdgpu_waves_per
                 // (the consistency test behind the candidates only: few tests get this far, and a wave whose lanes all failed skips it)
                 if (mt_candidate(ro, rd, v0, e1, e2, tmin, tmax, ct, cu, cv)) {
                     if (solution_consistent(ro, rd, v0, e1, e2, ct, cu, cv)) {
-                        if constexpr (ALPHA) { if (gbuf_discarded(a.scene, first + i, cu, cv)) continue; }      // a hole: the candidate does not exist
+                        if constexpr (FILTER == kFilterAlpha) { if (gbuf_discarded(a.scene, first + i, cu, cv)) continue; }      // a hole: the candidate does not exist
+                        if constexpr (FILTER == kFilterMask) {          // the ray's class by its kind, the mask test first: a culled candidate does not exist
+                            if ((uint32_t(a.masks.prim_masks[leaf[i].prim]) & (kind == 0 ? a.masks.shadow : a.masks.ao)) == 0u) continue;
+                            if (a.masks.alpha && gbuf_discarded(a.scene, first + i, cu, cv)) continue;
+                        }
                         found = true;
                         break;
                     }
@@ -508,7 +516,7 @@ __global__ __launch_bounds__(kQueueBlock *WAVES) __attribute__((amdgpu_waves_per
         if (a.tp.ao_spp) ao_payload = float(a.scene.node_count == 0 ? a.tp.ao_spp : (kind_bits ? a.tp.ao_spp - uint32_t(__popc(vis >> 1)) : (vis >> 8))) / float(a.tp.ao_spp);   // rgen:55: the AO rays that escaped
         if (vis & kRedoPixel) {                           // decision (vi): one of this pixel's rays met a candidate that contradicts itself
             static_assert(offsetof(RaygenArgs, scene) == 0, "the launch's arguments start with `a`");
-            const float2 again = redo_pixel_visibility<ALPHA>(reinterpret_cast<const RaygenArgs *>((const void *)__builtin_amdgcn_kernarg_segment_ptr()), x, y);
+            const float2 again = redo_pixel_visibility<FILTER>(reinterpret_cast<const RaygenArgs *>((const void *)__builtin_amdgcn_kernarg_segment_ptr()), x, y);
             shadow_payload = again.x; ao_payload = again.y;
             n_redo = 1;
         }
@@ -562,7 +570,7 @@ __global__ __launch_bounds__(kQueueBlock *WAVES) __attribute__((amdgpu_waves_per
 }
 
 // Mirror ray of raygen.rgen:59-65 (closest hit, reflection_hit.rchit / reflection_miss.rmiss) for one pixel of the image
-template <int STRIDE, bool ALPHA = false>
+template <int STRIDE, int FILTER = kFilterNone>
 __device__ __forceinline__ f4 reflection_payload(const RaygenArgs &a, const uint32_t x, const uint32_t y, int *stack, bool &second_ray) {
     const uint32_t W = a.width, H = a.height;
     f4 payload = f4{ 0.0f, 0.0f, 0.0f, 0.0f };
@@ -578,13 +586,13 @@ __device__ __forceinline__ f4 reflection_payload(const RaygenArgs &a, const uint
         const float ni2 = 2.0f * dot3(N, I);
         const f3 rdir = I - N * ni2;
         uint32_t overflow = 0;
-        payload = trace_reflection<STRIDE, ALPHA>(a.scene, a.pfd, a.tp, origin, rdir, stack, overflow, second_ray);
+        payload = trace_reflection<STRIDE>(a.scene, a.pfd, a.tp, origin, rdir, stack, overflow, second_ray, ray_filter<FILTER>(a.scene, a.masks, a.masks.reflection));
     }
     return payload;
 }
-template <bool ALPHA = false>
+template <int FILTER = kFilterNone>
 __device__ __forceinline__ void reflection_pixel(const RaygenArgs &a, const uint32_t x, const uint32_t y, int *stack, bool &second_ray) {
-    const f4 payload = reflection_payload<kTraceBlock, ALPHA>(a, x, y, stack, second_ray);
+    const f4 payload = reflection_payload<kTraceBlock, FILTER>(a, x, y, stack, second_ray);
     store_rgba16f(a.reflections, a.width, x, y, payload.x, payload.y, payload.z, payload.w);
 }
 
@@ -596,16 +604,16 @@ __device__ __forceinline__ void reflection_pixel(const RaygenArgs &a, const uint
 // the waves the scratch ring then had room for).  About one pixel of a 1080p frame on the BASELINE stand-ins, ~70-100 on sponza_hard_rot.  `second`: a second-bounce ray was
 // traced (the launch's ray count).
 struct RedoReflection { f4 payload; uint32_t second; };
-template <bool ALPHA = false>
+template <int FILTER = kFilterNone>
 __device__ __attribute__((noinline)) RedoReflection redo_pixel_reflection(const RaygenArgs *a, const uint32_t x, const uint32_t y) {
     int st[kTraceStack];
     bool second_ray = false;
-    const f4 payload = reflection_payload<1, ALPHA>(*a, x, y, st, second_ray);
+    const f4 payload = reflection_payload<1, FILTER>(*a, x, y, st, second_ray);
     return RedoReflection{ payload, second_ray ? 1u : 0u };
 }
 
 // ... one pixel per thread
-template <bool ALPHA = false>
+template <int FILTER = kFilterNone>
 __global__ __launch_bounds__(kTraceBlock) void reflection_kernel(const RaygenArgs a, const Stamps st) {
     vhr_stamp(st);
     __shared__ int s_refl_stack[kTraceStack * kTraceBlock];
@@ -613,7 +621,7 @@ __global__ __launch_bounds__(kTraceBlock) void reflection_kernel(const RaygenArg
     uint32_t x, y;
     pixel_of_thread(x, y, a.row_begin);
     bool second_ray = false;
-    if (x < a.width && y < a.row_end) reflection_pixel<ALPHA>(a, x, y, stack, second_ray);
+    if (x < a.width && y < a.row_end) reflection_pixel<FILTER>(a, x, y, stack, second_ray);
     if (a.stats) {
         const unsigned long long sec = __ballot(second_ray);
         if ((threadIdx.x & 63u) == 0 && sec) atomicAdd(&a.stats->second_bounce_rays, (unsigned long long)__popcll(sec));
@@ -645,8 +653,8 @@ __device__ __forceinline__ void mirror_ray_of_pixel(const RaygenArgs &a, f3 cam,
     rdir = I - N * ni2;                                                                      // rgen:61 reflect(I, N)
 }
 
-// ALPHA ("alpha_test_rays"): the walk's Reject is GbufDiscard, behind decision (vi) as ever; phase 3's redo applies it as well.
-template <bool SPILL, int BOUNCES, bool STATS = false, bool ALPHA = false>
+// FILTER: the walk's Reject is GbufDiscard ("alpha_test_rays") or RayMaskReject ("reflection_ray_mask"), behind decision (vi) as ever; phase 3's redo applies it as well.
+template <bool SPILL, int BOUNCES, bool STATS = false, int FILTER = kFilterNone>
 __global__ __launch_bounds__(kQueueBlock * 2) __attribute__((amdgpu_waves_per_eu(7, 7))) void reflection_queue_kernel(
     const RaygenArgs a, const uint32_t stack_levels, const uint32_t refill_threshold, const uint32_t tiles_x, const uint32_t tiles_total,
     const uint32_t early_exit, const Stamps st) {
@@ -738,7 +746,7 @@ __global__ __launch_bounds__(kQueueBlock * 2) __attribute__((amdgpu_waves_per_eu
             s_ray[orow][pix] = __uint_as_float(tri); s_ray[orow + 1][pix] = u; s_ray[orow + 2][pix] = v;
         }, &wc,
         [&](uint32_t pix) { atomicOr(&s_redo[pix >> 5], 1u << (pix & 31u)); },                    // decision (vi): the pixel is computed again in phase 3
-        alpha_reject<ALPHA>(a.scene));
+        ray_filter<FILTER>(a.scene, a.masks, a.masks.reflection));
     wave_lds_sync();
     if (STATS) t_walk += __builtin_readcyclecounter() - tw0;
     if constexpr (BOUNCES > 1) if (bounce == 0) {
@@ -786,7 +794,7 @@ __global__ __launch_bounds__(kQueueBlock * 2) __attribute__((amdgpu_waves_per_eu
         const uint32_t tri = traced ? __float_as_uint(s_ray[0][p]) : kNoHit;
         if (traced && ((s_redo[p >> 5] >> (p & 31u)) & 1u)) {                                // decision (vi): this pixel's ray asked for binary64
             static_assert(offsetof(RaygenArgs, scene) == 0, "the launch's arguments start with `a`");
-            const RedoReflection again = redo_pixel_reflection<ALPHA>(reinterpret_cast<const RaygenArgs *>((const void *)__builtin_amdgcn_kernarg_segment_ptr()), x, y);
+            const RedoReflection again = redo_pixel_reflection<FILTER>(reinterpret_cast<const RaygenArgs *>((const void *)__builtin_amdgcn_kernarg_segment_ptr()), x, y);
             payload = again.payload;
             ++n_redo;
             if (BOUNCES > 1) redo_second += int(again.second) - int(tri != kNoHit);          // (the launch's count of second-bounce rays)
@@ -843,16 +851,18 @@ __global__ __launch_bounds__(kQueueBlock * 2) __attribute__((amdgpu_waves_per_eu
 // (vhr_update_geometry looked); everywhere else the launches are the ones they were before the switch existed.
 static bool alpha_rays(const vhr_context *ctx) { return ctx->alpha_test_rays != 0 && ctx->scene_can_discard; }
 
+
 // The shadow / AO launch itself, by the options in force (everything launch_raygen decided is in `a`).  `alpha`: alpha_rays() as launch_raygen
-// saw it (a launch held back for "fuse_temporal" never has it).
-static void issue_raygen(vhr_context *ctx, const RaygenArgs &a_in, const uint32_t width, const uint32_t height, const bool alpha = false) {
+// saw it, `filter`: the launch's launch_filter() (a launch held back for "fuse_temporal" has neither).
+static void issue_raygen(vhr_context *ctx, const RaygenArgs &a_in, const uint32_t width, const uint32_t height, const bool alpha = false, const int filter = kFilterNone) {
     RaygenArgs a = a_in;
     a.co = CostOrderArgs{};
     (void)height;
     ctx->time_begin(kKernelRaygen);
     if (alpha) ++ctx->alpha_launches;
+    if (filter == kFilterMask) ++ctx->mask_launches;
     if (ctx->options[kOptRaygenVariant] == 0) {
-        with_bool(alpha, [&](auto al) { launch(ctx, raygen_kernel<decltype(al)::value>, dim3((width + 15) / 16, (a.row_end - a.row_begin + 15) / 16), dim3(kTraceBlock), 0, a); });
+        with_filter(filter, [&](auto al) { launch(ctx, raygen_kernel<decltype(al)::value>, dim3((width + 15) / 16, (a.row_end - a.row_begin + 15) / 16), dim3(kTraceBlock), 0, a); });
     } else {
         const uint32_t rows_traced = a.row_end - a.row_begin;
         // rows of a wave's tile: 8, or ("raygen_tile_rows" 0 = auto, the default) 6 for a launch whose 8x8 tiles would fill less than 70 % of the
@@ -880,12 +890,12 @@ static void issue_raygen(vhr_context *ctx, const RaygenArgs &a_in, const uint32_
             constexpr int WV = decltype(waves_c)::value;
             with_bool(q.spill, [&](auto sp) {
                 constexpr bool SP = decltype(sp)::value;
-                if (a.fuse_temporal && compact && !a.stats && !alpha) {   // "fuse_temporal": svgf.comp in the tiles' epilogues (the default node form only)
+                if (a.fuse_temporal && compact && !a.stats && filter == kFilterNone) {   // "fuse_temporal": svgf.comp in the tiles' epilogues (the default node form only)
                     go(raygen_queue_kernel<WV, true, SP, false, true>);
                     return;
                 }
                 with_bool(compact, [&](auto co) {
-                    with_bool(a.stats != nullptr, [&](auto st) { with_bool(alpha, [&](auto al) {
+                    with_bool(a.stats != nullptr, [&](auto st) { with_filter(filter, [&](auto al) {
                         go(raygen_queue_kernel<WV, decltype(co)::value, SP, decltype(st)::value, false, decltype(al)::value>);
                     }); });
                 });
@@ -959,6 +969,7 @@ int launch_raygen(vhr_context *ctx, const vhr_per_frame_data &pfd, uint32_t widt
     a.stats = ctx->ray_stats_enabled ? ctx->d_ray_stats : nullptr;
     ctx->raytraced_pixels = 0;                 // ray statistics are the hybrid path's again
     ctx->alpha_launches = 0;
+    ctx->mask_launches = 0;
     if (a.row_end <= a.row_begin || a.col_end <= a.col_begin) return VHR_OK;
     if (ctx->options[kOptTraceOverlap]) {      // strips / tiles: trace the margin the denoiser recomputes too (no exchange of raw visibility)
         a.row_begin = owned_begin > ctx->overlap ? owned_begin - ctx->overlap : 0u;
@@ -971,13 +982,23 @@ int launch_raygen(vhr_context *ctx, const vhr_per_frame_data &pfd, uint32_t widt
     // images, the queue kernel runs it in its tiles' epilogues (flush_deferred_raygen).  Only the default kernel has that epilogue, only
     // whole-image work on one stream qualifies, and only a pass nobody hooked an epilogue to (its owner expects the image when it runs).
     // With "alpha_test_rays" in force the launch is not held back: the epilogue has no alpha instantiation, the SVGF pass runs its own dispatch.
+    // The ray-class masks likewise: where the shadow or the AO mask acts the launch filters and is not held back.  (The per-pixel kernel of
+    // "raygen_variant" 0 traces the mirror ray too: one launch, one filter for the three classes.)
     const bool alpha = alpha_rays(ctx);
+    a.masks = RayMaskArgs{ nullptr, uint32_t(ctx->shadow_ray_mask), uint32_t(ctx->ao_ray_mask), uint32_t(ctx->reflection_ray_mask), alpha ? 1u : 0u };
+    const bool mirror_acts = a.reflections && a.tp.reflections && ctx->ray_mask_acts(a.masks.reflection);
+    const bool visibility_acts = ctx->ray_mask_acts(a.masks.shadow) || ctx->ray_mask_acts(a.masks.ao) || (ctx->options[kOptRaygenVariant] == 0 && mirror_acts);
+    if (visibility_acts || mirror_acts) {
+        if (const int rc = ensure_device_prim_masks(ctx)) return rc;
+        a.masks.prim_masks = ctx->d_prim_masks;
+    }
+    const int filter = launch_filter(visibility_acts, alpha);
     {
         // (the epilogue exists in the queue kernel on the 32-byte nodes only: issue_raygen)
         const bool default_kernel = ctx->options[kOptRaygenVariant] != 0 && ctx->options[kOptCompactNodes] != 0 && ctx->nodes16_valid;
         const bool whole = a.row_begin == 0 && a.row_end == height && a.col_begin == 0 && a.col_end == width;
         const bool mirror = a.reflections && a.tp.reflections;
-        if (ctx->options[kOptFuseTemporal] && !alpha && ctx->may_defer_raygen && default_kernel && whole && !mirror && !a.stats && ctx->frames_in_flight == 1 &&
+        if (ctx->options[kOptFuseTemporal] && filter == kFilterNone && ctx->may_defer_raygen && default_kernel && whole && !mirror && !a.stats && ctx->frames_in_flight == 1 &&
             (ctx->in_kernel_stamps() || !ctx->options[kOptPassTimestamps]) && a.scene.node_count != 0) {
             a.fuse_temporal = 0u;
             DeferredRaygen d;
@@ -990,7 +1011,7 @@ int launch_raygen(vhr_context *ctx, const vhr_per_frame_data &pfd, uint32_t widt
             return VHR_OK;
         }
     }
-    issue_raygen(ctx, a, width, height, alpha);
+    issue_raygen(ctx, a, width, height, alpha, filter);
     // The mirror ray's launch (raygen.rgen:59-65): not denoised, so owned rows (and columns) only.  It runs BEHIND the shadow / AO launch: beside it
     // (a second stream) the two take as long as one after the other, and with walk and shading in two launches the walk is no faster
     // (profiles/r4_reflection_concurrent.txt, r4d/r4e logs in profiles/r4_reflection_split.txt).
@@ -1023,6 +1044,8 @@ int launch_raygen(vhr_context *ctx, const vhr_per_frame_data &pfd, uint32_t widt
         }
         ctx->time_begin(kKernelReflection);
         if (alpha) ++ctx->alpha_launches;
+        const int mirror_filter = launch_filter(mirror_acts, alpha);
+        if (mirror_filter == kFilterMask) ++ctx->mask_launches;
         if (m.tp.reflections <= 2 && ctx->options[kOptReflectionVariant] != 0) {
             const QueueLaunch q = queue_launch(ctx, kOptReflectionLdsStackLevels, kOptReflectionEarlyExit, 2u);
             const TileGrid g = tile_grid(m.col_end - m.col_begin, owned_end - owned_begin, 8u);      // (reflection_queue_kernel: 8 x 8 pixels per wave)
@@ -1034,12 +1057,12 @@ int launch_raygen(vhr_context *ctx, const vhr_per_frame_data &pfd, uint32_t widt
             with_bool(q.spill, [&](auto sp) { with_bool(m.tp.reflections == 2, [&](auto two) { with_bool(m.stats != nullptr, [&](auto st) {
                 constexpr bool SP = decltype(sp)::value, ST = decltype(st)::value;
                 constexpr int B = decltype(two)::value ? 2 : 1;
-                with_bool(alpha, [&](auto al) {
+                with_filter(mirror_filter, [&](auto al) {
                     launch(ctx, reflection_queue_kernel<SP, B, ST, decltype(al)::value>, g.grid, g.block, q.lds_bytes, m, q.levels, q.threshold, g.tiles_x, g.tiles_total, q.early_exit);
                 });
             }); }); });
         } else {
-            with_bool(alpha, [&](auto al) { launch(ctx, reflection_kernel<decltype(al)::value>, dim3((width + 15) / 16, (owned_end - owned_begin + 15) / 16), dim3(kTraceBlock), 0, m); });
+            with_filter(mirror_filter, [&](auto al) { launch(ctx, reflection_kernel<decltype(al)::value>, dim3((width + 15) / 16, (owned_end - owned_begin + 15) / 16), dim3(kTraceBlock), 0, m); });
         }
         ctx->time_end(kKernelReflection);
         if (on_own_stream) {

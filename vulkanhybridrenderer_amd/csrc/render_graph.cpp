@@ -353,7 +353,8 @@ int vhr_graph_execute(vhr_context *ctx, uint32_t resource_idx, uint32_t image_id
         // this frame's front rewrites the slot's images: the back of the frame that used the slot last has to be through with them
         if (split && ctx->back_pending[slot]) HIP_TRY(ctx, hipStreamWaitEvent(ctx->front_stream, ctx->back_done[slot], 0));
     }
-    struct RestoreStream { vhr_context *c; hipStream_t s; ~RestoreStream() { c->stream = s; } } restore{ ctx, back };
+    struct RestoreStream { vhr_context *c; hipStream_t s; ~RestoreStream() { c->stream = s; c->in_execute = false; } } restore{ ctx, back };
+    ctx->in_execute = true;            // (cur_pass is set for stamped library passes only: this covers every callback of the frame)
     for (size_t pi = 0; pi < ctx->execution_order.size(); ++pi) {
         PassDescription &p = ctx->pass_descriptions[ctx->execution_order[pi]];
         ctx->stream = (split && pi < ctx->front_passes) ? ctx->front_stream : back;

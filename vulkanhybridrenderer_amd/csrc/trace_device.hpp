@@ -305,6 +305,40 @@ template <bool ALPHA> __device__ __forceinline__ AlphaReject<ALPHA> alpha_reject
     if constexpr (ALPHA) return GbufDiscard{ &sc }; else return NoReject{};
 }
 
+// Ray cull masks (vhr_set_primitive_masks, vhr_ray_query_masked, the "*_ray_mask" options): a candidate on primitive p does not exist for a
+// ray of mask m iff (masks[p] & m) == 0 -- VkAccelerationStructureInstanceKHR::mask against traceRayEXT's cullMask, per geometry.  The kernels
+// that filter carry this in their launch arguments (RaygenArgs, RayQueryArgs), never in DeviceScene.
+struct RayMaskArgs {
+    const uint8_t *prim_masks;            // one byte per primitive (never null in a launch that filters)
+    uint32_t shadow, ao, reflection;      // the hybrid path's class masks; the ray query: `shadow` = its cull_mask
+    uint32_t alpha;                       // wave-uniform: the alpha rule (gbuf_discarded) applies as well, behind the mask test
+};
+// RayMaskReject: the mask test, then (by the runtime bit) the alpha rule.  kAtHit, like GbufDiscard.  In wave_queue_walk the ray id picks the
+// ray's own mask where the launch has per-ray masks (the batched query), read at the candidate.
+struct RayMaskReject {
+    static constexpr bool kActive = true;
+    static constexpr bool kAtHit = true;
+    const DeviceScene *sc;
+    const uint8_t *prim_masks, *ray_masks;
+    uint32_t mask, alpha;
+    __device__ __forceinline__ bool culled(uint32_t tri, uint32_t m, float u, float v) const {
+        if ((uint32_t(prim_masks[sc->tris[tri].prim]) & m) == 0u) return true;
+        return alpha != 0u && gbuf_discarded(*sc, tri, u, v);
+    }
+    __device__ __forceinline__ bool operator()(uint32_t tri, float u, float v) const { return culled(tri, mask, u, v); }
+    __device__ __forceinline__ bool operator()(uint32_t ray, uint32_t tri, float u, float v) const {
+        return culled(tri, ray_masks ? uint32_t(ray_masks[ray]) & mask : mask, u, v);
+    }
+};
+// the hybrid path's and the ray query's walkers by their candidate filter: none, the alpha rule, or the mask (with the alpha rule as a runtime bit)
+constexpr int kFilterNone = 0, kFilterAlpha = 1, kFilterMask = 2;
+template <int FILTER> using RayFilter = std::conditional_t<FILTER == kFilterMask, RayMaskReject, AlphaReject<FILTER == kFilterAlpha>>;
+template <int FILTER> __device__ __forceinline__ RayFilter<FILTER> ray_filter(const DeviceScene &sc, const RayMaskArgs &m, uint32_t ray_mask,
+                                                                             const uint8_t *ray_masks = nullptr) {
+    if constexpr (FILTER == kFilterMask) return RayMaskReject{ &sc, m.prim_masks, ray_masks, ray_mask, m.alpha };
+    else return alpha_reject<FILTER == kFilterAlpha>(sc);
+}
+
 template <bool ANY_HIT, bool ALPHA = false, int STRIDE = kTraceBlock, typename Reject = NoReject>
 __device__ __forceinline__ bool traverse(const DeviceScene &sc, f3 o, f3 d, float tmin, float tmax, int *stack, Hit &best,
                                          uint32_t &overflow, Reject reject = Reject{}) {
@@ -469,13 +503,13 @@ __device__ __forceinline__ void hit_position_normal(const DeviceScene &sc, const
 
 // The mirror ray of raygen.rgen:59-65 with the optional second bounce: a mirror ray from the first hit about the shader's N
 // (normalised, facing the incoming ray), origin biased like raygen.rgen:29, shaded by reflection_hit.rchit without recursion.
-// ALPHA ("alpha_test_rays"): both bounces skip the candidates gbuf_discarded names.
-template <int STRIDE = kTraceBlock, bool ALPHA = false>
+// `reject` ("alpha_test_rays": GbufDiscard; "reflection_ray_mask": RayMaskReject): both bounces skip the candidates it names.
+template <int STRIDE = kTraceBlock, typename Reject = NoReject>
 __device__ __forceinline__ f4 trace_reflection(const DeviceScene &sc, const vhr_per_frame_data &pfd, const vhr_trace_params &tp, f3 origin,
-                                               f3 rdir, int *stack, uint32_t &overflow, bool &second_ray) {
+                                               f3 rdir, int *stack, uint32_t &overflow, bool &second_ray, Reject reject = Reject{}) {
     Hit hit;
     second_ray = false;
-    if (!traverse<false, false, STRIDE>(sc, origin, rdir, tp.tmin, tp.tmax, stack, hit, overflow, alpha_reject<ALPHA>(sc))) return f4{ 0.0f, 0.0f, 0.0f, 0.0f };   // reflection_miss.rmiss:7
+    if (!traverse<false, false, STRIDE>(sc, origin, rdir, tp.tmin, tp.tmax, stack, hit, overflow, reject)) return f4{ 0.0f, 0.0f, 0.0f, 0.0f };   // reflection_miss.rmiss:7
     if (tp.reflections < 2) return shade_reflection_hit(sc, pfd, hit);
     f3 hp, hn;
     (void)shade_reflection_hit(sc, pfd, hit, nullptr, &hp, &hn);
@@ -487,7 +521,7 @@ __device__ __forceinline__ f4 trace_reflection(const DeviceScene &sc, const vhr_
     second_ray = true;
     Hit hit2;
     f4 second = f4{ 0.0f, 0.0f, 0.0f, 0.0f };
-    if (traverse<false, false, STRIDE>(sc, o2, d2, tp.tmin, tp.tmax, stack, hit2, overflow, alpha_reject<ALPHA>(sc))) second = shade_reflection_hit(sc, pfd, hit2);
+    if (traverse<false, false, STRIDE>(sc, o2, d2, tp.tmin, tp.tmax, stack, hit2, overflow, reject)) second = shade_reflection_hit(sc, pfd, hit2);
     return shade_reflection_hit(sc, pfd, hit, &second);
 }
 

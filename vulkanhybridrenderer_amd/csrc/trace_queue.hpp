@@ -715,6 +715,16 @@ static void with_bool(const bool flag, F &&f) {
     if (flag) f(std::true_type{});
     else f(std::false_type{});
 }
+// A launch's candidate filter (kFilterNone / kFilterAlpha / kFilterMask, trace_device.hpp) likewise: the mask instantiation only where a mask of
+// the launch ACTS on the masks the primitives carry (vhr_context::ray_mask_acts; the alpha rule is then its runtime bit), else the alpha
+// instantiation or the plain kernels, as before masks existed.
+static int launch_filter(const bool mask_acts, const bool alpha) { return mask_acts ? kFilterMask : (alpha ? kFilterAlpha : kFilterNone); }
+template <typename F>
+static void with_filter(const int filter, F &&f) {
+    if (filter == kFilterMask) f(std::integral_constant<int, kFilterMask>{});
+    else if (filter == kFilterAlpha) f(std::integral_constant<int, kFilterAlpha>{});
+    else f(std::integral_constant<int, kFilterNone>{});
+}
 
 // "raygen_cost_order": the cost / order pointers of a queue-kernel launch of `n_blocks` blocks of `wv` waves (see vhr_context::CostOrder).
 // 1 (default) = launches of at least 2 048 blocks (a full round of waves or more), 2 = any launch (tests); the two launches an order connects must

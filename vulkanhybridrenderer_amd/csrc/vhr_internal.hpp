@@ -480,6 +480,23 @@ struct vhr_context {
     // once per vhr_update_geometry; without one the switch and VHR_RAY_QUERY_ALPHA_TEST launch the plain kernels
     bool scene_can_discard = false;
     uint32_t alpha_launches = 0;                 // launches of the last TraceRays that ran an alpha instantiation (vhr_get_binary64_statistics out[2])
+    // Ray cull masks (vhr_set_primitive_masks, vhr_ray_query_masked, "shadow_ray_mask" / "ao_ray_mask" / "reflection_ray_mask"): a candidate on
+    // primitive p does not exist for a ray of mask m iff (masks[p] & m) == 0.  The tree does not depend on them.  h_prim_masks is empty while
+    // every mask is 0xFF (a context that never sets one pays nothing); d_prim_masks is made by the first call that stores a value, or by the
+    // first launch that filters.  mask_present: the distinct values among the primitives' masks (bit v of 256) -- a ray mask m ACTS iff some
+    // present v has (v & m) == 0, and a launch none of whose masks acts is the launch it was before masks existed.
+    std::vector<uint8_t> h_prim_masks;
+    uint8_t *d_prim_masks = nullptr;
+    uint64_t mask_present[4] = { 0, 0, 0, 1ull << 63 };
+    uint64_t masks_not_ff = 0;                   // primitives whose mask is not 0xFF (vhr_get_ray_mask_statistics out[0])
+    int shadow_ray_mask = 255, ao_ray_mask = 255, reflection_ray_mask = 255;      // read at every launch of the hybrid path's rays
+    uint32_t mask_launches = 0;                  // launches of the last TraceRays that ran a mask instantiation (vhr_get_ray_mask_statistics out[1])
+    uint32_t rq_mask_ran = 0;                    // the last ray query ran one (out[2])
+    bool ray_mask_acts(uint32_t m) const {
+        for (uint32_t v = 0; v < 256u; ++v)
+            if (((mask_present[v >> 6] >> (v & 63u)) & 1u) && (v & m) == 0u) return true;
+        return false;
+    }
     // "object_motion_vectors" (vhr_set_option; like "alpha_test_rays" no entry of VHR_OPTION_TABLE): 1 = the refits keep every leaf record's state
     // before the last successful refit, and the stand-in G-buffer reprojects a moved surface through it.  Per record k: d_prev_tris[k] (the whole
     // 48 bytes, in the same slot) and d_prev_saved[k], the number of the refit that last saved it.  Refit number E = motion_epoch + 1 saves a
@@ -631,6 +648,7 @@ struct vhr_context {
     std::vector<vhr::SvgfCmd> recorded;
     int timing_kind = -1;              // kernel kind whose launches are being issued (between time_begin and time_end)
     vhr::PassDescription *cur_pass = nullptr;      // pass whose callback is running (vkCmdWriteTimestamp equivalents)
+    bool in_execute = false;           // inside vhr_graph_execute, any pass's callback included (vhr_set_primitive_masks refuses)
     void time_begin(int kind) { timing_kind = kind; }
     void time_end(int) { timing_kind = -1; }
     void dispatch_events(hipEvent_t &start, hipEvent_t &stop);
@@ -711,6 +729,10 @@ int flush_recorded(vhr_context *ctx);          // issue the commands a compute p
 int launch_calibration_read(vhr_context *ctx, const Image &img, uint32_t bytes_per_lane, uint32_t *sink);
 int launch_ray_triangle_pairs(vhr_context *ctx, const float *pairs, uint32_t n, uint32_t *hit, float *tuv);
 // vhr_ray_query's device path: `rays` (count x vhr_ray) and `results` (vhr_ray_hit or uint8_t per ray) are device memory; enqueued on ctx->stream
-int launch_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, bool any_hit, bool alpha_test, void *results);
+// cull_mask / ray_masks (device memory or null): vhr_ray_query_masked's; vhr_ray_query is (0xFF, null)
+int launch_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, bool any_hit, bool alpha_test, void *results, uint32_t cull_mask = 0xFFu,
+                     const uint8_t *ray_masks = nullptr);
+// the primitives' mask bytes on the device (made, from h_prim_masks or as all-0xFF, if no call has made them yet): before a launch that filters
+int ensure_device_prim_masks(vhr_context *ctx);
 
 }  // namespace vhr

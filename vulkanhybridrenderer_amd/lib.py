@@ -43,6 +43,7 @@ EXPORTS = [
     "vhr_update_vertices", "vhr_update_primitive_transforms", "vhr_refit_geometry", "vhr_get_refit_statistics", "vhr_get_refit_times",
     "vhr_get_bvh_sah_cost", "vhr_refit_geometry_partial", "vhr_get_partial_refit_statistics",
     "vhr_get_object_motion_statistics", "vhr_debug_triangle_records",
+    "vhr_set_primitive_masks", "vhr_get_primitive_masks", "vhr_ray_query_masked", "vhr_get_ray_mask_statistics",
 ]
 
 PATH_PREFIXES = ("hybrid", "raytraced", "rayquery", "forward_raster")      # vhr_<prefix>_{create,destroy,build,rebuild,last_error}
@@ -302,6 +303,10 @@ def load():
     L.vhr_comm_replan.argtypes = [vp, C.POINTER(TilePlanC), i32, i32, i32]
     L.vhr_calibration_stream_read.argtypes = [vp, i32, u32]
     L.vhr_ray_query.argtypes = [vp, vp, u32, u32, vp]
+    L.vhr_ray_query_masked.argtypes = [vp, vp, u32, u32, u32, vp, vp]
+    L.vhr_set_primitive_masks.argtypes = [vp, u32, u32, vp]
+    L.vhr_get_primitive_masks.argtypes = [vp, u32, u32, vp]
+    L.vhr_get_ray_mask_statistics.argtypes = [vp, C.POINTER(u64)]
     L.vhr_get_ray_query_statistics.argtypes = [vp, C.POINTER(u64)]
     L.vhr_ray_query_struct_layout.argtypes = [C.POINTER(u32)]
     L.vhr_update_vertices.argtypes = [vp, u32, u32, vp, u32]
@@ -424,6 +429,7 @@ class Context:
         p = np.ascontiguousarray(primitives)
         assert v.dtype == abi.vertex_dtype and p.dtype == abi.primitive_dtype
         self.check(self.L.vhr_update_geometry(self.handle, _p(v), len(v), _p(i), len(i), _p(p), len(p)), "UpdateGeometry")
+        self._primitive_count = len(p)
 
     # ---- refit: geometry that moves without a rebuild ----
     def update_vertices(self, vertices, first_vertex=0):
@@ -440,6 +446,27 @@ class Context:
         """vhr_update_primitive_transforms: (n, 16) float32, the layout of vhr_primitive::transform (scene.primitives["transform"])."""
         t = np.ascontiguousarray(transforms, np.float32).reshape(-1, 16)
         self.check(self.L.vhr_update_primitive_transforms(self.handle, int(first_primitive), len(t), _p(t) if len(t) else None), "update_primitive_transforms")
+
+    # ---- ray cull masks: per-primitive visibility for rays and ray queries ----
+    def set_primitive_masks(self, masks, first_primitive=0):
+        """vhr_set_primitive_masks: uint8 per primitive from first_primitive on (0xFF after update_geometry).  A candidate hit on primitive p
+        does not exist for a ray of mask m iff (masks[p] & m) == 0.  No refit is needed; takes effect at the next launch."""
+        m = np.ascontiguousarray(masks, np.uint8).reshape(-1)
+        self.check(self.L.vhr_set_primitive_masks(self.handle, int(first_primitive), len(m), _p(m) if len(m) else None), "set_primitive_masks")
+
+    def primitive_masks(self, first_primitive=0, count=None):
+        """vhr_get_primitive_masks: the masks of `count` primitives from first_primitive on (default: all that follow) as uint8."""
+        n = getattr(self, "_primitive_count", 0) - int(first_primitive) if count is None else int(count)
+        out = np.zeros(max(n, 0), np.uint8)
+        self.check(self.L.vhr_get_primitive_masks(self.handle, int(first_primitive), len(out), _p(out) if len(out) else None), "primitive_masks")
+        return out
+
+    def ray_mask_statistics(self):
+        """[primitives whose mask is not 0xFF, launches of the last trace_rays that ran a mask instantiation (0..2), 1 if the last ray
+        query ran one, 0]."""
+        out = (C.c_uint64 * 4)()
+        self.check(self.L.vhr_get_ray_mask_statistics(self.handle, out), "ray_mask_statistics")
+        return [int(x) for x in out]
 
     def refit_geometry(self):
         self.check(self.L.vhr_refit_geometry(self.handle), "refit_geometry")
@@ -855,22 +882,38 @@ class Context:
             a = aligned
         return a
 
-    def ray_query(self, rays, any_hit=False, alpha_test=False):
+    def ray_query(self, rays, any_hit=False, alpha_test=False, cull_mask=None, ray_masks=None):
         """vhr_ray_query on host arrays: rays (n, 8) float32 or abi.ray_dtype.  Returns abi.ray_hit_dtype[n] (closest hit; a miss has
         geometry_index = primitive_index = abi.RAY_MISS) or, with any_hit, bool[n] (occluded).  alpha_test: a candidate hit the G-buffer
-        pass would discard (alpha mask, alpha 0) does not exist for the ray."""
+        pass would discard (alpha mask, alpha 0) does not exist for the ray.  cull_mask (0..255) and / or ray_masks (uint8[n]):
+        vhr_ray_query_masked -- ray i's mask is cull_mask (default 0xFF) & ray_masks[i], and a candidate on a primitive whose mask shares no
+        bit with it does not exist for the ray; with both left at None this is vhr_ray_query itself."""
         r = self._rays_array(rays)
         n = len(r)
         out = np.zeros(n, np.uint8) if any_hit else np.zeros(n, abi.ray_hit_dtype)
         flags = abi.RAY_QUERY_HOST_MEMORY | (abi.RAY_QUERY_TERMINATE_ON_FIRST_HIT if any_hit else 0) | (abi.RAY_QUERY_ALPHA_TEST if alpha_test else 0)
-        self.check(self.L.vhr_ray_query(self.handle, r.ctypes.data if n else None, n, flags, out.ctypes.data if n else None), "ray_query")
+        if cull_mask is None and ray_masks is None:
+            self.check(self.L.vhr_ray_query(self.handle, r.ctypes.data if n else None, n, flags, out.ctypes.data if n else None), "ray_query")
+        else:
+            rm = None
+            if ray_masks is not None:
+                rm = np.ascontiguousarray(ray_masks, np.uint8).reshape(-1)
+                if len(rm) != n:
+                    raise ValueError(f"ray_query: {len(rm)} ray masks for {n} rays")
+            self.check(self.L.vhr_ray_query_masked(self.handle, r.ctypes.data if n else None, n, flags, 0xFF if cull_mask is None else int(cull_mask),
+                                                   rm.ctypes.data if rm is not None and n else None, out.ctypes.data if n else None), "ray_query")
         return out.astype(bool) if any_hit else out
 
-    def ray_query_device(self, rays_ptr, count, results_ptr, any_hit=False, alpha_test=False):
+    def ray_query_device(self, rays_ptr, count, results_ptr, any_hit=False, alpha_test=False, cull_mask=None, ray_masks_ptr=0):
         """vhr_ray_query on device memory (e.g. torch tensors' data_ptr()): `count` vhr_ray records at rays_ptr (16-byte aligned), results
-        (vhr_ray_hit, or one uint8 per ray with any_hit) at results_ptr.  Enqueued on current_stream(); returns without synchronising."""
+        (vhr_ray_hit, or one uint8 per ray with any_hit) at results_ptr.  Enqueued on current_stream(); returns without synchronising.
+        cull_mask and / or ray_masks_ptr (device memory, one uint8 per ray): vhr_ray_query_masked, as in ray_query()."""
         flags = (abi.RAY_QUERY_TERMINATE_ON_FIRST_HIT if any_hit else 0) | (abi.RAY_QUERY_ALPHA_TEST if alpha_test else 0)
-        self.check(self.L.vhr_ray_query(self.handle, rays_ptr or None, int(count), flags, results_ptr or None), "ray_query_device")
+        if cull_mask is None and not ray_masks_ptr:
+            self.check(self.L.vhr_ray_query(self.handle, rays_ptr or None, int(count), flags, results_ptr or None), "ray_query_device")
+        else:
+            self.check(self.L.vhr_ray_query_masked(self.handle, rays_ptr or None, int(count), flags, 0xFF if cull_mask is None else int(cull_mask),
+                                                   ray_masks_ptr or None, results_ptr or None), "ray_query_device")
 
     def ray_query_statistics(self):
         """The last ray query: [rays, rays with a hit, rays decided again in binary64, waves whose stack overflowed (must be 0)]."""
