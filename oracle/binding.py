@@ -17,7 +17,7 @@ _LIB = None
 
 def build(force=False):
     so = os.path.join(_HERE, "libvhr_oracle.so")
-    src = [os.path.join(_HERE, f) for f in ("vhr_oracle.c", "vhr_oracle.h", "Makefile")]
+    src = [os.path.join(_HERE, f) for f in ("vhr_oracle.c", "vhr_oracle.h", "vhr_exact.h", "Makefile")]
     if force or not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in src):
         subprocess.run(["make", "-C", _HERE, "-s"], check=True)
     return so
@@ -64,6 +64,7 @@ def lib():
         L.orc_scene_add_texture.argtypes = [vp, u32, u32, vp, i32, i32, i32, i32, i32]
         L.orc_scene_triangle_count.restype = u32
         L.orc_scene_triangle_count.argtypes = [vp]
+        L.orc_scene_triangles.argtypes = [vp, vp, vp]
         L.orc_scene_occluded.restype = i32
         L.orc_scene_occluded.argtypes = [vp, vp, vp, f32, f32, i32]
         L.orc_scene_closest.restype = i32
@@ -92,6 +93,13 @@ def lib():
         L.orc_audit_begin.argtypes = [i32, u32]
         L.orc_audit_end.restype = u32
         L.orc_audit_end.argtypes = [vp, vp]
+        L.orc_audit_log_rays.argtypes = [u32]
+        L.orc_audit_ray_log.restype = u32
+        L.orc_audit_ray_log.argtypes = [vp]
+        L.orc_ray_triangle_bounds.restype = i32
+        L.orc_ray_triangle_bounds.argtypes = [vp, vp, vp, vp, vp, f32, f32, vp]
+        L.orc_ray_truth.restype = C.c_uint64
+        L.orc_ray_truth.argtypes = [vp, vp, u32, vp, vp, u32, vp, vp]
         L.orc_ray_triangle_exact.restype = i32
         L.orc_ray_triangle_exact.argtypes = [vp, vp, vp, vp, vp, f32, f32, vp]
         L.orc_ray_triangle_rules.restype = i32
@@ -161,6 +169,13 @@ class Scene:
     @property
     def triangle_count(self):
         return lib().orc_scene_triangle_count(self.handle)
+
+    def triangles(self):
+        """((n, 3, 3) float32: v0, e1, e2 of every triangle as the oracle holds them, flat order; (n,) uint32: the triangle's primitive)."""
+        n = self.triangle_count
+        rec, prim = np.zeros((n, 3, 3), np.float32), np.zeros(n, np.uint32)
+        lib().orc_scene_triangles(self.handle, _p(rec), _p(prim))
+        return rec, prim
 
     def occluded(self, o, d, tmin, tmax, use_bvh=True):
         o, d = _c(o, np.float32), _c(d, np.float32)
@@ -335,18 +350,47 @@ audit_record_dtype = np.dtype([
     ("flat", "<u4"), ("mt", "u1"), ("pass_mask", "u1"), ("any_hit", "u1"), ("exact", "i1"), ("cls", "S1"), ("pad_", "u1", (3,))], align=True)
 
 
+RAY_KIND_SHADOW, RAY_KIND_AO, RAY_KIND_MIRROR, RAY_KIND_SECOND_BOUNCE, RAY_KIND_OTHER = 0, 1, 2, 3, 255
+ray_log_dtype = np.dtype([("pixel", "<u4"), ("kind", "<u4"), ("o", "<f4", (3,)), ("tmin", "<f4"), ("d", "<f4", (3,)), ("tmax", "<f4")])
+truth_pair_dtype = np.dtype([("flat", "<u4"), ("decision", "<i4"), ("det", "<f8"), ("u", "<f8"), ("v", "<f8"), ("t", "<f8"),
+                             ("eu", "<f8"), ("ev", "<f8"), ("et", "<f8"), ("margin", "<f8")])
+
+
+def ray_truth(scene, rays, prim_masks=None, ray_masks=None, cull_mask=0xFF):
+    """orc_ray_truth: every triangle of `scene` (a Scene of this module) against every ray of rays ((n, 8) float32: origin, tmin, direction,
+    tmax) in exact arithmetic, no boxes -> (offsets uint64[n + 1], pairs truth_pair_dtype[offsets[n]]): per ray its exact hits, the pairs the
+    binary64 filter left undecided (decision -1: settle them with tests/exact_rational.py) and the exact misses inside fp32
+    Moeller-Trumbore's error band.  prim_masks (uint8 per primitive), ray_masks (uint8 per ray), cull_mask: the ray cull masks."""
+    rays = _c(rays, np.float32).reshape(-1, 8)
+    n = len(rays)
+    pm = _c(prim_masks, np.uint8).reshape(-1) if prim_masks is not None else None
+    rm = _c(ray_masks, np.uint8).reshape(-1) if ray_masks is not None else None
+    assert rm is None or len(rm) == n
+    offsets = np.zeros(n + 1, np.uint64)
+    total = lib().orc_ray_truth(scene.handle, _p(rays), n, _p(pm), _p(rm), int(cull_mask), _p(offsets), None)
+    pairs = np.zeros(total, truth_pair_dtype)
+    lib().orc_ray_truth(scene.handle, _p(rays), n, _p(pm), _p(rm), int(cull_mask), _p(offsets), _p(pairs) if total else _p(np.zeros(1, truth_pair_dtype)))
+    return offsets.astype(np.int64), pairs
+
+
 class Audit:
     """with Audit(brute_force=False) as a: <oracle calls that trace rays>; then a.counts (audit_counts_dtype scalar), a.records."""
 
-    def __init__(self, brute_force=False, max_records=200000):
-        self.brute, self.cap = brute_force, max_records
-        self.counts, self.records = None, None
+    def __init__(self, brute_force=False, max_records=200000, ray_log=0):
+        """ray_log: room for that many ray_log_dtype records -- every audited ray with the pixel and kind orc_raygen's loop was at."""
+        self.brute, self.cap, self.log_cap = brute_force, max_records, ray_log
+        self.counts, self.records, self.ray_log = None, None, None
 
     def __enter__(self):
         lib().orc_audit_begin(int(self.brute), self.cap)
+        if self.log_cap:
+            lib().orc_audit_log_rays(self.log_cap)
         return self
 
     def __exit__(self, *exc):
+        if self.log_cap:
+            log = np.zeros(self.log_cap, ray_log_dtype)
+            self.ray_log = log[:lib().orc_audit_ray_log(_p(log))].copy()
         counts = np.zeros((), audit_counts_dtype)
         records = np.zeros(self.cap, audit_record_dtype)
         n = lib().orc_audit_end(_p(counts), _p(records))
@@ -359,6 +403,14 @@ def ray_triangle_exact(o, d, v0, e1, e2, tmin, tmax):
     a = [_c(x, np.float32) for x in (o, d, v0, e1, e2)]
     out = np.zeros(4, np.float64)
     r = lib().orc_ray_triangle_exact(*[_p(x) for x in a], float(np.float32(tmin)), float(np.float32(tmax)), _p(out))
+    return r, out
+
+
+def ray_triangle_bounds(o, d, v0, e1, e2, tmin, tmax):
+    """One pair as orc_ray_truth sees it: (decision, (det, u, v, t, eu, ev, et, margin) in binary64)."""
+    a = [_c(x, np.float32) for x in (o, d, v0, e1, e2)]
+    out = np.zeros(8, np.float64)
+    r = lib().orc_ray_triangle_bounds(*[_p(x) for x in a], float(np.float32(tmin)), float(np.float32(tmax)), _p(out))
     return r, out
 
 

@@ -17,7 +17,8 @@
  * value's magnitude exceeds that bound, or when P itself is 0 (every term is exactly 0).  Anything else is reported as
  * undecided (-1) and the caller settles it in exact rational arithmetic (tests/exact_rational.py, python Fractions on the
  * same bits) -- binary64 has 29 more bits than the inputs, so this happens on exact ties (a ray through a vertex or an
- * edge of axis-aligned geometry) and practically nowhere else.
+ * edge of axis-aligned geometry) and practically nowhere else.  tmax = +inf (ray queries) is an interval with no upper end: the
+ * comparison t < tmax is left out (inf * det against its own bound would leave every hit undecided).
  */
 #ifndef VHR_EXACT_H
 #define VHR_EXACT_H
@@ -86,7 +87,8 @@ static inline orc_exact_result exact_ray_triangle(const float of[3], const float
     VHR_EXACT_TEST(vn, pvn, 1);                                                   /* v >= 0 */
     VHR_EXACT_TEST((det - un) - vn, (pdet + pun) + pvn, 1);                       /* u + v <= 1 */
     VHR_EXACT_TEST(tn - tmin * det, ptn + fabs(tmin) * pdet, 0);                  /* t > tmin */
-    VHR_EXACT_TEST(tmax * det - tn, fabs(tmax) * pdet + ptn, 0);                  /* t < tmax */
+    if (tmax != (double)INFINITY)                                                 /* tmax = inf (ray queries): no upper end, and t is finite */
+        VHR_EXACT_TEST(tmax * det - tn, fabs(tmax) * pdet + ptn, 0);              /* t < tmax */
 #undef VHR_EXACT_TEST
     r.decision = undecided ? -1 : 1;
     return r;

@@ -555,6 +555,15 @@ int orc_scene_add_texture(orc_scene *s, uint32_t w, uint32_t h, const uint8_t *r
 }
 
 uint32_t orc_scene_triangle_count(const orc_scene *s) { return s->ntris; }
+/* the world-space records the oracle decides on, flat order: (v0, e1, e2) x ntris, and optionally each triangle's primitive */
+void orc_scene_triangles(const orc_scene *s, float *v0_e1_e2, uint32_t *prim) {
+    for (uint32_t i = 0; i < s->ntris; ++i) {
+        const orc_tri *t = &s->tris[i];
+        const float r[9] = { t->v0.x, t->v0.y, t->v0.z, t->e1.x, t->e1.y, t->e1.z, t->e2.x, t->e2.y, t->e2.z };
+        memcpy(v0_e1_e2 + 9 * (size_t)i, r, sizeof r);
+        if (prim) prim[i] = t->prim;
+    }
+}
 
 static inline int box_hit(const orc_node *n, v3 o, v3 inv, float tmin, float tmax) {
     float t0, t1, tn = tmin, tf = tmax;
@@ -589,8 +598,12 @@ static struct {
     int on, brute;
     uint32_t cap, nrec;
     orc_audit_record *rec;
+    uint32_t log_cap, nlog;            /* the ray log (orc_audit_log_rays): every audited ray with the pixel and kind its raygen loop set */
+    orc_ray_log_record *log;
     audit_slot slot[256];
 } g_audit;
+/* who traces: set by the raygen loop around its trace() calls, read by the ray log */
+static _Thread_local uint32_t t_ray_pixel = 0xffffffffu, t_ray_kind = ORC_RAY_KIND_OTHER;
 
 static void audit_push(const orc_audit_record *r) {
 #pragma omp critical(vhr_audit_records)
@@ -668,6 +681,11 @@ static void audit_ray(const orc_scene *s, v3 o, v3 d, float tmin, float tmax, in
     tid = omp_get_thread_num() & 255;
 #endif
     orc_audit_counts *c = &g_audit.slot[tid].c;
+    if (g_audit.log) {
+        orc_ray_log_record lr = { t_ray_pixel, t_ray_kind, { o.x, o.y, o.z }, tmin, { d.x, d.y, d.z }, tmax };
+#pragma omp critical(vhr_audit_ray_log)
+        { if (g_audit.nlog < g_audit.log_cap) g_audit.log[g_audit.nlog++] = lr; else g_audit.slot[0].c.records_dropped++; }
+    }
     if (!(isfinite(o.x) && isfinite(o.y) && isfinite(o.z) && isfinite(d.x) && isfinite(d.y) && isfinite(d.z))) { c->rays_not_finite++; return; }
     int ray_undecided = 0, exact_occluded = 0, occluded[AUD_RULES] = { 0, 0, 0, 0 };
     audit_best best[AUD_RULES] = { { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 } }, exact_best = { 0, 0, 0 };
@@ -709,8 +727,19 @@ void orc_audit_begin(int brute_force, uint32_t max_records) {
     g_audit.rec = (orc_audit_record *)malloc(sizeof(orc_audit_record) * (max_records ? max_records : 1));
     g_audit.on = 1;
 }
+void orc_audit_log_rays(uint32_t max_rays) {
+    g_audit.log = (orc_ray_log_record *)malloc(sizeof(orc_ray_log_record) * (max_rays ? max_rays : 1));
+    g_audit.log_cap = max_rays;
+    g_audit.nlog = 0;
+}
+uint32_t orc_audit_ray_log(orc_ray_log_record *out) {
+    if (out && g_audit.log) memcpy(out, g_audit.log, sizeof(orc_ray_log_record) * g_audit.nlog);
+    return g_audit.nlog;
+}
 uint32_t orc_audit_end(orc_audit_counts *out, orc_audit_record *records) {
     g_audit.on = 0;
+    free(g_audit.log);
+    g_audit.log = NULL;
     orc_audit_counts sum;
     memset(&sum, 0, sizeof sum);
     for (int i = 0; i < 256; ++i) {
@@ -742,6 +771,92 @@ int orc_ray_triangle_rules(const float o[3], const float d[3], const float v0[3]
     float t3 = t, u3 = u, v3_ = v;
     const int r6 = r5 ? 1 : mt_binary64(O, D, A, E1, E2, tmin, tmax, &t3, &u3, &v3_);
     return 1 | r5 << 1 | hit_in_triangle_box(O, D, A, E1, E2, t) << 2 | r6 << 3;
+}
+
+/* ------------------------------------------------------------------------------------------
+ * Per-ray exact truth (tests/ray_truth.py, tests/test_ray_truth.py, tests/test_gpu_ray_truth.py): every triangle of the scene against
+ * every ray of a batch with exact_ray_triangle() -- no boxes, so the answer owes nothing to any hierarchy -- and, per ray, the pairs that
+ * matter to a verdict on somebody's answer: every exact hit, every pair the binary64 filter leaves undecided (python Fractions settle
+ * them), and every exact miss inside fp32 Moeller-Trumbore's forward error band (margin <= 1).  Bounds and margin are
+ * tests/ray_truth.py's mt_error_margin() restated operation by operation (tests/test_ray_truth.py holds the two equal): k = 8 * 2^-24,
+ *      eu = k (P(un) + |u| P(det)) / |det|, ev, et alike with the permanents P of vhr_exact.h,
+ *      margin = min(|u|/eu, |1-u|/eu, |v|/ev, |1-u-v|/(eu+ev+2^-24), |t-tmin|/et, |tmax-t|/et).
+ * (tests/ray_truth.py then narrows the band misses to those whose numerators allow an fp32 hit at all: numerators_allow_a_hit.)
+ * A determinant that is CERTAINLY 0 (every term of it is exactly 0: a degenerate triangle, a ray along an axis in an axis-aligned
+ * plane) is 0 in fp32 as well -- products and sums of zeros -- so such a pair is a miss for everybody and is not returned.
+ * prim_masks (optional, one per primitive) with ray_masks (optional, one per ray) and cull_mask: ray i carries cull_mask & ray_masks[i],
+ * and a primitive whose mask shares no bit with it does not exist for that ray.
+ * Two calls: pairs == NULL counts (offsets[0..n] out, returns the total); then with room for that many pairs (offsets in). */
+static inline void truth_bounds(const float of[3], const float df[3], const float v0f[3], const float e1f[3], const float e2f[3],
+                                float tminf, float tmaxf, const orc_exact_result *ex, double *eu, double *ev, double *et, double *margin) {
+    double tv[3], ad[3], a1[3], a2[3], ppv[3], pqv[3];
+    for (int i = 0; i < 3; ++i) { tv[i] = fabs((double)of[i]) + fabs((double)v0f[i]); ad[i] = fabs((double)df[i]); a1[i] = fabs((double)e1f[i]); a2[i] = fabs((double)e2f[i]); }
+    for (int i = 0; i < 3; ++i) {
+        const int j = (i + 1) % 3, k = (i + 2) % 3;
+        ppv[i] = ad[j] * a2[k] + ad[k] * a2[j];
+        pqv[i] = tv[j] * a1[k] + tv[k] * a1[j];
+    }
+    const double pdet = (a1[0] * ppv[0] + a1[1] * ppv[1]) + a1[2] * ppv[2];
+    const double pun = (tv[0] * ppv[0] + tv[1] * ppv[1]) + tv[2] * ppv[2];
+    const double pvn = (ad[0] * pqv[0] + ad[1] * pqv[1]) + ad[2] * pqv[2];
+    const double ptn = (a2[0] * pqv[0] + a2[1] * pqv[1]) + a2[2] * pqv[2];
+    const double det = fabs(ex->det);
+    if (det == 0.0) { *eu = *ev = *et = INFINITY; *margin = 0.0; return; }
+    const double eps = 0x1p-24, k = 8.0 * eps, u = ex->u, v = ex->v, t = ex->t;
+    *eu = k * (pun + fabs(u) * pdet) / det;
+    *ev = k * (pvn + fabs(v) * pdet) / det;
+    *et = k * (ptn + fabs(t) * pdet) / det;
+    const double m[6] = { fabs(u) / *eu, fabs(1.0 - u) / *eu, fabs(v) / *ev, fabs((1.0 - u) - v) / ((*eu + *ev) + eps),
+                          fabs(t - (double)tminf) / *et, fabs((double)tmaxf - t) / *et };
+    double best = m[0];
+    for (int i = 1; i < 6; ++i) if (m[i] < best) best = m[i];
+    *margin = best;
+}
+
+/* one pair: the exact decision, (det, u, v, t), the bounds (eu, ev, et) and the margin as orc_ray_truth computes them */
+int orc_ray_triangle_bounds(const float o[3], const float d[3], const float v0[3], const float e1[3], const float e2[3], float tmin, float tmax,
+                            double out_det_u_v_t_eu_ev_et_margin[8]) {
+    const orc_exact_result ex = exact_ray_triangle(o, d, v0, e1, e2, tmin, tmax);
+    double *q = out_det_u_v_t_eu_ev_et_margin;
+    q[0] = ex.det; q[1] = ex.u; q[2] = ex.v; q[3] = ex.t;
+    truth_bounds(o, d, v0, e1, e2, tmin, tmax, &ex, &q[4], &q[5], &q[6], &q[7]);
+    return ex.decision;
+}
+
+uint64_t orc_ray_truth(const orc_scene *s, const float *rays, uint32_t n_rays, const uint8_t *prim_masks, const uint8_t *ray_masks,
+                       uint32_t cull_mask, uint64_t *offsets, orc_truth_pair *pairs) {
+    const int count_only = pairs == NULL;
+#pragma omp parallel for schedule(dynamic, 16)
+    for (int64_t r = 0; r < (int64_t)n_rays; ++r) {
+        const float *ray = rays + 8 * r;
+        const float of[3] = { ray[0], ray[1], ray[2] }, df[3] = { ray[4], ray[5], ray[6] }, tmin = ray[3], tmax = ray[7];
+        const uint32_t rmask = cull_mask & (ray_masks ? ray_masks[r] : 0xffu);
+        uint64_t k = 0;
+        orc_truth_pair *out = count_only ? NULL : pairs + offsets[r];
+        for (uint32_t i = 0; i < s->ntris; ++i) {
+            const orc_tri *tr = &s->tris[i];
+            if (prim_masks && !(prim_masks[tr->prim] & rmask)) continue;
+            const float v0f[3] = { tr->v0.x, tr->v0.y, tr->v0.z }, e1f[3] = { tr->e1.x, tr->e1.y, tr->e1.z }, e2f[3] = { tr->e2.x, tr->e2.y, tr->e2.z };
+            const orc_exact_result ex = exact_ray_triangle(of, df, v0f, e1f, e2f, tmin, tmax);
+            if (!isfinite(ex.det)) continue;                         /* a ray with a NaN or an infinity in it: a miss for everybody */
+            if (ex.decision == 0 && ex.det == 0.0) continue;         /* certainly 0 (a cancellation to 0 comes back undecided) */
+            double eu = 0, ev = 0, et = 0, margin = INFINITY;
+            truth_bounds(of, df, v0f, e1f, e2f, tmin, tmax, &ex, &eu, &ev, &et, &margin);
+            if (ex.decision == 0 && !(margin <= 1.0)) continue;
+            if (!count_only) {
+                orc_truth_pair *p = &out[k];
+                p->flat = i; p->decision = ex.decision; p->det = ex.det; p->u = ex.u; p->v = ex.v; p->t = ex.t;
+                p->eu = eu; p->ev = ev; p->et = et; p->margin = margin;
+            }
+            ++k;
+        }
+        if (count_only) offsets[r + 1] = k;
+    }
+    if (count_only) {
+        offsets[0] = 0;
+        for (uint32_t r = 0; r < n_rays; ++r) offsets[r + 1] += offsets[r];
+    }
+    return offsets[n_rays];
 }
 
 /* any_hit != 0: return on the first accepted triangle (gl_RayFlagsTerminateOnFirstHitEXT,
@@ -959,6 +1074,7 @@ void orc_raygen(const orc_scene *s, const orc_per_frame_data *pfd, const orc_tra
                 if (vis_mask) vis_mask[(size_t)y * W + x] = 0x40;
                 continue;
             }
+            t_ray_pixel = y * W + x;
             v3 P = get_world_space_position(pfd, d, u, v);                                /* :26 */
             v3 L = v3neg(V3(pfd->directional_light.direction[0], pfd->directional_light.direction[1],
                             pfd->directional_light.direction[2]));                        /* :27 */
@@ -974,6 +1090,7 @@ void orc_raygen(const orc_scene *s, const orc_per_frame_data *pfd, const orc_tra
                 m3 R = onb_from_unit_vector(L);                                           /* :35 */
                 v3 dir = m3_mul(R, cone_dir);
                 /* :37-41 four identical traces; the payload of the last one survives == one trace */
+                t_ray_kind = ORC_RAY_KIND_SHADOW;
                 int occluded = trace(s, origin, dir, tp->tmin, tp->tmax, 1, use_bvh).hit;
                 shadow_payload = occluded ? 0.0f : 1.0f;                                  /* miss.rmiss:7 */
                 ++rays;
@@ -987,6 +1104,7 @@ void orc_raygen(const orc_scene *s, const orc_per_frame_data *pfd, const orc_tra
                 v3 rnd_dir = cosine_hemisphere(rnd1, rnd2);
                 m3 R = onb_from_unit_vector(N);
                 v3 dir = m3_mul(R, rnd_dir);
+                t_ray_kind = ORC_RAY_KIND_AO;
                 int occluded = trace(s, origin, dir, tp->tmin, tp->ao_tmax, 1, use_bvh).hit;
                 ao_payload += occluded ? 0.0f : 1.0f;
                 if (!occluded && i < 5) mask |= (uint8_t)(2u << i);
@@ -1002,6 +1120,7 @@ void orc_raygen(const orc_scene *s, const orc_per_frame_data *pfd, const orc_tra
                     v3 I = normalize3(v3sub(P, cam));
                     float ni2 = 2.0f * dot3(N, I);
                     v3 rdir = v3sub(I, v3scale(N, ni2));                                   /* reflect(I, N) */
+                    t_ray_kind = ORC_RAY_KIND_MIRROR;
                     orc_hit h = trace(s, origin, rdir, tp->tmin, tp->tmax, 0, use_bvh);
                     ++rays;
                     if (h.hit && tp->reflections >= 2) {
@@ -1014,6 +1133,7 @@ void orc_raygen(const orc_scene *s, const orc_per_frame_data *pfd, const orc_tra
                         v3 nf = ni < 0.0f ? nn : v3neg(nn);
                         v3 d2 = v3sub(rdir, v3scale(nn, 2.0f * ni));
                         v3 o2 = v3add(hp, v3scale(nf, tp->normal_bias));
+                        t_ray_kind = ORC_RAY_KIND_SECOND_BOUNCE;
                         orc_hit h2 = trace(s, o2, d2, tp->tmin, tp->tmax, 0, use_bvh);
                         ++rays;
                         v4 second = { 0, 0, 0, 0 };                                        /* reflection_miss.rmiss:7 */
@@ -1026,6 +1146,7 @@ void orc_raygen(const orc_scene *s, const orc_per_frame_data *pfd, const orc_tra
                 store_rgba16f(reflections, W, (int)x, (int)y, payload.x, payload.y, payload.z, payload.w);
             }
             if (vis_mask) vis_mask[(size_t)y * W + x] = mask;
+            t_ray_pixel = 0xffffffffu; t_ray_kind = ORC_RAY_KIND_OTHER;
         }
     }
     if (rays_out) *rays_out = rays;

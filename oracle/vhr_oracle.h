@@ -93,6 +93,7 @@ void     orc_scene_destroy(orc_scene *s);
 int      orc_scene_add_texture(orc_scene *s, uint32_t w, uint32_t h, const uint8_t *rgba8, int format,
                                int mag_filter, int min_filter, int address_u, int address_v);
 uint32_t orc_scene_triangle_count(const orc_scene *s);
+void orc_scene_triangles(const orc_scene *s, float *v0_e1_e2 /* ntris x 9 */, uint32_t *prim /* optional, ntris */);
 
 /* any-hit / closest-hit queries for tests: use_bvh = 0 brute force, 1 oracle BVH */
 int      orc_scene_occluded(const orc_scene *s, const float o[3], const float d[3], float tmin, float tmax, int use_bvh);
@@ -209,12 +210,33 @@ typedef struct {
     char cls;                         /* 'B' 'C' 'D' 'E' as above, 'U' undecided */
     char pad_[3];
 } orc_audit_record;
+/* the ray log of an audit session: after orc_audit_log_rays(max) every audited ray is also recorded with the pixel (y * W + x) and the kind
+ * orc_raygen's loop was at; fetch with orc_audit_ray_log (NULL: the count) BEFORE orc_audit_end, which frees it */
+enum { ORC_RAY_KIND_SHADOW = 0, ORC_RAY_KIND_AO = 1, ORC_RAY_KIND_MIRROR = 2, ORC_RAY_KIND_SECOND_BOUNCE = 3, ORC_RAY_KIND_OTHER = 255 };
+typedef struct { uint32_t pixel, kind; float o[3], tmin, d[3], tmax; } orc_ray_log_record;
+void     orc_audit_log_rays(uint32_t max_rays);
+uint32_t orc_audit_ray_log(orc_ray_log_record *out);
 void     orc_audit_begin(int brute_force, uint32_t max_records);
 uint32_t orc_audit_end(orc_audit_counts *out, orc_audit_record *records /* room for max_records */);
 int      orc_ray_triangle_exact(const float o[3], const float d[3], const float v0[3], const float e1[3], const float e2[3],
                                 float tmin, float tmax, double out_det_u_v_t[4]);
 int      orc_ray_triangle_rules(const float o[3], const float d[3], const float v0[3], const float e1[3], const float e2[3],
                                 float tmin, float tmax, float out_t_u_v_det[4]);
+
+/* ---- per-ray exact truth: every triangle against every ray in exact arithmetic, no boxes (vhr_oracle.c, tests/ray_truth.py) ----
+ * rays: n_rays x (origin, tmin, direction, tmax).  Returned in CSR form (offsets[n_rays + 1], pairs): per ray every exact hit, every pair
+ * undecided in binary64 and every exact miss within fp32 Moeller-Trumbore's forward error band (margin <= 1).  pairs == NULL: count only. */
+typedef struct {
+    uint32_t flat;                    /* flat triangle index */
+    int32_t decision;                 /* 1 exact hit, 0 exact miss (in the band), -1 undecided in binary64 */
+    double det, u, v, t;              /* binary64 values of the exact quantities */
+    double eu, ev, et;                /* fp32 Moeller-Trumbore's forward error bounds on u, v, t */
+    double margin;                    /* distance of (u, v, t) to the nearest decision border in units of those bounds */
+} orc_truth_pair;
+int orc_ray_triangle_bounds(const float o[3], const float d[3], const float v0[3], const float e1[3], const float e2[3], float tmin, float tmax,
+                            double out_det_u_v_t_eu_ev_et_margin[8]);
+uint64_t orc_ray_truth(const orc_scene *s, const float *rays, uint32_t n_rays, const uint8_t *prim_masks /* optional */,
+                       const uint8_t *ray_masks /* optional */, uint32_t cull_mask, uint64_t *offsets, orc_truth_pair *pairs);
 
 int orc_max_threads(void);
 

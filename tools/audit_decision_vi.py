@@ -32,31 +32,7 @@ sys.path.insert(0, ROOT)
 from oracle import binding as ob                     # noqa: E402
 from vulkanhybridrenderer_amd import abi, camera, scenes   # noqa: E402
 from tests import exact_rational                     # noqa: E402
-
-EPS = 2.0 ** -24
-
-
-def mt_error_margin(rec):
-    """How far (in units of fp32 Moeller-Trumbore's forward error bound) the exact (u, v, t) sits from the nearest decision border.
-    <= 1 means: inside the band where the rounding of the fp32 evaluation decides."""
-    o, d, v0, e1, e2 = (np.asarray(rec[k], np.float64) for k in ("o", "d", "v0", "e1", "e2"))
-    tv = np.abs(o) + np.abs(v0)
-    ad, a1, a2 = np.abs(d), np.abs(e1), np.abs(e2)
-
-    def pcross(a, b):
-        return np.array([a[1] * b[2] + a[2] * b[1], a[2] * b[0] + a[0] * b[2], a[0] * b[1] + a[1] * b[0]])
-    ppv, pqv = pcross(ad, a2), pcross(tv, a1)
-    pdet, pun, pvn, ptn = a1 @ ppv, tv @ ppv, ad @ pqv, a2 @ pqv
-    det = abs(rec["xdet"])
-    if det == 0:
-        return 0.0
-    k = 8 * EPS                                       # 7 roundings to a numerator + the reciprocal and the product
-    u, v, t = rec["xu"], rec["xv"], rec["xt"]
-    eu = k * (pun + abs(u) * pdet) / det
-    ev = k * (pvn + abs(v) * pdet) / det
-    et = k * (ptn + abs(t) * pdet) / det
-    margins = [abs(u) / eu, abs(1 - u) / eu, abs(v) / ev, abs(1 - u - v) / (eu + ev + EPS), abs(t - rec["tmin"]) / et, abs(rec["tmax"] - t) / et]
-    return float(min(margins))
+from tests.ray_truth import mt_error_margin          # noqa: E402
 
 
 def settle_undecided(records):
