@@ -176,7 +176,7 @@ __global__ __launch_bounds__(kQueueBlock * 2) __attribute__((amdgpu_waves_per_eu
     uint32_t overflow = 0;
     // ---- walk 1: closest hit of the primary rays; the commit keeps t (PER_RAY) for the depth ----
     uint32_t cut_n = traced && total ? build_tile_cut_uniform(a.scene, cam, cam, s_cut_all[wave], lane) : 0u;
-    wave_queue_walk<SPILL, false, false, false, true>(
+    wave_queue_walk<SPILL, false, false, true>(
         a.scene, stack, stack_levels, lane, traced ? total : 0u, refill_threshold, early_exit, 0.0f, 0.0f, false, overflow, s_cut_all[wave], cut_n,
         [&](uint32_t r, uint32_t &pix, f3 &ro, f3 &rd, float &tmin, float &tmax) {
             pix = s_list[r];
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(kQueueBlock * 2) __attribute__((amdgpu_waves_per_eu
     wave_lds_sync();
     // ---- walk 2: the inline queries (frag:36-44), any hit; the answer (an occluder's triangle or kNoHit) lands in row 7 ----
     cut_n = nhit ? build_tile_cut_uniform(a.scene, omin, omax, s_cut_all[wave], lane) : 0u;
-    wave_queue_walk<SPILL, false, false>(
+    wave_queue_walk<SPILL, false>(
         a.scene, stack, stack_levels, lane, nhit, refill_threshold, early_exit, 0.1f, 10000.0f, true, overflow, s_cut_all[wave], cut_n,
         [&](uint32_t r, uint32_t &pix, f3 &ro, f3 &rd) {
             pix = s_list[r];
@@ -344,15 +344,6 @@ __device__ bool forward_discarded(const DeviceScene &sc, uint32_t tri_index, f3 
     return sample_texture(sc, prim.material.base_color_texture, at.uvx, at.uvy).w < prim.material.alpha_cutoff;   // :24-27
 }
 
-// a candidate filter for traverse<> / wave_queue_walk from a callable
-template <typename F>
-struct RejectBy {
-    static constexpr bool kActive = true;
-    F f;
-    template <typename... A>
-    __device__ __forceinline__ bool operator()(A... args) const { return f(args...); }
-};
-
 // default.frag:19-53 for the fragment of triangle tri_index at the pixel whose centre ray is (cam, cdir): the texel through the sRGB
 // attachment (B8G8R8A8_SRGB, bytes b g r a, alpha 1).  in_normal is object space and not renormalised (as in the rayquery path); the
 // shadow-map term is overwritten with 1.0 (:47), so in_pos and the shadow map are unused.
@@ -429,15 +420,14 @@ __global__ __launch_bounds__(kTraceBlock) void forward_raster_kernel(const Forwa
         const f3 cam = f3{ a.pfd.camera_view_inverse[12], a.pfd.camera_view_inverse[13], a.pfd.camera_view_inverse[14] };
         const f3 cdir = forward_sample_dir<1>(a.pfd, cam, x, fy, 0, W, H);
         const DeviceScene *sc = &a.scene;
-        const auto discarded = [sc, cam, cdir](uint32_t tri) { return forward_discarded(*sc, tri, cam, cdir); };
-        const RejectBy<decltype(discarded)> reject{ discarded };
+        const auto discarded = [sc, cam, cdir](uint32_t, uint32_t tri, float, float) { return forward_discarded(*sc, tri, cam, cdir); };
         uint32_t tris[S], texels[S];
 #pragma unroll
         for (uint32_t s = 0; s < S; ++s) {
             const f3 dir = forward_sample_dir<S>(a.pfd, cam, x, fy, s, W, H);
             Hit h;
             h.t = h.u = h.v = 0.0f; h.tri_index = 0; h.flat = 0;
-            const bool hit = traverse<false, false, kTraceBlock>(a.scene, cam, dir, 1.0f, 3.0e38f, stack, h, overflow, reject);
+            const bool hit = traverse<false, kTraceBlock>(a.scene, cam, dir, 1.0f, 3.0e38f, stack, h, overflow, discarded);
             tris[s] = hit ? h.tri_index : kNoHit;
             a.depth[pix * S + s] = hit ? forward_depth(a, cam, dir, h.t) : 0.0f;
             if (a.hits) forward_store_hit(a, pix * S + s, hit, h.tri_index, h.t, h.u, h.v);
@@ -527,11 +517,11 @@ __global__ __launch_bounds__(kQueueBlock * 2) __attribute__((amdgpu_waves_per_eu
     // ---- the sample rays: closest hit among the candidates whose fragment is not discarded ----
     const uint32_t cut_n = total ? build_tile_cut_uniform(a.scene, cam, cam, s_cut_all[wave], lane) : 0u;
     const DeviceScene *sc = &a.scene;
-    const auto discarded = [sc, cam, &s_cdir](uint32_t slot, uint32_t tri) {
+    const auto discarded = [sc, cam, &s_cdir](uint32_t slot, uint32_t tri, float, float) {
         const uint32_t p = slot / S;
         return forward_discarded(*sc, tri, cam, f3{ s_cdir[0][p], s_cdir[1][p], s_cdir[2][p] });
     };
-    wave_queue_walk<SPILL, false, false, false, true>(
+    wave_queue_walk<SPILL, false, false, true>(
         a.scene, stack, stack_levels, lane, total, refill_threshold, early_exit, 0.0f, 0.0f, false, overflow, s_cut_all[wave], cut_n,
         [&](uint32_t r, uint32_t &slot, f3 &ro, f3 &rd, float &tmin, float &tmax) {
             const uint32_t p = s_list[r / S], s = r % S;
@@ -547,7 +537,7 @@ __global__ __launch_bounds__(kQueueBlock * 2) __attribute__((amdgpu_waves_per_eu
                 forward_store_hit(a, (size_t(fy_of(p)) * W + px_of(p)) * S + slot % S, tri != kNoHit, tri, t, u, v);
             }
         },
-        nullptr, NoFlag{}, RejectBy<decltype(discarded)>{ discarded });
+        nullptr, NoFlag{}, discarded);
     wave_lds_sync();
     // ---- per pixel: the Depth samples, each sample's owner, the fragment list ----
     uint32_t nfrag = 0;

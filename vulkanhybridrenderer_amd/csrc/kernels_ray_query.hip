@@ -76,7 +76,7 @@ __device__ __forceinline__ void ray_query_store(const RayQueryArgs &a, const uin
 }
 
 // FILTER: kFilterAlpha (VHR_RAY_QUERY_ALPHA_TEST) -- a candidate gbuf_discarded names does not exist; kFilterMask (vhr_ray_query_masked) -- nor does
-// one whose primitive's mask shares no bit with the ray's mask, read at the candidate by ray id.  The walk's Reject, behind decision (vi) as ever.
+// one whose primitive's mask shares no bit with the ray's mask, read at the candidate by ray id.  The walk's candidate filter (trace_device.hpp).
 template <bool SPILL, int FILTER = kFilterNone>
 __global__ __launch_bounds__(kQueueBlock * 2) void ray_query_kernel(const RayQueryArgs a, const uint32_t stack_levels, const uint32_t refill_threshold,
                                                                     const uint32_t early_exit, const Stamps st) {
@@ -95,7 +95,7 @@ __global__ __launch_bounds__(kQueueBlock * 2) void ray_query_kernel(const RayQue
     stack[0] = kStackSentinel;
     uint32_t overflow = 0, hits = 0;
     bool flagged = false;                                 // decision (vi) asked for binary64 on the lane's current ray
-    wave_queue_walk<SPILL, false, true, false, true>(
+    wave_queue_walk<SPILL, true, false, true>(
         a.scene, stack, stack_levels, lane, total, refill_threshold, early_exit, 0.0f, 0.0f, any_hit, overflow, nullptr, 0u,
         [&](uint32_t r, uint32_t &ray, f3 &ro, f3 &rd, float &tmin, float &tmax) {
             ray = base + r;

@@ -52,6 +52,11 @@ __device__ f4 raytraced_hit_payload(const DeviceScene &sc, const vhr_per_frame_d
     return f4{ col.x, col.y, col.z, 1.0f };
 }
 
+// the walks' candidate filter: gl_RayFlagsNoOpaqueEXT runs shadow_anyhit.rahit at every candidate (ALPHA), else none
+template <bool ALPHA> __device__ __forceinline__ auto rahit_filter(const DeviceScene &sc) {
+    if constexpr (ALPHA) return RahitAlpha{ &sc }; else return NoFilter{};
+}
+
 struct RaytracedArgs {
     DeviceScene scene;
     vhr_per_frame_data pfd;
@@ -74,15 +79,15 @@ __device__ __forceinline__ void raytraced_pixel(const RaytracedArgs &a, const ui
     const f4 direction = mat4_mul(a.pfd.camera_view_inverse, f4{ tn.x, tn.y, tn.z, 0.0f });    // rgen:17
     f4 payload = f4{ 0.3f, 0.8f, 0.2f, 1.0f };                                       // miss.rmiss:7
     Hit h;
-    if (traverse<false, ALPHA>(a.scene, f3{ origin.x, origin.y, origin.z }, f3{ direction.x, direction.y, direction.z }, 0.1f, 10000.0f,
-                               stack, h, overflow)) {                                // rgen:20
+    if (traverse<false>(a.scene, f3{ origin.x, origin.y, origin.z }, f3{ direction.x, direction.y, direction.z }, 0.1f, 10000.0f,
+                        stack, h, overflow, rahit_filter<ALPHA>(a.scene))) {         // rgen:20
         hit_any = true;
         f3 position, unused_normal;
         hit_position_normal(a.scene, h, position, unused_normal);                    // rchit:24
         const f3 light_dir = -f3{ a.pfd.directional_light.direction[0], a.pfd.directional_light.direction[1], a.pfd.directional_light.direction[2] };
         Hit sh;
         // shadow ray, rchit:48-50 (alpha :41-43): shadow_payload stays true unless shadow_miss.rmiss:7 runs
-        const bool shadowed = traverse<true, ALPHA>(a.scene, position, light_dir, 0.1f, 10000.0f, stack, sh, overflow);
+        const bool shadowed = traverse<true>(a.scene, position, light_dir, 0.1f, 10000.0f, stack, sh, overflow, rahit_filter<ALPHA>(a.scene));
         payload = raytraced_hit_payload<ALPHA>(a.scene, a.pfd, h, shadowed);
     }
     a.out[size_t(y) * W + x] = make_uchar4(uint8_t(unorm8(payload.z)), uint8_t(unorm8(payload.y)), uint8_t(unorm8(payload.x)),
@@ -165,7 +170,7 @@ __global__ __launch_bounds__(kQueueBlock * 2) __attribute__((amdgpu_waves_per_eu
     // ---- walk 1: closest hit of the primary rays (rgen:20; ALPHA: gl_RayFlagsNoOpaqueEXT -> the any-hit filter) ----
     // (one origin for every ray: the shared descent follows the boxes around the camera)
     uint32_t cut_n = traced && total ? build_tile_cut_uniform(a.scene, origin, origin, s_cut_all[wave], lane) : 0u;
-    wave_queue_walk<SPILL, ALPHA, false>(
+    wave_queue_walk<SPILL, false>(
         a.scene, stack, stack_levels, lane, traced ? total : 0u, refill_threshold, early_exit, 0.1f, 10000.0f, false, overflow, s_cut_all[wave], cut_n,
         [&](uint32_t r, uint32_t &pix, f3 &ro, f3 &rd) {
             pix = s_list[r];
@@ -174,7 +179,8 @@ __global__ __launch_bounds__(kQueueBlock * 2) __attribute__((amdgpu_waves_per_eu
         },
         [&](uint32_t pix, uint32_t tri, float u, float v) {
             s_ray[0][pix] = __uint_as_float(tri); s_ray[1][pix] = u; s_ray[2][pix] = v;
-        });
+        },
+        nullptr, NoFlag{}, rahit_filter<ALPHA>(a.scene));
     wave_lds_sync();
     // ---- shadow rays from the primary hits, whole wave (rchit:24,48-50) ----
     uint32_t nhit = 0;
@@ -201,14 +207,15 @@ __global__ __launch_bounds__(kQueueBlock * 2) __attribute__((amdgpu_waves_per_eu
     wave_lds_sync();
     // ---- walk 2: any hit towards the light; the answer (an occluder's triangle or kNoHit) lands in row 3 ----
     cut_n = nhit ? build_tile_cut_uniform(a.scene, omin, omax, s_cut_all[wave], lane) : 0u;
-    wave_queue_walk<SPILL, ALPHA, false>(
+    wave_queue_walk<SPILL, false>(
         a.scene, stack, stack_levels, lane, nhit, refill_threshold, early_exit, 0.1f, 10000.0f, true, overflow, s_cut_all[wave], cut_n,
         [&](uint32_t r, uint32_t &pix, f3 &ro, f3 &rd) {
             pix = s_list[r];
             ro = f3{ s_ray[3][pix], s_ray[4][pix], s_ray[5][pix] };
             rd = light_dir;
         },
-        [&](uint32_t pix, uint32_t tri, float, float) { s_ray[3][pix] = __uint_as_float(tri); });
+        [&](uint32_t pix, uint32_t tri, float, float) { s_ray[3][pix] = __uint_as_float(tri); },
+        nullptr, NoFlag{}, rahit_filter<ALPHA>(a.scene));
     wave_lds_sync();
     // ---- closesthit.rchit / miss.rmiss and the image store, whole wave ----
 #pragma unroll

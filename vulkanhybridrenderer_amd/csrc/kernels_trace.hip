@@ -77,7 +77,7 @@ __device__ __forceinline__ void pixel_visibility(const RaygenArgs &a, const uint
         const f3 cone_dir = normalize3(uniform_sample_cone(rnd1, rnd2, a.tp.cone_cos_max));   // rgen:34
         const f3 dir = onb_transform(L, cone_dir);                                       // rgen:35,40
         // rgen:37-41 issues this trace four times with identical arguments; once is equivalent
-        const bool occluded = traverse<true, false, STRIDE>(a.scene, origin, dir, a.tp.tmin, a.tp.tmax, stack, hit, overflow, ray_filter<FILTER>(a.scene, a.masks, a.masks.shadow));
+        const bool occluded = traverse<true, STRIDE>(a.scene, origin, dir, a.tp.tmin, a.tp.tmax, stack, hit, overflow, ray_filter<FILTER>(a.scene, a.masks, a.masks.shadow));
         shadow_payload = occluded ? 0.0f : 1.0f;                                         // miss.rmiss:7
     }
     ao_payload = 0.0f;                                                                   // rgen:44-55
@@ -86,7 +86,7 @@ __device__ __forceinline__ void pixel_visibility(const RaygenArgs &a, const uint
         rnd2 = random01(rng);
         const f3 rnd_dir = cosine_hemisphere(rnd1, rnd2);
         const f3 dir = onb_transform(N, rnd_dir);
-        const bool occluded = traverse<true, false, STRIDE>(a.scene, origin, dir, a.tp.tmin, a.tp.ao_tmax, stack, hit, overflow, ray_filter<FILTER>(a.scene, a.masks, a.masks.ao));
+        const bool occluded = traverse<true, STRIDE>(a.scene, origin, dir, a.tp.tmin, a.tp.ao_tmax, stack, hit, overflow, ray_filter<FILTER>(a.scene, a.masks, a.masks.ao));
         ao_payload += occluded ? 0.0f : 1.0f;
     }
     if (a.tp.ao_spp) ao_payload /= float(a.tp.ao_spp); else ao_payload = 1.0f;
@@ -450,8 +450,9 @@ __global__ __launch_bounds__(kQueueBlock *WAVES) __attribute__((amdgpu_waves_per
                 // (the consistency test behind the candidates only: few tests get this far, and a wave whose lanes all failed skips it)
                 if (mt_candidate(ro, rd, v0, e1, e2, tmin, tmax, ct, cu, cv)) {
                     if (solution_consistent(ro, rd, v0, e1, e2, ct, cu, cv)) {
-                        if constexpr (FILTER == kFilterAlpha) { if (gbuf_discarded(a.scene, first + i, cu, cv)) continue; }      // a hole: the candidate does not exist
-                        if constexpr (FILTER == kFilterMask) {          // the ray's class by its kind, the mask test first: a culled candidate does not exist
+                        // the candidate filter ray_filter<FILTER>(a.scene, a.masks, kind == 0 ? a.masks.shadow : a.masks.ao) spelled out: the object costs STATS builds a spilled VGPR
+                        if constexpr (FILTER == kFilterAlpha) { if (gbuf_discarded(a.scene, first + i, cu, cv)) continue; }      // GbufDiscard
+                        if constexpr (FILTER == kFilterMask) {          // RayMaskReject, the ray's class by its kind
                             if ((uint32_t(a.masks.prim_masks[leaf[i].prim]) & (kind == 0 ? a.masks.shadow : a.masks.ao)) == 0u) continue;
                             if (a.masks.alpha && gbuf_discarded(a.scene, first + i, cu, cv)) continue;
                         }
@@ -653,7 +654,7 @@ __device__ __forceinline__ void mirror_ray_of_pixel(const RaygenArgs &a, f3 cam,
     rdir = I - N * ni2;                                                                      // rgen:61 reflect(I, N)
 }
 
-// FILTER: the walk's Reject is GbufDiscard ("alpha_test_rays") or RayMaskReject ("reflection_ray_mask"), behind decision (vi) as ever; phase 3's redo applies it as well.
+// FILTER: the walk's candidate filter is GbufDiscard ("alpha_test_rays") or RayMaskReject ("reflection_ray_mask"); phase 3's redo applies it as well.
 template <bool SPILL, int BOUNCES, bool STATS = false, int FILTER = kFilterNone>
 __global__ __launch_bounds__(kQueueBlock * 2) __attribute__((amdgpu_waves_per_eu(7, 7))) void reflection_queue_kernel(
     const RaygenArgs a, const uint32_t stack_levels, const uint32_t refill_threshold, const uint32_t tiles_x, const uint32_t tiles_total,
@@ -735,7 +736,7 @@ __global__ __launch_bounds__(kQueueBlock * 2) __attribute__((amdgpu_waves_per_eu
     // (first bounce only: the second bounce's origins are scattered over the scene, their descent ends at once -- measured: no gain)
     const uint32_t cut_n = total && bounce == 0 ? build_tile_cut_uniform(a.scene, omin, omax, s_cut_all[wave], lane) : 0u;
     const unsigned long long tw0 = STATS ? __builtin_readcyclecounter() : 0ull;
-    wave_queue_walk<SPILL, false, true, STATS>(
+    wave_queue_walk<SPILL, true, STATS>(
         a.scene, stack, stack_levels, lane, total, refill_threshold, early_exit, a.tp.tmin, a.tp.tmax, false, overflow, s_cut_all[wave], cut_n,
         [&](uint32_t r, uint32_t &pix, f3 &ro, f3 &rd) {
             pix = s_list[r];

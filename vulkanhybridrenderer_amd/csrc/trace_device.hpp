@@ -1,11 +1,11 @@
 // What every ray-tracing unit (kernels_trace.hip, kernels_raytraced.hip, kernels_forward.hip, kernels_standin.hip, kernels_ray_query.hip)
-// shares on the device: the triangle test of decision (vi), the per-lane walker traverse<>, the image and texture helpers and the
-// mirror ray's hit shader.  Device and host helpers only: no kernel and no launcher lives here.  (Until the ray-tracing unit was split
+// shares on the device: the triangle test of decision (vi), the candidate-filter protocol and its filters, the per-lane walker traverse<>,
+// the image and texture helpers and the mirror ray's hit shader.  Device and host helpers only: no kernel and no launcher lives here.  (Until the ray-tracing unit was split
 // by render path this was the head of kernels_trace.hip.)
 //
 // Replaces the driver's acceleration-structure traversal (traceRayEXT) by traverse<>(), and
 //   data/shaders/hybrid_render_path/reflection_hit.rchit:10-72 -> shade_reflection_hit
-//   data/shaders/raytraced_render_path/shadow_anyhit.rahit:8-27 -> alpha_ignored
+//   data/shaders/raytraced_render_path/shadow_anyhit.rahit:8-27 -> alpha_ignored (the filter RahitAlpha)
 //
 // Every unit that includes this is compiled with -ffp-contract=off: ray setup and Moeller-Trumbore follow the exact-arithmetic contract of
 // device_math.hpp so visibility results are bit-reproducible.
@@ -238,19 +238,26 @@ __device__ f4 sample_texture(const DeviceScene &sc, int idx, float u, float v) {
     return r;
 }
 
+// vertex K of triangle `tri` of a primitive, and a hit's uv0 as the shaders interpolate it (shadow_anyhit.rahit:19-20,
+// reflection_hit.rchit:21-22): barycentrics (1 - u - v, u, v), the products summed left to right
+template <int K> __device__ __forceinline__ const vhr_vertex &tri_vertex(const DeviceScene &sc, const vhr_primitive &prim, uint32_t tri) {
+    return sc.vertices[prim.vertex_offset + sc.indices[prim.index_offset + 3 * tri + K]];
+}
+struct Uv0 { float x, y; };
+__device__ __forceinline__ Uv0 interpolate_uv0(const DeviceScene &sc, const vhr_primitive &prim, uint32_t tri, float u, float v) {
+    const vhr_vertex &a = tri_vertex<0>(sc, prim, tri), &b = tri_vertex<1>(sc, prim, tri), &c = tri_vertex<2>(sc, prim, tri);
+    const float bx = 1.0f - u - v, by = u, bz = v;
+    return Uv0{ a.uv0[0] * bx + b.uv0[0] * by + c.uv0[0] * bz, a.uv0[1] * bx + b.uv0[1] * by + c.uv0[1] * bz };
+}
+
 // shadow_anyhit.rahit:8-27: true = ignoreIntersectionEXT.  textures[-1] (no base colour texture) reads (0, 0, 0, 0)
 // (decision ix of the oracle; out of bounds in the reference).
 __device__ bool alpha_ignored(const DeviceScene &sc, uint32_t tri_index, float u, float v) {
     const BvhTri &bt = sc.tris[tri_index];
     const vhr_primitive &prim = sc.primitives[bt.prim];                                  // rahit:9
     if (prim.material.alpha_mask != 1) return false;                                     // rahit:24 (the texture fetch has no other effect)
-    const vhr_vertex &a = sc.vertices[prim.vertex_offset + sc.indices[prim.index_offset + 3 * bt.tri + 0]];
-    const vhr_vertex &b = sc.vertices[prim.vertex_offset + sc.indices[prim.index_offset + 3 * bt.tri + 1]];
-    const vhr_vertex &c = sc.vertices[prim.vertex_offset + sc.indices[prim.index_offset + 3 * bt.tri + 2]];
-    const float bx = 1.0f - u - v, by = u, bz = v;                                       // rahit:19
-    const float uvx = a.uv0[0] * bx + b.uv0[0] * by + c.uv0[0] * bz;                     // rahit:20
-    const float uvy = a.uv0[1] * bx + b.uv0[1] * by + c.uv0[1] * bz;
-    const f4 albedo = sample_texture(sc, prim.material.base_color_texture, uvx, uvy);    // rahit:23
+    const Uv0 uv = interpolate_uv0(sc, prim, bt.tri, u, v);                              // rahit:19-20
+    const f4 albedo = sample_texture(sc, prim.material.base_color_texture, uv.x, uv.y);  // rahit:23
     return albedo.w < prim.material.alpha_cutoff;                                        // rahit:24-26
 }
 
@@ -263,6 +270,8 @@ __device__ bool gbuf_discarded(const DeviceScene &sc, uint32_t tri_index, float 
     const vhr_primitive &prim = sc.primitives[bt.prim];
     float alpha = prim.material.base_color[3];                                           // gbuf.frag:19-26
     if (prim.material.base_color_texture != -1) {
+        // interpolate_uv0, spelled out: through the helper the compiler orders this block differently in every kernel that inlines it, and two
+        // queue kernels' statistics builds spill differently (profiles/filter_protocol_resources.txt)
         const vhr_vertex &a = sc.vertices[prim.vertex_offset + sc.indices[prim.index_offset + 3 * bt.tri + 0]];
         const vhr_vertex &b = sc.vertices[prim.vertex_offset + sc.indices[prim.index_offset + 3 * bt.tri + 1]];
         const vhr_vertex &c = sc.vertices[prim.vertex_offset + sc.indices[prim.index_offset + 3 * bt.tri + 2]];
@@ -274,36 +283,27 @@ __device__ bool gbuf_discarded(const DeviceScene &sc, uint32_t tri_index, float 
     return (prim.material.alpha_mask == 1 && alpha < prim.material.alpha_cutoff) || alpha == 0.0f;   // gbuf.frag:27-32
 }
 
-// Per-lane BVH2 walk with the traversal stack in LDS (stack[level * kTraceBlock + thread]: conflict free; STRIDE 1: a private array).
-// ANY_HIT: gl_RayFlagsTerminateOnFirstHitEXT | SkipClosestHitShader (raygen.rgen:39,51) -- returns at the
-// first accepted triangle; the boolean result does not depend on the visiting order.
-// !ANY_HIT: closest hit = min t, ties broken by the smaller flat triangle index; subtrees are pruned with
-// tnear > best t only (strict), so equal-t candidates are always examined.
-// ALPHA: rays of the raytraced render path traced with gl_RayFlagsNoOpaqueEXT (raygen_test_alpha.rgen:20,
-// closesthit_test_alpha.rchit:42): every candidate first runs shadow_anyhit.rahit, an ignored candidate does not exist.
-// Reject (the forward raster path's fragment discard, decided per (pixel, triangle)): a candidate for which reject(triangle) -- in
-// wave_queue_walk reject(ray id, triangle) -- is true does not exist either.  NoReject: none, and no code.
-struct NoReject {
-    static constexpr bool kActive = false;
-    __device__ __forceinline__ bool operator()(uint32_t) const { return false; }
-    __device__ __forceinline__ bool operator()(uint32_t, uint32_t) const { return false; }
-};
-// GbufDiscard: the hybrid path's rays and the ray query with their alpha test on -- gbuf_discarded at the candidate.  A Reject with kAtHit is
-// handed the candidate's barycentrics as well: reject(triangle, u, v), in wave_queue_walk reject(ray id, triangle, u, v).
-struct GbufDiscard {
-    static constexpr bool kActive = true;
-    static constexpr bool kAtHit = true;
+// ---------------------------------------------------------------------------------------------
+// Candidate filters.  Both walkers (traverse<> below, wave_queue_walk<> in trace_queue.hpp) decide a leaf's triangle in three steps: the
+// triangle test with decision (vi) says whether the ray has a candidate at (t, u, v); the ray's filter says whether that candidate exists
+// for this ray; what is left is committed (any hit: the ray ends; closest hit: min t, then the smaller flat index).  A filter is a trivially
+// copyable callable with one call shape,
+//     bool operator()(uint32_t ray, uint32_t tri, float u, float v) const      // true: the candidate does not exist for this ray
+// `ray` is what the walk's fetch gave for the lane's ray (wave_queue_walk: pix; traverse<>: its trailing argument, 0 unless the caller says
+// otherwise), `tri` the triangle's index in sc.tris, (u, v) the candidate's barycentrics.  The one thing a walker asks of the type is whether it is
+// NoFilter, which costs no code.  (The features that brought the filters: DESIGN.md 4b, 4c.)
+// ---------------------------------------------------------------------------------------------
+struct NoFilter { __device__ __forceinline__ bool operator()(uint32_t, uint32_t, float, float) const { return false; } };
+// the raytraced path's gl_RayFlagsNoOpaqueEXT rays (raygen_test_alpha.rgen:20, closesthit_test_alpha.rchit:42): shadow_anyhit.rahit
+struct RahitAlpha {
     const DeviceScene *sc;
-    __device__ __forceinline__ bool operator()(uint32_t tri, float u, float v) const { return gbuf_discarded(*sc, tri, u, v); }
+    __device__ __forceinline__ bool operator()(uint32_t, uint32_t tri, float u, float v) const { return alpha_ignored(*sc, tri, u, v); }
+};
+// the hybrid path's rays and the ray query with their alpha test on: what the G-buffer pass discards
+struct GbufDiscard {
+    const DeviceScene *sc;
     __device__ __forceinline__ bool operator()(uint32_t, uint32_t tri, float u, float v) const { return gbuf_discarded(*sc, tri, u, v); }
 };
-template <typename R, typename = void> struct reject_at_hit : std::false_type {};
-template <typename R> struct reject_at_hit<R, std::void_t<decltype(R::kAtHit)>> : std::true_type {};
-// the hybrid path's and the ray query's walkers by their alpha switch: GbufDiscard or nothing
-template <bool ALPHA> using AlphaReject = std::conditional_t<ALPHA, GbufDiscard, NoReject>;
-template <bool ALPHA> __device__ __forceinline__ AlphaReject<ALPHA> alpha_reject(const DeviceScene &sc) {
-    if constexpr (ALPHA) return GbufDiscard{ &sc }; else return NoReject{};
-}
 
 // Ray cull masks (vhr_set_primitive_masks, vhr_ray_query_masked, the "*_ray_mask" options): a candidate on primitive p does not exist for a
 // ray of mask m iff (masks[p] & m) == 0 -- VkAccelerationStructureInstanceKHR::mask against traceRayEXT's cullMask, per geometry.  The kernels
@@ -313,35 +313,38 @@ struct RayMaskArgs {
     uint32_t shadow, ao, reflection;      // the hybrid path's class masks; the ray query: `shadow` = its cull_mask
     uint32_t alpha;                       // wave-uniform: the alpha rule (gbuf_discarded) applies as well, behind the mask test
 };
-// RayMaskReject: the mask test, then (by the runtime bit) the alpha rule.  kAtHit, like GbufDiscard.  In wave_queue_walk the ray id picks the
-// ray's own mask where the launch has per-ray masks (the batched query), read at the candidate.
+// the mask test, then (by the runtime bit) the alpha rule.  Where the launch has per-ray masks (the batched query: ray_masks != nullptr)
+// the ray id picks the ray's own, read at the candidate.
 struct RayMaskReject {
-    static constexpr bool kActive = true;
-    static constexpr bool kAtHit = true;
     const DeviceScene *sc;
     const uint8_t *prim_masks, *ray_masks;
     uint32_t mask, alpha;
-    __device__ __forceinline__ bool culled(uint32_t tri, uint32_t m, float u, float v) const {
+    __device__ __forceinline__ bool operator()(uint32_t ray, uint32_t tri, float u, float v) const {
+        const uint32_t m = ray_masks ? uint32_t(ray_masks[ray]) & mask : mask;
         if ((uint32_t(prim_masks[sc->tris[tri].prim]) & m) == 0u) return true;
         return alpha != 0u && gbuf_discarded(*sc, tri, u, v);
     }
-    __device__ __forceinline__ bool operator()(uint32_t tri, float u, float v) const { return culled(tri, mask, u, v); }
-    __device__ __forceinline__ bool operator()(uint32_t ray, uint32_t tri, float u, float v) const {
-        return culled(tri, ray_masks ? uint32_t(ray_masks[ray]) & mask : mask, u, v);
-    }
 };
-// the hybrid path's and the ray query's walkers by their candidate filter: none, the alpha rule, or the mask (with the alpha rule as a runtime bit)
+// the hybrid path's and the ray query's kernels name their filter by a launch-side constant: none, the alpha rule, or the mask (with the
+// alpha rule as a runtime bit)
 constexpr int kFilterNone = 0, kFilterAlpha = 1, kFilterMask = 2;
-template <int FILTER> using RayFilter = std::conditional_t<FILTER == kFilterMask, RayMaskReject, AlphaReject<FILTER == kFilterAlpha>>;
+template <int FILTER> using RayFilter = std::conditional_t<FILTER == kFilterMask, RayMaskReject, std::conditional_t<FILTER == kFilterAlpha, GbufDiscard, NoFilter>>;
 template <int FILTER> __device__ __forceinline__ RayFilter<FILTER> ray_filter(const DeviceScene &sc, const RayMaskArgs &m, uint32_t ray_mask,
                                                                              const uint8_t *ray_masks = nullptr) {
     if constexpr (FILTER == kFilterMask) return RayMaskReject{ &sc, m.prim_masks, ray_masks, ray_mask, m.alpha };
-    else return alpha_reject<FILTER == kFilterAlpha>(sc);
+    else if constexpr (FILTER == kFilterAlpha) return GbufDiscard{ &sc };
+    else return NoFilter{};
 }
 
-template <bool ANY_HIT, bool ALPHA = false, int STRIDE = kTraceBlock, typename Reject = NoReject>
+// Per-lane BVH2 walk with the traversal stack in LDS (stack[level * kTraceBlock + thread]: conflict free; STRIDE 1: a private array).
+// ANY_HIT: gl_RayFlagsTerminateOnFirstHitEXT | SkipClosestHitShader (raygen.rgen:39,51) -- returns at the
+// first accepted triangle; the boolean result does not depend on the visiting order.
+// !ANY_HIT: closest hit = min t, ties broken by the smaller flat triangle index; subtrees are pruned with
+// tnear > best t only (strict), so equal-t candidates are always examined.
+// Leaf: ray_triangle (the triangle test with decision (vi) inline), then filter(ray, triangle, u, v), then the commit.
+template <bool ANY_HIT, int STRIDE = kTraceBlock, typename Filter = NoFilter>
 __device__ __forceinline__ bool traverse(const DeviceScene &sc, f3 o, f3 d, float tmin, float tmax, int *stack, Hit &best,
-                                         uint32_t &overflow, Reject reject = Reject{}) {
+                                         uint32_t &overflow, Filter filter = Filter{}, uint32_t ray = 0) {
     if (sc.node_count == 0) return false;
     f3 bo, bd;
     box_ray(sc, o, d, bo, bd);                                  // "bvh_frame": the slab tests' ray; the triangle tests below keep (o, d)
@@ -376,9 +379,7 @@ __device__ __forceinline__ bool traverse(const DeviceScene &sc, f3 o, f3 d, floa
                 const float4 c = tp[2];
                 float t, u, w;
                 if (ray_triangle(o, d, f3{ a.x, a.y, a.z }, f3{ a.w, b.x, b.y }, f3{ b.z, b.w, c.x }, tmin, tmax, t, u, w)) {
-                    if (ALPHA && alpha_ignored(sc, first + i, u, w)) continue;
-                    if constexpr (reject_at_hit<Reject>::value) { if (reject(first + i, u, w)) continue; }
-                    else if constexpr (Reject::kActive) { if (reject(first + i)) continue; }
+                    if constexpr (!std::is_same_v<Filter, NoFilter>) { if (filter(ray, first + i, u, w)) continue; }
                     if (ANY_HIT) return true;
                     const uint32_t flat = __float_as_uint(c.w);
                     if (!found || t < best.t || (t == best.t && flat < best.flat)) {
@@ -422,9 +423,7 @@ __device__ __forceinline__ TriAttributes interpolate(const DeviceScene &sc, cons
 
 // gbuf.vert:21 passes the vertex tangent through; the rasteriser interpolates it like the normal
 __device__ __forceinline__ f4 interpolate_tangent(const DeviceScene &sc, const vhr_primitive &prim, uint32_t tri, float u, float v) {
-    const vhr_vertex &a = sc.vertices[prim.vertex_offset + sc.indices[prim.index_offset + 3 * tri + 0]];
-    const vhr_vertex &b = sc.vertices[prim.vertex_offset + sc.indices[prim.index_offset + 3 * tri + 1]];
-    const vhr_vertex &c = sc.vertices[prim.vertex_offset + sc.indices[prim.index_offset + 3 * tri + 2]];
+    const vhr_vertex &a = tri_vertex<0>(sc, prim, tri), &b = tri_vertex<1>(sc, prim, tri), &c = tri_vertex<2>(sc, prim, tri);
     const float bx = 1.0f - u - v, by = u, bz = v;
     return f4{ a.tangent[0] * bx + b.tangent[0] * by + c.tangent[0] * bz, a.tangent[1] * bx + b.tangent[1] * by + c.tangent[1] * bz,
                a.tangent[2] * bx + b.tangent[2] * by + c.tangent[2] * bz, a.tangent[3] * bx + b.tangent[3] * by + c.tangent[3] * bz };
@@ -503,13 +502,13 @@ __device__ __forceinline__ void hit_position_normal(const DeviceScene &sc, const
 
 // The mirror ray of raygen.rgen:59-65 with the optional second bounce: a mirror ray from the first hit about the shader's N
 // (normalised, facing the incoming ray), origin biased like raygen.rgen:29, shaded by reflection_hit.rchit without recursion.
-// `reject` ("alpha_test_rays": GbufDiscard; "reflection_ray_mask": RayMaskReject): both bounces skip the candidates it names.
-template <int STRIDE = kTraceBlock, typename Reject = NoReject>
+// `filter` ("alpha_test_rays": GbufDiscard; "reflection_ray_mask": RayMaskReject): both bounces skip the candidates it names.
+template <int STRIDE = kTraceBlock, typename Filter = NoFilter>
 __device__ __forceinline__ f4 trace_reflection(const DeviceScene &sc, const vhr_per_frame_data &pfd, const vhr_trace_params &tp, f3 origin,
-                                               f3 rdir, int *stack, uint32_t &overflow, bool &second_ray, Reject reject = Reject{}) {
+                                               f3 rdir, int *stack, uint32_t &overflow, bool &second_ray, Filter filter = Filter{}) {
     Hit hit;
     second_ray = false;
-    if (!traverse<false, false, STRIDE>(sc, origin, rdir, tp.tmin, tp.tmax, stack, hit, overflow, reject)) return f4{ 0.0f, 0.0f, 0.0f, 0.0f };   // reflection_miss.rmiss:7
+    if (!traverse<false, STRIDE>(sc, origin, rdir, tp.tmin, tp.tmax, stack, hit, overflow, filter)) return f4{ 0.0f, 0.0f, 0.0f, 0.0f };   // reflection_miss.rmiss:7
     if (tp.reflections < 2) return shade_reflection_hit(sc, pfd, hit);
     f3 hp, hn;
     (void)shade_reflection_hit(sc, pfd, hit, nullptr, &hp, &hn);
@@ -521,7 +520,7 @@ __device__ __forceinline__ f4 trace_reflection(const DeviceScene &sc, const vhr_
     second_ray = true;
     Hit hit2;
     f4 second = f4{ 0.0f, 0.0f, 0.0f, 0.0f };
-    if (traverse<false, false, STRIDE>(sc, o2, d2, tp.tmin, tp.tmax, stack, hit2, overflow, reject)) second = shade_reflection_hit(sc, pfd, hit2);
+    if (traverse<false, STRIDE>(sc, o2, d2, tp.tmin, tp.tmax, stack, hit2, overflow, filter)) second = shade_reflection_hit(sc, pfd, hit2);
     return shade_reflection_hit(sc, pfd, hit, &second);
 }
 

@@ -512,9 +512,9 @@ struct CostOrderArgs {
 // -o/d, near child first, far child pushed, boxes culled against the closest t so far (tn <= tbest keeps equal-t candidates:
 // decision vi), early exit of the node loop, LDS stack + scratch spill.  Leaves: every triangle, Moeller-Trumbore against the
 // full [tmin, tmax] interval, closest = min t then smaller flat index; with `any_hit` (wave-uniform) the first accepted
-// triangle ends the ray (gl_RayFlagsTerminateOnFirstHitEXT -- the boolean does not depend on the order).  ALPHA: every
-// candidate first runs shadow_anyhit.rahit (alpha_ignored); Reject: then reject(pix, triangle) (forward_raster_queue_kernel) or, for a Reject
-// with kAtHit (GbufDiscard: the hybrid path's mirror ray and the ray query with their alpha test on), reject(pix, triangle, u, v).  PER_RAY (the batched ray query, ray_query_kernel): every ray brings
+// triangle ends the ray (gl_RayFlagsTerminateOnFirstHitEXT -- the boolean does not depend on the order).  A candidate goes through three
+// steps: mt_candidate with decision (vi), then the ray's candidate filter -- filter(pix, triangle, u, v), the protocol of trace_device.hpp;
+// true: the candidate does not exist for this ray -- then the commit.  PER_RAY (the batched ray query, ray_query_kernel): every ray brings
 // its own interval -- fetch(r, pix, origin, direction, tmin, tmax), the ray's tmax seeds the cull -- and commit(pix, triangle, u, v, t)
 // is also told the hit's t; `tmin` / `tmax` are then unused.
 // ---------------------------------------------------------------------------------------------
@@ -525,13 +525,13 @@ constexpr uint32_t kNoHit = 0xffffffffu;
 struct WalkCounters { uint32_t nodes = 0, leaves = 0, triangles = 0, wave_trips = 0, refills = 0; };
 
 struct NoFlag { __device__ __forceinline__ void operator()(uint32_t) const {} };
-template <bool SPILL, bool ALPHA, bool DEFER, bool STATS = false, bool PER_RAY = false, typename Fetch, typename Commit, typename Flag = NoFlag,
-          typename Reject = NoReject>
+template <bool SPILL, bool DEFER, bool STATS = false, bool PER_RAY = false, typename Fetch, typename Commit, typename Flag = NoFlag,
+          typename Filter = NoFilter>
 __device__ __forceinline__ void wave_queue_walk(const DeviceScene &sc, int *stack, const uint32_t stack_levels, const uint32_t lane,
                                                 const uint32_t total, const uint32_t refill_threshold, const uint32_t early_exit,
                                                 const float tmin, const float tmax, const bool any_hit, uint32_t &overflow,
                                                 const float4 (*cut)[2], const uint32_t cut_n, Fetch fetch, Commit commit, WalkCounters *wc = nullptr,
-                                                Flag flag = Flag{}, Reject reject = Reject{}) {
+                                                Flag flag = Flag{}, Filter filter = Filter{}) {
     f3 ro = f3{ 0, 0, 0 }, rd = f3{ 0, 0, 1 }, rinv = f3{ 0, 0, 0 }, noi = f3{ 0, 0, 0 }, ainv = f3{ 0, 0, 0 };
     float tbest = 0.0f, best_u = 0.0f, best_v = 0.0f;
     uint32_t best_tri = kNoHit, best_flat = 0;
@@ -618,9 +618,7 @@ __device__ __forceinline__ void wave_queue_walk(const DeviceScene &sc, int *stac
                         if (DEFER) { flag(pix); continue; }
                         if (!mt_binary64(ro, rd, v0, e1, e2, ray_tmin, ray_tmax, t, uu, ww)) continue;
                     }
-                    if (ALPHA && alpha_ignored(sc, first + i, uu, ww)) continue;
-                    if constexpr (reject_at_hit<Reject>::value) { if (reject(pix, first + i, uu, ww)) continue; }
-                    else if constexpr (Reject::kActive) { if (reject(pix, first + i)) continue; }
+                    if constexpr (!std::is_same_v<Filter, NoFilter>) { if (filter(pix, first + i, uu, ww)) continue; }
                     const uint32_t flat = __float_as_uint(tc.w);
                     if (best_tri == kNoHit || t < tbest || (t == tbest && flat < best_flat)) {
                         tbest = t; best_tri = first + i; best_flat = flat; best_u = uu; best_v = ww;
