@@ -927,6 +927,34 @@ int vhr_get_primitive_masks(vhr_context *ctx, uint32_t first_primitive, uint32_t
  * most with "raygen_variant" 0), out[2] = 1 if the last ray query ran one, out[3] = 0. */
 int vhr_get_ray_mask_statistics(vhr_context *ctx, uint64_t out[4]);
 
+/* ---- Batched closest-point queries on the scene's BVH: the nearest surface to a point, or whether any lies within a distance ----
+ * Triangle i is a CANDIDATE of query q iff d2_i <= fl(max_distance * max_distance) and (masks[primitive of i] & cull_mask) != 0, where d2_i is
+ * the squared distance from the point to the closed triangle as the library's one fp32 point / triangle function computes it (every operation
+ * rounded once, IEEE division; vhr_debug_point_triangle runs it on explicit pairs).  max_distance = +inf bounds nothing; a negative or NaN
+ * max_distance and a non-finite point find nothing.
+ *   - Without VHR_POINT_QUERY_ANY_WITHIN: results = vhr_ray_hit[count].  t = the distance, the correctly rounded sqrtf(d2) of the winning
+ *     candidate; (u, v) = the barycentrics of its nearest point (v0 + u e1 + v e2, inside the closed unit triangle); geometry_index /
+ *     primitive_index as in a ray hit.  The winner has the smallest d2, ties go to the smaller flat triangle index (closest-hit's tie-break).
+ *     Nothing found: both indices 0xFFFFFFFF, t = u = v = 0.
+ *   - VHR_POINT_QUERY_ANY_WITHIN: results = uint8_t[count], 1 = a candidate exists.
+ *   - Results never depend on the tree: a query returns, bit for bit, what a loop of the function over all triangles in flat order returns --
+ *     on either builder's tree, with "bvh_frame", "bvh_presplit", any leaf size, after refits.  No alpha rule.  No frame state is read or
+ *     written: frames around a query are the frames without it.
+ *   - Device pointers by default: enqueued on the stream vhr_get_current_stream reports (between frames or inside a pass callback), the call
+ *     returns without synchronising.  VHR_POINT_QUERY_HOST_MEMORY: host pointers, staged; the call returns with results in place.
+ *     count == 0 returns VHR_OK and launches nothing; a context without geometry finds nothing.
+ *   - VHR_ERROR_INVALID_ARGUMENT (message in vhr_last_error, with the entry point's name) for a NULL pointer with count > 0, an unknown flag
+ *     bit, `points` not 16-byte aligned, `results` not 4-byte aligned or cull_mask > 0xFF -- checked first, in that order, on every context.
+ *     Then VHR_ERROR_NO_DEVICE on a host-only context, and VHR_ERROR_GRAPH while geometry updates are pending (vhr_refit_geometry first). */
+int vhr_closest_point_query(vhr_context *ctx, const vhr_point_query *points, uint32_t count, uint32_t flags, uint32_t cull_mask, void *results);
+/* The last vhr_closest_point_query (waits for the device): out[0] = queries, out[1] = queries that found something, out[2] = point / triangle
+ * evaluations, out[3] = waves whose traversal stack overflowed (must be 0).  All 0 before the first query. */
+int vhr_get_point_query_statistics(vhr_context *ctx, uint64_t out[4]);
+/* The query's point / triangle function on explicit pairs (host memory): 12 floats per pair (p, v0, e1, e2) -> 3 floats per pair (d2, u, v).
+ * A device context runs the device's copy, one pair per thread; a HOST-ONLY context runs the host's copy of the same source: the arithmetic is
+ * testable without a GPU, and the two are comparable, bit for bit, on one. */
+int vhr_debug_point_triangle(vhr_context *ctx, const float *pairs, uint32_t count, float *out);
+
 #ifdef __cplusplus
 }
 #endif

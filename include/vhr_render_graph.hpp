@@ -166,6 +166,12 @@ public:
     void QueryRays(const vhr_ray *rays, uint32_t count, uint32_t flags, uint32_t cull_mask, const uint8_t *ray_masks, void *results) {
         check(context.handle, vhr_ray_query_masked(context.handle, rays, count, flags, cull_mask, ray_masks, results), "QueryRays");
     }
+    // Extension: the nearest surface to each point, within its max_distance, on the TLAS this manager owns (vhr_closest_point_query).  `flags` =
+    // VHR_POINT_QUERY_ANY_WITHIN and / or VHR_POINT_QUERY_HOST_MEMORY; results = vhr_ray_hit[count] (t = the distance), or uint8_t[count] with
+    // the first; cull_mask as in QueryRays.  Device pointers: enqueued on the context's current stream, no synchronisation.
+    void QueryClosestPoints(const vhr_point_query *points, uint32_t count, uint32_t flags, void *results, uint32_t cull_mask = 0xFFu) {
+        check(context.handle, vhr_closest_point_query(context.handle, points, count, flags, cull_mask, results), "QueryClosestPoints");
+    }
     // Extension: per-primitive ray cull masks (VkAccelerationStructureInstanceKHR::mask, per geometry; 0xFF after UpdateGeometry).  No refit needed.
     void SetPrimitiveMasks(uint32_t first_primitive, const std::vector<uint8_t> &masks) {
         check(context.handle, vhr_set_primitive_masks(context.handle, first_primitive, uint32_t(masks.size()), masks.data()), "SetPrimitiveMasks");

@@ -127,6 +127,15 @@ enum {
     VHR_RAY_QUERY_ALPHA_TEST = 16               /* a candidate hit gbuf.frag:20-32 would discard does not exist for the ray (4 and 8 stay unknown flags) */
 };
 
+/* One query of vhr_closest_point_query (include/vhr_amd.h): a point and the largest distance at which a surface still counts (+inf: any).
+ * 16 bytes; an array of them must start at a 16-byte boundary (the kernel reads a query as one 16-byte load). */
+typedef struct vhr_point_query {
+    float point[3];
+    float max_distance;
+} vhr_point_query;
+#define VHR_POINT_QUERY_ANY_WITHIN   1u   /* results: uint8_t[count], 1 = some surface lies within max_distance */
+#define VHR_POINT_QUERY_HOST_MEMORY  2u   /* host pointers, staged; returns with results in place */
+
 /* VkFormat values (passed through unchanged from reference-side code) */
 enum {
     VHR_FORMAT_UNDEFINED           = 0,
@@ -205,6 +214,7 @@ static_assert(sizeof(vhr_trace_params) == 32, "vhr_trace_params");
 static_assert(sizeof(vhr_ray) == 32 && offsetof(vhr_ray, tmin) == 12 && offsetof(vhr_ray, direction) == 16 && offsetof(vhr_ray, tmax) == 28, "vhr_ray");
 static_assert(sizeof(vhr_ray_hit) == 24 && offsetof(vhr_ray_hit, geometry_index) == 12 && offsetof(vhr_ray_hit, primitive_index) == 16 &&
               offsetof(vhr_ray_hit, reserved) == 20, "vhr_ray_hit");
+static_assert(sizeof(vhr_point_query) == 16 && offsetof(vhr_point_query, max_distance) == 12, "vhr_point_query");
 #else
 _Static_assert(sizeof(vhr_vertex) == 56, "Vertex");
 _Static_assert(sizeof(vhr_material) == 44, "Material");
@@ -217,6 +227,7 @@ _Static_assert(sizeof(vhr_trace_params) == 32, "vhr_trace_params");
 _Static_assert(sizeof(vhr_ray) == 32 && offsetof(vhr_ray, tmin) == 12 && offsetof(vhr_ray, direction) == 16 && offsetof(vhr_ray, tmax) == 28, "vhr_ray");
 _Static_assert(sizeof(vhr_ray_hit) == 24 && offsetof(vhr_ray_hit, geometry_index) == 12 && offsetof(vhr_ray_hit, primitive_index) == 16 &&
                offsetof(vhr_ray_hit, reserved) == 20, "vhr_ray_hit");
+_Static_assert(sizeof(vhr_point_query) == 16 && offsetof(vhr_point_query, max_distance) == 12, "vhr_point_query");
 #endif
 
 #endif /* VHR_TYPES_H */

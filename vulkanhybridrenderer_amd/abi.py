@@ -58,6 +58,9 @@ ray_hit_dtype = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("geometry_i
 RAY_QUERY_TERMINATE_ON_FIRST_HIT, RAY_QUERY_HOST_MEMORY = 1, 2
 RAY_QUERY_ALPHA_TEST = 16         # a candidate hit the G-buffer pass would discard does not exist for the ray (4 and 8 are no flags)
 RAY_MISS = 0xFFFFFFFF              # vhr_ray_hit.geometry_index / primitive_index of a miss
+# vhr_closest_point_query (include/vhr_types.h: vhr_point_query; its results are ray_hit_dtype with t = the distance, RAY_MISS = nothing found)
+point_query_dtype = np.dtype([("point", "<f4", 3), ("max_distance", "<f4")])
+POINT_QUERY_ANY_WITHIN, POINT_QUERY_HOST_MEMORY = 1, 2
 
 assert vertex_dtype.itemsize == 56
 assert material_dtype.itemsize == 44
@@ -67,6 +70,7 @@ assert per_frame_dtype.itemsize == 584
 assert svgf_push_constants_dtype.itemsize == 24
 assert trace_params_dtype.itemsize == 32
 assert ray_dtype.itemsize == 32 and ray_hit_dtype.itemsize == 24
+assert point_query_dtype.itemsize == 16
 
 
 def default_trace_params(shadow=True, ao_spp=2, reflections=True):

@@ -8,6 +8,7 @@
 #include <string>
 
 #include "vhr_internal.hpp"
+#include "closest_point.hpp"  // point_triangle's host copy (vhr_debug_point_triangle on a host-only context)
 #include "fingerprint.h"      // build/fingerprint.h, written by the Makefile
 
 namespace vhr {
@@ -336,6 +337,7 @@ void vhr_destroy(vhr_context *ctx) {
     hipFree(ctx->d_ray_stats);
     for (auto &q : ctx->rq_scratch) { hipFree(q.counters); hipFree(q.list); }
     hipFree(ctx->d_rq_staging);
+    for (auto &q : ctx->pq_scratch) hipFree(q.counters);
     hipFree(ctx->d_tile_counter);
     for (vhr_context::CostOrder *co : { &ctx->cost_order_raygen, &ctx->cost_order_reflection, &ctx->cost_order_raytraced })
         for (int i = 0; i < 2; ++i) { hipFree(co->cost[i]); hipFree(co->order[i]); }
@@ -1185,6 +1187,69 @@ int vhr_get_ray_query_statistics(vhr_context *ctx, uint64_t out[4]) {
     RayQueryCounters c;
     HIP_TRY(ctx, hipMemcpy(&c, ctx->rq_last_counters, sizeof(c), hipMemcpyDeviceToHost));
     out[0] = ctx->rq_rays; out[1] = c.hits; out[2] = c.redo_count; out[3] = c.overflows;
+    return VHR_OK;
+}
+
+// vhr_closest_point_query: the arguments first (the same answer on every context), then the device; staged like the ray query's host path
+int vhr_closest_point_query(vhr_context *ctx, const vhr_point_query *points, uint32_t count, uint32_t flags, uint32_t cull_mask, void *results) {
+    if (!ctx) return VHR_ERROR_INVALID_ARGUMENT;
+    const std::string who("vhr_closest_point_query");
+    if (count > 0 && (!points || !results)) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": points and results must not be NULL when count > 0");
+    if (flags & ~uint32_t(VHR_POINT_QUERY_ANY_WITHIN | VHR_POINT_QUERY_HOST_MEMORY))
+        return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": unknown flag bits " + std::to_string(flags));
+    if (count > 0 && reinterpret_cast<uintptr_t>(points) % 16u) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": points must be 16-byte aligned");
+    if (count > 0 && reinterpret_cast<uintptr_t>(results) % 4u) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": results must be 4-byte aligned");
+    if (cull_mask > 0xFFu) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": cull_mask " + std::to_string(cull_mask) + " exceeds 0xFF");
+    if (ctx->host_only) return ctx->fail(VHR_ERROR_NO_DEVICE, who + ": host-only context: no device work");
+    { const int stale = ctx->refuse_if_stale("vhr_closest_point_query"); if (stale != VHR_OK) return stale; }
+    if (count == 0) return VHR_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool any_within = (flags & VHR_POINT_QUERY_ANY_WITHIN) != 0;
+    ctx->pq_queries = count;
+    if (!(flags & VHR_POINT_QUERY_HOST_MEMORY)) return vhr::launch_point_query(ctx, points, count, any_within, cull_mask, results);
+    // host memory: the points, then the results at the next 256-byte boundary, in the ray query's staging buffer
+    const uint64_t point_bytes = uint64_t(count) * sizeof(vhr_point_query), result_bytes = uint64_t(count) * (any_within ? 1u : sizeof(vhr_ray_hit));
+    const uint64_t result_offset = (point_bytes + 255u) & ~uint64_t(255u), staging = result_offset + result_bytes;
+    if (ctx->rq_staging_bytes < staging) {
+        (void)hipFree(ctx->d_rq_staging);
+        ctx->d_rq_staging = nullptr;
+        ctx->rq_staging_bytes = 0;
+        HIP_TRY(ctx, hipMalloc(&ctx->d_rq_staging, staging));
+        ctx->rq_staging_bytes = staging;
+    }
+    char *const d = static_cast<char *>(ctx->d_rq_staging);
+    HIP_TRY(ctx, hipMemcpyAsync(d, points, point_bytes, hipMemcpyHostToDevice, ctx->stream));
+    const int rc = vhr::launch_point_query(ctx, reinterpret_cast<const vhr_point_query *>(d), count, any_within, cull_mask, d + result_offset);
+    if (rc != VHR_OK) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(results, d + result_offset, result_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return VHR_OK;
+}
+
+int vhr_get_point_query_statistics(vhr_context *ctx, uint64_t out[4]) {
+    if (!ctx || !out) return VHR_ERROR_INVALID_ARGUMENT;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (ctx->host_only || ctx->pq_queries == 0 || !ctx->pq_last_counters) return VHR_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipDeviceSynchronize());         // the stream of the last query may be the caller's: wait for the device, then read
+    PointQueryCounters c;
+    HIP_TRY(ctx, hipMemcpy(&c, ctx->pq_last_counters, sizeof(c), hipMemcpyDeviceToHost));
+    out[0] = ctx->pq_queries; out[1] = c.found; out[2] = c.evaluations; out[3] = c.overflows;
+    return VHR_OK;
+}
+
+// a device context runs the device's copy of point_triangle, a host-only context the host's: one source (closest_point.hpp)
+int vhr_debug_point_triangle(vhr_context *ctx, const float *pairs, uint32_t count, float *out) {
+    if (!ctx || (count && (!pairs || !out))) return ctx ? ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_debug_point_triangle: null argument") : VHR_ERROR_INVALID_ARGUMENT;
+    if (!ctx->host_only) {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        return launch_point_triangle_pairs(ctx, pairs, count, out);
+    }
+    for (uint32_t i = 0; i < count; ++i) {
+        const float *s = pairs + size_t(i) * 12u;
+        const PointTriangle r = point_triangle(s, s + 3, s + 6, s + 9);
+        out[size_t(i) * 3u] = r.d2; out[size_t(i) * 3u + 1u] = r.u; out[size_t(i) * 3u + 2u] = r.v;
+    }
     return VHR_OK;
 }
 

@@ -356,6 +356,10 @@ struct RayQueryCounters { uint32_t redo_count, overflows; unsigned long long hit
 // ... and the list of rays decision (vi) hands to the binary64 launch; one set per stream queries were enqueued on, so that queries in flight
 // on different streams (between frames on the caller's, inside a pass on the frame's front stream) share nothing
 struct RayQueryScratch { hipStream_t stream; RayQueryCounters *counters; uint32_t *list; uint64_t capacity; };
+// vhr_closest_point_query's counters (csrc/kernels_point_query.hip): queries that found something, point_triangle evaluations, waves whose stack
+// overflowed; one set per stream queries were enqueued on, like the ray query's
+struct PointQueryCounters { unsigned long long found, evaluations; uint32_t overflows, pad; };
+struct PointQueryScratch { hipStream_t stream; PointQueryCounters *counters; };
 
 struct RayStats {
     unsigned long long unique_rays, covered_pixels, stack_overflows, node_visits, leaf_visits, triangle_tests, wave_iterations, second_bounce_rays;
@@ -614,6 +618,11 @@ struct vhr_context {
     void *d_rq_staging = nullptr;
     uint64_t rq_staging_bytes = 0;
     uint64_t rq_rays = 0;               // rays of the last query (0: none yet)
+    // vhr_closest_point_query: counters per stream; VHR_POINT_QUERY_HOST_MEMORY stages through d_rq_staging (both host-memory paths wait for
+    // their stream before they return, so neither finds the other's data in it)
+    std::vector<vhr::PointQueryScratch> pq_scratch;
+    const vhr::PointQueryCounters *pq_last_counters = nullptr;  // the last query's (vhr_get_point_query_statistics)
+    uint64_t pq_queries = 0;            // queries of the last call (0: none yet)
 
     int options[vhr::kOptCount];       // vhr_set_option; defaults from vhr::kOptionInfo (the constructor)
     vhr_context() { for (int i = 0; i < vhr::kOptCount; ++i) options[i] = vhr::kOptionInfo[i].def; }
@@ -732,6 +741,10 @@ int launch_ray_triangle_pairs(vhr_context *ctx, const float *pairs, uint32_t n, 
 // cull_mask / ray_masks (device memory or null): vhr_ray_query_masked's; vhr_ray_query is (0xFF, null)
 int launch_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, bool any_hit, bool alpha_test, void *results, uint32_t cull_mask = 0xFFu,
                      const uint8_t *ray_masks = nullptr);
+// vhr_closest_point_query's device path (csrc/kernels_point_query.hip): `points` (count x vhr_point_query) and `results` (vhr_ray_hit or uint8_t per
+// query) are device memory; enqueued on ctx->stream.  vhr_debug_point_triangle on a device context: host arrays, 12 floats in and 3 out per pair
+int launch_point_query(vhr_context *ctx, const vhr_point_query *points, uint32_t count, bool any_within, uint32_t cull_mask, void *results);
+int launch_point_triangle_pairs(vhr_context *ctx, const float *pairs, uint32_t n, float *out);
 // the primitives' mask bytes on the device (made, from h_prim_masks or as all-0xFF, if no call has made them yet): before a launch that filters
 int ensure_device_prim_masks(vhr_context *ctx);
 

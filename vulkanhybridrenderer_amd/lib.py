@@ -44,6 +44,7 @@ EXPORTS = [
     "vhr_get_bvh_sah_cost", "vhr_refit_geometry_partial", "vhr_get_partial_refit_statistics",
     "vhr_get_object_motion_statistics", "vhr_debug_triangle_records",
     "vhr_set_primitive_masks", "vhr_get_primitive_masks", "vhr_ray_query_masked", "vhr_get_ray_mask_statistics",
+    "vhr_closest_point_query", "vhr_get_point_query_statistics", "vhr_debug_point_triangle",
 ]
 
 PATH_PREFIXES = ("hybrid", "raytraced", "rayquery", "forward_raster")      # vhr_<prefix>_{create,destroy,build,rebuild,last_error}
@@ -309,6 +310,9 @@ def load():
     L.vhr_get_ray_mask_statistics.argtypes = [vp, C.POINTER(u64)]
     L.vhr_get_ray_query_statistics.argtypes = [vp, C.POINTER(u64)]
     L.vhr_ray_query_struct_layout.argtypes = [C.POINTER(u32)]
+    L.vhr_closest_point_query.argtypes = [vp, vp, u32, u32, u32, vp]
+    L.vhr_get_point_query_statistics.argtypes = [vp, C.POINTER(u64)]
+    L.vhr_debug_point_triangle.argtypes = [vp, C.c_void_p, u32, C.c_void_p]
     L.vhr_update_vertices.argtypes = [vp, u32, u32, vp, u32]
     L.vhr_update_primitive_transforms.argtypes = [vp, u32, u32, vp]
     L.vhr_refit_geometry.argtypes = [vp]
@@ -920,6 +924,63 @@ class Context:
         out = (C.c_uint64 * 4)()
         self.check(self.L.vhr_get_ray_query_statistics(self.handle, out), "ray_query_statistics")
         return [int(x) for x in out]
+
+    @staticmethod
+    def _points_array(points):
+        """(n, 4) float32 (point, max_distance) or abi.point_query_dtype -> a C-contiguous, 16-byte-aligned point_query_dtype array."""
+        a = np.asarray(points)
+        if a.dtype == abi.point_query_dtype:
+            if a.ndim != 1:
+                raise ValueError(f"closest_point_query: a point_query_dtype array must be 1-D, got shape {a.shape}")
+        elif a.dtype == np.float32:
+            if a.ndim != 2 or a.shape[1] != 4:
+                raise ValueError(f"closest_point_query: float32 points must have shape (n, 4), got {a.shape}")
+            a = np.ascontiguousarray(a).view(abi.point_query_dtype).reshape(-1)
+        else:
+            raise TypeError(f"closest_point_query: points must be float32 (n, 4) or abi.point_query_dtype, got {a.dtype}")
+        if not a.flags.c_contiguous or a.ctypes.data % 16:       # vhr_closest_point_query wants 16-byte-aligned points: copy into an aligned buffer
+            raw = np.empty(len(a) * abi.point_query_dtype.itemsize + 16, np.uint8)
+            start = -raw.ctypes.data % 16
+            aligned = raw[start:start + len(a) * abi.point_query_dtype.itemsize].view(abi.point_query_dtype)
+            aligned[:] = a
+            a = aligned
+        return a
+
+    def closest_point_query(self, points, any_within=False, cull_mask=None):
+        """vhr_closest_point_query on host arrays: points (n, 4) float32 (point, max_distance) or abi.point_query_dtype.  Returns
+        abi.ray_hit_dtype[n] -- t = the distance to the nearest surface within max_distance, (u, v) the barycentrics of the nearest point,
+        geometry_index = primitive_index = abi.RAY_MISS where there is none -- or, with any_within, bool[n].  cull_mask (0..255, default
+        0xFF): a triangle on a primitive whose mask shares no bit with it does not exist for the query."""
+        p = self._points_array(points)
+        n = len(p)
+        out = np.zeros(n, np.uint8) if any_within else np.zeros(n, abi.ray_hit_dtype)
+        flags = abi.POINT_QUERY_HOST_MEMORY | (abi.POINT_QUERY_ANY_WITHIN if any_within else 0)
+        self.check(self.L.vhr_closest_point_query(self.handle, p.ctypes.data if n else None, n, flags, 0xFF if cull_mask is None else int(cull_mask),
+                                                  out.ctypes.data if n else None), "closest_point_query")
+        return out.astype(bool) if any_within else out
+
+    def closest_point_query_device(self, points_ptr, count, results_ptr, any_within=False, cull_mask=None):
+        """vhr_closest_point_query on device memory (e.g. torch tensors' data_ptr()): `count` vhr_point_query records at points_ptr (16-byte
+        aligned), results (vhr_ray_hit, or one uint8 per query with any_within) at results_ptr.  Enqueued on current_stream(); returns
+        without synchronising."""
+        flags = abi.POINT_QUERY_ANY_WITHIN if any_within else 0
+        self.check(self.L.vhr_closest_point_query(self.handle, points_ptr or None, int(count), flags, 0xFF if cull_mask is None else int(cull_mask),
+                                                  results_ptr or None), "closest_point_query_device")
+
+    def point_query_statistics(self):
+        """The last closest-point query: [queries, queries that found something, point / triangle evaluations, waves whose stack overflowed (must be 0)]."""
+        out = (C.c_uint64 * 4)()
+        self.check(self.L.vhr_get_point_query_statistics(self.handle, out), "point_query_statistics")
+        return [int(x) for x in out]
+
+    def debug_point_triangle(self, pairs):
+        """The query's point / triangle function on explicit pairs: pairs = (n, 12) float32 (p, v0, e1, e2) -> (n, 3) float32 (d2, u, v).  A device
+        context runs the device's copy, a host-only context the host's."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.float32).reshape(-1, 12)
+        out = np.zeros((len(pairs), 3), np.float32)
+        n = len(pairs)
+        self.check(self.L.vhr_debug_point_triangle(self.handle, pairs.ctypes.data if n else None, n, out.ctypes.data if n else None), "debug_point_triangle")
+        return out
 
     def current_stream(self):
         """hipStream_t (as an int) the library is enqueueing on right now: inside a pass callback, the stream that pass is ordered on."""
