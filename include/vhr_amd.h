@@ -778,17 +778,18 @@ int vhr_get_bvh_forms_fingerprint(vhr_context *ctx, uint64_t out[2]);
  * primitive transforms.  Per frame: vhr_update_vertices / vhr_update_primitive_transforms (any number), vhr_refit_geometry,
  * vhr_update_per_frame_ubo, vhr_graph_execute.  Results do not depend on the tree, so a refitted tree publishes exactly the images and ray
  * query answers a rebuild from the same arrays publishes ("alpha_test_rays" and VHR_RAY_QUERY_ALPHA_TEST included: what a ray sees is decided
- * per candidate from the primitive's material and the current vertices' uv0, never from the tree); what degrades is speed (watch vhr_get_bvh_sah_cost and rebuild when it has grown).
+ * per candidate from the primitive's material and the current vertices' uv0, never from the tree); what degrades is speed (watch vhr_get_bvh_sah_cost and call vhr_rebuild_geometry when it has grown).
  *   - While updates are pending (an update call without a vhr_refit_geometry after it) vhr_graph_execute, vhr_ray_query and the vhr_standin_*
  *     calls fail with VHR_ERROR_GRAPH and a message that names vhr_refit_geometry: a stale tree is never traced silently.
  *   - Refused, with a message in vhr_last_error: no geometry yet (VHR_ERROR_GRAPH); a tree built with "bvh_presplit" whose references were
- *     split (vhr_get_bvh_presplit_level >= 0: VHR_ERROR_UNSUPPORTED, rebuild instead); a range outside the buffer, a NULL array with a
+ *     split (vhr_get_bvh_presplit_level >= 0: VHR_ERROR_UNSUPPORTED; vhr_rebuild_geometry instead, with "bvh_presplit" 0 for a tree that can be refitted); a range outside the buffer, a NULL array with a
  *     non-zero count, an unknown flag, non-finite host data (VHR_ERROR_INVALID_ARGUMENT).  Argument checks come first, on every context.
  *   - Topology changes (triangles or primitives added or removed) need vhr_update_geometry.  Frame state is left alone: the SVGF history,
  *     cost orders, statistics.  By default motion vectors stay what the G-buffer pass makes them (camera motion only), so moving geometry ghosts
  *     in the SVGF history; "object_motion_vectors" 1 (below) makes the stand-in G-buffer follow the geometry the refits moved.
  *   - A host-only context supports all of it on the host (the same arithmetic): it keeps the arrays and the tree of its last build.
- *   - vhr_resize keeps the refitted tree; vhr_update_geometry discards pending updates and everything a refit prepared. */
+ *   - vhr_resize keeps the refitted tree; vhr_update_geometry and vhr_rebuild_geometry (below) replace the tree and everything a refit
+ *     prepared; the first discards pending updates, the second builds from them. */
 #define VHR_UPDATE_DEVICE_MEMORY 2u   /* vhr_update_vertices: `vertices` is device memory (the counterpart of VHR_RAY_QUERY_HOST_MEMORY's default) */
 /* Overwrites vertices [first_vertex, first_vertex + vertex_count) of the last vhr_update_geometry (whole records: the stand-in raster stages
  * read normals, tangents and uvs too).  flags 0: a host array, validated here (finite positions), copied before the call returns.
@@ -804,7 +805,7 @@ int vhr_update_primitive_transforms(vhr_context *ctx, uint32_t first_primitive, 
  * check (the half-precision form falls back to the 48-byte nodes exactly as after a build).  With nothing pending: VHR_OK, nothing launched.
  * Synchronises like vhr_update_geometry (it reads its counters back); an asynchronous refit is out of scope.  If it meets non-finite
  * coordinates (device-memory vertices) it fails with VHR_ERROR_INVALID_ARGUMENT, the tree's arrays are NOT valid and updates stay pending
- * until a refit succeeds or the geometry is rebuilt. */
+ * until a refit succeeds or the geometry is rebuilt (vhr_rebuild_geometry, vhr_update_geometry). */
 int vhr_refit_geometry(vhr_context *ctx);
 /* out[0] = refits since the last build that succeeded, out[1] = triangle records written by the last refit, out[2] = nodes written, out[3] = records not
  * inside their leaf's box, out[4] = child boxes not inside the slot their parent holds for them (both counted in exact comparisons by a
@@ -859,9 +860,46 @@ int vhr_get_partial_refit_statistics(vhr_context *ctx, uint64_t out[8]);
  * last successful refit (0 after a build, after switching on and after a settle), out[2] = G-buffer launches since vhr_create that ran the
  * motion instantiation, out[3] = 0. */
 int vhr_get_object_motion_statistics(vhr_context *ctx, uint64_t out[4]);
+/* ---- Rebuild in place: a new tree from the arrays on the device (refit while the tree is good, rebuild when it is not) ----
+ * Builds a new tree over the geometry as it stands -- the arrays of the last vhr_update_geometry with every later vhr_update_vertices and
+ * vhr_update_primitive_transforms applied, pending or already refitted -- with the build options as they are set NOW ("bvh_leaf_triangles",
+ * "bvh_builder", "bvh_build_threads", "bvh_frame", "bvh_presplit", "bvh_device_max_depth", "bvh_host_checks").  Nothing is handed over again:
+ * the device builder reads the scene arrays where the walkers read them.  Every array the walkers read, the fingerprints, the form checks,
+ * vhr_get_bvh_statistics / _frame / _presplit_level / _builder and the half-precision fallback are bit for bit those of a fresh context with
+ * the same option values after vhr_update_geometry with the current arrays.  vhr_update_geometry's fallbacks apply unchanged (a one-leaf
+ * scene, a tree deeper than the walkers' stacks and "bvh_builder" 0 go to the host builder); a device context keeps no host copy of the scene,
+ * so the call then fetches vertices, indices and primitives from the device (out[1] below) and uploads the tree as vhr_update_geometry does.
+ *   - Pending updates are consumed: nothing is pending afterwards, the dirty ranges are forgotten, vhr_get_refit_statistics and
+ *     vhr_get_partial_refit_statistics read as after a build, both words of vhr_get_bvh_sah_cost are the new tree's, and vhr_get_build_times
+ *     describes this build (out[0] the build, out[1] the transfers the call had to make: 0 where the device built).
+ *   - Kept: the scene arrays and textures on the device, the primitives' ray cull masks (vhr_get_ray_mask_statistics out[0] with them),
+ *     whether the scene can discard, every option and the trace parameters, storage images, the render graph and the paths registered on the
+ *     context, the SVGF history, cost orders and all frame statistics.  Results never depend on the tree: frames and queries after a rebuild
+ *     are bit for bit those after a refit of the same updates.
+ *   - A tree built with "bvh_presplit" is NOT refused (updates still cannot be pending on one): the call builds again, and with "bvh_presplit"
+ *     set to 0 first it gives a tree that can be refitted, without a re-upload.
+ *   - "object_motion_vectors" 1: a successful rebuild counts as one successful refit in the contract above, stated per triangle instead of per
+ *     slot: afterwards the previous record of every slot that holds flat triangle f (with "bvh_presplit" there are several) is the current record
+ *     f had before the call, bit for bit; a triangle that did not move has previous == current; vhr_get_object_motion_statistics out[1] counts
+ *     the records that differ, and the next refit call with nothing pending settles them.
+ *   - Waits for every stream of the context before anything is replaced and returns with the tree in place, like vhr_update_geometry.
+ *   - Refused, in this order, with a message that names the call: a NULL context; a flag bit (flags must be 0: VHR_ERROR_INVALID_ARGUMENT,
+ *     checked first on every context); no geometry yet (VHR_ERROR_GRAPH); called while a graph records or executes or from inside a pass
+ *     (VHR_ERROR_GRAPH).  Then every vertex position is checked where it lives, before anything is freed or built: a non-finite coordinate
+ *     (vertices written through VHR_UPDATE_DEVICE_MEMORY are unvalidated) gives VHR_ERROR_INVALID_ARGUMENT, the old tree's arrays are
+ *     untouched, and updates stay -- or become -- pending, so nothing traces until a later refit or rebuild succeeds.
+ *   - A host-only context supports all of it on the host, from the arrays it keeps.
+ * Costs (tools/rebuild_rate.py, profiles/rebuild_rate.jsonl; MI355X): about 10 ms on sponza_proc (258 k triangles) and 23 - 24 ms on bistro_proc
+ * (2.9 M), about 0.9 and 0.8 of vhr_update_geometry with the same arrays and some 33 and 20 steady-state refits: a call for the frame in which the
+ * cost has grown, not for every frame.  The first refit of the new tree makes the refit's plan again (about 1.2 / 13 ms against 0.3 / 1.1 ms). */
+int vhr_rebuild_geometry(vhr_context *ctx, uint32_t flags);
+/* out[0] = successful rebuilds since the last vhr_update_geometry, out[1] = 1 if the last one fetched the scene arrays from the device for
+ * the host builder, out[2] = non-finite coordinates the last call met (0 on success), out[3] = records whose previous differs from current
+ * after it (0 with "object_motion_vectors" off), out[4..7] = 0.  All 0 after vhr_create and after vhr_update_geometry. */
+int vhr_get_rebuild_statistics(vhr_context *ctx, uint64_t out[8]);
 /* The surface-area cost of the tree -- the sum over the inner nodes of child box area x (1 for an inner child, the triangle count for a
  * leaf), over the root's area, on the padded boxes the walkers test: out[0] = as built, out[1] = as it is now.  The number to watch when
- * deciding to rebuild.  One reduction, computed when asked (waits for the context's streams). */
+ * deciding to call vhr_rebuild_geometry.  One reduction, computed when asked (waits for the context's streams). */
 int vhr_get_bvh_sah_cost(vhr_context *ctx, double out[2]);
 
 /* ---- Batched ray queries on the scene's BVH (rayQueryEXT with an opaque TLAS, cull mask 0xFF -- vhr_ray_query_masked below takes the cull mask;

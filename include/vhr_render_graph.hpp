@@ -190,6 +190,9 @@ public:
     void RefitUpdatedGeometry(bool force_partial = false) {
         check(context.handle, vhr_refit_geometry_partial(context.handle, force_partial ? VHR_REFIT_FORCE_PARTIAL : 0u), "RefitUpdatedGeometry");
     }
+    // ... and when the refitted tree has grown slow (vhr_get_bvh_sah_cost): a new tree from the arrays the context holds, pending updates included.
+    // Nothing is handed over again; masks, options, the SVGF history and (with "object_motion_vectors") last frame's records are kept.
+    void RebuildGeometry() { check(context.handle, vhr_rebuild_geometry(context.handle, 0u), "RebuildGeometry"); }
     DeviceContext &context;
 };
 

@@ -790,4 +790,36 @@ double bvh_sah_cost(const HostBvh &bvh) {
     return bvh_math::sah_cost(sum, bvh.nodes[0], single);
 }
 
+// ---- rebuild in place (vhr_rebuild_geometry): the host twins of k0_rebuild_finite_kernel / k0_rebuild_gather_kernel / k0_rebuild_scatter_kernel ----
+uint64_t count_non_finite_positions(const vhr_vertex *vertices, uint32_t vertex_count) {
+    uint64_t bad = 0;
+    for (uint32_t v = 0; v < vertex_count; ++v)
+        for (int a = 0; a < 3; ++a) bad += std::isfinite(vertices[v].pos[a]) ? 0u : 1u;
+    return bad;
+}
+
+void rebuild_gather_records(const std::vector<BvhTri> &tris, const std::vector<BvhTri> &prev_tris, const std::vector<uint32_t> &prev_saved, uint32_t epoch,
+                            uint32_t flat_count, std::vector<BvhTri> &flat) {
+    flat.assign(flat_count, BvhTri{});
+    const bool retry = prev_tris.size() == tris.size() && prev_saved.size() == tris.size();
+    for (size_t k = 0; k < tris.size(); ++k) {
+        const BvhTri &t = (retry && prev_saved[k] == epoch) ? prev_tris[k] : tris[k];      // (a presplit tree's references of one triangle hold the same words)
+        if (t.flat < flat_count) flat[t.flat] = t;
+    }
+}
+
+uint64_t rebuild_scatter_records(HostBvh &bvh, const std::vector<BvhTri> &flat, uint32_t epoch) {
+    const size_t n = bvh.tris.size();
+    bvh.prev_tris.resize(n);
+    bvh.prev_saved.assign(n, 0u);
+    uint64_t differing = 0;
+    for (size_t k = 0; k < n; ++k) {
+        const uint32_t f = bvh.tris[k].flat;
+        bvh.prev_tris[k] = f < flat.size() ? flat[f] : bvh.tris[k];
+        if (motion_differs(bvh, k)) { bvh.prev_saved[k] = epoch; ++differing; }
+    }
+    bvh.prev_differing = differing;
+    return differing;
+}
+
 }  // namespace vhr

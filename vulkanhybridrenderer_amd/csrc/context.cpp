@@ -395,6 +395,108 @@ static int fetch_device_tree(vhr_context *ctx, HostBvh &bvh) {
     return VHR_OK;
 }
 
+static hipError_t upload_array(void **dst, const void *src, size_t bytes) {
+    *dst = nullptr;
+    if (bytes == 0) return hipSuccess;
+    hipError_t e = hipMalloc(dst, bytes);
+    if (e != hipSuccess) return e;
+    return hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+}
+
+// The part of a build vhr_update_geometry and vhr_rebuild_geometry share: which builder, the device builder's fallbacks, the self-checks and
+// fingerprints, and the tree where the context keeps it (uploaded on a device context, in h_bvh on a host-only one).  The caller has put the
+// scene arrays where the builders read them (a device context: d_vertices / d_indices / d_primitives), set ctx->prim_tri_prefix, waited for the
+// context's streams and freed the old tree.  `scene`: the arrays in host memory for the host builder; all NULL on a device context that keeps no
+// host copy (vhr_rebuild_geometry): they are then fetched from the device if, and only if, the host builder runs (*fetched = true).
+// `who` names the entry point in messages; upload_ms grows by the transfers made here.
+struct HostSceneArrays { const vhr_vertex *vertices; const uint32_t *indices; const vhr_primitive *primitives; };
+static int build_and_install_tree(vhr_context *ctx, const char *who, HostSceneArrays scene, uint32_t primitive_count, uint64_t total_triangles, double &upload_ms, bool *fetched) {
+    HostBvh bvh;
+    bool device_built = false;
+    ctx->bvh_builder_used = 0;
+    // ---- "bvh_builder" 1: the tree built on the device (csrc/kernels_bvh.hip), where the reference builds its BLAS / TLAS ----
+    if (ctx->bvh_builder >= 1 && !ctx->host_only && total_triangles >= 2ull * uint64_t(ctx->bvh_leaf_tris)) {
+        // first flat triangle of every primitive
+        // (a primitive without triangles shares its prefix with the next one: the search below picks the LAST primitive whose prefix is
+        // <= t, which is the one that owns triangle t, because an empty primitive's successor starts at the same value)
+        const std::vector<uint32_t> prefix(ctx->prim_tri_prefix.begin(), ctx->prim_tri_prefix.begin() + primitive_count);
+        const auto t0 = std::chrono::steady_clock::now();
+        const int rc = device_build_bvh(ctx, prefix, uint32_t(total_triangles), ctx->bvh_leaf_tris, ctx->bvh_presplit, ctx->bvh_frame_mode);
+        const auto t1 = std::chrono::steady_clock::now();
+        if (rc == VHR_OK) {
+            device_built = true;
+            ctx->bvh_builder_used = 1;
+            ctx->bvh_build_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+            // its self-checks ran on the device (k0_check_forms_kernel); "bvh_host_checks" 1 fetches the tree and repeats them with the host's
+            // code (tests hold the two equal).  The fingerprint is computed when somebody asks for it (vhr_get_bvh_fingerprint).
+            ctx->bvh_fingerprint_valid = false;
+            if (ctx->bvh_host_checks) {
+                const int frc = fetch_device_tree(ctx, bvh);
+                if (frc != VHR_OK) return frc;
+            }
+        } else {
+            hipFree(ctx->d_nodes); hipFree(ctx->d_nodes16); hipFree(ctx->d_nodes_ch); hipFree(ctx->d_nodes48); hipFree(ctx->d_tris);
+            ctx->d_nodes = nullptr; ctx->d_nodes16 = nullptr; ctx->d_nodes_ch = nullptr; ctx->d_nodes48 = nullptr; ctx->d_tris = nullptr;
+            ctx->node_count = ctx->tri_count = 0;
+            if (rc != VHR_ERROR_OUT_OF_SLOTS) return rc;          // (out of slots: deeper than the walkers' stacks, or a one-leaf scene -> the host builder)
+        }
+    }
+    std::vector<vhr_vertex> fetched_vertices;
+    std::vector<uint32_t> fetched_indices;
+    std::vector<vhr_primitive> fetched_primitives;
+    if (!device_built && !ctx->host_only && !scene.vertices && !scene.indices && !scene.primitives) {      // no host copy: the host builder's input comes back from the device
+        const auto t0 = std::chrono::steady_clock::now();
+        fetched_vertices.resize(ctx->vertex_count); fetched_indices.resize(ctx->index_count); fetched_primitives.resize(ctx->primitive_count);
+        if (ctx->vertex_count) HIP_TRY(ctx, hipMemcpy(fetched_vertices.data(), ctx->d_vertices, sizeof(vhr_vertex) * ctx->vertex_count, hipMemcpyDeviceToHost));
+        if (ctx->index_count) HIP_TRY(ctx, hipMemcpy(fetched_indices.data(), ctx->d_indices, sizeof(uint32_t) * ctx->index_count, hipMemcpyDeviceToHost));
+        if (ctx->primitive_count) HIP_TRY(ctx, hipMemcpy(fetched_primitives.data(), ctx->d_primitives, sizeof(vhr_primitive) * ctx->primitive_count, hipMemcpyDeviceToHost));
+        scene = HostSceneArrays{ fetched_vertices.data(), fetched_indices.data(), fetched_primitives.data() };
+        upload_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (fetched) *fetched = true;
+    }
+    const auto t_build0 = std::chrono::steady_clock::now();
+    if (!device_built) {
+        build_bvh(scene.vertices, scene.indices, scene.primitives, primitive_count, bvh, ctx->bvh_leaf_tris, ctx->bvh_build_threads, ctx->bvh_presplit, ctx->bvh_frame_mode);          // UpdateBLAS + UpdateTLAS
+        ctx->bvh_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build0).count();
+        ctx->bvh_presplit_level = bvh.presplit_level;
+        for (int i = 0; i < 9; ++i) ctx->bvh_frame[i] = bvh.frame[i];
+        ctx->bvh_frame_on = bvh.frame_on;
+    }
+    if (uint64_t(device_built ? ctx->node_count : bvh.nodes48.size()) * sizeof(BvhNode48) >= (1ull << 31))     // an inner link of the 48-byte nodes is a non-negative 32-bit byte offset
+        return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, std::string(who) + ": more than 44 million BVH nodes");
+    const auto t_build1 = std::chrono::steady_clock::now();       // K0 proper ends here; the self-checks below are timed apart
+    if (!device_built || ctx->bvh_host_checks) {
+        check_node_forms(bvh, ctx->bvh_form_checks, ctx->bvh_build_threads);
+        ctx->nodes16_valid = bvh.nodes16_valid && ctx->bvh_form_checks[3] == 0;      // else the walkers stay on the 48-byte nodes
+        ctx->bvh_fingerprint = bvh_fingerprint(bvh);
+        ctx->bvh_tree_fingerprint = bvh_tree_fingerprint(bvh);
+        ctx->bvh_fingerprint_valid = true;
+    }
+    ctx->bvh_check_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build1).count();
+    if (ctx->host_only) {
+        ctx->node_count = uint32_t(bvh.nodes.size());
+        ctx->tri_count = uint32_t(bvh.tris.size());
+        ctx->bvh_depth = bvh.max_depth;
+        ctx->geometry_upload_ms = 0.0;
+        ctx->h_bvh = std::move(bvh);
+        return VHR_OK;
+    }
+    if (!device_built) {
+        const auto t_upload0 = std::chrono::steady_clock::now();
+        HIP_TRY(ctx, upload_array(reinterpret_cast<void **>(&ctx->d_nodes), bvh.nodes.data(), sizeof(BvhNode) * bvh.nodes.size()));
+        HIP_TRY(ctx, upload_array(reinterpret_cast<void **>(&ctx->d_nodes16), bvh.nodes16.data(), sizeof(BvhNode16) * bvh.nodes16.size()));
+        HIP_TRY(ctx, upload_array(reinterpret_cast<void **>(&ctx->d_nodes_ch), bvh.nodes_ch.data(), sizeof(BvhNodeCH) * bvh.nodes_ch.size()));
+        HIP_TRY(ctx, upload_array(reinterpret_cast<void **>(&ctx->d_nodes48), bvh.nodes48.data(), sizeof(BvhNode48) * bvh.nodes48.size()));
+        HIP_TRY(ctx, upload_array(reinterpret_cast<void **>(&ctx->d_tris), bvh.tris.data(), sizeof(BvhTri) * bvh.tris.size()));
+        for (int a = 0; a < 3; ++a) ctx->bvh_centre[a] = bvh.centre[a];
+        ctx->node_count = uint32_t(bvh.nodes.size());
+        ctx->tri_count = uint32_t(bvh.tris.size());
+        ctx->bvh_depth = bvh.max_depth;
+        upload_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_upload0).count();
+    }
+    return VHR_OK;
+}
+
 int vhr_update_geometry(vhr_context *ctx, const vhr_vertex *vertices, uint32_t vertex_count, const uint32_t *indices,
                         uint32_t index_count, const vhr_primitive *primitives, uint32_t primitive_count) {
     if (!ctx || (!vertices && vertex_count) || (!indices && index_count) || (!primitives && primitive_count))
@@ -439,6 +541,7 @@ int vhr_update_geometry(vhr_context *ctx, const vhr_vertex *vertices, uint32_t v
     for (uint64_t &w : ctx->refit_stats) w = 0;
     for (uint64_t &w : ctx->partial_stats) w = 0;
     ctx->refit_dirty = RefitDirty{};
+    for (uint64_t &w : ctx->rebuild_stats) w = 0;
     ctx->prim_tri_prefix.assign(size_t(primitive_count) + 1u, 0u);
     for (uint32_t p = 0; p < primitive_count; ++p) ctx->prim_tri_prefix[p + 1u] = ctx->prim_tri_prefix[p] + primitives[p].index_count / 3;
     if (!ctx->host_only) {
@@ -447,102 +550,32 @@ int vhr_update_geometry(vhr_context *ctx, const vhr_vertex *vertices, uint32_t v
         free_scene(ctx);
     }
 
-    auto upload = [&](void **dst, const void *src, size_t bytes) -> hipError_t {
-        *dst = nullptr;
-        if (bytes == 0) return hipSuccess;
-        hipError_t e = hipMalloc(dst, bytes);
-        if (e != hipSuccess) return e;
-        return hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-    };
     double upload_ms = 0.0;
     if (!ctx->host_only) {                 // the scene arrays first: the device builder reads them where the walkers will
         const auto t0 = std::chrono::steady_clock::now();
         std::vector<float> nm(size_t(primitive_count) * 9);
         for (uint32_t p = 0; p < primitive_count; ++p) normal_matrix3(primitives[p].transform, &nm[size_t(p) * 9]);
-        HIP_TRY(ctx, upload(reinterpret_cast<void **>(&ctx->d_vertices), vertices, sizeof(vhr_vertex) * vertex_count));
-        HIP_TRY(ctx, upload(reinterpret_cast<void **>(&ctx->d_indices), indices, sizeof(uint32_t) * index_count));
-        HIP_TRY(ctx, upload(reinterpret_cast<void **>(&ctx->d_primitives), primitives, sizeof(vhr_primitive) * primitive_count));
-        HIP_TRY(ctx, upload(reinterpret_cast<void **>(&ctx->d_normal_matrices), nm.data(), sizeof(float) * nm.size()));
+        HIP_TRY(ctx, upload_array(reinterpret_cast<void **>(&ctx->d_vertices), vertices, sizeof(vhr_vertex) * vertex_count));
+        HIP_TRY(ctx, upload_array(reinterpret_cast<void **>(&ctx->d_indices), indices, sizeof(uint32_t) * index_count));
+        HIP_TRY(ctx, upload_array(reinterpret_cast<void **>(&ctx->d_primitives), primitives, sizeof(vhr_primitive) * primitive_count));
+        HIP_TRY(ctx, upload_array(reinterpret_cast<void **>(&ctx->d_normal_matrices), nm.data(), sizeof(float) * nm.size()));
         upload_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
 
-    HostBvh bvh;
-    bool device_built = false;
-    ctx->bvh_builder_used = 0;
-    // ---- "bvh_builder" 1: the tree built on the device (csrc/kernels_bvh.hip), where the reference builds its BLAS / TLAS ----
-    if (ctx->bvh_builder >= 1 && !ctx->host_only && total_triangles >= 2ull * uint64_t(ctx->bvh_leaf_tris)) {
-        std::vector<uint32_t> prefix(primitive_count);
-        uint32_t acc = 0;
-        for (uint32_t p = 0; p < primitive_count; ++p) { prefix[p] = acc; acc += primitives[p].index_count / 3; }
-        // (a primitive without triangles shares its prefix with the next one: the search below picks the LAST primitive whose prefix is
-        // <= t, which is the one that owns triangle t, because an empty primitive's successor starts at the same value)
-        const auto t0 = std::chrono::steady_clock::now();
-        const int rc = device_build_bvh(ctx, prefix, uint32_t(total_triangles), ctx->bvh_leaf_tris, ctx->bvh_presplit, ctx->bvh_frame_mode);
-        const auto t1 = std::chrono::steady_clock::now();
-        if (rc == VHR_OK) {
-            device_built = true;
-            ctx->bvh_builder_used = 1;
-            ctx->bvh_build_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
-            // its self-checks ran on the device (k0_check_forms_kernel); "bvh_host_checks" 1 fetches the tree and repeats them with the host's
-            // code (tests hold the two equal).  The fingerprint is computed when somebody asks for it (vhr_get_bvh_fingerprint).
-            ctx->bvh_fingerprint_valid = false;
-            if (ctx->bvh_host_checks) {
-                const int frc = fetch_device_tree(ctx, bvh);
-                if (frc != VHR_OK) return frc;
-            }
-        } else {
-            hipFree(ctx->d_nodes); hipFree(ctx->d_nodes16); hipFree(ctx->d_nodes_ch); hipFree(ctx->d_nodes48); hipFree(ctx->d_tris);
-            ctx->d_nodes = nullptr; ctx->d_nodes16 = nullptr; ctx->d_nodes_ch = nullptr; ctx->d_nodes48 = nullptr; ctx->d_tris = nullptr;
-            ctx->node_count = ctx->tri_count = 0;
-            if (rc != VHR_ERROR_OUT_OF_SLOTS) return rc;          // (out of slots: deeper than the walkers' stacks, or a one-leaf scene -> the host builder)
-        }
+    {   // builder choice, fallback, self-checks and the tree's upload: shared with vhr_rebuild_geometry
+        const HostSceneArrays scene{ vertices, indices, primitives };
+        const int rc = build_and_install_tree(ctx, "UpdateGeometry", scene, primitive_count, total_triangles, upload_ms, nullptr);
+        if (rc != VHR_OK) return rc;
     }
-    const auto t_build0 = std::chrono::steady_clock::now();
-    if (!device_built) {
-        build_bvh(vertices, indices, primitives, primitive_count, bvh, ctx->bvh_leaf_tris, ctx->bvh_build_threads, ctx->bvh_presplit, ctx->bvh_frame_mode);          // UpdateBLAS + UpdateTLAS
-        ctx->bvh_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build0).count();
-        ctx->bvh_presplit_level = bvh.presplit_level;
-        for (int i = 0; i < 9; ++i) ctx->bvh_frame[i] = bvh.frame[i];
-        ctx->bvh_frame_on = bvh.frame_on;
-    }
-    if (uint64_t(device_built ? ctx->node_count : bvh.nodes48.size()) * sizeof(BvhNode48) >= (1ull << 31))     // an inner link of the 48-byte nodes is a non-negative 32-bit byte offset
-        return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "UpdateGeometry: more than 44 million BVH nodes");
-    const auto t_build1 = std::chrono::steady_clock::now();       // K0 proper ends here; the self-checks below are timed apart
-    if (!device_built || ctx->bvh_host_checks) {
-        check_node_forms(bvh, ctx->bvh_form_checks, ctx->bvh_build_threads);
-        ctx->nodes16_valid = bvh.nodes16_valid && ctx->bvh_form_checks[3] == 0;      // else the walkers stay on the 48-byte nodes
-        ctx->bvh_fingerprint = bvh_fingerprint(bvh);
-        ctx->bvh_tree_fingerprint = bvh_tree_fingerprint(bvh);
-        ctx->bvh_fingerprint_valid = true;
-    }
-    ctx->bvh_check_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build1).count();
     if (ctx->host_only) {
-        ctx->node_count = uint32_t(bvh.nodes.size());
-        ctx->tri_count = uint32_t(bvh.tris.size());
-        ctx->bvh_depth = bvh.max_depth;
-        ctx->geometry_upload_ms = 0.0;
         // ... and keeps the arrays and the tree: the refit's host twin works on them (vhr_update_vertices, vhr_refit_geometry)
         ctx->h_vertices.assign(vertices, vertices + vertex_count);
         ctx->h_indices.assign(indices, indices + index_count);
         ctx->h_primitives.assign(primitives, primitives + primitive_count);
-        ctx->h_bvh = std::move(bvh);
         ctx->vertex_count = vertex_count;
         ctx->index_count = index_count;
         ctx->primitive_count = primitive_count;
         return reset_motion(ctx);
-    }
-    if (!device_built) {
-        const auto t_upload0 = std::chrono::steady_clock::now();
-        HIP_TRY(ctx, upload(reinterpret_cast<void **>(&ctx->d_nodes), bvh.nodes.data(), sizeof(BvhNode) * bvh.nodes.size()));
-        HIP_TRY(ctx, upload(reinterpret_cast<void **>(&ctx->d_nodes16), bvh.nodes16.data(), sizeof(BvhNode16) * bvh.nodes16.size()));
-        HIP_TRY(ctx, upload(reinterpret_cast<void **>(&ctx->d_nodes_ch), bvh.nodes_ch.data(), sizeof(BvhNodeCH) * bvh.nodes_ch.size()));
-        HIP_TRY(ctx, upload(reinterpret_cast<void **>(&ctx->d_nodes48), bvh.nodes48.data(), sizeof(BvhNode48) * bvh.nodes48.size()));
-        HIP_TRY(ctx, upload(reinterpret_cast<void **>(&ctx->d_tris), bvh.tris.data(), sizeof(BvhTri) * bvh.tris.size()));
-        for (int a = 0; a < 3; ++a) ctx->bvh_centre[a] = bvh.centre[a];
-        ctx->node_count = uint32_t(bvh.nodes.size());
-        ctx->tri_count = uint32_t(bvh.tris.size());
-        ctx->bvh_depth = bvh.max_depth;
-        upload_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_upload0).count();
     }
     ctx->vertex_count = vertex_count;
     ctx->index_count = index_count;
@@ -821,6 +854,86 @@ int vhr_get_refit_statistics(vhr_context *ctx, uint64_t out[8]) {
 int vhr_get_refit_times(vhr_context *ctx, double out[4]) {
     if (!ctx || !out) return VHR_ERROR_INVALID_ARGUMENT;
     for (int i = 0; i < 4; ++i) out[i] = ctx->refit_times_ms[i];
+    return VHR_OK;
+}
+
+// ---- rebuild in place: a new tree over the scene arrays the context holds (refit while the tree is good, rebuild when it is not) ----
+int vhr_rebuild_geometry(vhr_context *ctx, uint32_t flags) {
+    if (!ctx) return VHR_ERROR_INVALID_ARGUMENT;
+    static const char *who = "vhr_rebuild_geometry";
+    if (flags) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, std::string(who) + ": unknown flag bits " + std::to_string(flags));
+    const bool has = ctx->host_only ? !ctx->h_bvh.nodes.empty() : (ctx->d_nodes != nullptr && ctx->node_count != 0);
+    if (!has) return ctx->fail(VHR_ERROR_GRAPH, std::string(who) + ": no geometry yet (vhr_update_geometry first)");
+    if (ctx->recording || ctx->cur_pass || ctx->in_execute) return ctx->fail(VHR_ERROR_GRAPH, std::string(who) + ": called from inside a pass");
+    const uint32_t primitive_count = ctx->primitive_count;
+    const uint64_t total_triangles = ctx->prim_tri_prefix.empty() ? 0u : ctx->prim_tri_prefix.back();
+    if (!ctx->host_only) {                   // frames in flight read the tree; a pending device-memory update is a copy on the context's stream
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        { const int src_ = ctx->sync_streams(); if (src_ != VHR_OK) return src_; }
+    }
+    // every position, before anything is freed or built: device-memory vertices are unvalidated, and the builder's bin index must not see a NaN
+    uint64_t non_finite = 0;
+    if (ctx->host_only) non_finite = count_non_finite_positions(ctx->h_vertices.data(), ctx->vertex_count);
+    else { const int rc = device_count_non_finite_positions(ctx, &non_finite); if (rc != VHR_OK) return rc; }
+    ctx->rebuild_stats[kRebuildNonFinite] = non_finite;
+    if (non_finite) {                        // (the old tree's arrays are untouched, but they are not these vertices' tree: nothing traces until a refit or a rebuild succeeds)
+        ctx->refit_pending = true;
+        ctx->refit_dirty.vertices.add(0u, ctx->vertex_count);
+        return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, std::string(who) + ": " + std::to_string(non_finite) +
+                         " non-finite coordinates in the vertex positions: nothing was rebuilt; update the vertices and rebuild or refit again");
+    }
+    // "object_motion_vectors": the old tree's current records in flat triangle order, for the new tree's slots (vhr_internal.hpp has the rules)
+    const bool carry = ctx->motion_valid();
+    const uint32_t epoch = ctx->motion_epoch + 1u;
+    std::vector<BvhTri> h_flat;
+    BvhTri *d_flat = nullptr;
+    if (carry) {
+        if (ctx->host_only) rebuild_gather_records(ctx->h_bvh.tris, ctx->h_bvh.prev_tris, ctx->h_bvh.prev_saved, epoch, uint32_t(total_triangles), h_flat);
+        else { const int rc = device_rebuild_gather(ctx, uint32_t(total_triangles), &d_flat); if (rc != VHR_OK) return rc; }
+    }
+    // the old tree and everything a refit had prepared for it; the scene arrays, the textures and the primitives' masks stay where they are
+    ctx->refit_pending = ctx->sah_cost_built_valid = false;
+    for (uint64_t &w : ctx->refit_stats) w = 0;
+    for (uint64_t &w : ctx->partial_stats) w = 0;
+    ctx->refit_dirty = RefitDirty{};
+    ctx->rebuild_stats[kRebuildFetched] = ctx->rebuild_stats[kRebuildDiffering] = 0;
+    if (!ctx->host_only) {
+        vhr::free_refit_plan(ctx);
+        hipFree(ctx->d_nodes); hipFree(ctx->d_nodes16); hipFree(ctx->d_nodes_ch); hipFree(ctx->d_nodes48); hipFree(ctx->d_tris);
+        ctx->d_nodes = nullptr; ctx->d_nodes16 = nullptr; ctx->d_nodes_ch = nullptr; ctx->d_nodes48 = nullptr; ctx->d_tris = nullptr;
+        ctx->node_count = ctx->tri_count = 0;
+    }
+    double transfer_ms = 0.0;
+    bool fetched = false;
+    const HostSceneArrays scene = ctx->host_only ? HostSceneArrays{ ctx->h_vertices.data(), ctx->h_indices.data(), ctx->h_primitives.data() } : HostSceneArrays{ nullptr, nullptr, nullptr };
+    int rc = build_and_install_tree(ctx, who, scene, primitive_count, total_triangles, transfer_ms, &fetched);
+    uint64_t differing = 0;
+    if (rc == VHR_OK && carry) {
+        if (ctx->host_only) differing = rebuild_scatter_records(ctx->h_bvh, h_flat, epoch);
+        else rc = device_rebuild_scatter(ctx, d_flat, uint32_t(total_triangles), &differing);
+    }
+    if (d_flat) hipFree(d_flat);
+    if (rc != VHR_OK) {                      // no tree, as after a vhr_update_geometry that failed: the previous records go with it
+        free_motion(ctx);
+        return rc;
+    }
+    if (!ctx->host_only) ctx->geometry_upload_ms = transfer_ms;
+    if (carry) {                             // the rebuild is refit number `epoch` of the contract at vhr_get_object_motion_statistics
+        ctx->motion_epoch = epoch;
+        ctx->motion_differing = ctx->motion_refit_differing = differing;
+    } else {
+        rc = reset_motion(ctx);              // (option off: frees nothing; on without arrays: previous = current)
+        if (rc != VHR_OK) return rc;
+    }
+    ctx->rebuild_stats[kRebuildFetched] = fetched ? 1u : 0u;
+    ctx->rebuild_stats[kRebuildDiffering] = differing;
+    ++ctx->rebuild_stats[kRebuildCount];
+    return VHR_OK;
+}
+
+int vhr_get_rebuild_statistics(vhr_context *ctx, uint64_t out[8]) {
+    if (!ctx || !out) return VHR_ERROR_INVALID_ARGUMENT;
+    for (int i = 0; i < kRebuildStatWords; ++i) out[i] = ctx->rebuild_stats[i];
     return VHR_OK;
 }
 

@@ -878,6 +878,63 @@ __global__ __launch_bounds__(256) void k0_motion_settle_kernel(const BvhTri *__r
     float4 *pslot = reinterpret_cast<float4 *>(motion.prev + k);
     pslot[0] = slot[0]; pslot[1] = slot[1]; pslot[2] = slot[2];
 }
+// ---- rebuild in place (vhr_rebuild_geometry; vhr_internal.hpp has the carry-over's rules) ----
+// Three bandwidth-bound passes, one thread per element, nothing but loads, stores and one count.
+// The finiteness pass: vertices written through VHR_UPDATE_DEVICE_MEMORY are unvalidated, and a NaN must not reach the builder's bin index.  A
+// vertex is 56 bytes, so its position is 8-byte aligned and no more: one 8-byte and one 4-byte load (the other 44 bytes are not read).  The
+// count is of coordinates, by their exponent bits (all ones: inf or NaN); reduced over the wave, one vector atomic per wave that met any.
+__global__ __launch_bounds__(256) void k0_rebuild_finite_kernel(const vhr_vertex *__restrict__ vertices, uint32_t n, unsigned long long *__restrict__ non_finite) {
+    const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+    uint32_t bad = 0;
+    if (v < n) {
+        const float2 xy = *reinterpret_cast<const float2 *>(vertices[v].pos);
+        const float z = vertices[v].pos[2];
+        const uint32_t w[3] = { __float_as_uint(xy.x), __float_as_uint(xy.y), __float_as_uint(z) };
+#pragma unroll
+        for (int a = 0; a < 3; ++a) bad += (w[a] & 0x7f800000u) == 0x7f800000u ? 1u : 0u;
+    }
+    for (int off = 32; off > 0; off >>= 1) bad += uint32_t(__shfl_xor(int(bad), off));
+    if ((threadIdx.x & 63u) == 0u && bad) atomicAdd(non_finite, (unsigned long long)bad);
+}
+// The gather, before the old tree is freed: record k's 48 bytes to flat[record.flat] (the flat index is the record's last word).  A record a
+// failed refit attempt of number `epoch` saved gives its previous record (its slot holds the attempt's values).  The references a presplit tree
+// holds of one triangle carry the same words, so their stores to one flat slot do not race for the result.  A flat index outside the scene's
+// triangles cannot happen and is never used as an address.
+__global__ __launch_bounds__(256) void k0_rebuild_gather_kernel(const BvhTri *__restrict__ tris, uint32_t n, const RefitMotion motion, uint32_t flat_count,
+                                                                BvhTri *__restrict__ flat) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k >= n) return;
+    const float4 *slot = reinterpret_cast<const float4 *>((motion.saved[k] == motion.epoch ? motion.prev : tris) + k);
+    const float4 q0 = slot[0], q1 = slot[1], q2 = slot[2];
+    const uint32_t f = __float_as_uint(q2.w);
+    if (f >= flat_count) return;
+    float4 *out = reinterpret_cast<float4 *>(flat + f);
+    out[0] = q0; out[1] = q1; out[2] = q2;
+}
+// The scatter, after the build: slot k of the new tree takes previous = flat[its record's flat index] and saved = `epoch` if the nine words
+// differ from its current record (motion_differs, as the refit counts them), else 0 -- which is what the settle pass of the next refit call and
+// the invariant at vhr_context::d_prev_saved expect of refit number `epoch`.  Every word of both arrays is written.
+__global__ __launch_bounds__(256) void k0_rebuild_scatter_kernel(const BvhTri *__restrict__ tris, uint32_t n, const BvhTri *__restrict__ flat, uint32_t flat_count,
+                                                                 const RefitMotion motion, unsigned long long *__restrict__ differing) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    uint32_t differs = 0;
+    if (k < n) {
+        const float4 *slot = reinterpret_cast<const float4 *>(tris + k);
+        const float4 now[3] = { slot[0], slot[1], slot[2] };
+        const uint32_t f = __float_as_uint(now[2].w);
+        float4 was[3] = { now[0], now[1], now[2] };
+        if (f < flat_count) {
+            const float4 *src = reinterpret_cast<const float4 *>(flat + f);
+            was[0] = src[0]; was[1] = src[1]; was[2] = src[2];
+        }
+        float4 *pslot = reinterpret_cast<float4 *>(motion.prev + k);
+        pslot[0] = was[0]; pslot[1] = was[1]; pslot[2] = was[2];
+        differs = motion_differs(was, now);
+        motion.saved[k] = differs ? motion.epoch : 0u;
+    }
+    for (int off = 32; off > 0; off >>= 1) differs += uint32_t(__shfl_xor(int(differs), off));
+    if ((threadIdx.x & 63u) == 0u && differs) atomicAdd(differing, (unsigned long long)differs);
+}
 // one node (bvh_math::refit_slots): its two slots from its children's unpadded boxes, its own unpadded box for its parent
 __device__ __forceinline__ void refit_node(uint32_t k, BvhNode *nodes, const BvhTri *tris, Box6 *self_box, const RefitFrame &f, bool single) {
     BvhNode nd = nodes[k];
@@ -1555,6 +1612,66 @@ int device_motion_settle(vhr_context *ctx) {
     hipLaunchKernelGGL(k0_motion_settle_kernel, refit_grid(ctx->tri_count), dim3(256), 0, ctx->stream, ctx->d_tris, ctx->tri_count, motion);
     REFIT_TRY(hipStreamSynchronize(ctx->stream));
     REFIT_TRY(hipGetLastError());
+    return VHR_OK;
+}
+
+// ---- rebuild in place (vhr_rebuild_geometry): the three passes around device_build_bvh; the caller has waited for the context's streams ----
+#define REBUILD_TRY(expr)                                                                                  \
+    do {                                                                                                    \
+        hipError_t e_ = (expr);                                                                             \
+        if (e_ != hipSuccess) return ctx->fail(VHR_ERROR_DEVICE, std::string("rebuild: ") + #expr + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+int device_count_non_finite_positions(vhr_context *ctx, uint64_t *count) {
+    *count = 0;
+    if (!ctx->vertex_count) return VHR_OK;
+    Scratch tmp;
+    unsigned long long *d_count, h_count = 0;
+    REBUILD_TRY(tmp.alloc(&d_count, size_t(1)));
+    REBUILD_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), ctx->stream));
+    hipLaunchKernelGGL(k0_rebuild_finite_kernel, refit_grid(ctx->vertex_count), dim3(256), 0, ctx->stream, ctx->d_vertices, ctx->vertex_count, d_count);
+    REBUILD_TRY(hipMemcpyAsync(&h_count, d_count, sizeof(h_count), hipMemcpyDeviceToHost, ctx->stream));
+    REBUILD_TRY(hipStreamSynchronize(ctx->stream));
+    REBUILD_TRY(hipGetLastError());
+    *count = h_count;
+    return VHR_OK;
+}
+
+int device_rebuild_gather(vhr_context *ctx, uint32_t flat_count, BvhTri **d_flat) {
+    *d_flat = nullptr;
+    const RefitMotion motion = refit_motion(ctx);
+    if (!motion.prev || !ctx->tri_count || !flat_count) return VHR_OK;
+    BvhTri *flat = nullptr;
+    REBUILD_TRY(hipMalloc(reinterpret_cast<void **>(&flat), sizeof(BvhTri) * size_t(flat_count)));
+    hipError_t e = hipMemsetAsync(flat, 0, sizeof(BvhTri) * size_t(flat_count), ctx->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k0_rebuild_gather_kernel, refit_grid(ctx->tri_count), dim3(256), 0, ctx->stream, ctx->d_tris, ctx->tri_count, motion, flat_count, flat);
+        e = hipStreamSynchronize(ctx->stream);
+    }
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) { hipFree(flat); REBUILD_TRY(e); }
+    *d_flat = flat;
+    return VHR_OK;
+}
+
+int device_rebuild_scatter(vhr_context *ctx, const BvhTri *d_flat, uint32_t flat_count, uint64_t *differing) {
+    *differing = 0;
+    hipFree(ctx->d_prev_tris); hipFree(ctx->d_prev_saved);
+    ctx->d_prev_tris = nullptr; ctx->d_prev_saved = nullptr;
+    if (!ctx->tri_count) return VHR_OK;
+    hipStream_t s = ctx->stream;
+    Scratch tmp;
+    unsigned long long *d_count, h_count = 0;
+    REBUILD_TRY(tmp.alloc(&d_count, size_t(1)));
+    REBUILD_TRY(hipMalloc(reinterpret_cast<void **>(&ctx->d_prev_tris), sizeof(BvhTri) * size_t(ctx->tri_count)));
+    REBUILD_TRY(hipMalloc(reinterpret_cast<void **>(&ctx->d_prev_saved), sizeof(uint32_t) * size_t(ctx->tri_count)));
+    REBUILD_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s));
+    const RefitMotion motion{ ctx->d_prev_tris, ctx->d_prev_saved, ctx->motion_epoch + 1u };
+    hipLaunchKernelGGL(k0_rebuild_scatter_kernel, refit_grid(ctx->tri_count), dim3(256), 0, s, ctx->d_tris, ctx->tri_count, d_flat, flat_count, motion, d_count);
+    REBUILD_TRY(hipMemcpyAsync(&h_count, d_count, sizeof(h_count), hipMemcpyDeviceToHost, s));
+    REBUILD_TRY(hipStreamSynchronize(s));
+    REBUILD_TRY(hipGetLastError());
+    *differing = h_count;
     return VHR_OK;
 }
 

@@ -267,6 +267,27 @@ int device_bvh_sah_cost(vhr_context *ctx, double *cost);
 // "object_motion_vectors": the settle pass of a refit call with nothing pending -- every record the last refit saved gets previous = current
 int device_motion_settle(vhr_context *ctx);
 
+// ---- rebuild in place (vhr_rebuild_geometry): a new tree over the scene arrays the context holds, state carried across its slot permutation ----
+// vhr_get_rebuild_statistics' words
+enum RebuildStat { kRebuildCount = 0, kRebuildFetched = 1, kRebuildNonFinite = 2, kRebuildDiffering = 3, kRebuildStatWords = 8 };
+// "object_motion_vectors" across a rebuild.  The new tree puts triangle f's record in another slot (with "bvh_presplit" in several), so the
+// previous records travel by flat triangle index: before the old tree goes, its current records are gathered into flat order (a record a
+// failed refit attempt of number `epoch` has saved already -- prev_saved[k] == epoch -- gives its previous record instead: its slot holds that
+// attempt's values); after the build every slot k of the new tree takes previous = flat[tris[k].flat] and prev_saved[k] = epoch if the nine
+// words differ from its current record, else 0.  The rebuild is refit number `epoch` = motion_epoch + 1, so the invariant at
+// vhr_context::d_prev_saved holds when the caller has counted it: prev_saved[k] < motion_epoch implies previous == current.
+// The host twins (csrc/bvh_build.cpp):
+uint64_t count_non_finite_positions(const vhr_vertex *vertices, uint32_t vertex_count);      // coordinates, as the refit's counter counts them
+void rebuild_gather_records(const std::vector<BvhTri> &tris, const std::vector<BvhTri> &prev_tris, const std::vector<uint32_t> &prev_saved, uint32_t epoch,
+                            uint32_t flat_count, std::vector<BvhTri> &flat);
+// fills bvh.prev_tris / prev_saved / prev_differing for the new tree; returns the records whose previous differs from current
+uint64_t rebuild_scatter_records(HostBvh &bvh, const std::vector<BvhTri> &flat, uint32_t epoch);
+// the device side (csrc/kernels_bvh.hip); the caller has waited for the context's streams
+int device_count_non_finite_positions(vhr_context *ctx, uint64_t *count);
+int device_rebuild_gather(vhr_context *ctx, uint32_t flat_count, BvhTri **d_flat);      // *d_flat: 48 bytes per flat triangle, the caller's to hipFree
+// allocates ctx->d_prev_tris / d_prev_saved for the tree the context now holds (the old ones are freed) and fills them from d_flat
+int device_rebuild_scatter(vhr_context *ctx, const BvhTri *d_flat, uint32_t flat_count, uint64_t *differing);
+
 enum class PassKind { Graphics, Raytracing, Compute };
 
 // Pass time stamps written by the kernels themselves (r3c).  vkCmdWriteTimestamp pairs (render_graph.cpp:167-182) used to ride on the
@@ -507,6 +528,7 @@ struct vhr_context {
     // record it rewrites unless d_prev_saved[k] == E already (a retry after a failed attempt: the record then holds the attempt's garbage, the
     // previous array the state to keep), and settles a clean record saved by refit E - 1 (previous = current: it has stopped).  Invariant
     // between refits: d_prev_saved[k] < motion_epoch implies previous == current.  A host-only context keeps the same in h_bvh.prev_*.
+    // vhr_rebuild_geometry counts as refit E too: it replaces both arrays for the new tree's slots (the rules stand at rebuild_scatter_records above).
     int object_motion_vectors = 0;
     vhr::BvhTri *d_prev_tris = nullptr;
     uint32_t *d_prev_saved = nullptr;
@@ -544,6 +566,7 @@ struct vhr_context {
     vhr::RefitDirty refit_dirty;
     uint64_t partial_stats[vhr::kPartialStatWords] = {};
     std::vector<uint32_t> prim_tri_prefix;       // triangles before primitive p (primitive_count + 1 entries): the dirty share of a primitive range
+    uint64_t rebuild_stats[vhr::kRebuildStatWords] = {};      // vhr_rebuild_geometry (vhr_get_rebuild_statistics); all 0 after vhr_update_geometry
     // a host-only context keeps the arrays and the tree of its last build: the refit's host twin works on them
     std::vector<vhr_vertex> h_vertices;
     std::vector<uint32_t> h_indices;

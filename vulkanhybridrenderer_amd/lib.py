@@ -45,6 +45,7 @@ EXPORTS = [
     "vhr_get_object_motion_statistics", "vhr_debug_triangle_records",
     "vhr_set_primitive_masks", "vhr_get_primitive_masks", "vhr_ray_query_masked", "vhr_get_ray_mask_statistics",
     "vhr_closest_point_query", "vhr_get_point_query_statistics", "vhr_debug_point_triangle",
+    "vhr_rebuild_geometry", "vhr_get_rebuild_statistics",
 ]
 
 PATH_PREFIXES = ("hybrid", "raytraced", "rayquery", "forward_raster")      # vhr_<prefix>_{create,destroy,build,rebuild,last_error}
@@ -322,6 +323,8 @@ def load():
     L.vhr_refit_geometry_partial.argtypes = [vp, u32]
     L.vhr_get_partial_refit_statistics.argtypes = [vp, C.POINTER(u64)]
     L.vhr_get_object_motion_statistics.argtypes = [vp, C.POINTER(u64)]
+    L.vhr_rebuild_geometry.argtypes = [vp, u32]
+    L.vhr_get_rebuild_statistics.argtypes = [vp, C.POINTER(u64)]
     L.vhr_debug_triangle_records.argtypes = [vp, i32, C.c_void_p, u32, C.POINTER(u32)]
     L.vhr_set_kernel_timing.argtypes = [vp, i32]
     L.vhr_get_kernel_time.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(u64), i32]
@@ -479,6 +482,18 @@ class Context:
         """vhr_refit_geometry_partial: only the records the pending updates' ranges touch and their leaves' ancestors; the same arrays as
         refit_geometry().  force=True: the dirty path whatever the dirty share (the first refit after a build is whole-tree regardless)."""
         self.check(self.L.vhr_refit_geometry_partial(self.handle, REFIT_FORCE_PARTIAL if force else 0), "refit_geometry_partial")
+
+    def rebuild_geometry(self, flags=0):
+        """vhr_rebuild_geometry: a new tree, built with the options as they are set now, over the arrays the context holds -- pending updates
+        included.  Masks, options, frame state and (with "object_motion_vectors") last frame's records are kept; nothing is re-uploaded."""
+        self.check(self.L.vhr_rebuild_geometry(self.handle, int(flags)), "rebuild_geometry")
+
+    def rebuild_statistics(self):
+        """vhr_get_rebuild_statistics: (successful rebuilds since update_geometry, 1 if the last fetched the scene for the host builder,
+        non-finite coordinates the last call met, records whose previous differs from current after it, 0, 0, 0, 0)."""
+        out = (C.c_uint64 * 8)()
+        self.check(self.L.vhr_get_rebuild_statistics(self.handle, out), "rebuild_statistics")
+        return tuple(int(v) for v in out)
 
     def partial_refit_statistics(self):
         out = (C.c_uint64 * 8)()
