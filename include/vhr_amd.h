@@ -906,7 +906,7 @@ int vhr_get_bvh_sah_cost(vhr_context *ctx, double out[2]);
  *      VHR_RAY_QUERY_ALPHA_TEST: a non-opaque one) ----
  * Traces `count` caller-made rays against the geometry of the last vhr_update_geometry.  The flags of rayQueryInitializeEXT this
  * stands for are gl_RayFlagsTerminateOnFirstHitEXT (VHR_RAY_QUERY_TERMINATE_ON_FIRST_HIT) or none; the mask is 0xFF (any other: vhr_ray_query_masked).
- *   - All geometry is opaque and two-sided; a triangle is hit iff tmin < t < tmax (decision (vi): fp32 Moeller-Trumbore, a candidate whose
+ *   - All geometry is opaque and two-sided (face culling: vhr_ray_query_faces below); a triangle is hit iff tmin < t < tmax (decision (vi): fp32 Moeller-Trumbore, a candidate whose
  *     solution contradicts itself decided again in binary64 -- the same test, bit for bit, as every walker of the library and the oracle).
  *   - Without the flag: results = vhr_ray_hit[count], the hit of smallest t, ties broken by the smaller flat triangle index (primitive-major
  *     order of vhr_update_geometry); a miss is geometry_index = primitive_index = 0xFFFFFFFF, t = u = v = 0.  With it: results =
@@ -992,6 +992,43 @@ int vhr_get_point_query_statistics(vhr_context *ctx, uint64_t out[4]);
  * A device context runs the device's copy, one pair per thread; a HOST-ONLY context runs the host's copy of the same source: the arithmetic is
  * testable without a GPU, and the two are comparable, bit for bit, on one. */
 int vhr_debug_point_triangle(vhr_context *ctx, const float *pairs, uint32_t count, float *out);
+
+/* ---- Ray face culling and the hit kind of ray queries (gl_RayFlagsCullBackFacingTrianglesEXT / gl_RayFlagsCullFrontFacingTrianglesEXT of
+ *      rayQueryInitializeEXT; rayQueryGetIntersectionFrontFaceEXT, gl_HitKindFrontFacingTriangleEXT) ----
+ * A triangle (v0, v1, v2) of primitive p is FRONT-FACING for a ray of direction d iff (det > 0) != flip[p], where det = e1 . (d x e2),
+ * e1 = v1 - v0, e2 = v2 - v0 in world space: the vertices appear counter-clockwise from the ray's origin (glTF's winding, the raster pipeline's
+ * VK_FRONT_FACE_COUNTER_CLOCKWISE, an instance with VK_GEOMETRY_INSTANCE_TRIANGLE_FRONT_COUNTERCLOCKWISE_BIT_KHR).  det is computed in
+ * binary64 from the leaf record's fp32 edges, operation for operation as decision (vi)'s binary64 Moeller-Trumbore computes its determinant
+ * (products of two fp32 values exact, every other operation rounded once): at grazing incidence the fp32 determinant's sign is rounding noise.
+ * Whatever is not > 0 is back-facing (det == 0, a NaN direction), so the two cull modes partition a ray's candidates.  Facing is decided in
+ * OBJECT space, as Vulkan and glTF decide it: flip[p] = 1 iff the determinant of the upper 3 x 3 of vhr_primitive::transform is < 0 (binary64,
+ * cofactors along the first row: (m00 (m11 m22 - m12 m21) - m01 (m10 m22 - m12 m20)) + m02 (m10 m21 - m11 m20); zero gives 0).
+ *   - vhr_ray_query_faces is vhr_ray_query_masked -- contract, flags, validation order, error codes, stream and memory rules, no frame state
+ *     read or written, refused while updates are pending -- with one more rule: a candidate on a back-facing triangle does not exist for a ray
+ *     with VHR_FACE_CULL_BACK, one on a front-facing triangle does not exist with VHR_FACE_CULL_FRONT.  It ends no any-hit ray, shrinks no
+ *     closest t and takes no part in the (t, flat index) tie-break.  Per candidate: decision (vi) with its binary64 re-decision, the mask test,
+ *     the face test, the alpha rule.  Results never depend on the tree.  "The closest front-facing hit" is not "the closest hit, dropped if it
+ *     faces backwards": the filter sits inside the walk.
+ *   - face_cull > 2 (Vulkan forbids both bits together): VHR_ERROR_INVALID_ARGUMENT, checked with the other arguments, behind cull_mask > 0xFF.
+ *   - Without VHR_RAY_QUERY_TERMINATE_ON_FIRST_HIT, vhr_ray_hit::reserved of a hit is its HIT KIND, VHR_HIT_KIND_FRONT_FACING (0xFE) or
+ *     VHR_HIT_KIND_BACK_FACING (0xFF), decided by the same function on the committed triangle; 0 on a miss.  For every face_cull, NONE included.
+ *     vhr_ray_query and vhr_ray_query_masked still write 0 there.
+ *   - Launches: the face instantiation of the two ray-query kernels where face_cull != 0, and in closest-hit mode whatever face_cull is (the kind
+ *     is reported); terminate-on-first-hit with VHR_FACE_CULL_NONE launches exactly what vhr_ray_query_masked launches.
+ *   - The flip bytes are computed by vhr_update_geometry and vhr_update_primitive_transforms; both refits, vhr_rebuild_geometry and vhr_resize
+ *     keep them.  They are no part of any fingerprint or of vhr_hybrid_save_state's blob.  Their device copy is made by the first query that
+ *     needs it: a context that never culls pays nothing.
+ *   - Every render path stays two-sided, and closest-point queries have no facing. */
+int vhr_ray_query_faces(vhr_context *ctx, const vhr_ray *rays, uint32_t count, uint32_t flags, uint32_t cull_mask,
+                        const uint8_t *ray_masks, uint32_t face_cull, void *results);
+/* The flip bytes of `count` primitives from first_primitive on (0 or 1 each).  Checks as vhr_get_primitive_masks; works on a host-only context. */
+int vhr_get_primitive_facing_flips(vhr_context *ctx, uint32_t first_primitive, uint32_t count, uint8_t *out);
+/* out[0] = primitives with flip = 1, out[1] = 1 if the last ray query of any kind launched the face instantiation, else 0, out[2] = out[3] = 0. */
+int vhr_get_face_cull_statistics(vhr_context *ctx, uint64_t out[4]);
+/* The facing function on explicit pairs (host memory): 9 floats per pair (d, e1, e2), `flips` one byte per pair or NULL for all 0 -> one byte
+ * per pair, VHR_HIT_KIND_FRONT_FACING or VHR_HIT_KIND_BACK_FACING.  A device context runs the device's copy, one pair per thread; a HOST-ONLY
+ * context runs the host's copy of the same source (as vhr_debug_point_triangle does). */
+int vhr_debug_ray_facing(vhr_context *ctx, const float *pairs, const uint8_t *flips, uint32_t count, uint8_t *out);
 
 #ifdef __cplusplus
 }

@@ -166,6 +166,12 @@ public:
     void QueryRays(const vhr_ray *rays, uint32_t count, uint32_t flags, uint32_t cull_mask, const uint8_t *ray_masks, void *results) {
         check(context.handle, vhr_ray_query_masked(context.handle, rays, count, flags, cull_mask, ray_masks, results), "QueryRays");
     }
+    // ... and with rayQueryInitializeEXT's face cull flags (vhr_ray_query_faces): face_cull = VHR_FACE_CULL_NONE / BACK / FRONT -- a candidate on
+    // a triangle facing away from (BACK) or towards (FRONT) the ray does not exist for it -- and a closest hit's vhr_ray_hit::reserved is its hit
+    // kind, VHR_HIT_KIND_FRONT_FACING or VHR_HIT_KIND_BACK_FACING (rayQueryGetIntersectionFrontFaceEXT), whatever face_cull is.
+    void QueryRays(const vhr_ray *rays, uint32_t count, uint32_t flags, uint32_t cull_mask, const uint8_t *ray_masks, uint32_t face_cull, void *results) {
+        check(context.handle, vhr_ray_query_faces(context.handle, rays, count, flags, cull_mask, ray_masks, face_cull, results), "QueryRays");
+    }
     // Extension: the nearest surface to each point, within its max_distance, on the TLAS this manager owns (vhr_closest_point_query).  `flags` =
     // VHR_POINT_QUERY_ANY_WITHIN and / or VHR_POINT_QUERY_HOST_MEMORY; results = vhr_ray_hit[count] (t = the distance), or uint8_t[count] with
     // the first; cull_mask as in QueryRays.  Device pointers: enqueued on the context's current stream, no synchronisation.

@@ -118,7 +118,7 @@ typedef struct vhr_ray_hit {
     float t, u, v;                 /* rayQueryGetIntersectionTEXT and the barycentrics (u, v); 0 on a miss */
     uint32_t geometry_index;       /* rayQueryGetIntersectionGeometryIndexEXT = the primitive (vhr_update_geometry order); 0xFFFFFFFF = miss */
     uint32_t primitive_index;      /* rayQueryGetIntersectionPrimitiveIndexEXT = the triangle within that primitive; 0xFFFFFFFF on a miss */
-    uint32_t reserved;             /* 0 */
+    uint32_t reserved;             /* 0; from vhr_ray_query_faces the hit kind of a hit (VHR_HIT_KIND_*), 0 on a miss */
 } vhr_ray_hit;
 
 enum {
@@ -126,6 +126,13 @@ enum {
     VHR_RAY_QUERY_HOST_MEMORY = 2,              /* rays and results are host memory: staged, and the call returns with the results in place */
     VHR_RAY_QUERY_ALPHA_TEST = 16               /* a candidate hit gbuf.frag:20-32 would discard does not exist for the ray (4 and 8 stay unknown flags) */
 };
+
+/* vhr_ray_query_faces' face_cull (one of the three: Vulkan forbids both cull bits together) and the hit kind it reports in vhr_ray_hit::reserved */
+#define VHR_FACE_CULL_NONE  0u
+#define VHR_FACE_CULL_BACK  1u   /* gl_RayFlagsCullBackFacingTrianglesEXT  */
+#define VHR_FACE_CULL_FRONT 2u   /* gl_RayFlagsCullFrontFacingTrianglesEXT */
+#define VHR_HIT_KIND_FRONT_FACING 0xFEu   /* gl_HitKindFrontFacingTriangleEXT */
+#define VHR_HIT_KIND_BACK_FACING  0xFFu
 
 /* One query of vhr_closest_point_query (include/vhr_amd.h): a point and the largest distance at which a surface still counts (+inf: any).
  * 16 bytes; an array of them must start at a 16-byte boundary (the kernel reads a query as one 16-byte load). */

@@ -9,6 +9,7 @@
 
 #include "vhr_internal.hpp"
 #include "closest_point.hpp"  // point_triangle's host copy (vhr_debug_point_triangle on a host-only context)
+#include "ray_facing.hpp"     // ray_hit_kind's host copy (vhr_debug_ray_facing on a host-only context) and facing_flip
 #include "fingerprint.h"      // build/fingerprint.h, written by the Makefile
 
 namespace vhr {
@@ -53,6 +54,16 @@ int vhr::ensure_device_prim_masks(vhr_context *ctx) {
     HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->d_prim_masks), ctx->primitive_count));
     if (ctx->h_prim_masks.empty()) HIP_TRY(ctx, hipMemsetAsync(ctx->d_prim_masks, 0xFF, ctx->primitive_count, ctx->stream));
     else HIP_TRY(ctx, hipMemcpyAsync(ctx->d_prim_masks, ctx->h_prim_masks.data(), ctx->primitive_count, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));          // (once per scene; launches on the context's other streams may read it next)
+    return VHR_OK;
+}
+
+// the primitives' facing-flip bytes on the device, for a launch of the ray query's face instantiation (h_prim_flips: one byte per primitive, kept
+// by vhr_update_geometry and vhr_update_primitive_transforms)
+int vhr::ensure_device_prim_flips(vhr_context *ctx) {
+    if (ctx->d_prim_flips || ctx->primitive_count == 0) return VHR_OK;
+    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->d_prim_flips), ctx->primitive_count));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_prim_flips, ctx->h_prim_flips.data(), ctx->primitive_count, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));          // (once per scene; launches on the context's other streams may read it next)
     return VHR_OK;
 }
@@ -303,6 +314,7 @@ static void free_scene(vhr_context *ctx) {
     hipFree(ctx->d_vertices); hipFree(ctx->d_indices); hipFree(ctx->d_primitives); hipFree(ctx->d_normal_matrices);
     hipFree(ctx->d_nodes); hipFree(ctx->d_nodes16); hipFree(ctx->d_nodes_ch); hipFree(ctx->d_nodes48); hipFree(ctx->d_tris);
     hipFree(ctx->d_prim_masks); ctx->d_prim_masks = nullptr;
+    hipFree(ctx->d_prim_flips); ctx->d_prim_flips = nullptr;
     ctx->d_vertices = nullptr; ctx->d_indices = nullptr; ctx->d_primitives = nullptr; ctx->d_normal_matrices = nullptr;
     ctx->d_nodes = nullptr; ctx->d_nodes16 = nullptr; ctx->d_nodes_ch = nullptr; ctx->d_nodes48 = nullptr; ctx->d_tris = nullptr;
     ctx->vertex_count = ctx->index_count = ctx->primitive_count = ctx->node_count = ctx->tri_count = 0;
@@ -567,6 +579,9 @@ int vhr_update_geometry(vhr_context *ctx, const vhr_vertex *vertices, uint32_t v
         const int rc = build_and_install_tree(ctx, "UpdateGeometry", scene, primitive_count, total_triangles, upload_ms, nullptr);
         if (rc != VHR_OK) return rc;
     }
+    // every primitive's facing flip by its transform (vhr_ray_query_faces; the device copy went with the scene's arrays and is made again on demand)
+    ctx->h_prim_flips.resize(primitive_count);
+    for (uint32_t p = 0; p < primitive_count; ++p) ctx->h_prim_flips[p] = facing_flip(primitives[p].transform);
     if (ctx->host_only) {
         // ... and keeps the arrays and the tree: the refit's host twin works on them (vhr_update_vertices, vhr_refit_geometry)
         ctx->h_vertices.assign(vertices, vertices + vertex_count);
@@ -676,6 +691,12 @@ int vhr_update_primitive_transforms(vhr_context *ctx, uint32_t first_primitive, 
         }
         HIP_TRY(ctx, hipMemcpyAsync(ctx->d_primitives + first_primitive, prims.data(), sizeof(vhr_primitive) * count, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(ctx->d_normal_matrices + size_t(first_primitive) * 9, nm.data(), sizeof(float) * nm.size(), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    // the facing flips follow the new transforms (no query runs while the update is pending; the refit brings the records the bytes belong to)
+    for (uint32_t p = 0; p < count; ++p) ctx->h_prim_flips[first_primitive + p] = facing_flip(transforms + size_t(p) * 16);
+    if (ctx->d_prim_flips) {
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_prim_flips + first_primitive, ctx->h_prim_flips.data() + first_primitive, count, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     ctx->refit_pending = true;
@@ -917,8 +938,10 @@ int vhr_rebuild_geometry(vhr_context *ctx, uint32_t flags) {
         free_motion(ctx);
         return rc;
     }
+    // the facing flips stay: they follow the transforms, which a rebuild does not change (a host-only context holds them and computes the bytes again)
+    if (ctx->host_only) for (uint32_t p = 0; p < primitive_count; ++p) ctx->h_prim_flips[p] = facing_flip(ctx->h_primitives[p].transform);
     if (!ctx->host_only) ctx->geometry_upload_ms = transfer_ms;
-    if (carry) {                             // the rebuild is refit number `epoch` of the contract at vhr_get_object_motion_statistics
+    if (carry) {                            // the rebuild is refit number `epoch` of the contract at vhr_get_object_motion_statistics
         ctx->motion_epoch = epoch;
         ctx->motion_differing = ctx->motion_refit_differing = differing;
     } else {
@@ -1239,10 +1262,11 @@ int vhr_get_drain_statistics(vhr_context *ctx, uint64_t out[4]) {
     return VHR_OK;
 }
 
-// vhr_ray_query and vhr_ray_query_masked: one body.  `who` names the entry point in messages; `masked` = the second (cull_mask checked, the
-// filtering kernels where the mask acts or per-ray masks are given).
+// vhr_ray_query, vhr_ray_query_masked and vhr_ray_query_faces: one body.  `who` names the entry point in messages; `masked` = the second and the
+// third (cull_mask checked, the filtering kernels where the mask acts or per-ray masks are given); face_cull = the third's VHR_FACE_CULL_* (checked
+// behind cull_mask), -1 from the others.
 static int ray_query_impl(vhr_context *ctx, const char *who_, const bool masked, const vhr_ray *rays, uint32_t count, uint32_t flags, uint32_t cull_mask,
-                          const uint8_t *ray_masks, void *results) {
+                          const uint8_t *ray_masks, void *results, const int64_t face_cull = -1) {
     if (!ctx) return VHR_ERROR_INVALID_ARGUMENT;
     const std::string who(who_);
     // the arguments first (the same answer on every context), then the device
@@ -1252,6 +1276,8 @@ static int ray_query_impl(vhr_context *ctx, const char *who_, const bool masked,
     if (count > 0 && reinterpret_cast<uintptr_t>(rays) % 16u) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": rays must be 16-byte aligned");
     if (count > 0 && reinterpret_cast<uintptr_t>(results) % 4u) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": results must be 4-byte aligned");
     if (masked && cull_mask > 0xFFu) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": cull_mask " + std::to_string(cull_mask) + " exceeds 0xFF");
+    if (face_cull > int64_t(VHR_FACE_CULL_FRONT))
+        return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": face_cull " + std::to_string(face_cull) + " is none of VHR_FACE_CULL_NONE / BACK / FRONT (the two do not combine)");
     if (ctx->host_only) return ctx->fail(VHR_ERROR_NO_DEVICE, who + ": host-only context: no device work");
     { const int stale = ctx->refuse_if_stale(who_); if (stale != VHR_OK) return stale; }
     if (count == 0) return VHR_OK;
@@ -1260,7 +1286,7 @@ static int ray_query_impl(vhr_context *ctx, const char *who_, const bool masked,
     const uint64_t ray_bytes = uint64_t(count) * sizeof(vhr_ray), result_bytes = uint64_t(count) * (any_hit ? 1u : sizeof(vhr_ray_hit));
     ctx->rq_rays = count;
     if (!masked) { cull_mask = 0xFFu; ray_masks = nullptr; }
-    if (!(flags & VHR_RAY_QUERY_HOST_MEMORY)) return vhr::launch_ray_query(ctx, rays, count, any_hit, alpha_test, results, cull_mask, ray_masks);
+    if (!(flags & VHR_RAY_QUERY_HOST_MEMORY)) return vhr::launch_ray_query(ctx, rays, count, any_hit, alpha_test, results, cull_mask, ray_masks, int(face_cull));
     // host memory: staged through the context's own buffer (rays, then the results at the next 256-byte boundary)
     // (vhr_ray_query_masked's per-ray masks, one byte each, behind the results at the next 256-byte boundary)
     const uint64_t result_offset = (ray_bytes + 255u) & ~uint64_t(255u), mask_offset = (result_offset + result_bytes + 255u) & ~uint64_t(255u);
@@ -1276,7 +1302,7 @@ static int ray_query_impl(vhr_context *ctx, const char *who_, const bool masked,
     HIP_TRY(ctx, hipMemcpyAsync(d, rays, ray_bytes, hipMemcpyHostToDevice, ctx->stream));
     if (ray_masks) HIP_TRY(ctx, hipMemcpyAsync(d + mask_offset, ray_masks, count, hipMemcpyHostToDevice, ctx->stream));
     const int rc = vhr::launch_ray_query(ctx, reinterpret_cast<const vhr_ray *>(d), count, any_hit, alpha_test, d + result_offset, cull_mask,
-                                         ray_masks ? reinterpret_cast<const uint8_t *>(d + mask_offset) : nullptr);
+                                         ray_masks ? reinterpret_cast<const uint8_t *>(d + mask_offset) : nullptr, int(face_cull));
     if (rc != VHR_OK) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(results, d + result_offset, result_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1289,6 +1315,43 @@ int vhr_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, uint32_
 
 int vhr_ray_query_masked(vhr_context *ctx, const vhr_ray *rays, uint32_t count, uint32_t flags, uint32_t cull_mask, const uint8_t *ray_masks, void *results) {
     return ray_query_impl(ctx, "vhr_ray_query_masked", true, rays, count, flags, cull_mask, ray_masks, results);
+}
+
+int vhr_ray_query_faces(vhr_context *ctx, const vhr_ray *rays, uint32_t count, uint32_t flags, uint32_t cull_mask, const uint8_t *ray_masks,
+                        uint32_t face_cull, void *results) {
+    return ray_query_impl(ctx, "vhr_ray_query_faces", true, rays, count, flags, cull_mask, ray_masks, results, int64_t(face_cull));
+}
+
+int vhr_get_primitive_facing_flips(vhr_context *ctx, uint32_t first_primitive, uint32_t count, uint8_t *out) {
+    if (!ctx) return VHR_ERROR_INVALID_ARGUMENT;
+    if (count > 0 && !out) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_get_primitive_facing_flips: out must not be NULL when count > 0");
+    { const int rc = mask_state_checks(ctx, "vhr_get_primitive_facing_flips", first_primitive, count, false); if (rc != VHR_OK) return rc; }
+    if (count == 0) return VHR_OK;
+    std::memcpy(out, ctx->h_prim_flips.data() + first_primitive, count);
+    return VHR_OK;
+}
+
+int vhr_get_face_cull_statistics(vhr_context *ctx, uint64_t out[4]) {
+    if (!ctx || !out) return VHR_ERROR_INVALID_ARGUMENT;
+    uint64_t flipped = 0;
+    const bool has = ctx->host_only ? !ctx->h_bvh.nodes.empty() : (ctx->d_nodes != nullptr && ctx->node_count != 0);
+    if (has) for (uint32_t p = 0; p < ctx->primitive_count; ++p) flipped += ctx->h_prim_flips[p];
+    out[0] = flipped; out[1] = ctx->rq_face_ran; out[2] = 0; out[3] = 0;
+    return VHR_OK;
+}
+
+// a device context runs the device's copy of ray_hit_kind, a host-only context the host's: one source (ray_facing.hpp)
+int vhr_debug_ray_facing(vhr_context *ctx, const float *pairs, const uint8_t *flips, uint32_t count, uint8_t *out) {
+    if (!ctx || (count && (!pairs || !out))) return ctx ? ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_debug_ray_facing: null argument") : VHR_ERROR_INVALID_ARGUMENT;
+    if (!ctx->host_only) {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        return launch_ray_facing_pairs(ctx, pairs, flips, count, out);
+    }
+    for (uint32_t i = 0; i < count; ++i) {
+        const float *s = pairs + size_t(i) * 9u;
+        out[i] = uint8_t(ray_hit_kind(s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], s[8], flips != nullptr && flips[i] != 0));
+    }
+    return VHR_OK;
 }
 
 int vhr_get_ray_query_statistics(vhr_context *ctx, uint64_t out[4]) {

@@ -1,5 +1,6 @@
 // The batched ray query (vhr_ray_query) and the debug kernel that runs the walkers' triangle test on explicit pairs
-// (vhr_debug_ray_triangle).  (Split from the end of kernels_trace.hip; built with the same flags.)
+// (vhr_debug_ray_triangle), with the face rule of vhr_ray_query_faces and its pairs kernel (vhr_debug_ray_facing).  (Split from the end of
+// kernels_trace.hip; built with the same flags.)
 #define VHR_TRACE_UNIT unit_ray_query      // names this unit's copy of the sRGB decode table (trace_device.hpp), which comes with the header:
                                            // gbuf_discarded (VHR_RAY_QUERY_ALPHA_TEST) samples base-colour textures here
 #include "trace_queue.hpp"
@@ -42,6 +43,38 @@ int launch_ray_triangle_pairs(vhr_context *ctx, const float *pairs, uint32_t n, 
 }
 
 // ---------------------------------------------------------------------------------------------
+// vhr_debug_ray_facing on a device context: ray_hit_kind (ray_facing.hpp) on explicit pairs, 9 floats each (d, e1, e2) and a flip byte (flips may
+// be null: all 0) -> one byte, 0xFE front / 0xFF back.  One pair per thread.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void ray_facing_pairs_kernel(const float *pairs, const uint8_t *flips, const uint32_t n, uint8_t *out, const Stamps st) {
+    vhr_stamp(st);
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float *p = pairs + size_t(i) * 9u;
+    out[i] = uint8_t(ray_hit_kind(p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], flips != nullptr && flips[i] != 0));
+}
+
+int launch_ray_facing_pairs(vhr_context *ctx, const float *pairs, const uint8_t *flips, uint32_t n, uint8_t *out) {
+    if (n == 0) return VHR_OK;
+    float *d_pairs = nullptr;
+    uint8_t *d_flips = nullptr, *d_out = nullptr;
+    const size_t pb = size_t(n) * 9u * sizeof(float);
+    int rc = VHR_OK;
+    if (hipMalloc(&d_pairs, pb) != hipSuccess || hipMalloc(&d_out, n) != hipSuccess || (flips && hipMalloc(&d_flips, n) != hipSuccess))
+        rc = ctx->fail(VHR_ERROR_DEVICE, "vhr_debug_ray_facing: device allocation failed");
+    if (rc == VHR_OK && (hipMemcpyAsync(d_pairs, pairs, pb, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+                         (flips && hipMemcpyAsync(d_flips, flips, n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)))
+        rc = ctx->fail(VHR_ERROR_DEVICE, "vhr_debug_ray_facing: upload failed");
+    if (rc == VHR_OK) {
+        launch(ctx, ray_facing_pairs_kernel, dim3((n + 255u) / 256u), dim3(256), 0, static_cast<const float *>(d_pairs), static_cast<const uint8_t *>(d_flips), n, d_out);
+        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(out, d_out, n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
+            rc = ctx->fail(VHR_ERROR_DEVICE, "vhr_debug_ray_facing: launch or download failed");
+    }
+    (void)hipFree(d_pairs); (void)hipFree(d_flips); (void)hipFree(d_out);
+    return rc;
+}
+
+// ---------------------------------------------------------------------------------------------
 // vhr_ray_query: batched rayQueryEXT on the scene's BVH (the reference's RayqueryRenderPath, rayquery_render_path/default.frag:36-45,
 // asks the same of the TLAS from a fragment shader).  Launch 1 (ray_query_kernel): every wave owns kQueryWaveRays consecutive rays of
 // the batch and runs wave_queue_walk over them (PER_RAY: each ray's own [tmin, tmax]; no tile, so no shared descent).  Decision (vi)
@@ -64,19 +97,38 @@ struct RayQueryArgs {
     uint32_t count, any_hit;
     RayMaskArgs masks;                    // vhr_ray_query_masked (the kFilterMask instantiations): masks.shadow = its cull_mask
     const uint8_t *ray_masks;             // one byte per ray, ANDed with the cull mask, or null
+    // vhr_ray_query_faces (the kFilterFace instantiations; the others never read these)
+    const uint8_t *prim_flips;            // one byte per primitive (never null there)
+    uint32_t face_cull;                   // VHR_FACE_CULL_*
 };
 static_assert(sizeof(vhr_ray) == 2 * sizeof(float4), "vhr_ray is two float4");
 
+// `kind`: vhr_ray_hit::reserved -- 0 from every instantiation but kFilterFace, whose closest hits carry their hit kind there
 __device__ __forceinline__ void ray_query_store(const RayQueryArgs &a, const uint32_t ray, const bool any_hit, const bool hit, const float t,
-                                                const float u, const float v, const uint32_t prim, const uint32_t tri) {
+                                                const float u, const float v, const uint32_t prim, const uint32_t tri, const uint32_t kind = 0u) {
     if (any_hit) { static_cast<uint8_t *>(a.results)[ray] = hit ? 1u : 0u; return; }
     uint32_t *const r = static_cast<uint32_t *>(a.results) + size_t(ray) * 6u;      // vhr_ray_hit (results is 4-byte aligned)
     r[0] = hit ? __float_as_uint(t) : 0u; r[1] = hit ? __float_as_uint(u) : 0u; r[2] = hit ? __float_as_uint(v) : 0u;
-    r[3] = hit ? prim : kNoHit; r[4] = hit ? tri : kNoHit; r[5] = 0u;
+    r[3] = hit ? prim : kNoHit; r[4] = hit ? tri : kNoHit; r[5] = hit ? kind : 0u;
+}
+
+// the hit kind of the committed triangle (kFilterFace, closest hit): the function the face filter culls by, on the record and the ray's direction
+__device__ __forceinline__ uint32_t committed_hit_kind(const RayQueryArgs &a, const uint32_t ray, const uint32_t tri_index) {
+    const BvhTri &bt = a.scene.tris[tri_index];
+    const float4 q = a.rays[size_t(ray) * 2u + 1u];
+    return ray_hit_kind(q.x, q.y, q.z, bt.e1[0], bt.e1[1], bt.e1[2], bt.e2[0], bt.e2[1], bt.e2[2], a.prim_flips[bt.prim] != 0);
+}
+// a launch's candidate filter: ray_filter<> (trace_device.hpp) for the three the hybrid path shares, the face rule built here.  `ray_masks`: null
+// where `ray_mask` already holds the ray's own (the redo kernel)
+template <int FILTER> __device__ __forceinline__ auto query_filter(const RayQueryArgs &a, const uint32_t ray_mask, const uint8_t *ray_masks) {
+    if constexpr (FILTER == kFilterFace) return RayFaceReject{ &a.scene, a.masks.prim_masks, ray_masks, a.prim_flips, a.rays, ray_mask, a.masks.alpha, a.face_cull };
+    else return ray_filter<FILTER>(a.scene, a.masks, ray_mask, ray_masks);
 }
 
 // FILTER: kFilterAlpha (VHR_RAY_QUERY_ALPHA_TEST) -- a candidate gbuf_discarded names does not exist; kFilterMask (vhr_ray_query_masked) -- nor does
-// one whose primitive's mask shares no bit with the ray's mask, read at the candidate by ray id.  The walk's candidate filter (trace_device.hpp).
+// one whose primitive's mask shares no bit with the ray's mask, read at the candidate by ray id; kFilterFace (vhr_ray_query_faces) -- nor one on a
+// triangle the ray's face cull mode removes, behind the mask test and before the alpha rule (both runtime there), and a closest hit is stored
+// with its hit kind.  The walk's candidate filter (trace_device.hpp).
 template <bool SPILL, int FILTER = kFilterNone>
 __global__ __launch_bounds__(kQueueBlock * 2) void ray_query_kernel(const RayQueryArgs a, const uint32_t stack_levels, const uint32_t refill_threshold,
                                                                     const uint32_t early_exit, const Stamps st) {
@@ -106,13 +158,15 @@ __global__ __launch_bounds__(kQueueBlock * 2) void ray_query_kernel(const RayQue
         [&](uint32_t ray, uint32_t tri, float u, float v, float t) {
             const bool hit = tri != kNoHit;
             hits += hit ? 1u : 0u;
-            ray_query_store(a, ray, any_hit, hit, t, u, v, hit ? a.scene.tris[tri].prim : 0u, hit ? a.scene.tris[tri].tri : 0u);
+            uint32_t kind = 0u;
+            if constexpr (FILTER == kFilterFace) { if (hit && !any_hit) kind = committed_hit_kind(a, ray, tri); }
+            ray_query_store(a, ray, any_hit, hit, t, u, v, hit ? a.scene.tris[tri].prim : 0u, hit ? a.scene.tris[tri].tri : 0u, kind);
             if (flagged) {                                // (rare: a plain vector atomic per listed ray)
                 a.redo_list[atomicAdd(&a.counters->redo_count, 1u)] = ray;
                 flagged = false;
             }
         }, nullptr,
-        [&](uint32_t) { flagged = true; }, ray_filter<FILTER>(a.scene, a.masks, a.masks.shadow, a.ray_masks));
+        [&](uint32_t) { flagged = true; }, query_filter<FILTER>(a, a.masks.shadow, a.ray_masks));
     for (int off = 32; off > 0; off >>= 1) hits += uint32_t(__shfl_xor(int(hits), off));
     const bool wave_overflow = __any(overflow != 0u);
     if (lane == 0) {
@@ -138,16 +192,19 @@ __global__ __launch_bounds__(kTraceBlock) void ray_query_redo_kernel(const RayQu
         best.t = best.u = best.v = 0.0f; best.tri_index = 0; best.flat = 0;
         bool hit, was;
         uint32_t ray_mask = a.masks.shadow;
-        if constexpr (FILTER == kFilterMask) { if (a.ray_masks) ray_mask &= uint32_t(a.ray_masks[ray]); }
+        if constexpr (FILTER == kFilterMask || FILTER == kFilterFace) { if (a.ray_masks) ray_mask &= uint32_t(a.ray_masks[ray]); }
+        const uint32_t id = FILTER == kFilterFace ? ray : 0u;          // (the face filter reads the ray's direction by it; the others ask for nothing)
         if (any_hit) {
             was = static_cast<const uint8_t *>(a.results)[ray] != 0u;
-            hit = traverse<true>(a.scene, o, d, p.w, q.w, s_stack + threadIdx.x, best, overflow, ray_filter<FILTER>(a.scene, a.masks, ray_mask));
+            hit = traverse<true>(a.scene, o, d, p.w, q.w, s_stack + threadIdx.x, best, overflow, query_filter<FILTER>(a, ray_mask, nullptr), id);
         } else {
             was = static_cast<const uint32_t *>(a.results)[size_t(ray) * 6u + 3u] != kNoHit;
-            hit = traverse<false>(a.scene, o, d, p.w, q.w, s_stack + threadIdx.x, best, overflow, ray_filter<FILTER>(a.scene, a.masks, ray_mask));
+            hit = traverse<false>(a.scene, o, d, p.w, q.w, s_stack + threadIdx.x, best, overflow, query_filter<FILTER>(a, ray_mask, nullptr), id);
         }
+        uint32_t kind = 0u;
+        if constexpr (FILTER == kFilterFace) { if (hit && !any_hit) kind = committed_hit_kind(a, ray, best.tri_index); }
         ray_query_store(a, ray, any_hit, hit, best.t, best.u, best.v, hit && !any_hit ? a.scene.tris[best.tri_index].prim : 0u,
-                        hit && !any_hit ? a.scene.tris[best.tri_index].tri : 0u);
+                        hit && !any_hit ? a.scene.tris[best.tri_index].tri : 0u, kind);
         delta += int(hit) - int(was);
     }
     if (delta) atomicAdd(&a.counters->hits, (unsigned long long)(long long)delta);
@@ -155,8 +212,9 @@ __global__ __launch_bounds__(kTraceBlock) void ray_query_redo_kernel(const RayQu
 }
 
 int launch_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, bool any_hit, bool alpha_test, void *results, uint32_t cull_mask,
-                     const uint8_t *ray_masks) {
+                     const uint8_t *ray_masks, int face_cull) {
     ctx->rq_mask_ran = 0;
+    ctx->rq_face_ran = 0;
     if (count == 0) return VHR_OK;
     RayQueryScratch *q = nullptr;                  // this stream's counters and list
     for (RayQueryScratch &e : ctx->rq_scratch) if (e.stream == ctx->stream) q = &e;
@@ -201,14 +259,30 @@ int launch_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, bool
         a.masks.prim_masks = ctx->d_prim_masks;
         ctx->rq_mask_ran = 1;
     }
-    const int filter = launch_filter(mask_acts, alpha);
+    // vhr_ray_query_faces: the face instantiation where a cull mode is set, and in closest-hit mode whatever it is (the hit kind is reported);
+    // terminate-on-first-hit with VHR_FACE_CULL_NONE is vhr_ray_query_masked's launch
+    const bool face = face_cull > 0 || (face_cull == 0 && !any_hit);
+    a.prim_flips = nullptr;
+    a.face_cull = face ? uint32_t(face_cull) : 0u;
+    if (face && ctx->primitive_count != 0) {
+        if (const int rc = ensure_device_prim_flips(ctx)) return rc;
+        a.prim_flips = ctx->d_prim_flips;
+    }
+    ctx->rq_face_ran = face ? 1u : 0u;
+    const int filter = face ? kFilterFace : launch_filter(mask_acts, alpha);
+    const uint32_t redo_blocks = std::min<uint32_t>((count + kTraceBlock - 1u) / kTraceBlock, uint32_t(ctx->cu_count) * 4u);
     ctx->time_begin(kKernelRayQuery);
-    with_bool(ql.spill, [&](auto sp) { with_filter(filter, [&](auto al) {
-        launch(ctx, ray_query_kernel<decltype(sp)::value, decltype(al)::value>, grid, dim3(kQueueBlock * 2), ql.lds_bytes, a, ql.levels, ql.threshold, ql.early_exit);
-    }); });
-    if (a.scene.node_count != 0) {
-        const uint32_t redo_blocks = std::min<uint32_t>((count + kTraceBlock - 1u) / kTraceBlock, uint32_t(ctx->cu_count) * 4u);
-        with_filter(filter, [&](auto al) { launch(ctx, ray_query_redo_kernel<decltype(al)::value>, dim3(redo_blocks), dim3(kTraceBlock), 0, a); });
+    if (face) {
+        with_bool(ql.spill, [&](auto sp) {
+            launch(ctx, ray_query_kernel<decltype(sp)::value, kFilterFace>, grid, dim3(kQueueBlock * 2), ql.lds_bytes, a, ql.levels, ql.threshold, ql.early_exit);
+        });
+        if (a.scene.node_count != 0) launch(ctx, ray_query_redo_kernel<kFilterFace>, dim3(redo_blocks), dim3(kTraceBlock), 0, a);
+    } else {
+        with_bool(ql.spill, [&](auto sp) { with_filter(filter, [&](auto al) {
+            launch(ctx, ray_query_kernel<decltype(sp)::value, decltype(al)::value>, grid, dim3(kQueueBlock * 2), ql.lds_bytes, a, ql.levels, ql.threshold, ql.early_exit);
+        }); });
+        if (a.scene.node_count != 0)
+            with_filter(filter, [&](auto al) { launch(ctx, ray_query_redo_kernel<decltype(al)::value>, dim3(redo_blocks), dim3(kTraceBlock), 0, a); });
     }
     ctx->time_end(kKernelRayQuery);
     if (hipGetLastError() != hipSuccess) return ctx->fail(VHR_ERROR_DEVICE, "vhr_ray_query: kernel launch failed");

@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "device_math.hpp"
+#include "ray_facing.hpp"
 #include "vhr_internal.hpp"
 
 #ifndef VHR_TRACE_UNIT
@@ -325,9 +326,37 @@ struct RayMaskReject {
         return alpha != 0u && gbuf_discarded(*sc, tri, u, v);
     }
 };
+// Ray face culling (vhr_ray_query_faces; gl_RayFlagsCullBackFacingTrianglesEXT / CullFrontFacing): a candidate on a triangle that faces away from
+// (VHR_FACE_CULL_BACK) or towards (VHR_FACE_CULL_FRONT) the ray does not exist for it.  What RayMaskReject carries, plus the primitives' flip
+// bytes, the cull mode (wave-uniform) and the rays array: the ray id picks the ray's direction, read at the candidate as its mask is, and the
+// record's edges are read again by the triangle's index -- nothing of the face rule is alive in the walk's box loop.  The mask test (runtime:
+// only where the mask acts, prim_masks != nullptr), then the face test (ray_facing.hpp: the binary64 determinant's sign), then the alpha rule
+// (runtime bit): one instantiation serves face + mask + alpha.  The ray query's kernels only (kFilterFace); no render path culls faces.
+struct RayFaceReject {
+    const DeviceScene *sc;
+    const uint8_t *prim_masks, *ray_masks, *flips;
+    const float4 *rays;                   // 2 x float4 per ray, as RayQueryArgs::rays
+    uint32_t mask, alpha, cull;
+    __device__ __forceinline__ bool operator()(uint32_t ray, uint32_t tri, float u, float v) const {
+        const BvhTri &bt = sc->tris[tri];
+        if (prim_masks) {
+            const uint32_t m = ray_masks ? uint32_t(ray_masks[ray]) & mask : mask;
+            if ((uint32_t(prim_masks[bt.prim]) & m) == 0u) return true;
+        }
+        if (cull != kFaceCullNone) {
+            const float4 q = rays[size_t(ray) * 2u + 1u];
+            const FacingPvec p = facing_pvec(q.x, q.y, q.z, bt.e2[0], bt.e2[1], bt.e2[2]);
+            asm volatile("" ::: "memory");            // e1 and the flip byte are fetched behind the cross product, not held through it
+            const bool front = facing_front(p, bt.e1[0], bt.e1[1], bt.e1[2], flips[bt.prim] != 0);
+            if (ray_face_culled(cull, front)) return true;
+        }
+        return alpha != 0u && gbuf_discarded(*sc, tri, u, v);
+    }
+};
 // the hybrid path's and the ray query's kernels name their filter by a launch-side constant: none, the alpha rule, or the mask (with the
-// alpha rule as a runtime bit)
-constexpr int kFilterNone = 0, kFilterAlpha = 1, kFilterMask = 2;
+// alpha rule as a runtime bit); the ray query alone has a fourth, the face rule (with the mask and the alpha rule as runtime bits), which it
+// constructs itself (kernels_ray_query.hip): ray_filter<> and with_filter() below know the first three
+constexpr int kFilterNone = 0, kFilterAlpha = 1, kFilterMask = 2, kFilterFace = 3;
 template <int FILTER> using RayFilter = std::conditional_t<FILTER == kFilterMask, RayMaskReject, std::conditional_t<FILTER == kFilterAlpha, GbufDiscard, NoFilter>>;
 template <int FILTER> __device__ __forceinline__ RayFilter<FILTER> ray_filter(const DeviceScene &sc, const RayMaskArgs &m, uint32_t ray_mask,
                                                                              const uint8_t *ray_masks = nullptr) {

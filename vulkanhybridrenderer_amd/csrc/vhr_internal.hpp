@@ -522,6 +522,13 @@ struct vhr_context {
             if (((mask_present[v >> 6] >> (v & 63u)) & 1u) && (v & m) == 0u) return true;
         return false;
     }
+    // Ray face culling (vhr_ray_query_faces): facing is decided in object space, the leaf records hold world-space edges, so a primitive whose
+    // transform mirrors carries flip = 1 (facing_flip, ray_facing.hpp).  One byte per primitive, computed where the host reads transforms
+    // (vhr_update_geometry, vhr_update_primitive_transforms; refits, rebuilds and vhr_resize keep it); no part of any fingerprint or saved state.
+    // d_prim_flips is made by the first launch of the face instantiation and dropped when a byte changes: a context that never culls pays nothing.
+    std::vector<uint8_t> h_prim_flips;
+    uint8_t *d_prim_flips = nullptr;
+    uint32_t rq_face_ran = 0;                    // the last ray query launched the face instantiation (vhr_get_face_cull_statistics out[1])
     // "object_motion_vectors" (vhr_set_option; like "alpha_test_rays" no entry of VHR_OPTION_TABLE): 1 = the refits keep every leaf record's state
     // before the last successful refit, and the stand-in G-buffer reprojects a moved surface through it.  Per record k: d_prev_tris[k] (the whole
     // 48 bytes, in the same slot) and d_prev_saved[k], the number of the refit that last saved it.  Refit number E = motion_epoch + 1 saves a
@@ -762,13 +769,18 @@ int launch_calibration_read(vhr_context *ctx, const Image &img, uint32_t bytes_p
 int launch_ray_triangle_pairs(vhr_context *ctx, const float *pairs, uint32_t n, uint32_t *hit, float *tuv);
 // vhr_ray_query's device path: `rays` (count x vhr_ray) and `results` (vhr_ray_hit or uint8_t per ray) are device memory; enqueued on ctx->stream
 // cull_mask / ray_masks (device memory or null): vhr_ray_query_masked's; vhr_ray_query is (0xFF, null)
+// face_cull: vhr_ray_query_faces' (VHR_FACE_CULL_*), or -1 from the two older entry points (no face rule, no hit kind)
 int launch_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, bool any_hit, bool alpha_test, void *results, uint32_t cull_mask = 0xFFu,
-                     const uint8_t *ray_masks = nullptr);
+                     const uint8_t *ray_masks = nullptr, int face_cull = -1);
+// vhr_debug_ray_facing on a device context: host arrays, 9 floats (d, e1, e2) and a flip byte (or null) in, one hit-kind byte out per pair
+int launch_ray_facing_pairs(vhr_context *ctx, const float *pairs, const uint8_t *flips, uint32_t n, uint8_t *out);
 // vhr_closest_point_query's device path (csrc/kernels_point_query.hip): `points` (count x vhr_point_query) and `results` (vhr_ray_hit or uint8_t per
 // query) are device memory; enqueued on ctx->stream.  vhr_debug_point_triangle on a device context: host arrays, 12 floats in and 3 out per pair
 int launch_point_query(vhr_context *ctx, const vhr_point_query *points, uint32_t count, bool any_within, uint32_t cull_mask, void *results);
 int launch_point_triangle_pairs(vhr_context *ctx, const float *pairs, uint32_t n, float *out);
 // the primitives' mask bytes on the device (made, from h_prim_masks or as all-0xFF, if no call has made them yet): before a launch that filters
 int ensure_device_prim_masks(vhr_context *ctx);
+// the primitives' facing-flip bytes on the device (made from h_prim_flips if no launch has made them yet): before a launch of the face instantiation
+int ensure_device_prim_flips(vhr_context *ctx);
 
 }  // namespace vhr

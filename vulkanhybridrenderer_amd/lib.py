@@ -46,6 +46,7 @@ EXPORTS = [
     "vhr_set_primitive_masks", "vhr_get_primitive_masks", "vhr_ray_query_masked", "vhr_get_ray_mask_statistics",
     "vhr_closest_point_query", "vhr_get_point_query_statistics", "vhr_debug_point_triangle",
     "vhr_rebuild_geometry", "vhr_get_rebuild_statistics",
+    "vhr_ray_query_faces", "vhr_get_primitive_facing_flips", "vhr_get_face_cull_statistics", "vhr_debug_ray_facing",
 ]
 
 PATH_PREFIXES = ("hybrid", "raytraced", "rayquery", "forward_raster")      # vhr_<prefix>_{create,destroy,build,rebuild,last_error}
@@ -306,6 +307,10 @@ def load():
     L.vhr_calibration_stream_read.argtypes = [vp, i32, u32]
     L.vhr_ray_query.argtypes = [vp, vp, u32, u32, vp]
     L.vhr_ray_query_masked.argtypes = [vp, vp, u32, u32, u32, vp, vp]
+    L.vhr_ray_query_faces.argtypes = [vp, vp, u32, u32, u32, vp, u32, vp]
+    L.vhr_get_primitive_facing_flips.argtypes = [vp, u32, u32, vp]
+    L.vhr_get_face_cull_statistics.argtypes = [vp, C.POINTER(u64)]
+    L.vhr_debug_ray_facing.argtypes = [vp, C.c_void_p, C.c_void_p, u32, C.c_void_p]
     L.vhr_set_primitive_masks.argtypes = [vp, u32, u32, vp]
     L.vhr_get_primitive_masks.argtypes = [vp, u32, u32, vp]
     L.vhr_get_ray_mask_statistics.argtypes = [vp, C.POINTER(u64)]
@@ -474,6 +479,36 @@ class Context:
         out = (C.c_uint64 * 4)()
         self.check(self.L.vhr_get_ray_mask_statistics(self.handle, out), "ray_mask_statistics")
         return [int(x) for x in out]
+
+    # ---- ray face culling: the primitives' facing flips (the query itself: ray_query(face_cull=...)) ----
+    def primitive_facing_flips(self, first_primitive=0, count=None):
+        """vhr_get_primitive_facing_flips: uint8 per primitive from first_primitive on (default: all that follow), 1 = the primitive's
+        transform mirrors (a negative determinant of its upper 3 x 3), so its triangles' facing is the reverse of their world-space winding."""
+        n = getattr(self, "_primitive_count", 0) - int(first_primitive) if count is None else int(count)
+        out = np.zeros(max(n, 0), np.uint8)
+        self.check(self.L.vhr_get_primitive_facing_flips(self.handle, int(first_primitive), len(out), _p(out) if len(out) else None), "primitive_facing_flips")
+        return out
+
+    def face_cull_statistics(self):
+        """[primitives with flip = 1, 1 if the last ray query of any kind launched the face instantiation, 0, 0]."""
+        out = (C.c_uint64 * 4)()
+        self.check(self.L.vhr_get_face_cull_statistics(self.handle, out), "face_cull_statistics")
+        return [int(x) for x in out]
+
+    def debug_ray_facing(self, pairs, flips=None):
+        """The facing function on explicit pairs: pairs = (n, 9) float32 (d, e1, e2), flips = uint8[n] or None (all 0) -> uint8[n],
+        abi.HIT_KIND_FRONT_FACING or abi.HIT_KIND_BACK_FACING.  A device context runs the device's copy, a host-only context the host's."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.float32).reshape(-1, 9)
+        n = len(pairs)
+        f = None
+        if flips is not None:
+            f = np.ascontiguousarray(flips, np.uint8).reshape(-1)
+            if len(f) != n:
+                raise ValueError(f"debug_ray_facing: {len(f)} flips for {n} pairs")
+        out = np.zeros(n, np.uint8)
+        self.check(self.L.vhr_debug_ray_facing(self.handle, pairs.ctypes.data if n else None, f.ctypes.data if f is not None and n else None, n,
+                                               out.ctypes.data if n else None), "debug_ray_facing")
+        return out
 
     def refit_geometry(self):
         self.check(self.L.vhr_refit_geometry(self.handle), "refit_geometry")
@@ -901,34 +936,44 @@ class Context:
             a = aligned
         return a
 
-    def ray_query(self, rays, any_hit=False, alpha_test=False, cull_mask=None, ray_masks=None):
+    def ray_query(self, rays, any_hit=False, alpha_test=False, cull_mask=None, ray_masks=None, face_cull=None):
         """vhr_ray_query on host arrays: rays (n, 8) float32 or abi.ray_dtype.  Returns abi.ray_hit_dtype[n] (closest hit; a miss has
         geometry_index = primitive_index = abi.RAY_MISS) or, with any_hit, bool[n] (occluded).  alpha_test: a candidate hit the G-buffer
         pass would discard (alpha mask, alpha 0) does not exist for the ray.  cull_mask (0..255) and / or ray_masks (uint8[n]):
         vhr_ray_query_masked -- ray i's mask is cull_mask (default 0xFF) & ray_masks[i], and a candidate on a primitive whose mask shares no
-        bit with it does not exist for the ray; with both left at None this is vhr_ray_query itself."""
+        bit with it does not exist for the ray; with both left at None this is vhr_ray_query itself.  face_cull (abi.FACE_CULL_NONE / BACK /
+        FRONT): vhr_ray_query_faces -- a candidate on a triangle facing away from (BACK) or towards (FRONT) the ray does not exist for it, and
+        a closest hit's `reserved` is its hit kind (abi.HIT_KIND_*), NONE included; None keeps the entry points above."""
         r = self._rays_array(rays)
         n = len(r)
         out = np.zeros(n, np.uint8) if any_hit else np.zeros(n, abi.ray_hit_dtype)
         flags = abi.RAY_QUERY_HOST_MEMORY | (abi.RAY_QUERY_TERMINATE_ON_FIRST_HIT if any_hit else 0) | (abi.RAY_QUERY_ALPHA_TEST if alpha_test else 0)
-        if cull_mask is None and ray_masks is None:
+        if cull_mask is None and ray_masks is None and face_cull is None:
             self.check(self.L.vhr_ray_query(self.handle, r.ctypes.data if n else None, n, flags, out.ctypes.data if n else None), "ray_query")
+            return out.astype(bool) if any_hit else out
+        rm = None
+        if ray_masks is not None:
+            rm = np.ascontiguousarray(ray_masks, np.uint8).reshape(-1)
+            if len(rm) != n:
+                raise ValueError(f"ray_query: {len(rm)} ray masks for {n} rays")
+        if face_cull is not None:
+            self.check(self.L.vhr_ray_query_faces(self.handle, r.ctypes.data if n else None, n, flags, 0xFF if cull_mask is None else int(cull_mask),
+                                                  rm.ctypes.data if rm is not None and n else None, int(face_cull), out.ctypes.data if n else None), "ray_query")
         else:
-            rm = None
-            if ray_masks is not None:
-                rm = np.ascontiguousarray(ray_masks, np.uint8).reshape(-1)
-                if len(rm) != n:
-                    raise ValueError(f"ray_query: {len(rm)} ray masks for {n} rays")
             self.check(self.L.vhr_ray_query_masked(self.handle, r.ctypes.data if n else None, n, flags, 0xFF if cull_mask is None else int(cull_mask),
                                                    rm.ctypes.data if rm is not None and n else None, out.ctypes.data if n else None), "ray_query")
         return out.astype(bool) if any_hit else out
 
-    def ray_query_device(self, rays_ptr, count, results_ptr, any_hit=False, alpha_test=False, cull_mask=None, ray_masks_ptr=0):
+    def ray_query_device(self, rays_ptr, count, results_ptr, any_hit=False, alpha_test=False, cull_mask=None, ray_masks_ptr=0, face_cull=None):
         """vhr_ray_query on device memory (e.g. torch tensors' data_ptr()): `count` vhr_ray records at rays_ptr (16-byte aligned), results
         (vhr_ray_hit, or one uint8 per ray with any_hit) at results_ptr.  Enqueued on current_stream(); returns without synchronising.
-        cull_mask and / or ray_masks_ptr (device memory, one uint8 per ray): vhr_ray_query_masked, as in ray_query()."""
+        cull_mask and / or ray_masks_ptr (device memory, one uint8 per ray): vhr_ray_query_masked, as in ray_query(); face_cull:
+        vhr_ray_query_faces, likewise."""
         flags = (abi.RAY_QUERY_TERMINATE_ON_FIRST_HIT if any_hit else 0) | (abi.RAY_QUERY_ALPHA_TEST if alpha_test else 0)
-        if cull_mask is None and not ray_masks_ptr:
+        if face_cull is not None:
+            self.check(self.L.vhr_ray_query_faces(self.handle, rays_ptr or None, int(count), flags, 0xFF if cull_mask is None else int(cull_mask),
+                                                  ray_masks_ptr or None, int(face_cull), results_ptr or None), "ray_query_device")
+        elif cull_mask is None and not ray_masks_ptr:
             self.check(self.L.vhr_ray_query(self.handle, rays_ptr or None, int(count), flags, results_ptr or None), "ray_query_device")
         else:
             self.check(self.L.vhr_ray_query_masked(self.handle, rays_ptr or None, int(count), flags, 0xFF if cull_mask is None else int(cull_mask),
