@@ -1,5 +1,5 @@
 """vhr_rebuild_geometry on the device: the tree equals a fresh context's whichever builder makes it, queries and frames do not see the
-rebuild, the object-motion records travel across the new tree's slot permutation (the gather / scatter kernels of csrc/kernels_bvh.hip), and
+rebuild, the object-motion records travel across the new tree's slot permutation (the gather / scatter kernels of csrc/kernels_bvh_refit.hip), and
 a non-finite device-memory vertex is met by the check pass before anything is freed or built."""
 import numpy as np
 import pytest

@@ -630,7 +630,7 @@ bool nodes16_in_range(const HostBvh &bvh) {
     return true;
 }
 
-// ---- refit: the host side of csrc/kernels_bvh.hip's k0_refit_* kernels (the arithmetic of both: bvh_math.hpp) ----
+// ---- refit: the host side of csrc/kernels_bvh_refit.hip's k0_refit_* kernels (the arithmetic of both: bvh_math.hpp) ----
 namespace {
 // the walk of both refits relies on this and on nothing else: links in range, children numbered after their parents, records of this scene
 bool refit_can_walk(const HostBvh &bvh, const vhr_primitive *primitives, uint32_t primitive_count, bool links) {

@@ -1,9 +1,9 @@
 // K0: the arithmetic both builders share -- the one definition of a leaf record, its box, a padded slot, a leaf link, the three derived
 // node forms, their containment checks, the refit's own check, the scene centre and the surface-area term.
 //
-// The host builder (bvh_build.cpp) and the device builder (kernels_bvh.hip) owe each other BITS: the same records, the same child boxes,
-// the same tree fingerprint, the same derived forms.  Every function here is `__host__ __device__ inline` over plain arrays and the structs
-// of vhr_internal.hpp, both files are compiled without FMA contraction, and neither keeps a copy of any of it.  The one place the two
+// The host builder (bvh_build.cpp) and the device builder (kernels_bvh.hip, with its refits in kernels_bvh_refit.hip) owe each other BITS: the
+// same records, the same child boxes, the same tree fingerprint, the same derived forms.  Every function here is `__host__ __device__ inline`
+// over plain arrays and the structs of vhr_internal.hpp, both sides are compiled without FMA contraction, and neither keeps a copy of any of it.  The one place the two
 // sides have different bodies is the float -> half conversion (half_nearest / half_upward): the device uses the hardware's, the host a
 // software one with the same rounding -- nearest-even, ties included ("one definition of the BVH arithmetic").
 #pragma once

@@ -1,5 +1,5 @@
 // The point / triangle distance of vhr_closest_point_query: ONE definition for the device (kernels_point_query.hip: the walker's leaf test and the
-// pairs kernel of vhr_debug_point_triangle) and for the host (context.cpp: vhr_debug_point_triangle on a host-only context).  The two owe each
+// pairs kernel of vhr_debug_point_triangle) and for the host (queries.cpp: vhr_debug_point_triangle on a host-only context).  The two owe each
 // other BITS (tests/test_gpu_point_query.py), so everything here is plain fp32, every operation rounded once in the order written (both files
 // are built with -ffp-contract=off), every quotient an IEEE division, every selection a comparison -- no fminf / fmaxf, whose answer for (-0, +0)
 // is the implementation's choice -- and no intrinsic.

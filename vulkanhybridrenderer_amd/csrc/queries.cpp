@@ -1,0 +1,179 @@
+// Query half of the C ABI (include/vhr_amd.h): batched ray queries and closest-point queries on the scene's tree, their host-memory staging
+// and statistics, and the pair entry points that run one shared function (ray / triangle, facing, point / triangle) on a list of inputs.
+#include <cstring>
+#include <string>
+
+#include "vhr_internal.hpp"
+#include "closest_point.hpp"  // point_triangle's host copy (vhr_debug_point_triangle on a host-only context)
+#include "ray_facing.hpp"     // ray_hit_kind's host copy (vhr_debug_ray_facing on a host-only context)
+
+using namespace vhr;
+
+void vhr::free_query_scratch(vhr_context *ctx) {
+    for (auto &q : ctx->rq_scratch) { hipFree(q.counters); hipFree(q.list); }
+    hipFree(ctx->d_rq_staging);
+    for (auto &q : ctx->pq_scratch) hipFree(q.counters);
+}
+
+// the host-memory paths' staging buffer holds at least `staging` bytes (it grows to the largest query so far; its old contents are not kept)
+static int grow_staging(vhr_context *ctx, uint64_t staging) {
+    if (ctx->rq_staging_bytes >= staging) return VHR_OK;
+    (void)hipFree(ctx->d_rq_staging);
+    ctx->d_rq_staging = nullptr;
+    ctx->rq_staging_bytes = 0;
+    HIP_TRY(ctx, hipMalloc(&ctx->d_rq_staging, staging));
+    ctx->rq_staging_bytes = staging;
+    return VHR_OK;
+}
+
+extern "C" {
+
+// vhr_ray_query, vhr_ray_query_masked and vhr_ray_query_faces: one body.  `who` names the entry point in messages; `masked` = the second and the
+// third (cull_mask checked, the filtering kernels where the mask acts or per-ray masks are given); face_cull = the third's VHR_FACE_CULL_* (checked
+// behind cull_mask), -1 from the others.
+static int ray_query_impl(vhr_context *ctx, const char *who_, const bool masked, const vhr_ray *rays, uint32_t count, uint32_t flags, uint32_t cull_mask,
+                          const uint8_t *ray_masks, void *results, const int64_t face_cull = -1) {
+    if (!ctx) return VHR_ERROR_INVALID_ARGUMENT;
+    const std::string who(who_);
+    // the arguments first (the same answer on every context), then the device
+    if (flags & ~uint32_t(VHR_RAY_QUERY_TERMINATE_ON_FIRST_HIT | VHR_RAY_QUERY_HOST_MEMORY | VHR_RAY_QUERY_ALPHA_TEST))
+        return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": unknown flag bits " + std::to_string(flags));
+    if (count > 0 && (!rays || !results)) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": rays and results must not be NULL when count > 0");
+    if (count > 0 && reinterpret_cast<uintptr_t>(rays) % 16u) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": rays must be 16-byte aligned");
+    if (count > 0 && reinterpret_cast<uintptr_t>(results) % 4u) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": results must be 4-byte aligned");
+    if (masked && cull_mask > 0xFFu) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": cull_mask " + std::to_string(cull_mask) + " exceeds 0xFF");
+    if (face_cull > int64_t(VHR_FACE_CULL_FRONT))
+        return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": face_cull " + std::to_string(face_cull) + " is none of VHR_FACE_CULL_NONE / BACK / FRONT (the two do not combine)");
+    if (ctx->host_only) return ctx->fail(VHR_ERROR_NO_DEVICE, who + ": host-only context: no device work");
+    VHR_TRY(ctx->refuse_if_stale(who_));
+    if (count == 0) return VHR_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool any_hit = (flags & VHR_RAY_QUERY_TERMINATE_ON_FIRST_HIT) != 0, alpha_test = (flags & VHR_RAY_QUERY_ALPHA_TEST) != 0;
+    const uint64_t ray_bytes = uint64_t(count) * sizeof(vhr_ray), result_bytes = uint64_t(count) * (any_hit ? 1u : sizeof(vhr_ray_hit));
+    ctx->rq_rays = count;
+    if (!masked) { cull_mask = 0xFFu; ray_masks = nullptr; }
+    if (!(flags & VHR_RAY_QUERY_HOST_MEMORY)) return vhr::launch_ray_query(ctx, rays, count, any_hit, alpha_test, results, cull_mask, ray_masks, int(face_cull));
+    // host memory: staged through the context's own buffer (rays, then the results at the next 256-byte boundary)
+    // (vhr_ray_query_masked's per-ray masks, one byte each, behind the results at the next 256-byte boundary)
+    const uint64_t result_offset = (ray_bytes + 255u) & ~uint64_t(255u), mask_offset = (result_offset + result_bytes + 255u) & ~uint64_t(255u);
+    VHR_TRY(grow_staging(ctx, ray_masks ? mask_offset + count : result_offset + result_bytes));
+    char *const d = static_cast<char *>(ctx->d_rq_staging);
+    HIP_TRY(ctx, hipMemcpyAsync(d, rays, ray_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (ray_masks) HIP_TRY(ctx, hipMemcpyAsync(d + mask_offset, ray_masks, count, hipMemcpyHostToDevice, ctx->stream));
+    VHR_TRY(vhr::launch_ray_query(ctx, reinterpret_cast<const vhr_ray *>(d), count, any_hit, alpha_test, d + result_offset, cull_mask,
+                                  ray_masks ? reinterpret_cast<const uint8_t *>(d + mask_offset) : nullptr, int(face_cull)));
+    HIP_TRY(ctx, hipMemcpyAsync(results, d + result_offset, result_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return VHR_OK;
+}
+
+int vhr_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, uint32_t flags, void *results) {
+    return ray_query_impl(ctx, "vhr_ray_query", false, rays, count, flags, 0xFFu, nullptr, results);
+}
+
+int vhr_ray_query_masked(vhr_context *ctx, const vhr_ray *rays, uint32_t count, uint32_t flags, uint32_t cull_mask, const uint8_t *ray_masks, void *results) {
+    return ray_query_impl(ctx, "vhr_ray_query_masked", true, rays, count, flags, cull_mask, ray_masks, results);
+}
+
+int vhr_ray_query_faces(vhr_context *ctx, const vhr_ray *rays, uint32_t count, uint32_t flags, uint32_t cull_mask, const uint8_t *ray_masks,
+                        uint32_t face_cull, void *results) {
+    return ray_query_impl(ctx, "vhr_ray_query_faces", true, rays, count, flags, cull_mask, ray_masks, results, int64_t(face_cull));
+}
+
+// a device context runs the device's copy of ray_hit_kind, a host-only context the host's: one source (ray_facing.hpp)
+int vhr_debug_ray_facing(vhr_context *ctx, const float *pairs, const uint8_t *flips, uint32_t count, uint8_t *out) {
+    if (!ctx || (count && (!pairs || !out))) return ctx ? ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_debug_ray_facing: null argument") : VHR_ERROR_INVALID_ARGUMENT;
+    if (!ctx->host_only) {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        return launch_ray_facing_pairs(ctx, pairs, flips, count, out);
+    }
+    for (uint32_t i = 0; i < count; ++i) {
+        const float *s = pairs + size_t(i) * 9u;
+        out[i] = uint8_t(ray_hit_kind(s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], s[8], flips != nullptr && flips[i] != 0));
+    }
+    return VHR_OK;
+}
+
+int vhr_get_ray_query_statistics(vhr_context *ctx, uint64_t out[4]) {
+    if (!ctx || !out) return VHR_ERROR_INVALID_ARGUMENT;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (ctx->host_only || ctx->rq_rays == 0 || !ctx->rq_last_counters) return VHR_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipDeviceSynchronize());         // the stream of the last query may be the caller's: wait for the device, then read
+    RayQueryCounters c;
+    HIP_TRY(ctx, hipMemcpy(&c, ctx->rq_last_counters, sizeof(c), hipMemcpyDeviceToHost));
+    out[0] = ctx->rq_rays; out[1] = c.hits; out[2] = c.redo_count; out[3] = c.overflows;
+    return VHR_OK;
+}
+
+// vhr_closest_point_query: the arguments first (the same answer on every context), then the device; staged like the ray query's host path
+int vhr_closest_point_query(vhr_context *ctx, const vhr_point_query *points, uint32_t count, uint32_t flags, uint32_t cull_mask, void *results) {
+    if (!ctx) return VHR_ERROR_INVALID_ARGUMENT;
+    const std::string who("vhr_closest_point_query");
+    if (count > 0 && (!points || !results)) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": points and results must not be NULL when count > 0");
+    if (flags & ~uint32_t(VHR_POINT_QUERY_ANY_WITHIN | VHR_POINT_QUERY_HOST_MEMORY))
+        return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": unknown flag bits " + std::to_string(flags));
+    if (count > 0 && reinterpret_cast<uintptr_t>(points) % 16u) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": points must be 16-byte aligned");
+    if (count > 0 && reinterpret_cast<uintptr_t>(results) % 4u) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": results must be 4-byte aligned");
+    if (cull_mask > 0xFFu) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": cull_mask " + std::to_string(cull_mask) + " exceeds 0xFF");
+    if (ctx->host_only) return ctx->fail(VHR_ERROR_NO_DEVICE, who + ": host-only context: no device work");
+    VHR_TRY(ctx->refuse_if_stale("vhr_closest_point_query"));
+    if (count == 0) return VHR_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool any_within = (flags & VHR_POINT_QUERY_ANY_WITHIN) != 0;
+    ctx->pq_queries = count;
+    if (!(flags & VHR_POINT_QUERY_HOST_MEMORY)) return vhr::launch_point_query(ctx, points, count, any_within, cull_mask, results);
+    // host memory: the points, then the results at the next 256-byte boundary, in the ray query's staging buffer
+    const uint64_t point_bytes = uint64_t(count) * sizeof(vhr_point_query), result_bytes = uint64_t(count) * (any_within ? 1u : sizeof(vhr_ray_hit));
+    const uint64_t result_offset = (point_bytes + 255u) & ~uint64_t(255u);
+    VHR_TRY(grow_staging(ctx, result_offset + result_bytes));
+    char *const d = static_cast<char *>(ctx->d_rq_staging);
+    HIP_TRY(ctx, hipMemcpyAsync(d, points, point_bytes, hipMemcpyHostToDevice, ctx->stream));
+    VHR_TRY(vhr::launch_point_query(ctx, reinterpret_cast<const vhr_point_query *>(d), count, any_within, cull_mask, d + result_offset));
+    HIP_TRY(ctx, hipMemcpyAsync(results, d + result_offset, result_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return VHR_OK;
+}
+
+int vhr_get_point_query_statistics(vhr_context *ctx, uint64_t out[4]) {
+    if (!ctx || !out) return VHR_ERROR_INVALID_ARGUMENT;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (ctx->host_only || ctx->pq_queries == 0 || !ctx->pq_last_counters) return VHR_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipDeviceSynchronize());         // the stream of the last query may be the caller's: wait for the device, then read
+    PointQueryCounters c;
+    HIP_TRY(ctx, hipMemcpy(&c, ctx->pq_last_counters, sizeof(c), hipMemcpyDeviceToHost));
+    out[0] = ctx->pq_queries; out[1] = c.found; out[2] = c.evaluations; out[3] = c.overflows;
+    return VHR_OK;
+}
+
+// a device context runs the device's copy of point_triangle, a host-only context the host's: one source (closest_point.hpp)
+int vhr_debug_point_triangle(vhr_context *ctx, const float *pairs, uint32_t count, float *out) {
+    if (!ctx || (count && (!pairs || !out))) return ctx ? ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_debug_point_triangle: null argument") : VHR_ERROR_INVALID_ARGUMENT;
+    if (!ctx->host_only) {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        return launch_point_triangle_pairs(ctx, pairs, count, out);
+    }
+    for (uint32_t i = 0; i < count; ++i) {
+        const float *s = pairs + size_t(i) * 12u;
+        const PointTriangle r = point_triangle(s, s + 3, s + 6, s + 9);
+        out[size_t(i) * 3u] = r.d2; out[size_t(i) * 3u + 1u] = r.u; out[size_t(i) * 3u + 2u] = r.v;
+    }
+    return VHR_OK;
+}
+
+int vhr_ray_query_struct_layout(uint32_t out[8]) {
+    if (!out) return VHR_ERROR_INVALID_ARGUMENT;
+    out[0] = sizeof(vhr_ray); out[1] = offsetof(vhr_ray, tmin); out[2] = offsetof(vhr_ray, direction); out[3] = offsetof(vhr_ray, tmax);
+    out[4] = sizeof(vhr_ray_hit); out[5] = offsetof(vhr_ray_hit, geometry_index); out[6] = offsetof(vhr_ray_hit, primitive_index);
+    out[7] = offsetof(vhr_ray_hit, reserved);
+    return 8;
+}
+
+int vhr_debug_ray_triangle(vhr_context *ctx, const float *pairs, uint32_t count, uint32_t *hit, float *tuv) {
+    if (!ctx || (count && (!pairs || !hit || !tuv))) return ctx ? ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_debug_ray_triangle: null argument") : VHR_ERROR_INVALID_ARGUMENT;
+    if (ctx->host_only) return ctx->fail(VHR_ERROR_DEVICE, "vhr_debug_ray_triangle: host-only context");
+    return launch_ray_triangle_pairs(ctx, pairs, count, hit, tuv);
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // Which side of a triangle a ray meets (vhr_ray_query_faces: face culling and the hit kind): ONE definition for the device (kernels_ray_query.hip:
-// the face filter of both walkers, the hit kind at the commit and the pairs kernel of vhr_debug_ray_facing) and for the host (context.cpp:
+// the face filter of both walkers, the hit kind at the commit and the pairs kernel of vhr_debug_ray_facing) and for the host (queries.cpp:
 // vhr_debug_ray_facing on a host-only context, and the primitives' flip bytes).  The counterpart of closest_point.hpp; every unit that includes
 // it is built with -ffp-contract=off.
 //

@@ -14,12 +14,6 @@
 
 using namespace vhr;
 
-#define HIP_TRY(ctx, expr)                                                                                  \
-    do {                                                                                                    \
-        hipError_t e_ = (expr);                                                                             \
-        if (e_ != hipSuccess) return (ctx)->fail(VHR_ERROR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 static const char *kRenderOutput = "RENDER_OUTPUT";
 static const char *kRaygen = "hybrid_render_path/raygen.rgen";
 static const char *kMiss = "hybrid_render_path/miss.rmiss";
@@ -423,7 +417,7 @@ int vhr_graph_execute(vhr_context *ctx, uint32_t resource_idx, uint32_t image_id
 int vhr_graph_gather_performance_statistics(vhr_context *ctx) {
     if (!ctx) return VHR_ERROR_INVALID_ARGUMENT;
     if (ctx->host_only) return VHR_OK;
-    { const int src_ = ctx->sync_streams(); if (src_ != VHR_OK) return src_; }  // VK_QUERY_RESULT_WAIT_BIT, render_graph.cpp:192-193
+    VHR_TRY(ctx->sync_streams());  // VK_QUERY_RESULT_WAIT_BIT, render_graph.cpp:192-193
     vhr::PassStampPair host_stamps[vhr::kMaxStampedPasses];
     bool have_stamps = false;
     for (auto &name : ctx->execution_order) {

@@ -240,7 +240,7 @@ bool refit_bvh(const vhr_vertex *vertices, const uint32_t *indices, const vhr_pr
                uint32_t motion_epoch = 0);
 // surface-area cost of the tree: sum over the inner nodes of child area x (1 for an inner child, the triangle count for a leaf), over the root's area
 double bvh_sah_cost(const HostBvh &bvh);
-// the device side (csrc/kernels_bvh.hip): what a refit needs beyond what a build leaves behind, prepared at the first refit
+// the device side (csrc/kernels_bvh_refit.hip): what a refit needs beyond what a build leaves behind, prepared at the first refit
 struct RefitPlan;
 void free_refit_plan(vhr_context *ctx);
 int device_refit_bvh(vhr_context *ctx);
@@ -282,7 +282,7 @@ void rebuild_gather_records(const std::vector<BvhTri> &tris, const std::vector<B
                             uint32_t flat_count, std::vector<BvhTri> &flat);
 // fills bvh.prev_tris / prev_saved / prev_differing for the new tree; returns the records whose previous differs from current
 uint64_t rebuild_scatter_records(HostBvh &bvh, const std::vector<BvhTri> &flat, uint32_t epoch);
-// the device side (csrc/kernels_bvh.hip); the caller has waited for the context's streams
+// the device side (csrc/kernels_bvh_refit.hip); the caller has waited for the context's streams
 int device_count_non_finite_positions(vhr_context *ctx, uint64_t *count);
 int device_rebuild_gather(vhr_context *ctx, uint32_t flat_count, BvhTri **d_flat);      // *d_flat: 48 bytes per flat triangle, the caller's to hipFree
 // allocates ctx->d_prev_tris / d_prev_saved for the tree the context now holds (the old ones are freed) and fills them from d_flat
@@ -544,6 +544,7 @@ struct vhr_context {
     uint64_t motion_refit_differing = 0;         // ... as the last refit attempt counted them (taken over when it succeeds)
     uint64_t motion_launches = 0;                // G-buffer launches that ran the motion instantiation
     bool motion_valid() const { return object_motion_vectors && (host_only ? !h_bvh.prev_tris.empty() : d_prev_tris != nullptr); }
+    bool has_geometry() const { return host_only ? !h_bvh.nodes.empty() : (d_nodes != nullptr && node_count != 0); }      // is there a tree?
     int bvh_host_checks = 0;                        // "bvh_host_checks" 1: a device-built tree is fetched and the host's self-checks repeated on it
     uint64_t bvh_form_checks[4] = { 0, 0, 0, 0 };   // check_node_forms of the last build (vhr_get_bvh_form_checks)
     float bvh_centre[3] = { 0, 0, 0 };
@@ -708,7 +709,27 @@ struct vhr_context {
     int fail(int code, const std::string &msg) { error = msg; return code; }
 };
 
+// The two early returns of the C ABI's host code.  HIP_TRY: a HIP call that fails ends the function with VHR_ERROR_DEVICE and "<the call>: <HIP's
+// text>" as the context's error.  VHR_TRY: a status of the library's own that is not VHR_OK is handed on as it is (its maker has set the error).
+#define HIP_TRY(ctx, expr)                                                                                  \
+    do {                                                                                                    \
+        hipError_t e_ = (expr);                                                                             \
+        if (e_ != hipSuccess) return (ctx)->fail(VHR_ERROR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+#define VHR_TRY(expr)                                                                                       \
+    do {                                                                                                    \
+        const int rc_ = (expr);                                                                             \
+        if (rc_ != VHR_OK) return rc_;                                                                      \
+    } while (0)
+
 namespace vhr {
+
+// csrc/geometry.cpp: the scene's device arrays and tree for vhr_destroy, the previous records for the "object_motion_vectors" option
+void free_scene(vhr_context *ctx);               // scene arrays, tree, refit plan, masks, flips, previous records; counts to 0
+void free_tree(vhr_context *ctx);                // the five tree arrays (freed and nulled), node_count and tri_count to 0: a device context has no tree
+int reset_motion(vhr_context *ctx);              // previous = current for the tree the context holds (none: nothing to keep); the caller has waited for the streams
+// csrc/queries.cpp: the queries' per-stream scratch and their staging buffer, for vhr_destroy
+void free_query_scratch(vhr_context *ctx);
 
 int flush_deferred_raygen(vhr_context *ctx, const TemporalArgs *fuse);      // csrc/kernels_trace.hip; no-op without a held-back launch
 bool deferred_raygen_matches(const vhr_context *ctx, const TemporalArgs &t);
