@@ -1030,6 +1030,51 @@ int vhr_get_face_cull_statistics(vhr_context *ctx, uint64_t out[4]);
  * context runs the host's copy of the same source (as vhr_debug_point_triangle does). */
 int vhr_debug_ray_facing(vhr_context *ctx, const float *pairs, const uint8_t *flips, uint32_t count, uint8_t *out);
 
+/* ---- Surface points of hits: where a hit is, which way the surface faces, and what gbuf.frag would have written there ----
+ * A vhr_ray_hit says which triangle and where on it (rayQueryGetIntersection*EXT); vhr_resolve_hits turns a batch of them into
+ * vhr_surface_point records (include/vhr_types.h) from the scene arrays the context holds -- the current ones, also where the vertices came
+ * through VHR_UPDATE_DEVICE_MEMORY -- what reflection_hit.rchit:11-24 and gbuf.frag:19-56 compute from the same indices.
+ *   - Only u, v, geometry_index and primitive_index of a hit are read; t and reserved are ignored, so the results of vhr_ray_query* and of
+ *     vhr_closest_point_query go in unchanged.
+ *   - NOT RESOLVED, the whole record zero (flags == 0): a miss (either index 0xFFFFFFFF), geometry_index not less than the primitive count,
+ *     primitive_index not less than that primitive's index_count / 3, u or v not finite.  `hits` is the caller's data: each of these checks
+ *     comes before any gather, so no hit array makes the kernel read outside the scene arrays.  A context without geometry resolves nothing.
+ *   - The record: (v0, e1, e2) from the primitive's transform and the triangle's three positions by the function the builders and the refits
+ *     use (transform * vec4(pos, 1), columns left to right; e1 = w1 - w0, e2 = w2 - w0) -- bit for bit the leaf record the walkers tested.
+ *     There is no slot lookup and the tree is never read: results are the same on every tree, with "bvh_presplit", after refits and rebuilds.
+ *   - position = (v0 + u e1) + v e2 per component, every operation rounded once: the point the closest-point query measured to, the P of the
+ *     object-motion contract.
+ *   - geometric_normal = cross(e1, e2), negated where the primitive's flip byte is 1 (vhr_get_primitive_facing_flips), each component divided by
+ *     sqrtf(n . n) (IEEE division and square root).  By vhr_ray_query_faces' rule a ray of direction d is front-facing iff
+ *     d . geometric_normal < 0; the two can differ in sign only at grazing incidence, where the binary64 determinant and the fp32 cross
+ *     product may disagree.  VHR_SURFACE_DEGENERATE and the zero vector where n . n is not a positive finite number: a triangle without area,
+ *     and also one whose products underflow to 0 (|e1 x e2| below about 1e-22, e.g. two edges of 1e-11) or overflow.
+ *   - uv0, uv1: barycentrics (1 - u - v, u, v), the products summed left to right (as the shaders' interpolation).
+ *   - shading_normal: the stand-in G-buffer's gbuf.frag:35-43 operation for operation -- the interpolated object-space normal; with
+ *     VHR_SURFACE_MATERIAL and material.normal_map >= 0 its tangent-space perturbation (VHR_SURFACE_NORMAL_MAPPED; the reference's
+ *     cross(tangent_space_normal, tangent) included); then the normal matrix and the normalisation.  Where the squared length of what is
+ *     normalised is not a positive finite number: 0 and VHR_SURFACE_NO_SHADING_NORMAL, never a NaN.
+ *   - VHR_SURFACE_MATERIAL: base_color (gbuf.frag:19-26: the factor, or the base-colour texture's texel), metallic and roughness
+ *     (gbuf.frag:50-56), as the stand-in G-buffer evaluates them, before any UNORM or half store; VHR_SURFACE_DISCARDED where gbuf.frag:27-32
+ *     would discard the fragment (the rule of VHR_RAY_QUERY_ALPHA_TEST: a hit found with that flag is never DISCARDED).  Without the flag
+ *     the three fields are 0, no texture is read and no normal map is applied.
+ *   - Memory and streams as for the queries: device pointers by default, enqueued on the stream vhr_get_current_stream reports (between frames
+ *     or inside a pass callback), no synchronisation; VHR_SURFACE_HOST_MEMORY: host pointers, staged, the call returns with results in place.
+ *     No frame state is read or written.
+ *   - VHR_ERROR_INVALID_ARGUMENT (message in vhr_last_error, with the entry point's name) for, in this order: a NULL context; a NULL pointer
+ *     with count > 0; an unknown flag bit; `hits` not 4-byte aligned; `out` not 16-byte aligned -- on every context.  count == 0 then returns
+ *     VHR_OK.  VHR_ERROR_NO_DEVICE on a host-only context with VHR_SURFACE_MATERIAL or without VHR_SURFACE_HOST_MEMORY.  VHR_ERROR_GRAPH,
+ *     naming vhr_refit_geometry, while geometry updates are pending: a hit belongs to the geometry it was found on.
+ *   - A HOST-ONLY context answers the geometry part (everything but VHR_SURFACE_MATERIAL) from the arrays it keeps, with the host's copy of the
+ *     same source: the arithmetic is testable without a GPU, and the two are comparable, bit for bit, on one. */
+int vhr_resolve_hits(vhr_context *ctx, const vhr_ray_hit *hits, uint32_t count, uint32_t flags, vhr_surface_point *out);
+/* The last vhr_resolve_hits (waits for the device): out[0] = hits, out[1] = records with VHR_SURFACE_VALID, out[2] = records with
+ * VHR_SURFACE_DISCARDED, out[3] = 1 if the material instantiation ran.  All 0 before the first call. */
+int vhr_get_surface_statistics(vhr_context *ctx, uint64_t out[4]);
+/* The layout this library was built with, for bindings: out[0] = sizeof(vhr_surface_point), then the offsets of flags, geometric_normal,
+ * metallic, shading_normal, roughness, base_color and uv0.  Returns 8. */
+int vhr_surface_point_layout(uint32_t out[8]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -178,6 +178,13 @@ public:
     void QueryClosestPoints(const vhr_point_query *points, uint32_t count, uint32_t flags, void *results, uint32_t cull_mask = 0xFFu) {
         check(context.handle, vhr_closest_point_query(context.handle, points, count, flags, cull_mask, results), "QueryClosestPoints");
     }
+    // Extension: the surface points of hits (vhr_resolve_hits) -- position, geometric and shading normal, uv and, with VHR_SURFACE_MATERIAL, what
+    // gbuf.frag writes there -- from the scene arrays this manager owns.  `hits` as QueryRays and QueryClosestPoints return them; `flags` =
+    // VHR_SURFACE_MATERIAL and / or VHR_SURFACE_HOST_MEMORY; `out` starts at a 16-byte boundary.  Device pointers: enqueued on the context's
+    // current stream, no synchronisation.
+    void ResolveHits(const vhr_ray_hit *hits, uint32_t count, uint32_t flags, vhr_surface_point *out) {
+        check(context.handle, vhr_resolve_hits(context.handle, hits, count, flags, out), "ResolveHits");
+    }
     // Extension: per-primitive ray cull masks (VkAccelerationStructureInstanceKHR::mask, per geometry; 0xFF after UpdateGeometry).  No refit needed.
     void SetPrimitiveMasks(uint32_t first_primitive, const std::vector<uint8_t> &masks) {
         check(context.handle, vhr_set_primitive_masks(context.handle, first_primitive, uint32_t(masks.size()), masks.data()), "SetPrimitiveMasks");

@@ -143,6 +143,28 @@ typedef struct vhr_point_query {
 #define VHR_POINT_QUERY_ANY_WITHIN   1u   /* results: uint8_t[count], 1 = some surface lies within max_distance */
 #define VHR_POINT_QUERY_HOST_MEMORY  2u   /* host pointers, staged; returns with results in place */
 
+/* The surface point of one hit (vhr_resolve_hits, include/vhr_amd.h).  80 bytes; an array of them must start at a 16-byte boundary (the kernel
+ * writes a record as five 16-byte stores). */
+typedef struct vhr_surface_point {
+    float    position[3];               /* world space */
+    uint32_t flags;                     /* VHR_SURFACE_* result bits below; 0 = not resolved */
+    float    geometric_normal[3];       /* unit, on the FRONT side of the triangle; 0 if degenerate */
+    float    metallic;
+    float    shading_normal[3];         /* gbuf.frag:35-43, world space, unit */
+    float    roughness;
+    float    base_color[4];             /* gbuf.frag:19-26, linear RGBA before any UNORM store */
+    float    uv0[2], uv1[2];
+} vhr_surface_point;
+/* request flags */
+#define VHR_SURFACE_MATERIAL      1u    /* sample the textures: base_color, metallic, roughness, normal map, DISCARDED */
+#define VHR_SURFACE_HOST_MEMORY   2u    /* host pointers, staged; returns with results in place */
+/* result bits in vhr_surface_point::flags */
+#define VHR_SURFACE_VALID               1u
+#define VHR_SURFACE_DEGENERATE          2u   /* |e1 x e2|^2 is not in (0, inf): geometric_normal = 0 */
+#define VHR_SURFACE_NO_SHADING_NORMAL   4u   /* the vector gbuf.frag:43 normalises has squared length not in (0, inf): shading_normal = 0 */
+#define VHR_SURFACE_NORMAL_MAPPED       8u
+#define VHR_SURFACE_DISCARDED          16u   /* gbuf.frag:27-32 would discard here (the rule of gbuf_discarded) */
+
 /* VkFormat values (passed through unchanged from reference-side code) */
 enum {
     VHR_FORMAT_UNDEFINED           = 0,
@@ -222,6 +244,9 @@ static_assert(sizeof(vhr_ray) == 32 && offsetof(vhr_ray, tmin) == 12 && offsetof
 static_assert(sizeof(vhr_ray_hit) == 24 && offsetof(vhr_ray_hit, geometry_index) == 12 && offsetof(vhr_ray_hit, primitive_index) == 16 &&
               offsetof(vhr_ray_hit, reserved) == 20, "vhr_ray_hit");
 static_assert(sizeof(vhr_point_query) == 16 && offsetof(vhr_point_query, max_distance) == 12, "vhr_point_query");
+static_assert(sizeof(vhr_surface_point) == 80 && offsetof(vhr_surface_point, flags) == 12 && offsetof(vhr_surface_point, geometric_normal) == 16 &&
+              offsetof(vhr_surface_point, metallic) == 28 && offsetof(vhr_surface_point, shading_normal) == 32 && offsetof(vhr_surface_point, roughness) == 44 &&
+              offsetof(vhr_surface_point, base_color) == 48 && offsetof(vhr_surface_point, uv0) == 64 && offsetof(vhr_surface_point, uv1) == 72, "vhr_surface_point");
 #else
 _Static_assert(sizeof(vhr_vertex) == 56, "Vertex");
 _Static_assert(sizeof(vhr_material) == 44, "Material");
@@ -235,6 +260,9 @@ _Static_assert(sizeof(vhr_ray) == 32 && offsetof(vhr_ray, tmin) == 12 && offseto
 _Static_assert(sizeof(vhr_ray_hit) == 24 && offsetof(vhr_ray_hit, geometry_index) == 12 && offsetof(vhr_ray_hit, primitive_index) == 16 &&
                offsetof(vhr_ray_hit, reserved) == 20, "vhr_ray_hit");
 _Static_assert(sizeof(vhr_point_query) == 16 && offsetof(vhr_point_query, max_distance) == 12, "vhr_point_query");
+_Static_assert(sizeof(vhr_surface_point) == 80 && offsetof(vhr_surface_point, flags) == 12 && offsetof(vhr_surface_point, geometric_normal) == 16 &&
+               offsetof(vhr_surface_point, metallic) == 28 && offsetof(vhr_surface_point, shading_normal) == 32 && offsetof(vhr_surface_point, roughness) == 44 &&
+               offsetof(vhr_surface_point, base_color) == 48 && offsetof(vhr_surface_point, uv0) == 64 && offsetof(vhr_surface_point, uv1) == 72, "vhr_surface_point");
 #endif
 
 #endif /* VHR_TYPES_H */

@@ -64,6 +64,11 @@ POINT_QUERY_ANY_WITHIN, POINT_QUERY_HOST_MEMORY = 1, 2
 # vhr_ray_query_faces (include/vhr_types.h): its face_cull, and the hit kind it reports in vhr_ray_hit.reserved
 FACE_CULL_NONE, FACE_CULL_BACK, FACE_CULL_FRONT = 0, 1, 2
 HIT_KIND_FRONT_FACING, HIT_KIND_BACK_FACING = 0xFE, 0xFF
+# vhr_resolve_hits (include/vhr_types.h: vhr_surface_point; an array of them starts at a 16-byte boundary), its request flags and result bits
+surface_point_dtype = np.dtype([("position", "<f4", 3), ("flags", "<u4"), ("geometric_normal", "<f4", 3), ("metallic", "<f4"),
+                                ("shading_normal", "<f4", 3), ("roughness", "<f4"), ("base_color", "<f4", 4), ("uv0", "<f4", 2), ("uv1", "<f4", 2)])
+SURFACE_MATERIAL, SURFACE_HOST_MEMORY = 1, 2
+SURFACE_VALID, SURFACE_DEGENERATE, SURFACE_NO_SHADING_NORMAL, SURFACE_NORMAL_MAPPED, SURFACE_DISCARDED = 1, 2, 4, 8, 16
 
 assert vertex_dtype.itemsize == 56
 assert material_dtype.itemsize == 44
@@ -74,6 +79,7 @@ assert svgf_push_constants_dtype.itemsize == 24
 assert trace_params_dtype.itemsize == 32
 assert ray_dtype.itemsize == 32 and ray_hit_dtype.itemsize == 24
 assert point_query_dtype.itemsize == 16
+assert surface_point_dtype.itemsize == 80
 
 
 def default_trace_params(shadow=True, ao_spp=2, reflections=True):

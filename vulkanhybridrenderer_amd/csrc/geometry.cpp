@@ -123,10 +123,8 @@ static std::string range_exceeds(const std::string &who, uint32_t first, uint32_
     return who + ": range [" + std::to_string(first) + ", +" + std::to_string(count) + ") exceeds " + what + " (" + std::to_string(size) + ")";
 }
 
-extern "C" {
-
-// inverseTranspose(mat3(transform)) -- hybrid_render_path.cpp:44 (used by the stand-in G-buffer only)
-static void normal_matrix3(const float *m, float out[9]) {
+// inverseTranspose(mat3(transform)) -- hybrid_render_path.cpp:44 (the stand-in G-buffer and vhr_resolve_hits)
+void vhr::normal_matrix3(const float *m, float out[9]) {
     double a = m[0], b = m[4], c = m[8], d = m[1], e = m[5], f = m[9], g = m[2], h = m[6], i = m[10];
     double c00 = e * i - f * h, c01 = -(d * i - f * g), c02 = d * h - e * g;
     double c10 = -(b * i - c * h), c11 = a * i - c * g, c12 = -(a * h - b * g);
@@ -137,6 +135,8 @@ static void normal_matrix3(const float *m, float out[9]) {
     out[1] = float(c10 * id); out[4] = float(c11 * id); out[7] = float(c12 * id);
     out[2] = float(c20 * id); out[5] = float(c21 * id); out[8] = float(c22 * id);
 }
+
+extern "C" {
 
 // the device-built tree on the host (for "bvh_host_checks" and the fingerprint)
 static int fetch_device_tree(vhr_context *ctx, HostBvh &bvh) {

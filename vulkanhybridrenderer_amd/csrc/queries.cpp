@@ -1,11 +1,12 @@
-// Query half of the C ABI (include/vhr_amd.h): batched ray queries and closest-point queries on the scene's tree, their host-memory staging
-// and statistics, and the pair entry points that run one shared function (ray / triangle, facing, point / triangle) on a list of inputs.
+// Query half of the C ABI (include/vhr_amd.h): batched ray queries and closest-point queries on the scene's tree, the surface points of their
+// hits (vhr_resolve_hits), their host-memory staging and statistics, and the pair entry points that run one shared function (ray / triangle, facing, point / triangle) on a list of inputs.
 #include <cstring>
 #include <string>
 
 #include "vhr_internal.hpp"
 #include "closest_point.hpp"  // point_triangle's host copy (vhr_debug_point_triangle on a host-only context)
 #include "ray_facing.hpp"     // ray_hit_kind's host copy (vhr_debug_ray_facing on a host-only context)
+#include "surface_point.hpp"  // surface_geometry's host copy (vhr_resolve_hits on a host-only context)
 
 using namespace vhr;
 
@@ -13,6 +14,7 @@ void vhr::free_query_scratch(vhr_context *ctx) {
     for (auto &q : ctx->rq_scratch) { hipFree(q.counters); hipFree(q.list); }
     hipFree(ctx->d_rq_staging);
     for (auto &q : ctx->pq_scratch) hipFree(q.counters);
+    for (auto &q : ctx->sp_scratch) hipFree(q.counters);
 }
 
 // the host-memory paths' staging buffer holds at least `staging` bytes (it grows to the largest query so far; its old contents are not kept)
@@ -160,6 +162,86 @@ int vhr_debug_point_triangle(vhr_context *ctx, const float *pairs, uint32_t coun
         out[size_t(i) * 3u] = r.d2; out[size_t(i) * 3u + 1u] = r.u; out[size_t(i) * 3u + 2u] = r.v;
     }
     return VHR_OK;
+}
+
+// vhr_resolve_hits on a host-only context: the geometry part from the arrays the context keeps, by the source the kernel runs (surface_point.hpp)
+static void resolve_hits_host(vhr_context *ctx, const vhr_ray_hit *hits, uint32_t count, vhr_surface_point *out) {
+    ctx->sp_host_counters = SurfaceCounters{};
+    const uint32_t primitive_count = ctx->has_geometry() ? ctx->primitive_count : 0u;
+    for (uint32_t i = 0; i < count; ++i) {
+        // (hits need 4-byte alignment only, which is vhr_ray_hit's own; out is 16-byte aligned)
+        const vhr_ray_hit &h = hits[i];
+        vhr_surface_point &o = out[i];
+        std::memset(&o, 0, sizeof(o));
+        if (!surface_hit_addressable(h.u, h.v, h.geometry_index, h.primitive_index, primitive_count)) continue;
+        const vhr_primitive &prim = ctx->h_primitives[h.geometry_index];
+        if (!(h.primitive_index < prim.index_count / 3u)) continue;
+        const uint32_t *ix = ctx->h_indices.data() + (size_t(prim.index_offset) + 3u * size_t(h.primitive_index));
+        const vhr_vertex *vx = ctx->h_vertices.data() + prim.vertex_offset;
+        float M[9];
+        normal_matrix3(prim.transform, M);
+        const SurfaceGeometry s = surface_geometry(prim.transform, ctx->h_prim_flips[h.geometry_index] != 0, M, vx[ix[0]], vx[ix[1]], vx[ix[2]], h.u, h.v);
+        for (int k = 0; k < 3; ++k) { o.position[k] = s.position[k]; o.geometric_normal[k] = s.geometric_normal[k]; o.shading_normal[k] = s.shading_normal[k]; }
+        for (int k = 0; k < 2; ++k) { o.uv0[k] = s.uv0[k]; o.uv1[k] = s.uv1[k]; }
+        o.flags = s.flags;
+        ++ctx->sp_host_counters.valid;
+    }
+}
+
+// vhr_resolve_hits: the arguments first (the same answer on every context), then the device; staged like the queries' host paths
+int vhr_resolve_hits(vhr_context *ctx, const vhr_ray_hit *hits, uint32_t count, uint32_t flags, vhr_surface_point *out) {
+    if (!ctx) return VHR_ERROR_INVALID_ARGUMENT;
+    const std::string who("vhr_resolve_hits");
+    if (count > 0 && (!hits || !out)) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": hits and out must not be NULL when count > 0");
+    if (flags & ~uint32_t(VHR_SURFACE_MATERIAL | VHR_SURFACE_HOST_MEMORY)) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": unknown flag bits " + std::to_string(flags));
+    if (count > 0 && reinterpret_cast<uintptr_t>(hits) % 4u) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": hits must be 4-byte aligned");
+    if (count > 0 && reinterpret_cast<uintptr_t>(out) % 16u) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": out must be 16-byte aligned");
+    if (count == 0) return VHR_OK;
+    const bool material = (flags & VHR_SURFACE_MATERIAL) != 0, host_memory = (flags & VHR_SURFACE_HOST_MEMORY) != 0;
+    if (ctx->host_only && (material || !host_memory))
+        return ctx->fail(VHR_ERROR_NO_DEVICE, who + ": host-only context: " + (material ? "no textures are sampled without a device (VHR_SURFACE_MATERIAL)" : "no device memory (VHR_SURFACE_HOST_MEMORY)"));
+    VHR_TRY(ctx->refuse_if_stale("vhr_resolve_hits"));
+    ctx->sp_hits = count;
+    ctx->sp_material = material;
+    if (ctx->host_only) { resolve_hits_host(ctx, hits, count, out); return VHR_OK; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!host_memory) return vhr::launch_resolve_hits(ctx, hits, count, material, out);
+    // host memory: the hits, then the records at the next 256-byte boundary, in the ray query's staging buffer
+    const uint64_t hit_bytes = uint64_t(count) * sizeof(vhr_ray_hit), out_bytes = uint64_t(count) * sizeof(vhr_surface_point);
+    const uint64_t out_offset = (hit_bytes + 255u) & ~uint64_t(255u);
+    VHR_TRY(grow_staging(ctx, out_offset + out_bytes));
+    char *const d = static_cast<char *>(ctx->d_rq_staging);
+    HIP_TRY(ctx, hipMemcpyAsync(d, hits, hit_bytes, hipMemcpyHostToDevice, ctx->stream));
+    VHR_TRY(vhr::launch_resolve_hits(ctx, reinterpret_cast<const vhr_ray_hit *>(d), count, material, reinterpret_cast<vhr_surface_point *>(d + out_offset)));
+    HIP_TRY(ctx, hipMemcpyAsync(out, d + out_offset, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return VHR_OK;
+}
+
+int vhr_get_surface_statistics(vhr_context *ctx, uint64_t out[4]) {
+    if (!ctx || !out) return VHR_ERROR_INVALID_ARGUMENT;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (ctx->sp_hits == 0) return VHR_OK;
+    SurfaceCounters c = ctx->sp_host_counters;
+    if (!ctx->host_only) {
+        if (!ctx->sp_last_counters) return VHR_OK;
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, hipDeviceSynchronize());     // the stream of the last call may be the caller's: wait for the device, then read
+        SurfaceCounters slots[kSurfaceCounterSlots];
+        HIP_TRY(ctx, hipMemcpy(slots, ctx->sp_last_counters, sizeof(slots), hipMemcpyDeviceToHost));
+        c = SurfaceCounters{};
+        for (const SurfaceCounters &slot : slots) { c.valid += slot.valid; c.discarded += slot.discarded; }
+    }
+    out[0] = ctx->sp_hits; out[1] = c.valid; out[2] = c.discarded; out[3] = ctx->sp_material ? 1u : 0u;
+    return VHR_OK;
+}
+
+int vhr_surface_point_layout(uint32_t out[8]) {
+    if (!out) return VHR_ERROR_INVALID_ARGUMENT;
+    out[0] = sizeof(vhr_surface_point); out[1] = offsetof(vhr_surface_point, flags); out[2] = offsetof(vhr_surface_point, geometric_normal);
+    out[3] = offsetof(vhr_surface_point, metallic); out[4] = offsetof(vhr_surface_point, shading_normal); out[5] = offsetof(vhr_surface_point, roughness);
+    out[6] = offsetof(vhr_surface_point, base_color); out[7] = offsetof(vhr_surface_point, uv0);
+    return 8;
 }
 
 int vhr_ray_query_struct_layout(uint32_t out[8]) {

@@ -381,6 +381,14 @@ struct RayQueryScratch { hipStream_t stream; RayQueryCounters *counters; uint32_
 // overflowed; one set per stream queries were enqueued on, like the ray query's
 struct PointQueryCounters { unsigned long long found, evaluations; uint32_t overflows, pad; };
 struct PointQueryScratch { hipStream_t stream; PointQueryCounters *counters; };
+// vhr_resolve_hits' counters (csrc/kernels_surface.hip): records with VHR_SURFACE_VALID, records with VHR_SURFACE_DISCARDED; one set per stream
+// calls were enqueued on, like the queries'.  A set is kSurfaceCounterSlots slots of one 64-byte line each, a wave adds to the slot of its block's
+// index and vhr_get_surface_statistics sums them: a resolve is one wave per 64 hits and little work per hit, and that many adds to ONE address
+// queue up behind each other (measured: 16 384 waves' adds to one counter took 0.2 ms of a 2^20-hit call, whatever else the kernel did)
+constexpr uint32_t kSurfaceCounterSlots = 128;
+struct SurfaceCounters { unsigned long long valid, discarded, pad[6]; };
+static_assert(sizeof(SurfaceCounters) == 64, "SurfaceCounters: one line per slot");
+struct SurfaceScratch { hipStream_t stream; SurfaceCounters *counters; };
 
 struct RayStats {
     unsigned long long unique_rays, covered_pixels, stack_overflows, node_visits, leaf_visits, triangle_tests, wave_iterations, second_bounce_rays;
@@ -654,6 +662,13 @@ struct vhr_context {
     std::vector<vhr::PointQueryScratch> pq_scratch;
     const vhr::PointQueryCounters *pq_last_counters = nullptr;  // the last query's (vhr_get_point_query_statistics)
     uint64_t pq_queries = 0;            // queries of the last call (0: none yet)
+    // vhr_resolve_hits: counters per stream; VHR_SURFACE_HOST_MEMORY stages through d_rq_staging as the queries' host-memory paths do.  A host-only
+    // context counts on the host (sp_host_counters)
+    std::vector<vhr::SurfaceScratch> sp_scratch;
+    const vhr::SurfaceCounters *sp_last_counters = nullptr;     // the last call's (vhr_get_surface_statistics)
+    vhr::SurfaceCounters sp_host_counters = {};
+    uint64_t sp_hits = 0;               // hits of the last call (0: none yet)
+    bool sp_material = false;           // ... and whether it ran the material instantiation
 
     int options[vhr::kOptCount];       // vhr_set_option; defaults from vhr::kOptionInfo (the constructor)
     vhr_context() { for (int i = 0; i < vhr::kOptCount; ++i) options[i] = vhr::kOptionInfo[i].def; }
@@ -726,6 +741,7 @@ namespace vhr {
 
 // csrc/geometry.cpp: the scene's device arrays and tree for vhr_destroy, the previous records for the "object_motion_vectors" option
 void free_scene(vhr_context *ctx);               // scene arrays, tree, refit plan, masks, flips, previous records; counts to 0
+void normal_matrix3(const float *m, float out[9]);      // inverseTranspose(mat3(transform)), column-major: what d_normal_matrices holds per primitive
 void free_tree(vhr_context *ctx);                // the five tree arrays (freed and nulled), node_count and tri_count to 0: a device context has no tree
 int reset_motion(vhr_context *ctx);              // previous = current for the tree the context holds (none: nothing to keep); the caller has waited for the streams
 // csrc/queries.cpp: the queries' per-stream scratch and their staging buffer, for vhr_destroy
@@ -799,6 +815,9 @@ int launch_ray_facing_pairs(vhr_context *ctx, const float *pairs, const uint8_t 
 // query) are device memory; enqueued on ctx->stream.  vhr_debug_point_triangle on a device context: host arrays, 12 floats in and 3 out per pair
 int launch_point_query(vhr_context *ctx, const vhr_point_query *points, uint32_t count, bool any_within, uint32_t cull_mask, void *results);
 int launch_point_triangle_pairs(vhr_context *ctx, const float *pairs, uint32_t n, float *out);
+// vhr_resolve_hits' device path (csrc/kernels_surface.hip): `hits` (count x vhr_ray_hit) and `out` (count x vhr_surface_point) are device memory;
+// enqueued on ctx->stream
+int launch_resolve_hits(vhr_context *ctx, const vhr_ray_hit *hits, uint32_t count, bool material, vhr_surface_point *out);
 // the primitives' mask bytes on the device (made, from h_prim_masks or as all-0xFF, if no call has made them yet): before a launch that filters
 int ensure_device_prim_masks(vhr_context *ctx);
 // the primitives' facing-flip bytes on the device (made from h_prim_flips if no launch has made them yet): before a launch of the face instantiation

@@ -47,6 +47,7 @@ EXPORTS = [
     "vhr_closest_point_query", "vhr_get_point_query_statistics", "vhr_debug_point_triangle",
     "vhr_rebuild_geometry", "vhr_get_rebuild_statistics",
     "vhr_ray_query_faces", "vhr_get_primitive_facing_flips", "vhr_get_face_cull_statistics", "vhr_debug_ray_facing",
+    "vhr_resolve_hits", "vhr_get_surface_statistics", "vhr_surface_point_layout",
 ]
 
 PATH_PREFIXES = ("hybrid", "raytraced", "rayquery", "forward_raster")      # vhr_<prefix>_{create,destroy,build,rebuild,last_error}
@@ -319,6 +320,9 @@ def load():
     L.vhr_closest_point_query.argtypes = [vp, vp, u32, u32, u32, vp]
     L.vhr_get_point_query_statistics.argtypes = [vp, C.POINTER(u64)]
     L.vhr_debug_point_triangle.argtypes = [vp, C.c_void_p, u32, C.c_void_p]
+    L.vhr_resolve_hits.argtypes = [vp, vp, u32, u32, vp]
+    L.vhr_get_surface_statistics.argtypes = [vp, C.POINTER(u64)]
+    L.vhr_surface_point_layout.argtypes = [C.POINTER(u32)]
     L.vhr_update_vertices.argtypes = [vp, u32, u32, vp, u32]
     L.vhr_update_primitive_transforms.argtypes = [vp, u32, u32, vp]
     L.vhr_refit_geometry.argtypes = [vp]
@@ -1031,6 +1035,32 @@ class Context:
         """The last closest-point query: [queries, queries that found something, point / triangle evaluations, waves whose stack overflowed (must be 0)]."""
         out = (C.c_uint64 * 4)()
         self.check(self.L.vhr_get_point_query_statistics(self.handle, out), "point_query_statistics")
+        return [int(x) for x in out]
+
+    def resolve_hits(self, hits, material=False):
+        """vhr_resolve_hits on host arrays: hits = abi.ray_hit_dtype[n], as ray_query() and closest_point_query() return them (only u, v,
+        geometry_index and primitive_index are read).  Returns abi.surface_point_dtype[n], 16-byte aligned: position, geometric normal (unit, on
+        the triangle's front side), shading normal, uv0 / uv1 and, with material, base_color / metallic / roughness and the normal map's
+        perturbation as the G-buffer pass evaluates them; flags = abi.SURFACE_* result bits, 0 (and an all-zero record) for a hit that was
+        not resolved -- a miss, an index outside the scene, barycentrics that are no numbers.  A host-only context answers without material."""
+        h = np.ascontiguousarray(hits, dtype=abi.ray_hit_dtype).reshape(-1)
+        n = len(h)
+        raw = np.zeros(n * abi.surface_point_dtype.itemsize + 16, np.uint8)
+        start = -raw.ctypes.data % 16
+        out = raw[start:start + n * abi.surface_point_dtype.itemsize].view(abi.surface_point_dtype)
+        flags = abi.SURFACE_HOST_MEMORY | (abi.SURFACE_MATERIAL if material else 0)
+        self.check(self.L.vhr_resolve_hits(self.handle, h.ctypes.data if n else None, n, flags, out.ctypes.data if n else None), "resolve_hits")
+        return out
+
+    def resolve_hits_device(self, hits_ptr, count, out_ptr, material=False):
+        """vhr_resolve_hits on device memory (e.g. torch tensors' data_ptr()): `count` vhr_ray_hit records at hits_ptr (4-byte aligned),
+        vhr_surface_point records (80 bytes each) at out_ptr (16-byte aligned).  Enqueued on current_stream(); returns without synchronising."""
+        self.check(self.L.vhr_resolve_hits(self.handle, hits_ptr or None, int(count), abi.SURFACE_MATERIAL if material else 0, out_ptr or None), "resolve_hits_device")
+
+    def surface_statistics(self):
+        """The last resolve_hits: [hits, records with SURFACE_VALID, records with SURFACE_DISCARDED, 1 if the material instantiation ran]."""
+        out = (C.c_uint64 * 4)()
+        self.check(self.L.vhr_get_surface_statistics(self.handle, out), "surface_statistics")
         return [int(x) for x in out]
 
     def debug_point_triangle(self, pairs):
