@@ -320,3 +320,74 @@ def test_queries_between_and_inside_frames_leave_the_frames_identical(frames_in_
     for between, inside in results:
         assert between.view(abi.ray_hit_dtype).reshape(-1).tobytes() == want.tobytes()
         assert np.array_equal(inside.astype(bool), occ)
+
+
+def test_host_memory_calls_share_one_staging_buffer_and_keep_their_statistics():
+    """The three host-memory paths stage through ONE buffer per context: a sequence in which it grows, is reused by a smaller call of another
+    layout and grows again -- counts on either side of a workgroup of each kernel (2 x 256 rays, 128 points, 256 hits) -- and after every step the
+    answer is, bit for bit, the device-memory call's on torch tensors, the step's statistics are that call's, and the other two getters
+    still report their own last call."""
+    import torch
+    from tests import ray_truth as rt
+    scene = rt.soup_scene(2)
+    rays = rt.soup_rays(scene, 2, 1025)
+    rng = np.random.default_rng(23)
+    masks = rng.integers(0, 256, len(rays)).astype(np.uint8)
+    lo, hi = ray_queries.scene_bounds(scene)
+    points = np.concatenate([rng.uniform(lo - 0.2, hi + 0.2, (129, 3)), rng.choice([np.inf, 0.05, 0.5], (129, 1))], axis=1).astype(np.float32)
+    ctx = lib.Context(64, 64)
+    try:
+        ctx.upload_scene(scene)
+        ctx.set_primitive_masks(rng.integers(1, 256, len(scene.primitives)).astype(np.uint8))
+        getters = {"ray": ctx.ray_query_statistics, "point": ctx.point_query_statistics, "surface": ctx.surface_statistics}
+        last = {k: g() for k, g in getters.items()}
+        assert all(v == [0, 0, 0, 0] for v in last.values())
+
+        def dev(a):
+            return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+        def step(kind, count, device_call, host_call, what):
+            want = device_call()
+            want_stats = getters[kind]()
+            got = host_call()
+            assert got.dtype == want.dtype and len(got) == count and got.tobytes() == want.tobytes(), f"{what}: host-memory and device-memory answers differ"
+            stats = getters[kind]()
+            assert stats[0] == count and stats == want_stats, (what, stats, want_stats)
+            last[kind] = stats
+            for other, g in getters.items():
+                assert g() == last[other], (what, other, g(), last[other])
+            return got
+
+        def ray_device(n, any_hit=False, with_masks=True, **kw):
+            d_rays, d_masks = dev(rays[:n]), dev(masks[:n])
+            out = torch.zeros(n, dtype=torch.uint8, device="cuda") if any_hit else torch.zeros((n, 6), dtype=torch.int32, device="cuda")
+            ctx.ray_query_device(d_rays.data_ptr(), n, out.data_ptr(), any_hit=any_hit, ray_masks_ptr=d_masks.data_ptr() if with_masks else 0, **kw)
+            return out.cpu().numpy().astype(bool) if any_hit else out.cpu().numpy().view(abi.ray_hit_dtype).reshape(-1)
+
+        def point_device(n):
+            d_points = dev(points[:n])
+            out = torch.zeros((n, 6), dtype=torch.int32, device="cuda")
+            ctx.closest_point_query_device(d_points.data_ptr(), n, out.data_ptr())
+            return out.cpu().numpy().view(abi.ray_hit_dtype).reshape(-1)
+
+        def resolve_device(hits, material):
+            d_hits = dev(hits.view(np.uint32).reshape(-1, 6))
+            out = torch.zeros((len(hits), 20), dtype=torch.float32, device="cuda")
+            ctx.resolve_hits_device(d_hits.data_ptr(), len(hits), out.data_ptr(), material=material)
+            return out.cpu().numpy().view(abi.surface_point_dtype).reshape(-1)
+
+        hits = step("ray", 513, lambda: ray_device(513, cull_mask=0x7F), lambda: ctx.ray_query(rays[:513], cull_mask=0x7F, ray_masks=masks[:513]), "1: masked, 513 rays")
+        assert 0 < int((hits["geometry_index"] != MISS).sum()) < 513 and ctx.ray_mask_statistics()[2] == 1
+        found = step("point", 129, lambda: point_device(129), lambda: ctx.closest_point_query(points), "2: 129 points")
+        assert 0 < int((found["geometry_index"] != MISS).sum()) < 129
+        surf = step("surface", 513, lambda: resolve_device(hits, False), lambda: ctx.resolve_hits(hits), "3: resolve 513 hits")
+        assert ctx.surface_statistics()[1] == int((hits["geometry_index"] != MISS).sum()) == int((surf["flags"] & abi.SURFACE_VALID != 0).sum())
+        step("ray", 3, lambda: ray_device(3, any_hit=True, with_masks=False), lambda: ctx.ray_query(rays[:3], any_hit=True), "4: any hit, 3 rays")
+        one = hits[hits["geometry_index"] != MISS][:1]
+        step("surface", 1, lambda: resolve_device(one, True), lambda: ctx.resolve_hits(one, material=True), "5: resolve 1 hit")
+        assert ctx.surface_statistics() == [1, 1, ctx.surface_statistics()[2], 1]
+        faces = step("ray", 1025, lambda: ray_device(1025, face_cull=abi.FACE_CULL_BACK), lambda: ctx.ray_query(rays, ray_masks=masks, face_cull=abi.FACE_CULL_BACK),
+                     "6: faces, 1025 rays")
+        assert ctx.face_cull_statistics()[1] == 1 and set(np.unique(faces["reserved"])) <= {0, abi.HIT_KIND_FRONT_FACING}
+    finally:
+        ctx.close()

@@ -20,19 +20,10 @@ __global__ __launch_bounds__(256) void point_triangle_pairs_kernel(const float *
 }
 
 int launch_point_triangle_pairs(vhr_context *ctx, const float *pairs, uint32_t n, float *out) {
-    if (n == 0) return VHR_OK;
-    float *d_pairs = nullptr, *d_out = nullptr;
-    const size_t pb = size_t(n) * 12u * sizeof(float), ob = size_t(n) * 3u * sizeof(float);
-    int rc = VHR_OK;
-    if (hipMalloc(&d_pairs, pb) != hipSuccess || hipMalloc(&d_out, ob) != hipSuccess) rc = ctx->fail(VHR_ERROR_DEVICE, "vhr_debug_point_triangle: device allocation failed");
-    if (rc == VHR_OK && hipMemcpyAsync(d_pairs, pairs, pb, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = ctx->fail(VHR_ERROR_DEVICE, "vhr_debug_point_triangle: upload failed");
-    if (rc == VHR_OK) {
-        launch(ctx, point_triangle_pairs_kernel, dim3((n + 255u) / 256u), dim3(256), 0, static_cast<const float *>(d_pairs), n, d_out);
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
-            rc = ctx->fail(VHR_ERROR_DEVICE, "vhr_debug_point_triangle: launch or download failed");
-    }
-    (void)hipFree(d_pairs); (void)hipFree(d_out);
-    return rc;
+    PairArray a[2] = { { pairs, nullptr, size_t(n) * 12u * sizeof(float) }, { nullptr, out, size_t(n) * 3u * sizeof(float) } };
+    return run_pairs(ctx, "vhr_debug_point_triangle", a, [&] {
+        launch(ctx, point_triangle_pairs_kernel, dim3((n + 255u) / 256u), dim3(256), 0, static_cast<const float *>(a[0].d), n, static_cast<float *>(a[1].d));
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -190,24 +181,16 @@ __global__ __launch_bounds__(kPointBlock) void point_query_kernel(const PointQue
 
 int launch_point_query(vhr_context *ctx, const vhr_point_query *points, uint32_t count, bool any_within, uint32_t cull_mask, void *results) {
     if (count == 0) return VHR_OK;
-    PointQueryScratch *s = nullptr;                // this stream's counters
-    for (PointQueryScratch &e : ctx->pq_scratch) if (e.stream == ctx->stream) s = &e;
-    if (!s) {
-        PointQueryCounters *c = nullptr;
-        if (hipMalloc(reinterpret_cast<void **>(&c), sizeof(PointQueryCounters)) != hipSuccess) return ctx->fail(VHR_ERROR_DEVICE, "vhr_closest_point_query: device allocation failed");
-        ctx->pq_scratch.push_back(PointQueryScratch{ ctx->stream, c });
-        s = &ctx->pq_scratch.back();
-    }
-    ctx->pq_last_counters = s->counters;
+    const QueryScratch *const s = stream_scratch(ctx, ctx->pq_scratch, sizeof(PointQueryCounters), "vhr_closest_point_query");      // this stream's counters
+    if (!s) return VHR_ERROR_DEVICE;
     PointQueryArgs a;
     a.scene = ctx->device_scene();
     a.points = reinterpret_cast<const float4 *>(points);
     a.results = results;
-    a.counters = s->counters;
+    ctx->pq_last_counters = a.counters = static_cast<PointQueryCounters *>(s->counters);
     a.prim_masks = nullptr;
     a.count = count;
     a.cull_mask = cull_mask;
-    if (hipMemsetAsync(s->counters, 0, sizeof(PointQueryCounters), ctx->stream) != hipSuccess) return ctx->fail(VHR_ERROR_DEVICE, "vhr_closest_point_query: hipMemsetAsync failed");
     // the mask instantiations only where the cull mask acts on the masks the primitives carry: the defaults launch the plain ones
     const bool mask_acts = ctx->ray_mask_acts(cull_mask);
     if (mask_acts) {

@@ -24,22 +24,10 @@ __global__ __launch_bounds__(256) void ray_triangle_pairs_kernel(const float *pa
 }
 
 int launch_ray_triangle_pairs(vhr_context *ctx, const float *pairs, uint32_t n, uint32_t *hit, float *tuv) {
-    if (n == 0) return VHR_OK;
-    float *d_pairs = nullptr, *d_tuv = nullptr;
-    uint32_t *d_hit = nullptr;
-    const size_t pb = size_t(n) * 17u * sizeof(float), tb = size_t(n) * 3u * sizeof(float), hb = size_t(n) * sizeof(uint32_t);
-    int rc = VHR_OK;
-    if (hipMalloc(&d_pairs, pb) != hipSuccess || hipMalloc(&d_tuv, tb) != hipSuccess || hipMalloc(&d_hit, hb) != hipSuccess)
-        rc = ctx->fail(VHR_ERROR_DEVICE, "vhr_debug_ray_triangle: device allocation failed");
-    if (rc == VHR_OK && hipMemcpyAsync(d_pairs, pairs, pb, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = ctx->fail(VHR_ERROR_DEVICE, "vhr_debug_ray_triangle: upload failed");
-    if (rc == VHR_OK) {
-        launch(ctx, ray_triangle_pairs_kernel, dim3((n + 255u) / 256u), dim3(256), 0, static_cast<const float *>(d_pairs), n, d_hit, d_tuv);
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(hit, d_hit, hb, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-            hipMemcpyAsync(tuv, d_tuv, tb, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
-            rc = ctx->fail(VHR_ERROR_DEVICE, "vhr_debug_ray_triangle: launch or download failed");
-    }
-    (void)hipFree(d_pairs); (void)hipFree(d_tuv); (void)hipFree(d_hit);
-    return rc;
+    PairArray a[3] = { { pairs, nullptr, size_t(n) * 17u * sizeof(float) }, { nullptr, hit, size_t(n) * sizeof(uint32_t) }, { nullptr, tuv, size_t(n) * 3u * sizeof(float) } };
+    return run_pairs(ctx, "vhr_debug_ray_triangle", a, [&] {
+        launch(ctx, ray_triangle_pairs_kernel, dim3((n + 255u) / 256u), dim3(256), 0, static_cast<const float *>(a[0].d), n, static_cast<uint32_t *>(a[1].d), static_cast<float *>(a[2].d));
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -55,23 +43,10 @@ __global__ __launch_bounds__(256) void ray_facing_pairs_kernel(const float *pair
 }
 
 int launch_ray_facing_pairs(vhr_context *ctx, const float *pairs, const uint8_t *flips, uint32_t n, uint8_t *out) {
-    if (n == 0) return VHR_OK;
-    float *d_pairs = nullptr;
-    uint8_t *d_flips = nullptr, *d_out = nullptr;
-    const size_t pb = size_t(n) * 9u * sizeof(float);
-    int rc = VHR_OK;
-    if (hipMalloc(&d_pairs, pb) != hipSuccess || hipMalloc(&d_out, n) != hipSuccess || (flips && hipMalloc(&d_flips, n) != hipSuccess))
-        rc = ctx->fail(VHR_ERROR_DEVICE, "vhr_debug_ray_facing: device allocation failed");
-    if (rc == VHR_OK && (hipMemcpyAsync(d_pairs, pairs, pb, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-                         (flips && hipMemcpyAsync(d_flips, flips, n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)))
-        rc = ctx->fail(VHR_ERROR_DEVICE, "vhr_debug_ray_facing: upload failed");
-    if (rc == VHR_OK) {
-        launch(ctx, ray_facing_pairs_kernel, dim3((n + 255u) / 256u), dim3(256), 0, static_cast<const float *>(d_pairs), static_cast<const uint8_t *>(d_flips), n, d_out);
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(out, d_out, n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
-            rc = ctx->fail(VHR_ERROR_DEVICE, "vhr_debug_ray_facing: launch or download failed");
-    }
-    (void)hipFree(d_pairs); (void)hipFree(d_flips); (void)hipFree(d_out);
-    return rc;
+    PairArray a[3] = { { pairs, nullptr, size_t(n) * 9u * sizeof(float) }, { flips, nullptr, flips ? size_t(n) : 0u }, { nullptr, out, size_t(n) } };
+    return run_pairs(ctx, "vhr_debug_ray_facing", a, [&] {
+        launch(ctx, ray_facing_pairs_kernel, dim3((n + 255u) / 256u), dim3(256), 0, static_cast<const float *>(a[0].d), static_cast<const uint8_t *>(a[1].d), n, static_cast<uint8_t *>(a[2].d));
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -216,17 +191,8 @@ int launch_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, bool
     ctx->rq_mask_ran = 0;
     ctx->rq_face_ran = 0;
     if (count == 0) return VHR_OK;
-    RayQueryScratch *q = nullptr;                  // this stream's counters and list
-    for (RayQueryScratch &e : ctx->rq_scratch) if (e.stream == ctx->stream) q = &e;
-    if (!q) {
-        ctx->rq_scratch.push_back(RayQueryScratch{ ctx->stream, nullptr, nullptr, 0 });
-        q = &ctx->rq_scratch.back();
-        if (hipMalloc(reinterpret_cast<void **>(&q->counters), sizeof(RayQueryCounters)) != hipSuccess) {
-            q->counters = nullptr;
-            ctx->rq_scratch.pop_back();
-            return ctx->fail(VHR_ERROR_DEVICE, "vhr_ray_query: device allocation failed");
-        }
-    }
+    QueryScratch *const q = stream_scratch(ctx, ctx->rq_scratch, sizeof(RayQueryCounters), "vhr_ray_query");     // this stream's counters and list
+    if (!q) return VHR_ERROR_DEVICE;
     if (q->capacity < count) {
         (void)hipFree(q->list);                     // (synchronises: a query still in flight is done with it)
         q->list = nullptr;
@@ -235,17 +201,14 @@ int launch_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, bool
             return ctx->fail(VHR_ERROR_DEVICE, "vhr_ray_query: device allocation failed");
         q->capacity = count;
     }
-    ctx->rq_last_counters = q->counters;
     RayQueryArgs a;
     a.scene = ctx->device_scene();
     a.rays = reinterpret_cast<const float4 *>(rays);
     a.results = results;
     a.redo_list = q->list;
-    a.counters = q->counters;
+    ctx->rq_last_counters = a.counters = static_cast<RayQueryCounters *>(q->counters);
     a.count = count;
     a.any_hit = any_hit ? 1u : 0u;
-    if (hipMemsetAsync(q->counters, 0, sizeof(RayQueryCounters), ctx->stream) != hipSuccess)
-        return ctx->fail(VHR_ERROR_DEVICE, "vhr_ray_query: hipMemsetAsync failed");
     const QueueLaunch ql = queue_launch(ctx, kOptLdsStackLevels, kOptEarlyExit, 2u);
     const dim3 grid(uint32_t((uint64_t(count) + 2u * kQueryWaveRays - 1u) / (2u * kQueryWaveRays)));
     // the flag on a scene none of whose primitives can discard asks for nothing: the plain kernels

@@ -120,27 +120,19 @@ __global__ __launch_bounds__(256) void resolve_hits_kernel(const ResolveArgs a, 
 
 int launch_resolve_hits(vhr_context *ctx, const vhr_ray_hit *hits, uint32_t count, bool material, vhr_surface_point *out) {
     if (count == 0) return VHR_OK;
-    SurfaceScratch *s = nullptr;                   // this stream's counters
-    for (SurfaceScratch &e : ctx->sp_scratch) if (e.stream == ctx->stream) s = &e;
-    if (!s) {
-        SurfaceCounters *c = nullptr;
-        if (hipMalloc(reinterpret_cast<void **>(&c), sizeof(SurfaceCounters) * kSurfaceCounterSlots) != hipSuccess) return ctx->fail(VHR_ERROR_DEVICE, "vhr_resolve_hits: device allocation failed");
-        ctx->sp_scratch.push_back(SurfaceScratch{ ctx->stream, c });
-        s = &ctx->sp_scratch.back();
-    }
-    ctx->sp_last_counters = s->counters;
+    const QueryScratch *const s = stream_scratch(ctx, ctx->sp_scratch, sizeof(SurfaceCounters) * kSurfaceCounterSlots, "vhr_resolve_hits");        // this stream's counters
+    if (!s) return VHR_ERROR_DEVICE;
     ResolveArgs a;
     a.scene = ctx->device_scene();
     a.hits = reinterpret_cast<const uint32_t *>(hits);
     a.out = reinterpret_cast<float4 *>(out);
-    a.counters = s->counters;
+    ctx->sp_last_counters = a.counters = static_cast<SurfaceCounters *>(s->counters);
     a.flips = nullptr;
     a.count = count;
     if (ctx->primitive_count != 0) {
         if (const int rc = ensure_device_prim_flips(ctx)) return rc;
         a.flips = ctx->d_prim_flips;
     }
-    if (hipMemsetAsync(s->counters, 0, sizeof(SurfaceCounters) * kSurfaceCounterSlots, ctx->stream) != hipSuccess) return ctx->fail(VHR_ERROR_DEVICE, "vhr_resolve_hits: hipMemsetAsync failed");
     const dim3 grid(uint32_t((uint64_t(count) + 255u) / 256u));
     if (material) launch(ctx, resolve_hits_kernel<true>, grid, dim3(256), 0, a);
     else launch(ctx, resolve_hits_kernel<false>, grid, dim3(256), 0, a);

@@ -11,22 +11,58 @@
 using namespace vhr;
 
 void vhr::free_query_scratch(vhr_context *ctx) {
-    for (auto &q : ctx->rq_scratch) { hipFree(q.counters); hipFree(q.list); }
+    for (auto *all : { &ctx->rq_scratch, &ctx->pq_scratch, &ctx->sp_scratch })
+        for (QueryScratch &q : *all) { hipFree(q.counters); hipFree(q.list); }
     hipFree(ctx->d_rq_staging);
-    for (auto &q : ctx->pq_scratch) hipFree(q.counters);
-    for (auto &q : ctx->sp_scratch) hipFree(q.counters);
 }
 
-// the host-memory paths' staging buffer holds at least `staging` bytes (it grows to the largest query so far; its old contents are not kept)
-static int grow_staging(vhr_context *ctx, uint64_t staging) {
-    if (ctx->rq_staging_bytes >= staging) return VHR_OK;
-    (void)hipFree(ctx->d_rq_staging);
-    ctx->d_rq_staging = nullptr;
-    ctx->rq_staging_bytes = 0;
-    HIP_TRY(ctx, hipMalloc(&ctx->d_rq_staging, staging));
-    ctx->rq_staging_bytes = staging;
+QueryScratch *vhr::stream_scratch(vhr_context *ctx, std::vector<QueryScratch> &all, size_t counter_bytes, const char *who) {
+    QueryScratch *q = nullptr;
+    for (QueryScratch &e : all) if (e.stream == ctx->stream) q = &e;
+    if (!q) {
+        void *counters = nullptr;
+        if (hipMalloc(&counters, counter_bytes) != hipSuccess) { ctx->fail(VHR_ERROR_DEVICE, std::string(who) + ": device allocation failed"); return nullptr; }
+        all.push_back(QueryScratch{ ctx->stream, counters, nullptr, 0 });
+        q = &all.back();
+    }
+    if (hipMemsetAsync(q->counters, 0, counter_bytes, ctx->stream) != hipSuccess) { ctx->fail(VHR_ERROR_DEVICE, std::string(who) + ": hipMemsetAsync failed"); return nullptr; }
+    return q;
+}
+
+// A host-memory call, staged through the context's one buffer (it grows to the largest call so far; its old contents are not kept): the input,
+// the output at the next 256-byte boundary and -- the ray query's per-ray masks -- a second input (or null) at the boundary behind that.  Copies
+// in, has `enqueue(in, out, in2)` launch on the staged pointers, copies out and waits for ctx->stream, so no call finds another's data in the buffer.
+template <typename Enqueue>
+static int staged_call(vhr_context *ctx, const void *in, uint64_t in_bytes, const void *in2, uint64_t in2_bytes, void *out, uint64_t out_bytes, Enqueue &&enqueue) {
+    const uint64_t out_offset = (in_bytes + 255u) & ~uint64_t(255u), in2_offset = (out_offset + out_bytes + 255u) & ~uint64_t(255u);
+    const uint64_t staging = in2 ? in2_offset + in2_bytes : out_offset + out_bytes;
+    if (ctx->rq_staging_bytes < staging) {
+        (void)hipFree(ctx->d_rq_staging);
+        ctx->d_rq_staging = nullptr;
+        ctx->rq_staging_bytes = 0;
+        HIP_TRY(ctx, hipMalloc(&ctx->d_rq_staging, staging));
+        ctx->rq_staging_bytes = staging;
+    }
+    char *const d = static_cast<char *>(ctx->d_rq_staging);
+    HIP_TRY(ctx, hipMemcpyAsync(d, in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (in2) HIP_TRY(ctx, hipMemcpyAsync(d + in2_offset, in2, in2_bytes, hipMemcpyHostToDevice, ctx->stream));
+    VHR_TRY(enqueue(d, d + out_offset, in2 ? d + in2_offset : nullptr));
+    HIP_TRY(ctx, hipMemcpyAsync(out, d + out_offset, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return VHR_OK;
 }
+
+// the counters of an entry point's last call: its stream may be the caller's, so wait for the device, then read
+static int read_last_counters(vhr_context *ctx, void *out, const void *counters, size_t bytes) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    HIP_TRY(ctx, hipMemcpy(out, counters, bytes, hipMemcpyDeviceToHost));
+    return VHR_OK;
+}
+
+// The argument tests the entry points share.  Each keeps its own ORDER of them: which message wins when a call has two faults is behaviour.
+static bool misaligned(const void *p, uint32_t count, uintptr_t boundary) { return count > 0 && reinterpret_cast<uintptr_t>(p) % boundary; }
+static int invalid(vhr_context *ctx, const std::string &msg) { return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, msg); }
 
 extern "C" {
 
@@ -38,35 +74,26 @@ static int ray_query_impl(vhr_context *ctx, const char *who_, const bool masked,
     if (!ctx) return VHR_ERROR_INVALID_ARGUMENT;
     const std::string who(who_);
     // the arguments first (the same answer on every context), then the device
-    if (flags & ~uint32_t(VHR_RAY_QUERY_TERMINATE_ON_FIRST_HIT | VHR_RAY_QUERY_HOST_MEMORY | VHR_RAY_QUERY_ALPHA_TEST))
-        return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": unknown flag bits " + std::to_string(flags));
-    if (count > 0 && (!rays || !results)) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": rays and results must not be NULL when count > 0");
-    if (count > 0 && reinterpret_cast<uintptr_t>(rays) % 16u) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": rays must be 16-byte aligned");
-    if (count > 0 && reinterpret_cast<uintptr_t>(results) % 4u) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": results must be 4-byte aligned");
-    if (masked && cull_mask > 0xFFu) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": cull_mask " + std::to_string(cull_mask) + " exceeds 0xFF");
+    if (flags & ~uint32_t(VHR_RAY_QUERY_TERMINATE_ON_FIRST_HIT | VHR_RAY_QUERY_HOST_MEMORY | VHR_RAY_QUERY_ALPHA_TEST)) return invalid(ctx, who + ": unknown flag bits " + std::to_string(flags));
+    if (count > 0 && (!rays || !results)) return invalid(ctx, who + ": rays and results must not be NULL when count > 0");
+    if (misaligned(rays, count, 16u)) return invalid(ctx, who + ": rays must be 16-byte aligned");
+    if (misaligned(results, count, 4u)) return invalid(ctx, who + ": results must be 4-byte aligned");
+    if (masked && cull_mask > 0xFFu) return invalid(ctx, who + ": cull_mask " + std::to_string(cull_mask) + " exceeds 0xFF");
     if (face_cull > int64_t(VHR_FACE_CULL_FRONT))
-        return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": face_cull " + std::to_string(face_cull) + " is none of VHR_FACE_CULL_NONE / BACK / FRONT (the two do not combine)");
+        return invalid(ctx, who + ": face_cull " + std::to_string(face_cull) + " is none of VHR_FACE_CULL_NONE / BACK / FRONT (the two do not combine)");
     if (ctx->host_only) return ctx->fail(VHR_ERROR_NO_DEVICE, who + ": host-only context: no device work");
     VHR_TRY(ctx->refuse_if_stale(who_));
     if (count == 0) return VHR_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const bool any_hit = (flags & VHR_RAY_QUERY_TERMINATE_ON_FIRST_HIT) != 0, alpha_test = (flags & VHR_RAY_QUERY_ALPHA_TEST) != 0;
-    const uint64_t ray_bytes = uint64_t(count) * sizeof(vhr_ray), result_bytes = uint64_t(count) * (any_hit ? 1u : sizeof(vhr_ray_hit));
     ctx->rq_rays = count;
     if (!masked) { cull_mask = 0xFFu; ray_masks = nullptr; }
-    if (!(flags & VHR_RAY_QUERY_HOST_MEMORY)) return vhr::launch_ray_query(ctx, rays, count, any_hit, alpha_test, results, cull_mask, ray_masks, int(face_cull));
-    // host memory: staged through the context's own buffer (rays, then the results at the next 256-byte boundary)
-    // (vhr_ray_query_masked's per-ray masks, one byte each, behind the results at the next 256-byte boundary)
-    const uint64_t result_offset = (ray_bytes + 255u) & ~uint64_t(255u), mask_offset = (result_offset + result_bytes + 255u) & ~uint64_t(255u);
-    VHR_TRY(grow_staging(ctx, ray_masks ? mask_offset + count : result_offset + result_bytes));
-    char *const d = static_cast<char *>(ctx->d_rq_staging);
-    HIP_TRY(ctx, hipMemcpyAsync(d, rays, ray_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (ray_masks) HIP_TRY(ctx, hipMemcpyAsync(d + mask_offset, ray_masks, count, hipMemcpyHostToDevice, ctx->stream));
-    VHR_TRY(vhr::launch_ray_query(ctx, reinterpret_cast<const vhr_ray *>(d), count, any_hit, alpha_test, d + result_offset, cull_mask,
-                                  ray_masks ? reinterpret_cast<const uint8_t *>(d + mask_offset) : nullptr, int(face_cull)));
-    HIP_TRY(ctx, hipMemcpyAsync(results, d + result_offset, result_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return VHR_OK;
+    const auto enqueue = [&](const void *r, void *out, const void *masks) {
+        return vhr::launch_ray_query(ctx, static_cast<const vhr_ray *>(r), count, any_hit, alpha_test, out, cull_mask, static_cast<const uint8_t *>(masks), int(face_cull));
+    };
+    if (!(flags & VHR_RAY_QUERY_HOST_MEMORY)) return enqueue(rays, results, ray_masks);
+    // host memory: the rays, the results and (vhr_ray_query_masked, vhr_ray_query_faces) the per-ray masks, one byte each
+    return staged_call(ctx, rays, uint64_t(count) * sizeof(vhr_ray), ray_masks, count, results, uint64_t(count) * (any_hit ? 1u : sizeof(vhr_ray_hit)), enqueue);
 }
 
 int vhr_ray_query(vhr_context *ctx, const vhr_ray *rays, uint32_t count, uint32_t flags, void *results) {
@@ -85,10 +112,7 @@ int vhr_ray_query_faces(vhr_context *ctx, const vhr_ray *rays, uint32_t count, u
 // a device context runs the device's copy of ray_hit_kind, a host-only context the host's: one source (ray_facing.hpp)
 int vhr_debug_ray_facing(vhr_context *ctx, const float *pairs, const uint8_t *flips, uint32_t count, uint8_t *out) {
     if (!ctx || (count && (!pairs || !out))) return ctx ? ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_debug_ray_facing: null argument") : VHR_ERROR_INVALID_ARGUMENT;
-    if (!ctx->host_only) {
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        return launch_ray_facing_pairs(ctx, pairs, flips, count, out);
-    }
+    if (!ctx->host_only) return launch_ray_facing_pairs(ctx, pairs, flips, count, out);
     for (uint32_t i = 0; i < count; ++i) {
         const float *s = pairs + size_t(i) * 9u;
         out[i] = uint8_t(ray_hit_kind(s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], s[8], flips != nullptr && flips[i] != 0));
@@ -100,10 +124,8 @@ int vhr_get_ray_query_statistics(vhr_context *ctx, uint64_t out[4]) {
     if (!ctx || !out) return VHR_ERROR_INVALID_ARGUMENT;
     out[0] = out[1] = out[2] = out[3] = 0;
     if (ctx->host_only || ctx->rq_rays == 0 || !ctx->rq_last_counters) return VHR_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipDeviceSynchronize());         // the stream of the last query may be the caller's: wait for the device, then read
     RayQueryCounters c;
-    HIP_TRY(ctx, hipMemcpy(&c, ctx->rq_last_counters, sizeof(c), hipMemcpyDeviceToHost));
+    VHR_TRY(read_last_counters(ctx, &c, ctx->rq_last_counters, sizeof(c)));
     out[0] = ctx->rq_rays; out[1] = c.hits; out[2] = c.redo_count; out[3] = c.overflows;
     return VHR_OK;
 }
@@ -112,39 +134,28 @@ int vhr_get_ray_query_statistics(vhr_context *ctx, uint64_t out[4]) {
 int vhr_closest_point_query(vhr_context *ctx, const vhr_point_query *points, uint32_t count, uint32_t flags, uint32_t cull_mask, void *results) {
     if (!ctx) return VHR_ERROR_INVALID_ARGUMENT;
     const std::string who("vhr_closest_point_query");
-    if (count > 0 && (!points || !results)) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": points and results must not be NULL when count > 0");
-    if (flags & ~uint32_t(VHR_POINT_QUERY_ANY_WITHIN | VHR_POINT_QUERY_HOST_MEMORY))
-        return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": unknown flag bits " + std::to_string(flags));
-    if (count > 0 && reinterpret_cast<uintptr_t>(points) % 16u) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": points must be 16-byte aligned");
-    if (count > 0 && reinterpret_cast<uintptr_t>(results) % 4u) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": results must be 4-byte aligned");
-    if (cull_mask > 0xFFu) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": cull_mask " + std::to_string(cull_mask) + " exceeds 0xFF");
+    if (count > 0 && (!points || !results)) return invalid(ctx, who + ": points and results must not be NULL when count > 0");
+    if (flags & ~uint32_t(VHR_POINT_QUERY_ANY_WITHIN | VHR_POINT_QUERY_HOST_MEMORY)) return invalid(ctx, who + ": unknown flag bits " + std::to_string(flags));
+    if (misaligned(points, count, 16u)) return invalid(ctx, who + ": points must be 16-byte aligned");
+    if (misaligned(results, count, 4u)) return invalid(ctx, who + ": results must be 4-byte aligned");
+    if (cull_mask > 0xFFu) return invalid(ctx, who + ": cull_mask " + std::to_string(cull_mask) + " exceeds 0xFF");
     if (ctx->host_only) return ctx->fail(VHR_ERROR_NO_DEVICE, who + ": host-only context: no device work");
     VHR_TRY(ctx->refuse_if_stale("vhr_closest_point_query"));
     if (count == 0) return VHR_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const bool any_within = (flags & VHR_POINT_QUERY_ANY_WITHIN) != 0;
     ctx->pq_queries = count;
-    if (!(flags & VHR_POINT_QUERY_HOST_MEMORY)) return vhr::launch_point_query(ctx, points, count, any_within, cull_mask, results);
-    // host memory: the points, then the results at the next 256-byte boundary, in the ray query's staging buffer
-    const uint64_t point_bytes = uint64_t(count) * sizeof(vhr_point_query), result_bytes = uint64_t(count) * (any_within ? 1u : sizeof(vhr_ray_hit));
-    const uint64_t result_offset = (point_bytes + 255u) & ~uint64_t(255u);
-    VHR_TRY(grow_staging(ctx, result_offset + result_bytes));
-    char *const d = static_cast<char *>(ctx->d_rq_staging);
-    HIP_TRY(ctx, hipMemcpyAsync(d, points, point_bytes, hipMemcpyHostToDevice, ctx->stream));
-    VHR_TRY(vhr::launch_point_query(ctx, reinterpret_cast<const vhr_point_query *>(d), count, any_within, cull_mask, d + result_offset));
-    HIP_TRY(ctx, hipMemcpyAsync(results, d + result_offset, result_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return VHR_OK;
+    const auto enqueue = [&](const void *p, void *out, const void *) { return vhr::launch_point_query(ctx, static_cast<const vhr_point_query *>(p), count, any_within, cull_mask, out); };
+    if (!(flags & VHR_POINT_QUERY_HOST_MEMORY)) return enqueue(points, results, nullptr);
+    return staged_call(ctx, points, uint64_t(count) * sizeof(vhr_point_query), nullptr, 0, results, uint64_t(count) * (any_within ? 1u : sizeof(vhr_ray_hit)), enqueue);
 }
 
 int vhr_get_point_query_statistics(vhr_context *ctx, uint64_t out[4]) {
     if (!ctx || !out) return VHR_ERROR_INVALID_ARGUMENT;
     out[0] = out[1] = out[2] = out[3] = 0;
     if (ctx->host_only || ctx->pq_queries == 0 || !ctx->pq_last_counters) return VHR_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipDeviceSynchronize());         // the stream of the last query may be the caller's: wait for the device, then read
     PointQueryCounters c;
-    HIP_TRY(ctx, hipMemcpy(&c, ctx->pq_last_counters, sizeof(c), hipMemcpyDeviceToHost));
+    VHR_TRY(read_last_counters(ctx, &c, ctx->pq_last_counters, sizeof(c)));
     out[0] = ctx->pq_queries; out[1] = c.found; out[2] = c.evaluations; out[3] = c.overflows;
     return VHR_OK;
 }
@@ -152,10 +163,7 @@ int vhr_get_point_query_statistics(vhr_context *ctx, uint64_t out[4]) {
 // a device context runs the device's copy of point_triangle, a host-only context the host's: one source (closest_point.hpp)
 int vhr_debug_point_triangle(vhr_context *ctx, const float *pairs, uint32_t count, float *out) {
     if (!ctx || (count && (!pairs || !out))) return ctx ? ctx->fail(VHR_ERROR_INVALID_ARGUMENT, "vhr_debug_point_triangle: null argument") : VHR_ERROR_INVALID_ARGUMENT;
-    if (!ctx->host_only) {
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        return launch_point_triangle_pairs(ctx, pairs, count, out);
-    }
+    if (!ctx->host_only) return launch_point_triangle_pairs(ctx, pairs, count, out);
     for (uint32_t i = 0; i < count; ++i) {
         const float *s = pairs + size_t(i) * 12u;
         const PointTriangle r = point_triangle(s, s + 3, s + 6, s + 9);
@@ -192,10 +200,10 @@ static void resolve_hits_host(vhr_context *ctx, const vhr_ray_hit *hits, uint32_
 int vhr_resolve_hits(vhr_context *ctx, const vhr_ray_hit *hits, uint32_t count, uint32_t flags, vhr_surface_point *out) {
     if (!ctx) return VHR_ERROR_INVALID_ARGUMENT;
     const std::string who("vhr_resolve_hits");
-    if (count > 0 && (!hits || !out)) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": hits and out must not be NULL when count > 0");
-    if (flags & ~uint32_t(VHR_SURFACE_MATERIAL | VHR_SURFACE_HOST_MEMORY)) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": unknown flag bits " + std::to_string(flags));
-    if (count > 0 && reinterpret_cast<uintptr_t>(hits) % 4u) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": hits must be 4-byte aligned");
-    if (count > 0 && reinterpret_cast<uintptr_t>(out) % 16u) return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, who + ": out must be 16-byte aligned");
+    if (count > 0 && (!hits || !out)) return invalid(ctx, who + ": hits and out must not be NULL when count > 0");
+    if (flags & ~uint32_t(VHR_SURFACE_MATERIAL | VHR_SURFACE_HOST_MEMORY)) return invalid(ctx, who + ": unknown flag bits " + std::to_string(flags));
+    if (misaligned(hits, count, 4u)) return invalid(ctx, who + ": hits must be 4-byte aligned");
+    if (misaligned(out, count, 16u)) return invalid(ctx, who + ": out must be 16-byte aligned");
     if (count == 0) return VHR_OK;
     const bool material = (flags & VHR_SURFACE_MATERIAL) != 0, host_memory = (flags & VHR_SURFACE_HOST_MEMORY) != 0;
     if (ctx->host_only && (material || !host_memory))
@@ -205,17 +213,9 @@ int vhr_resolve_hits(vhr_context *ctx, const vhr_ray_hit *hits, uint32_t count, 
     ctx->sp_material = material;
     if (ctx->host_only) { resolve_hits_host(ctx, hits, count, out); return VHR_OK; }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!host_memory) return vhr::launch_resolve_hits(ctx, hits, count, material, out);
-    // host memory: the hits, then the records at the next 256-byte boundary, in the ray query's staging buffer
-    const uint64_t hit_bytes = uint64_t(count) * sizeof(vhr_ray_hit), out_bytes = uint64_t(count) * sizeof(vhr_surface_point);
-    const uint64_t out_offset = (hit_bytes + 255u) & ~uint64_t(255u);
-    VHR_TRY(grow_staging(ctx, out_offset + out_bytes));
-    char *const d = static_cast<char *>(ctx->d_rq_staging);
-    HIP_TRY(ctx, hipMemcpyAsync(d, hits, hit_bytes, hipMemcpyHostToDevice, ctx->stream));
-    VHR_TRY(vhr::launch_resolve_hits(ctx, reinterpret_cast<const vhr_ray_hit *>(d), count, material, reinterpret_cast<vhr_surface_point *>(d + out_offset)));
-    HIP_TRY(ctx, hipMemcpyAsync(out, d + out_offset, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return VHR_OK;
+    const auto enqueue = [&](const void *h, void *o, const void *) { return vhr::launch_resolve_hits(ctx, static_cast<const vhr_ray_hit *>(h), count, material, static_cast<vhr_surface_point *>(o)); };
+    if (!host_memory) return enqueue(hits, out, nullptr);
+    return staged_call(ctx, hits, uint64_t(count) * sizeof(vhr_ray_hit), nullptr, 0, out, uint64_t(count) * sizeof(vhr_surface_point), enqueue);
 }
 
 int vhr_get_surface_statistics(vhr_context *ctx, uint64_t out[4]) {
@@ -225,10 +225,8 @@ int vhr_get_surface_statistics(vhr_context *ctx, uint64_t out[4]) {
     SurfaceCounters c = ctx->sp_host_counters;
     if (!ctx->host_only) {
         if (!ctx->sp_last_counters) return VHR_OK;
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        HIP_TRY(ctx, hipDeviceSynchronize());     // the stream of the last call may be the caller's: wait for the device, then read
         SurfaceCounters slots[kSurfaceCounterSlots];
-        HIP_TRY(ctx, hipMemcpy(slots, ctx->sp_last_counters, sizeof(slots), hipMemcpyDeviceToHost));
+        VHR_TRY(read_last_counters(ctx, slots, ctx->sp_last_counters, sizeof(slots)));
         c = SurfaceCounters{};
         for (const SurfaceCounters &slot : slots) { c.valid += slot.valid; c.discarded += slot.discarded; }
     }

@@ -374,21 +374,19 @@ struct SvgfCmd {
 // vhr_ray_query's counters (csrc/kernels_ray_query.hip): rays the binary64 launch walked again (= entries of the redo list), waves whose stack
 // overflowed, rays with a hit.  A buffer of the query's own: no frame reads or writes it.
 struct RayQueryCounters { uint32_t redo_count, overflows; unsigned long long hits; };
-// ... and the list of rays decision (vi) hands to the binary64 launch; one set per stream queries were enqueued on, so that queries in flight
-// on different streams (between frames on the caller's, inside a pass on the frame's front stream) share nothing
-struct RayQueryScratch { hipStream_t stream; RayQueryCounters *counters; uint32_t *list; uint64_t capacity; };
+// The scratch of a query entry point: its counters and, for the ray query alone, the list of rays decision (vi) hands to the binary64 launch
+// (`capacity` entries; null elsewhere).  One set per stream calls were enqueued on, so that calls in flight on different streams (between frames
+// on the caller's, inside a pass on the frame's front stream) share nothing
+struct QueryScratch { hipStream_t stream; void *counters; uint32_t *list; uint64_t capacity; };
 // vhr_closest_point_query's counters (csrc/kernels_point_query.hip): queries that found something, point_triangle evaluations, waves whose stack
-// overflowed; one set per stream queries were enqueued on, like the ray query's
+// overflowed
 struct PointQueryCounters { unsigned long long found, evaluations; uint32_t overflows, pad; };
-struct PointQueryScratch { hipStream_t stream; PointQueryCounters *counters; };
-// vhr_resolve_hits' counters (csrc/kernels_surface.hip): records with VHR_SURFACE_VALID, records with VHR_SURFACE_DISCARDED; one set per stream
-// calls were enqueued on, like the queries'.  A set is kSurfaceCounterSlots slots of one 64-byte line each, a wave adds to the slot of its block's
-// index and vhr_get_surface_statistics sums them: a resolve is one wave per 64 hits and little work per hit, and that many adds to ONE address
+// vhr_resolve_hits' counters (csrc/kernels_surface.hip): records with VHR_SURFACE_VALID, records with VHR_SURFACE_DISCARDED.  A set is
+// kSurfaceCounterSlots slots of one 64-byte line each, a wave adds to the slot of its block's index and vhr_get_surface_statistics sums them: a resolve is one wave per 64 hits and little work per hit, and that many adds to ONE address
 // queue up behind each other (measured: 16 384 waves' adds to one counter took 0.2 ms of a 2^20-hit call, whatever else the kernel did)
 constexpr uint32_t kSurfaceCounterSlots = 128;
 struct SurfaceCounters { unsigned long long valid, discarded, pad[6]; };
 static_assert(sizeof(SurfaceCounters) == 64, "SurfaceCounters: one line per slot");
-struct SurfaceScratch { hipStream_t stream; SurfaceCounters *counters; };
 
 struct RayStats {
     unsigned long long unique_rays, covered_pixels, stack_overflows, node_visits, leaf_visits, triangle_tests, wave_iterations, second_bounce_rays;
@@ -652,19 +650,19 @@ struct vhr_context {
     uint64_t raytraced_pixels = 0;      // != 0: the last TraceRays was the raytraced render path's (primary rays launched)
     // vhr_ray_query: its own scratch, which no frame touches -- counters and redo list per stream, and (VHR_RAY_QUERY_HOST_MEMORY, which waits
     // for its stream before it returns) the device copies of the caller's rays and results; the buffers grow to the largest query so far
-    std::vector<vhr::RayQueryScratch> rq_scratch;
+    std::vector<vhr::QueryScratch> rq_scratch;
     const vhr::RayQueryCounters *rq_last_counters = nullptr;   // the last query's (vhr_get_ray_query_statistics)
     void *d_rq_staging = nullptr;
     uint64_t rq_staging_bytes = 0;
     uint64_t rq_rays = 0;               // rays of the last query (0: none yet)
     // vhr_closest_point_query: counters per stream; VHR_POINT_QUERY_HOST_MEMORY stages through d_rq_staging (both host-memory paths wait for
     // their stream before they return, so neither finds the other's data in it)
-    std::vector<vhr::PointQueryScratch> pq_scratch;
+    std::vector<vhr::QueryScratch> pq_scratch;
     const vhr::PointQueryCounters *pq_last_counters = nullptr;  // the last query's (vhr_get_point_query_statistics)
     uint64_t pq_queries = 0;            // queries of the last call (0: none yet)
     // vhr_resolve_hits: counters per stream; VHR_SURFACE_HOST_MEMORY stages through d_rq_staging as the queries' host-memory paths do.  A host-only
     // context counts on the host (sp_host_counters)
-    std::vector<vhr::SurfaceScratch> sp_scratch;
+    std::vector<vhr::QueryScratch> sp_scratch;
     const vhr::SurfaceCounters *sp_last_counters = nullptr;     // the last call's (vhr_get_surface_statistics)
     vhr::SurfaceCounters sp_host_counters = {};
     uint64_t sp_hits = 0;               // hits of the last call (0: none yet)
@@ -746,6 +744,9 @@ void free_tree(vhr_context *ctx);                // the five tree arrays (freed 
 int reset_motion(vhr_context *ctx);              // previous = current for the tree the context holds (none: nothing to keep); the caller has waited for the streams
 // csrc/queries.cpp: the queries' per-stream scratch and their staging buffer, for vhr_destroy
 void free_query_scratch(vhr_context *ctx);
+// ... and this stream's entry of one of the three vectors, for a launch of entry point `who`: made on first use -- allocated before it is
+// inserted, so a failed allocation leaves no half-made entry -- and its `counter_bytes` of counters zeroed on the stream.  nullptr: the context's error says why
+QueryScratch *stream_scratch(vhr_context *ctx, std::vector<QueryScratch> &all, size_t counter_bytes, const char *who);
 
 int flush_deferred_raygen(vhr_context *ctx, const TemporalArgs *fuse);      // csrc/kernels_trace.hip; no-op without a held-back launch
 bool deferred_raygen_matches(const vhr_context *ctx, const TemporalArgs &t);
@@ -759,6 +760,31 @@ inline void launch(vhr_context *ctx, K kernel, dim3 grid, dim3 block, size_t lds
     const Stamps st = ctx->take_stamps();             // every kernel's last parameter
     if (start || stop) hipExtLaunchKernelGGL(kernel, grid, block, lds, ctx->stream, start, stop, 0, args..., st);
     else hipLaunchKernelGGL(kernel, grid, block, lds, ctx->stream, args..., st);
+}
+
+// The pair entry points on a device context (vhr_debug_ray_triangle, vhr_debug_ray_facing, vhr_debug_point_triangle): the device copy `d` of a
+// host array that is uploaded from `src` or downloaded into `dst` (`bytes` 0: an optional input that is absent, `d` stays null; the first array is
+// never optional).  run_pairs selects the context's device, allocates, uploads, lets `enqueue` launch on ctx->stream, downloads, waits, and
+// frees on every path.
+struct PairArray { const void *src; void *dst; size_t bytes; void *d = nullptr; };
+template <size_t N, typename Enqueue>
+inline int run_pairs(vhr_context *ctx, const char *who_, PairArray (&arrays)[N], Enqueue &&enqueue) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (arrays[0].bytes == 0) return VHR_OK;
+    const std::string who(who_);
+    int rc = VHR_OK;
+    for (PairArray &a : arrays)
+        if (rc == VHR_OK && a.bytes && hipMalloc(&a.d, a.bytes) != hipSuccess) rc = ctx->fail(VHR_ERROR_DEVICE, who + ": device allocation failed");
+    for (PairArray &a : arrays)
+        if (rc == VHR_OK && a.src && a.d && hipMemcpyAsync(a.d, a.src, a.bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = ctx->fail(VHR_ERROR_DEVICE, who + ": upload failed");
+    if (rc == VHR_OK) {
+        enqueue();
+        bool ok = hipGetLastError() == hipSuccess;
+        for (PairArray &a : arrays) ok = ok && (!a.dst || hipMemcpyAsync(a.dst, a.d, a.bytes, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
+        if (!ok || hipStreamSynchronize(ctx->stream) != hipSuccess) rc = ctx->fail(VHR_ERROR_DEVICE, who + ": launch or download failed");
+    }
+    for (PairArray &a : arrays) (void)hipFree(a.d);
+    return rc;
 }
 
 uint32_t format_stride(int32_t format);   // VkUtils::FormatStride (vulkan_utils.h:128-148)

@@ -295,6 +295,9 @@ def load():
     L.vhr_tile_plan_exchanges.argtypes = [C.POINTER(TilePlanC), u32, u32, C.POINTER(RectExchangeC), u32]
     L.vhr_tile_plan_replan.argtypes = [C.POINTER(TilePlanC), C.POINTER(TilePlanC), C.POINTER(RectExchangeC), u32]
     L.vhr_comm_create_tiled.argtypes = [vp, C.POINTER(TilePlanC), C.c_char_p, C.POINTER(vp)]
+    L.vhr_get_tile_cost_map.argtypes = [vp, vp, u32, u32]
+    L.vhr_comm_use_library.argtypes = [C.c_char_p]
+    L.vhr_comm_library.restype = C.c_char_p
     L.vhr_comm_get_unique_id.argtypes = [C.c_char_p]
     L.vhr_comm_create.argtypes = [vp, C.POINTER(StripPlanC), C.c_char_p, C.POINTER(vp)]
     L.vhr_comm_destroy.argtypes = [vp]
@@ -424,6 +427,12 @@ class Context:
             raise VhrError(f"{what}: {self.L.vhr_last_error(self.handle).decode()}")
         return rc
 
+    def _read(self, name, n, what=None, ctype=C.c_uint64):
+        """The `n` uint64 (or `ctype`) values vhr_get_<name> fills in, as a list; `what` labels a failure (default: name)."""
+        out = (ctype * n)()
+        self.check(getattr(self.L, "vhr_get_" + name)(self.handle, out), what or name)
+        return list(out)
+
     def synchronize(self):
         self.check(self.L.vhr_synchronize(self.handle), "synchronize")
 
@@ -480,9 +489,7 @@ class Context:
     def ray_mask_statistics(self):
         """[primitives whose mask is not 0xFF, launches of the last trace_rays that ran a mask instantiation (0..2), 1 if the last ray
         query ran one, 0]."""
-        out = (C.c_uint64 * 4)()
-        self.check(self.L.vhr_get_ray_mask_statistics(self.handle, out), "ray_mask_statistics")
-        return [int(x) for x in out]
+        return self._read("ray_mask_statistics", 4)
 
     # ---- ray face culling: the primitives' facing flips (the query itself: ray_query(face_cull=...)) ----
     def primitive_facing_flips(self, first_primitive=0, count=None):
@@ -495,9 +502,7 @@ class Context:
 
     def face_cull_statistics(self):
         """[primitives with flip = 1, 1 if the last ray query of any kind launched the face instantiation, 0, 0]."""
-        out = (C.c_uint64 * 4)()
-        self.check(self.L.vhr_get_face_cull_statistics(self.handle, out), "face_cull_statistics")
-        return [int(x) for x in out]
+        return self._read("face_cull_statistics", 4)
 
     def debug_ray_facing(self, pairs, flips=None):
         """The facing function on explicit pairs: pairs = (n, 9) float32 (d, e1, e2), flips = uint8[n] or None (all 0) -> uint8[n],
@@ -530,27 +535,20 @@ class Context:
     def rebuild_statistics(self):
         """vhr_get_rebuild_statistics: (successful rebuilds since update_geometry, 1 if the last fetched the scene for the host builder,
         non-finite coordinates the last call met, records whose previous differs from current after it, 0, 0, 0, 0)."""
-        out = (C.c_uint64 * 8)()
-        self.check(self.L.vhr_get_rebuild_statistics(self.handle, out), "rebuild_statistics")
-        return tuple(int(v) for v in out)
+        return tuple(self._read("rebuild_statistics", 8))
 
     def partial_refit_statistics(self):
-        out = (C.c_uint64 * 8)()
-        self.check(self.L.vhr_get_partial_refit_statistics(self.handle, out), "partial_refit_statistics")
-        return dict(partial_refits=int(out[0]), dirty_records=int(out[1]), dirty_nodes=int(out[2]), forms_rewritten=int(out[3]), ran_as=int(out[4]),
-                    centre_moved=int(out[5]), vertex_ranges=int(out[6]), primitive_ranges=int(out[7]))
+        return dict(zip(("partial_refits", "dirty_records", "dirty_nodes", "forms_rewritten", "ran_as", "centre_moved", "vertex_ranges", "primitive_ranges"),
+                        self._read("partial_refit_statistics", 8)))
 
     def object_motion_statistics(self):
         """"object_motion_vectors": whether the previous records exist, how many differ from the current ones after the last successful refit,
         and the G-buffer launches that ran the motion instantiation since the context was created."""
-        out = (C.c_uint64 * 4)()
-        self.check(self.L.vhr_get_object_motion_statistics(self.handle, out), "object_motion_statistics")
-        return dict(active=int(out[0]), differing_records=int(out[1]), motion_launches=int(out[2]))
+        return dict(zip(("active", "differing_records", "motion_launches"), self._read("object_motion_statistics", 4)))
 
     def triangle_records(self, previous=False):
         """vhr_debug_triangle_records: (n, 9) float32, (v0, e1, e2) of every triangle in flat (primitive-major) order; previous=True: the
         records before the last refit ("object_motion_vectors" 1)."""
-        import numpy as np
         n = C.c_uint32(0)
         rc = self.L.vhr_debug_triangle_records(self.handle, 1 if previous else 0, None, 0, C.byref(n))  # the count: "too small" unless the scene is empty
         if rc != -1 or n.value == 0:                      # a refusal (no geometry, a presplit tree, no previous records) surfaces here
@@ -560,22 +558,16 @@ class Context:
         return out
 
     def refit_statistics(self):
-        out = (C.c_uint64 * 8)()
-        self.check(self.L.vhr_get_refit_statistics(self.handle, out), "refit_statistics")
-        return dict(refits=int(out[0]), records=int(out[1]), nodes=int(out[2]), records_outside=int(out[3]), children_outside=int(out[4]),
-                    non_finite=int(out[5]), half_nodes=int(out[6]), upward_launches=int(out[7]))
+        return dict(zip(("refits", "records", "nodes", "records_outside", "children_outside", "non_finite", "half_nodes", "upward_launches"),
+                        self._read("refit_statistics", 8)))
 
     def refit_times_ms(self):
         """(host wall time, leaf pass, upward pass, forms + checks) of the last refit; the device times need set_kernel_timing(False, refit=True)."""
-        out = (C.c_double * 4)()
-        self.check(self.L.vhr_get_refit_times(self.handle, out), "refit_times")
-        return tuple(float(v) for v in out)
+        return tuple(self._read("refit_times", 4, ctype=C.c_double))
 
     def bvh_sah_cost(self):
         """(as built, now): the tree's surface-area cost, the number to watch when deciding to rebuild."""
-        out = (C.c_double * 2)()
-        self.check(self.L.vhr_get_bvh_sah_cost(self.handle, out), "bvh_sah_cost")
-        return float(out[0]), float(out[1])
+        return tuple(self._read("bvh_sah_cost", 2, ctype=C.c_double))
 
     def upload_scene(self, scene):
         for t in scene.textures:
@@ -783,32 +775,25 @@ class Context:
         self.check(self.L.vhr_set_ray_statistics(self.handle, int(enable)), "set_ray_statistics")
 
     def ray_statistics(self):
-        out = (C.c_uint64 * 4)()
-        self.check(self.L.vhr_get_ray_statistics(self.handle, out), "ray_statistics")
-        return dict(unique_rays=out[0], reference_issued_rays=out[1], covered_pixels=out[2], stack_overflows=out[3])
+        return dict(zip(("unique_rays", "reference_issued_rays", "covered_pixels", "stack_overflows"), self._read("ray_statistics", 4)))
 
     def calibration_stream_read(self, storage_image, bytes_per_lane):
         self.check(self.L.vhr_calibration_stream_read(self.handle, storage_image, bytes_per_lane), "calibration_stream_read")
 
     def traversal_statistics(self):
-        out = (C.c_uint64 * 4)()
-        self.check(self.L.vhr_get_traversal_statistics(self.handle, out), "traversal_statistics")
-        d = dict(node_visits=out[0], leaf_visits=out[1], triangle_tests=out[2], wave_iterations=out[3])
-        d["active_lane_utilisation"] = (out[0] + out[2]) / (64.0 * out[3]) if out[3] else 0.0
+        d = dict(zip(("node_visits", "leaf_visits", "triangle_tests", "wave_iterations"), self._read("traversal_statistics", 4)))
+        d["active_lane_utilisation"] = (d["node_visits"] + d["triangle_tests"]) / (64.0 * d["wave_iterations"]) if d["wave_iterations"] else 0.0
         return d
 
     def reflection_statistics(self):
         """The mirror-ray launch's counters (reflection_queue_kernel with statistics enabled)."""
-        out = (C.c_uint64 * 10)()
-        self.check(self.L.vhr_get_reflection_statistics(self.handle, out), "reflection_statistics")
-        d = dict(rays=out[0], second_bounce_rays=out[1], node_visits=out[2], leaf_visits=out[3], triangle_tests=out[4], wave_iterations=out[5],
-                 refills=out[6], waves=out[7], cycles_total=out[8], cycles_walk=out[9])
-        d["active_lane_utilisation"] = (out[2] + out[4]) / (64.0 * out[5]) if out[5] else 0.0
+        d = dict(zip(("rays", "second_bounce_rays", "node_visits", "leaf_visits", "triangle_tests", "wave_iterations", "refills", "waves", "cycles_total", "cycles_walk"),
+                     self._read("reflection_statistics", 10)))
+        d["active_lane_utilisation"] = (d["node_visits"] + d["triangle_tests"]) / (64.0 * d["wave_iterations"]) if d["wave_iterations"] else 0.0
         return d
 
     def ray_triangle(self, pairs):
         """Decision (vi) as the device computes it, on explicit pairs: pairs = (n, 17) float32 (o, d, v0, e1, e2, tmin, tmax) -> (hit (n,) bool, tuv (n, 3) float32)."""
-        import numpy as np
         pairs = np.ascontiguousarray(pairs, dtype=np.float32).reshape(-1, 17)
         hit = np.zeros(len(pairs), np.uint32)
         tuv = np.zeros((len(pairs), 3), np.float32)
@@ -818,20 +803,15 @@ class Context:
     def binary64_statistics(self):
         """Decision (vi)'s binary64 half in the queue kernels of the last vhr_trace_rays (statistics enabled): pixels the any-hit launch and the mirror
         ray's launch computed again by the per-pixel code."""
-        out = (C.c_uint64 * 4)()
-        self.check(self.L.vhr_get_binary64_statistics(self.handle, out), "binary64_statistics")
-        return dict(pixels_again=int(out[0]), mirror_pixels_again=int(out[1]))
+        return dict(zip(("pixels_again", "mirror_pixels_again"), self._read("binary64_statistics", 4)))
 
     def alpha_launches(self):
         """Launches of the last vhr_trace_rays that ran an "alpha_test_rays" instantiation (0 with the switch off, and on a scene none of
         whose primitives can discard): 1 = the shadow / AO launch, 2 = that and the mirror ray's."""
-        out = (C.c_uint64 * 4)()
-        self.check(self.L.vhr_get_binary64_statistics(self.handle, out), "binary64_statistics")
-        return int(out[2])
+        return self._read("binary64_statistics", 4)[2]
 
     def wave_lifetimes(self, capacity=1 << 20):
         """Lifetimes (shader clock ticks) of the last ray-tracing launch's waves (what raygen_cost_order sorts by)."""
-        import numpy as np
         out = np.zeros(capacity, dtype=np.uint32)
         n = C.c_uint32(0)
         self.check(self.L.vhr_debug_wave_lifetimes(self.handle, out.ctypes.data_as(C.POINTER(C.c_uint32)), capacity, C.byref(n)), "wave_lifetimes")
@@ -839,71 +819,48 @@ class Context:
 
     def tile_cost_map(self):
         """vhr_get_tile_cost_map: the last frame's wave lifetimes (any-hit + mirror-ray launch) per 8 x 8-pixel cell, (ceil(H / 8), ceil(W / 8)) uint32."""
-        import numpy as np
         rows, cols = (self.height + 7) // 8, (self.width + 7) // 8
         out = np.zeros((rows, cols), np.uint32)
-        self.L.vhr_get_tile_cost_map.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         self.check(self.L.vhr_get_tile_cost_map(self.handle, out.ctypes.data_as(C.c_void_p), cols, rows), "tile_cost_map")
         return out
 
     def traversal_cycles(self):
-        out = (C.c_uint64 * 8)()
-        self.check(self.L.vhr_get_traversal_cycles(self.handle, out), "traversal_cycles")
-        return dict(total=out[0], setup=out[1], refill=out[2], nodes=out[3], leaves=out[4], refills=out[5], waves=out[6], drain_iterations=out[7])
+        return dict(zip(("total", "setup", "refill", "nodes", "leaves", "refills", "waves", "drain_iterations"), self._read("traversal_cycles", 8)))
 
     def bvh_form_checks(self):
         """Host-side self-check of the last build: (boxes checked, CH violations, 48-byte-node violations, compact-node violations)."""
-        out = (C.c_uint64 * 4)()
-        self.check(self.L.vhr_get_bvh_form_checks(self.handle, out), "bvh_form_checks")
-        return tuple(int(v) for v in out)
+        return tuple(self._read("bvh_form_checks", 4))
 
     def bvh_frame(self):
         """Option "bvh_frame": the frame the current tree's boxes are in, a 3 x 3 array (row i = axis i in world coordinates; the identity = the world axes)."""
-        import numpy as np
-        out = (C.c_float * 9)()
-        self.check(self.L.vhr_get_bvh_frame(self.handle, out), "get_bvh_frame")
-        return np.array(list(out), np.float32).reshape(3, 3)
+        return np.array(self._read("bvh_frame", 9, "get_bvh_frame", C.c_float), np.float32).reshape(3, 3)
 
     def bvh_presplit_level(self):
         """Option "bvh_presplit": the grid level the current tree's references were split on, -1 = one reference per triangle."""
-        out = C.c_int32()
-        self.check(self.L.vhr_get_bvh_presplit_level(self.handle, C.byref(out)), "get_bvh_presplit_level")
-        return int(out.value)
+        return self._read("bvh_presplit_level", 1, "get_bvh_presplit_level", C.c_int32)[0]
 
     def bvh_builder_used(self):
         """Which builder made the current tree: 1 = the device's (option "bvh_builder" 1, the default), 0 = the host's."""
-        out = C.c_int32()
-        self.check(self.L.vhr_get_bvh_builder(self.handle, C.byref(out)), "get_bvh_builder")
-        return int(out.value)
+        return self._read("bvh_builder", 1, "get_bvh_builder", C.c_int32)[0]
 
     def bvh_fingerprint(self):
-        out = C.c_uint64()
-        self.check(self.L.vhr_get_bvh_fingerprint(self.handle, C.byref(out)), "bvh_fingerprint")
-        return int(out.value)
+        return self._read("bvh_fingerprint", 1)[0]
 
     def bvh_tree_fingerprint(self):
         """A hash of the tree, not of its arrays: equal for the host's and the device's build of a scene."""
-        out = C.c_uint64()
-        self.check(self.L.vhr_get_bvh_tree_fingerprint(self.handle, C.byref(out)), "bvh_tree_fingerprint")
-        return int(out.value)
+        return self._read("bvh_tree_fingerprint", 1)[0]
 
     def bvh_forms_fingerprint(self):
         """(hash of the scene centre and the derived node forms as they stand, the same after the host derives them again from the
         (lo, hi) nodes): equal for any tree, whichever builder made or refitted it."""
-        out = (C.c_uint64 * 2)()
-        self.check(self.L.vhr_get_bvh_forms_fingerprint(self.handle, out), "bvh_forms_fingerprint")
-        return int(out[0]), int(out[1])
+        return tuple(self._read("bvh_forms_fingerprint", 2))
 
     def build_times_ms(self):
         """K0: (host BVH build, upload of scene + tree) of the last upload_scene, milliseconds."""
-        out = (C.c_double * 2)()
-        self.check(self.L.vhr_get_build_times(self.handle, out), "build_times")
-        return float(out[0]), float(out[1])
+        return tuple(self._read("build_times", 2, ctype=C.c_double))
 
     def drain_statistics(self):
-        out = (C.c_uint64 * 4)()
-        self.check(self.L.vhr_get_drain_statistics(self.handle, out), "drain_statistics")
-        return dict(cut_entries=out[0], drain_trips_le4=out[1], drain_trips_le8=out[2], drain_trips_le16=out[3])
+        return dict(zip(("cut_entries", "drain_trips_le4", "drain_trips_le8", "drain_trips_le16"), self._read("drain_statistics", 4)))
 
     def get_option(self, key):
         out = C.c_int32()
@@ -911,34 +868,44 @@ class Context:
         return int(out.value)
 
     def bvh_statistics(self):
-        out = (C.c_uint64 * 5)()
-        self.check(self.L.vhr_get_bvh_statistics(self.handle, out), "bvh_statistics")
-        return dict(nodes=out[0], triangles=out[1], max_depth=out[2], node_bytes=out[3], triangle_bytes=out[4])
+        return dict(zip(("nodes", "triangles", "max_depth", "node_bytes", "triangle_bytes"), self._read("bvh_statistics", 5)))
 
     KERNEL_KINDS = {"raygen": 0, "svgf_temporal": 1, "svgf_atrous": 2, "blit": 3, "reflection": 4, "ssao": 5, "ssao_blur": 6, "ssr": 7, "svgf_atrous_async": 8,
                     "ray_query": 9, "rayquery_forward": 10, "forward_raster": 11}
     REFIT_TIMING_BIT = 12          # a bit of vhr_set_kernel_timing's mask only (set_kernel_timing(..., refit=True)); the times come from refit_times_ms()
 
     @staticmethod
-    def _rays_array(rays):
-        """(n, 8) float32 (origin, tmin, direction, tmax) or abi.ray_dtype -> a C-contiguous, 16-byte-aligned ray_dtype array."""
-        a = np.asarray(rays)
-        if a.dtype == abi.ray_dtype:
+    def _aligned_zeros(n, dtype):
+        """n zeroed records of `dtype` that start at a 16-byte boundary."""
+        raw = np.zeros(n * dtype.itemsize + 16, np.uint8)
+        start = -raw.ctypes.data % 16
+        return raw[start:start + n * dtype.itemsize].view(dtype)
+
+    @staticmethod
+    def _records_array(a, dtype, columns, who):
+        """(n, columns) float32 or a 1-D array of `dtype` -> a C-contiguous, 16-byte-aligned array of `dtype`; `who` = the names the errors
+        use: (method, records, dtype)."""
+        who, what, name = who
+        a = np.asarray(a)
+        if a.dtype == dtype:
             if a.ndim != 1:
-                raise ValueError(f"ray_query: a ray_dtype array must be 1-D, got shape {a.shape}")
+                raise ValueError(f"{who}: a {name} array must be 1-D, got shape {a.shape}")
         elif a.dtype == np.float32:
-            if a.ndim != 2 or a.shape[1] != 8:
-                raise ValueError(f"ray_query: float32 rays must have shape (n, 8), got {a.shape}")
-            a = np.ascontiguousarray(a).view(abi.ray_dtype).reshape(-1)
+            if a.ndim != 2 or a.shape[1] != columns:
+                raise ValueError(f"{who}: float32 {what} must have shape (n, {columns}), got {a.shape}")
+            a = np.ascontiguousarray(a).view(dtype).reshape(-1)
         else:
-            raise TypeError(f"ray_query: rays must be float32 (n, 8) or abi.ray_dtype, got {a.dtype}")
-        if not a.flags.c_contiguous or a.ctypes.data % 16:       # vhr_ray_query wants 16-byte-aligned rays: copy into an aligned buffer
-            raw = np.empty(len(a) * abi.ray_dtype.itemsize + 16, np.uint8)
-            start = -raw.ctypes.data % 16
-            aligned = raw[start:start + len(a) * abi.ray_dtype.itemsize].view(abi.ray_dtype)
+            raise TypeError(f"{who}: {what} must be float32 (n, {columns}) or abi.{name}, got {a.dtype}")
+        if not a.flags.c_contiguous or a.ctypes.data % 16:       # the entry points want 16-byte-aligned records: copy into an aligned buffer
+            aligned = Context._aligned_zeros(len(a), dtype)
             aligned[:] = a
             a = aligned
         return a
+
+    @staticmethod
+    def _rays_array(rays):
+        """(n, 8) float32 (origin, tmin, direction, tmax) or abi.ray_dtype -> a C-contiguous, 16-byte-aligned ray_dtype array."""
+        return Context._records_array(rays, abi.ray_dtype, 8, ("ray_query", "rays", "ray_dtype"))
 
     def ray_query(self, rays, any_hit=False, alpha_test=False, cull_mask=None, ray_masks=None, face_cull=None):
         """vhr_ray_query on host arrays: rays (n, 8) float32 or abi.ray_dtype.  Returns abi.ray_hit_dtype[n] (closest hit; a miss has
@@ -985,30 +952,12 @@ class Context:
 
     def ray_query_statistics(self):
         """The last ray query: [rays, rays with a hit, rays decided again in binary64, waves whose stack overflowed (must be 0)]."""
-        out = (C.c_uint64 * 4)()
-        self.check(self.L.vhr_get_ray_query_statistics(self.handle, out), "ray_query_statistics")
-        return [int(x) for x in out]
+        return self._read("ray_query_statistics", 4)
 
     @staticmethod
     def _points_array(points):
         """(n, 4) float32 (point, max_distance) or abi.point_query_dtype -> a C-contiguous, 16-byte-aligned point_query_dtype array."""
-        a = np.asarray(points)
-        if a.dtype == abi.point_query_dtype:
-            if a.ndim != 1:
-                raise ValueError(f"closest_point_query: a point_query_dtype array must be 1-D, got shape {a.shape}")
-        elif a.dtype == np.float32:
-            if a.ndim != 2 or a.shape[1] != 4:
-                raise ValueError(f"closest_point_query: float32 points must have shape (n, 4), got {a.shape}")
-            a = np.ascontiguousarray(a).view(abi.point_query_dtype).reshape(-1)
-        else:
-            raise TypeError(f"closest_point_query: points must be float32 (n, 4) or abi.point_query_dtype, got {a.dtype}")
-        if not a.flags.c_contiguous or a.ctypes.data % 16:       # vhr_closest_point_query wants 16-byte-aligned points: copy into an aligned buffer
-            raw = np.empty(len(a) * abi.point_query_dtype.itemsize + 16, np.uint8)
-            start = -raw.ctypes.data % 16
-            aligned = raw[start:start + len(a) * abi.point_query_dtype.itemsize].view(abi.point_query_dtype)
-            aligned[:] = a
-            a = aligned
-        return a
+        return Context._records_array(points, abi.point_query_dtype, 4, ("closest_point_query", "points", "point_query_dtype"))
 
     def closest_point_query(self, points, any_within=False, cull_mask=None):
         """vhr_closest_point_query on host arrays: points (n, 4) float32 (point, max_distance) or abi.point_query_dtype.  Returns
@@ -1033,9 +982,7 @@ class Context:
 
     def point_query_statistics(self):
         """The last closest-point query: [queries, queries that found something, point / triangle evaluations, waves whose stack overflowed (must be 0)]."""
-        out = (C.c_uint64 * 4)()
-        self.check(self.L.vhr_get_point_query_statistics(self.handle, out), "point_query_statistics")
-        return [int(x) for x in out]
+        return self._read("point_query_statistics", 4)
 
     def resolve_hits(self, hits, material=False):
         """vhr_resolve_hits on host arrays: hits = abi.ray_hit_dtype[n], as ray_query() and closest_point_query() return them (only u, v,
@@ -1045,9 +992,7 @@ class Context:
         not resolved -- a miss, an index outside the scene, barycentrics that are no numbers.  A host-only context answers without material."""
         h = np.ascontiguousarray(hits, dtype=abi.ray_hit_dtype).reshape(-1)
         n = len(h)
-        raw = np.zeros(n * abi.surface_point_dtype.itemsize + 16, np.uint8)
-        start = -raw.ctypes.data % 16
-        out = raw[start:start + n * abi.surface_point_dtype.itemsize].view(abi.surface_point_dtype)
+        out = self._aligned_zeros(n, abi.surface_point_dtype)
         flags = abi.SURFACE_HOST_MEMORY | (abi.SURFACE_MATERIAL if material else 0)
         self.check(self.L.vhr_resolve_hits(self.handle, h.ctypes.data if n else None, n, flags, out.ctypes.data if n else None), "resolve_hits")
         return out
@@ -1059,9 +1004,7 @@ class Context:
 
     def surface_statistics(self):
         """The last resolve_hits: [hits, records with SURFACE_VALID, records with SURFACE_DISCARDED, 1 if the material instantiation ran]."""
-        out = (C.c_uint64 * 4)()
-        self.check(self.L.vhr_get_surface_statistics(self.handle, out), "surface_statistics")
-        return [int(x) for x in out]
+        return self._read("surface_statistics", 4)
 
     def debug_point_triangle(self, pairs):
         """The query's point / triangle function on explicit pairs: pairs = (n, 12) float32 (p, v0, e1, e2) -> (n, 3) float32 (d2, u, v).  A device
@@ -1324,18 +1267,14 @@ def tile_plan_replan(old, new):
 
 def comm_use_library(path):
     """vhr_comm_use_library: the RCCL library csrc/comm.cpp loads (before the process's first vhr_comm_* call); None = the default resolution."""
-    L = load()
-    L.vhr_comm_use_library.argtypes = [C.c_char_p]
-    rc = L.vhr_comm_use_library(path.encode() if path else None)
+    rc = load().vhr_comm_use_library(path.encode() if path else None)
     if rc != 0:
         raise VhrError(f"vhr_comm_use_library: {rc} (the RCCL entry points are already bound)")
 
 
 def comm_library():
     """vhr_comm_library: the file the RCCL entry points came from, or the reason they could not be resolved."""
-    L = load()
-    L.vhr_comm_library.restype = C.c_char_p
-    return L.vhr_comm_library().decode()
+    return load().vhr_comm_library().decode()
 
 
 def comm_use_library_from_environment():
