@@ -350,7 +350,7 @@ audit_record_dtype = np.dtype([
     ("flat", "<u4"), ("mt", "u1"), ("pass_mask", "u1"), ("any_hit", "u1"), ("exact", "i1"), ("cls", "S1"), ("pad_", "u1", (3,))], align=True)
 
 
-RAY_KIND_SHADOW, RAY_KIND_AO, RAY_KIND_MIRROR, RAY_KIND_SECOND_BOUNCE, RAY_KIND_OTHER = 0, 1, 2, 3, 255
+RAY_KIND_SHADOW, RAY_KIND_AO, RAY_KIND_MIRROR, RAY_KIND_SECOND_BOUNCE, RAY_KIND_PRIMARY, RAY_KIND_OTHER = 0, 1, 2, 3, 4, 255
 ray_log_dtype = np.dtype([("pixel", "<u4"), ("kind", "<u4"), ("o", "<f4", (3,)), ("tmin", "<f4"), ("d", "<f4", (3,)), ("tmax", "<f4")])
 truth_pair_dtype = np.dtype([("flat", "<u4"), ("decision", "<i4"), ("det", "<f8"), ("u", "<f8"), ("v", "<f8"), ("t", "<f8"),
                              ("eu", "<f8"), ("ev", "<f8"), ("et", "<f8"), ("margin", "<f8")])
@@ -377,7 +377,7 @@ class Audit:
     """with Audit(brute_force=False) as a: <oracle calls that trace rays>; then a.counts (audit_counts_dtype scalar), a.records."""
 
     def __init__(self, brute_force=False, max_records=200000, ray_log=0):
-        """ray_log: room for that many ray_log_dtype records -- every audited ray with the pixel and kind orc_raygen's loop was at."""
+        """ray_log: room for that many ray_log_dtype records -- every audited ray with the pixel and kind its pixel loop was at."""
         self.brute, self.cap, self.log_cap = brute_force, max_records, ray_log
         self.counts, self.records, self.ray_log = None, None, None
 

@@ -1249,12 +1249,15 @@ void orc_raytraced(const orc_scene *s, const orc_per_frame_data *pfd, uint32_t W
             v3 tn = normalize3(V3(target.x, target.y, target.z));
             v4 direction = mat4_mul_v4(pfd->camera_view_inverse, (v4){ tn.x, tn.y, tn.z, 0.0f });   /* :17 */
             v4 payload = { 0.0f, 0.0f, 0.0f, 0.0f };                                                /* :19 */
+            t_ray_pixel = y * W + x; t_ray_kind = ORC_RAY_KIND_PRIMARY;
             /* :20 gl_RayFlagsOpaqueEXT (alpha: gl_RayFlagsNoOpaqueEXT -> shadow_anyhit.rahit filters candidates), miss 0 */
             orc_hit h = trace_filtered(s, V3(origin.x, origin.y, origin.z), V3(direction.x, direction.y, direction.z), 0.1f, 10000.0f,
                                        0, use_bvh, alpha);
             ++rays;
+            t_ray_kind = ORC_RAY_KIND_SHADOW;                                        /* closesthit.rchit's shadow ray */
             if (h.hit) payload = raytraced_closest_hit(s, pfd, &h, alpha, use_bvh, &rays);
             else payload = (v4){ 0.3f, 0.8f, 0.2f, 1.0f };                                          /* miss.rmiss:7 */
+            t_ray_pixel = 0xffffffffu; t_ray_kind = ORC_RAY_KIND_OTHER;
             uint8_t *o = out_bgra8 + ((size_t)y * W + x) * 4;                        /* :22 imageStore to B8G8R8A8_UNORM */
             o[0] = unorm8(payload.z); o[1] = unorm8(payload.y); o[2] = unorm8(payload.x); o[3] = unorm8(payload.w);
         }
@@ -1330,6 +1333,7 @@ void orc_gbuffer_albedo(const orc_scene *s, const orc_per_frame_data *pfd, uint3
             float bx = 0, by = 0, bz = 0, uvx = 0, uvy = 0, tmin = 1.0f;
             v4 al = { 0, 0, 0, 0 };
             int visible = 0;
+            t_ray_pixel = (uint32_t)px; t_ray_kind = ORC_RAY_KIND_PRIMARY;
             for (int layer = 0; layer < ORC_GBUFFER_MAX_LAYERS; ++layer) {
                 h = trace(s, cam, dir, tmin, 3.0e38f, 0, 1);
                 if (!h.hit) break;
@@ -1353,6 +1357,7 @@ void orc_gbuffer_albedo(const orc_scene *s, const orc_per_frame_data *pfd, uint3
                 visible = 1;
                 break;
             }
+            t_ray_pixel = 0xffffffffu; t_ray_kind = ORC_RAY_KIND_OTHER;
             if (!visible) {                                            /* clears: hybrid_render_path.cpp:16-19 */
                 store_rgba16f(normals_ids, W, x, y, 0, 0, 0, 0);
                 store_rgba16f(motion_mr, W, x, y, 0, 0, -1.0f, -1.0f);

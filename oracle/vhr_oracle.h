@@ -211,8 +211,8 @@ typedef struct {
     char pad_[3];
 } orc_audit_record;
 /* the ray log of an audit session: after orc_audit_log_rays(max) every audited ray is also recorded with the pixel (y * W + x) and the kind
- * orc_raygen's loop was at; fetch with orc_audit_ray_log (NULL: the count) BEFORE orc_audit_end, which frees it */
-enum { ORC_RAY_KIND_SHADOW = 0, ORC_RAY_KIND_AO = 1, ORC_RAY_KIND_MIRROR = 2, ORC_RAY_KIND_SECOND_BOUNCE = 3, ORC_RAY_KIND_OTHER = 255 };
+ * the pixel loop was at (orc_raygen's; orc_gbuffer's and orc_raytraced's primary rays are PRIMARY, orc_raytraced's shadow ray SHADOW); fetch with orc_audit_ray_log (NULL: the count) BEFORE orc_audit_end, which frees it */
+enum { ORC_RAY_KIND_SHADOW = 0, ORC_RAY_KIND_AO = 1, ORC_RAY_KIND_MIRROR = 2, ORC_RAY_KIND_SECOND_BOUNCE = 3, ORC_RAY_KIND_PRIMARY = 4, ORC_RAY_KIND_OTHER = 255 };
 typedef struct { uint32_t pixel, kind; float o[3], tmin, d[3], tmax; } orc_ray_log_record;
 void     orc_audit_log_rays(uint32_t max_rays);
 uint32_t orc_audit_ray_log(orc_ray_log_record *out);

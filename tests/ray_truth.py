@@ -1,5 +1,5 @@
 """Ray answers judged against exact arithmetic.  TEST INFRASTRUCTURE (tests/test_ray_truth.py, tests/test_gpu_ray_truth.py,
-tools/ray_truth_scale.py, tools/audit_decision_vi.py).
+tests/test_closest_truth.py, tests/test_gpu_closest_truth.py, tools/ray_truth_scale.py, tools/audit_decision_vi.py).
 
 The truth of a ray is what oracle/vhr_oracle.c's orc_ray_truth returns for it -- every triangle of the scene decided without rounding
 (oracle/vhr_exact.h; the pairs its binary64 filter leaves open are settled here with tests/exact_rational.py, so no ray is ever left
@@ -15,6 +15,8 @@ A pair is "explained" when its margin is <= 1.  The verdict on an answer (the de
     closest hit, answer (k, t, u, v):  k in X -> |t - xt| <= et, |u - xu| <= eu, |v - xv| <= ev;   k not in X -> k in N;
                                        every j in X with xt_j < xt_k - (et_j + et_k) is explained (else a nearer true hit was lost);
     closest hit, answer "miss":        every j in X is explained;
+    closest hit, answer k alone:       the same without the clause on (t, u, v), and no j < k in X whose world record equals k's bit for bit
+                                       (judge_closest_triangle: for images that name the triangle and carry no t, u, v);
     any hit, "occluded":               X or N is not empty;          any hit, "not occluded": every j in X is explained.
 
 The bounds are derived, not tuned: k = 8 * 2^-24 (7 roundings to a numerator, the reciprocal and the product) times the permanents of
@@ -204,6 +206,7 @@ class Truth:
         self.n, self.ntris = len(rays), int(osc.triangle_count)
         ray = np.repeat(np.arange(self.n, dtype=np.int64), np.diff(offsets))
         tris, _ = osc.triangles()
+        self.tris = tris                                   # (ntris, 3, 3) float32 world records (v0, e1, e2): judge_closest_triangle's ties
         keep = np.ones(len(pairs), bool)
         # exact misses and open pairs: could fp32 call them a hit at all?  (numerators_allow_a_hit)
         cand = np.nonzero(pairs["decision"] != 1)[0]
@@ -268,6 +271,7 @@ class Verdict:
     reasons: dict                     # name -> ray indices
     explained_d: int = 0              # answers on a triangle of N (class D, explained)
     explained_lost: int = 0           # true hits the answer passed over that lie inside the band (class E / C, explained)
+    ties: int = 0                     # judge_closest_triangle: answers in X that share their world record with another exact hit of the ray
 
     @property
     def violations(self):
@@ -300,6 +304,39 @@ def judge_closest(truth, hit, flat, t, u, v):
                "miss, but a true hit exists": np.nonzero(lost)[0]}
     return Verdict(unknown | values | nearer | lost, reasons, int((found & ~in_x).sum()),
                    int((passed & T.explained).sum() + (T.hit & ~hit[T.ray] & T.explained).sum()))
+
+
+def identical_records(world_tris):
+    """(n, 3, 3) float32 world records -> int64[n]: the smallest flat index whose (v0, e1, e2) equals this one's bit for bit."""
+    rec = np.ascontiguousarray(world_tris, np.float32).reshape(len(world_tris), 9).view(np.uint32)
+    _, first, inverse = np.unique(rec, axis=0, return_index=True, return_inverse=True)
+    return first[inverse.reshape(-1)].astype(np.int64)                # (np.unique's first occurrence is the smallest index)
+
+
+def judge_closest_triangle(truth, hit, flat, world_tris=None):
+    """The verdict on WHICH triangle a closest-hit answer names, for answers that carry no (t, u, v) (an image that encodes the triangle):
+    judge_closest's clauses with the found pair's own exact values, so its clause on the values never fires, and one more --
+
+        ties:  the answer k is in X and some j < k in X has a world record (v0, e1, e2) identical to k's bit for bit.
+
+    Identical operands give identical (t, u, v) in fp32 and in binary64, in every walker, so "min t, then the smaller flat index" decides
+    that case with no excuse: no band is consulted.  world_tris: (ntris, 3, 3) float32, default the truth's own scene."""
+    T = truth
+    hit, flat = np.asarray(hit, bool), np.asarray(flat, np.int64)
+    idx, found = T.find(flat, hit)
+    own = [np.where(found, x[idx], 0.0) if len(T.key) else np.zeros(T.n) for x in (T.t, T.u, T.v)]
+    v = judge_closest(T, hit, flat, *own)
+    assert not len(v.reasons["t, u or v beyond fp32's error bound"])
+    del v.reasons["t, u or v beyond fp32's error bound"]
+    same = identical_records(T.tris if world_tris is None else world_tris)
+    in_x = found & T.hit[idx] if len(T.key) else found
+    k = np.where(in_x, flat, -1)
+    twin = T.hit & in_x[T.ray] & (same[T.flat] == same[np.maximum(k, 0)[T.ray]]) & (T.flat != k[T.ray])      # another exact hit, same operands
+    tie = _over(T, twin & (T.flat < k[T.ray]))                                                             # ... that comes first
+    v.reasons["tie not broken towards the smaller flat index"] = np.nonzero(tie)[0]
+    v.bad = v.bad | tie
+    v.ties = int(_over(T, twin).sum())
+    return v
 
 
 def judge_any(truth, occluded):
