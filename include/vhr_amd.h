@@ -641,7 +641,9 @@ int vhr_get_ray_statistics(vhr_context *ctx, uint64_t out[4]);
  *  "bvh_frame" 1 (default) = the boxes along the frame (a rotation, found by the builder: csrc/bvh_frame.hpp) that minimises the summed area
  *  of the triangles' boxes, if that beats the world axes by 5 % -- a scene whose dominant orientation is not the world's walks up to twice as
  *  fast for it, a scene along the world axes keeps them and its tree, bit for bit (the search costs such a scene ~1.5 ms of K0) --, 0 = the world
- *  axes whatever the scene; the walkers rotate a ray once for the box tests and intersect triangles in world space as ever: images
+ *  axes whatever the scene; a box in a frame is padded by 1e-3 + 1e-5 |frame coordinate| + 2^-18 W, W = the power of two at or above twice the
+ *  largest |world coordinate| of the triangles when the tree was built (the rotation's rounding follows the world magnitude; on the world axes
+ *  the last term is 0); the walkers rotate a ray once for the box tests and intersect triangles in world space as ever: images
  *  bit-identical, both builders, the same tree (vhr_get_bvh_frame tells which frame the current tree uses; "bvh_presplit" is not combined with a rotated frame).
  *  Not in the table either, because it CHANGES IMAGES (the table's entries are result-neutral), and read at every launch: "alpha_test_rays"
  *  0 (default) = every triangle is opaque to the hybrid path's shadow, AO and mirror rays, as in the reference's hybrid path
@@ -704,6 +706,23 @@ int vhr_debug_ray_triangle(vhr_context *ctx, const float *pairs, uint32_t count,
  * (VHR_ERROR_INVALID_ARGUMENT).  A "bvh_presplit" tree with split references has several records per triangle: VHR_ERROR_UNSUPPORTED.
  * Waits for the context's streams; works on a host-only context. */
 int vhr_debug_triangle_records(vhr_context *ctx, int32_t previous, float *out, uint32_t capacity_triangles, uint32_t *count);
+/* Diagnostics: the tree's arrays as the walkers read them, byte for byte, to HOST memory -- the bytes in device memory on a device context,
+ * the host builder's on a host-only one -- for a judge outside the library (tests/tree_truth.py decodes them from the layouts'
+ * description and compares them with exact geometry).  nodes: 64 bytes per node, both child boxes as (lo.x, hi.x, lo.y, hi.y, lo.z, hi.z)
+ * floats, then child0, child1, two unused words; nodes_ch: 64 bytes, (c0.x, c1.x, c0.y, c1.y, c0.z, c1.z), h0[3], h1[3], child0, child1,
+ * two unused words; nodes48: 48 bytes, the same six centres, three words of two upper-16 half extents each ((h0.x, h0.y), (h0.z, h1.x),
+ * (h1.y, h1.z), the first in bits 31..16), child0, child1, one unused word; nodes16: 32 bytes, six IEEE-half centres relative to the
+ * scene centre (c0.x, c1.x, c0.y, c1.y, c0.z, c1.z), six half extents in the same order, child0, child1.  A child >= 0 is an inner node's
+ * index (nodes, nodes_ch) or its byte offset (nodes48, nodes16); a child < 0 is a leaf, v = ~child, first record v >> 2, (v & 3) + 1 records.
+ * records: 48 bytes per record in slot order -- v0[3], e1[3], e2[3] floats, primitive, triangle within it, flat triangle index -- every
+ * reference of a "bvh_presplit" tree.  header: [0..2] the scene centre (float bits), [3..11] the frame, row-major, row i = axis i in world
+ * coordinates, [12] 1 if the boxes live in that frame, [13] 1 if the 32-byte form is valid for the walkers ("compact_nodes" 1 then walks
+ * it), [14] nodes, [15] records, [16] depth, [17] the frame padding's world magnitude (float bits; 0 on the world axes: see "bvh_frame"),
+ * [18..23] 0.  counts[0] / counts[1] = nodes / records, also when a capacity is too small or an array is NULL where the count is not 0
+ * (VHR_ERROR_INVALID_ARGUMENT).  Checks in this order: NULL header or counts, the capacities, then the state (VHR_ERROR_GRAPH from inside
+ * a pass or without geometry).  Waits for the context's streams; launches nothing; works on a host-only context. */
+int vhr_debug_bvh_arrays(vhr_context *ctx, uint32_t header[24], void *nodes, void *nodes_ch, void *nodes48, void *nodes16, void *records, uint32_t capacity_nodes,
+                         uint32_t capacity_records, uint32_t counts[2]);
 /* What the last frame's rays cost, where: those lifetimes -- the any-hit launch's and the mirror ray's -- summed into a map of 8 x 8-pixel cells,
  * out[cy * cols + cx], cols >= ceil(width / 8), rows >= ceil(height / 8).  The cost map vhr_tile_plan_make_weighted cuts a grid by (cell = 8).
  * VHR_ERROR_NOT_FOUND when no queue kernel has left lifetimes ("raygen_cost_order" 0, or 1 on launches below 2 048 workgroups: set it to 2). */
@@ -804,12 +823,15 @@ int vhr_update_primitive_transforms(vhr_context *ctx, uint32_t first_primitive, 
  * launch per level, the top levels in one), padded like a build's, the scene centre and the three derived node forms with their containment
  * check (the half-precision form falls back to the 48-byte nodes exactly as after a build).  With nothing pending: VHR_OK, nothing launched.
  * Synchronises like vhr_update_geometry (it reads its counters back); an asynchronous refit is out of scope.  If it meets non-finite
- * coordinates (device-memory vertices) it fails with VHR_ERROR_INVALID_ARGUMENT, the tree's arrays are NOT valid and updates stay pending
- * until a refit succeeds or the geometry is rebuilt (vhr_rebuild_geometry, vhr_update_geometry). */
+ * coordinates (device-memory vertices) or, on a tree in a "bvh_frame", record corners beyond the world magnitude the tree's padding was built
+ * with (vhr_debug_bvh_arrays header[17]: at least twice the largest |coordinate| at build time -- a refit pads as the build did, so that a
+ * partial refit leaves what a whole one leaves), it fails with VHR_ERROR_INVALID_ARGUMENT, the tree's arrays are NOT valid and updates stay
+ * pending until a refit succeeds or the geometry is rebuilt (vhr_rebuild_geometry, vhr_update_geometry). */
 int vhr_refit_geometry(vhr_context *ctx);
 /* out[0] = refits since the last build that succeeded, out[1] = triangle records written by the last refit, out[2] = nodes written, out[3] = records not
  * inside their leaf's box, out[4] = child boxes not inside the slot their parent holds for them (both counted in exact comparisons by a
- * check pass after the refit; must be 0), out[5] = non-finite coordinates met (must be 0), out[6] = 1 if the walkers are on the
+ * check pass after the refit; must be 0), out[5] = coordinates met that the tree cannot hold: non-finite ones and, on a tree in a "bvh_frame",
+ * finite corner coordinates beyond its world magnitude (must be 0), out[6] = 1 if the walkers are on the
  * half-precision nodes after it, out[7] = launches of the upward pass (0 on a host-only context). */
 int vhr_get_refit_statistics(vhr_context *ctx, uint64_t out[8]);
 /* The last refit, milliseconds: out[0] = host wall time of vhr_refit_geometry; with bit 12 set in vhr_set_kernel_timing's mask also the

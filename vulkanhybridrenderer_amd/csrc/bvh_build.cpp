@@ -355,6 +355,14 @@ void build_bvh(const vhr_vertex *vertices, const uint32_t *indices, const vhr_pr
         lap("frame search");
     }
     const bool framed = out.frame_on;
+    // the world magnitude the frame's padding is built with (bvh_math.hpp, "the frame's padding"; the device builder: k0_frame_boxes_kernel)
+    out.frame_magnitude = 0.0f;
+    if (framed) {
+        float largest = 0.0f;
+        for (const BvhTri &t : b.tris) largest = std::max(largest, bvh_math::record_magnitude(t));
+        out.frame_magnitude = bvh_math::frame_magnitude_of(largest);
+    }
+    const float frame_pad = bvh_math::frame_pad_of(out.frame_magnitude);
     parallel_for(n, hw, [&](size_t i0, size_t i1) {
     for (size_t i = i0; i < i1; ++i) {
         const BvhTri &t = b.tris[i];
@@ -478,7 +486,7 @@ void build_bvh(const vhr_vertex *vertices, const uint32_t *indices, const vhr_pr
 
     const float inf = std::numeric_limits<float>::infinity();
     auto set_child = [&](BvhNode &node, int which, const TmpNode &child, int32_t link) {
-        bvh_math::pad_slot(child.box.lo, child.box.hi, which == 0 ? node.box0 : node.box1);
+        bvh_math::pad_slot(child.box.lo, child.box.hi, frame_pad, which == 0 ? node.box0 : node.box1);
         (which == 0 ? node.child0 : node.child1) = link;
     };
 
@@ -646,9 +654,14 @@ bool refit_can_walk(const HostBvh &bvh, const vhr_primitive *primitives, uint32_
         if (t.prim >= primitive_count || t.tri >= primitives[t.prim].index_count / 3) return false;
     return true;
 }
-// record `tri` re-derived in its slot from (prim, tri); returns the non-finite coordinates met
-uint32_t refit_record(BvhTri &tri, const vhr_vertex *vertices, const uint32_t vi[3], const vhr_primitive &pr) {
-    return bvh_math::world_record(pr.transform, vertices[vi[0]].pos, vertices[vi[1]].pos, vertices[vi[2]].pos, tri.v0, tri.e1, tri.e2);
+// record `tri` re-derived in its slot from (prim, tri); returns the coordinates met that the tree cannot hold: non-finite ones and, in a frame,
+// those beyond the world magnitude its padding was built with
+// (`beyond` grows by the latter alone: the two want different remedies, and the refit's message says which it met)
+uint32_t refit_record(BvhTri &tri, const vhr_vertex *vertices, const uint32_t vi[3], const vhr_primitive &pr, const HostBvh &bvh, uint64_t &beyond) {
+    const uint32_t bad = bvh_math::world_record(pr.transform, vertices[vi[0]].pos, vertices[vi[1]].pos, vertices[vi[2]].pos, tri.v0, tri.e1, tri.e2);
+    const uint32_t far = bvh_math::coordinates_beyond(tri.v0, tri.e1, tri.e2, bvh.frame_magnitude, bvh.frame_on);
+    beyond += far;
+    return bad + far;
 }
 void record_corners(const BvhTri &tri, const uint32_t *indices, const vhr_primitive &pr, uint32_t vi[3]) {
     for (int c = 0; c < 3; ++c) vi[c] = pr.vertex_offset + indices[pr.index_offset + 3 * tri.tri + c];
@@ -681,21 +694,23 @@ bool refit_bvh(const vhr_vertex *vertices, const uint32_t *indices, const vhr_pr
     const bool motion = motion_epoch != 0 && bvh.prev_tris.size() == n_tris && bvh.prev_saved.size() == n_tris;
     const unsigned hw = host_threads(threads);
     // 1. the records, each in its slot
-    std::atomic<uint64_t> non_finite{ 0 }, differing{ 0 };
+    std::atomic<uint64_t> non_finite{ 0 }, differing{ 0 }, beyond{ 0 };
     parallel_for(n_tris, hw, [&](size_t i0, size_t i1) {
-        uint64_t bad = 0, differs = 0;
+        uint64_t bad = 0, differs = 0, far = 0;
         for (size_t i = i0; i < i1; ++i) {
             const vhr_primitive &pr = primitives[bvh.tris[i].prim];
             uint32_t vi[3];
             record_corners(bvh.tris[i], indices, pr, vi);
             if (motion) motion_save(bvh, i, motion_epoch);
-            bad += refit_record(bvh.tris[i], vertices, vi, pr);
+            bad += refit_record(bvh.tris[i], vertices, vi, pr, bvh, far);
             if (motion) differs += motion_differs(bvh, i);
         }
         non_finite += bad;
         differing += differs;
+        beyond += far;
     });
     counts[2] = non_finite;
+    bvh.refit_beyond = beyond;
     bvh.prev_differing = differing;
     // 2. + 3. the boxes bottom-up (children have larger indices than their parents), padded into the parents' slots; and what a partial refit
     // starts from: the unpadded boxes, every node's parent, every record's leaf node
@@ -704,7 +719,7 @@ bool refit_bvh(const vhr_vertex *vertices, const uint32_t *indices, const vhr_pr
     bvh.owner.assign(n_tris, 0u);
     for (size_t k = n_nodes; k-- > 0;) {
         BvhNode &nd = bvh.nodes[k];
-        bvh_math::refit_slots(nd, n_nodes == 1, bvh.tris.data(), bvh.self_box.data(), bvh.frame, bvh.frame_on, &bvh.self_box[6 * k], &bvh.self_box[6 * k + 3]);
+        bvh_math::refit_slots(nd, n_nodes == 1, bvh.tris.data(), bvh.self_box.data(), bvh.frame, bvh.frame_on, bvh_math::frame_pad_of(bvh.frame_magnitude), &bvh.self_box[6 * k], &bvh.self_box[6 * k + 3]);
         const int32_t both[2] = { nd.child0, nd.child1 };
         for (int32_t link : both) {
             if (link >= 0) { bvh.parent[size_t(link)] = uint32_t(k); continue; }
@@ -743,6 +758,7 @@ bool refit_bvh_partial(const vhr_vertex *vertices, const uint32_t *indices, cons
     if (!refit_can_walk(bvh, primitives, primitive_count, false)) return false;
     const bool motion = motion_epoch != 0 && bvh.prev_tris.size() == n_tris && bvh.prev_saved.size() == n_tris;
     bvh.prev_differing = 0;
+    bvh.refit_beyond = 0;
     const unsigned hw = host_threads(threads);
     // 1. mark, and the dirty records
     std::vector<uint8_t> mark(n_nodes, 0);
@@ -757,14 +773,14 @@ bool refit_bvh_partial(const vhr_vertex *vertices, const uint32_t *indices, cons
             continue;
         }
         if (motion) motion_save(bvh, i, motion_epoch);
-        counts[2] += refit_record(tri, vertices, vi, pr);
+        counts[2] += refit_record(tri, vertices, vi, pr, bvh, bvh.refit_beyond);
         if (motion) bvh.prev_differing += motion_differs(bvh, i);
         ++out[0];
         for (uint32_t node = bvh.owner[i]; node != 0xffffffffu && !mark[node]; node = bvh.parent[node]) { mark[node] = 1; ++out[1]; }
     }
     // 2. + 3. the dirty nodes' boxes, bottom-up, from the boxes the clean ones keep
     for (size_t k = n_nodes; k-- > 0;)
-        if (mark[k]) bvh_math::refit_slots(bvh.nodes[k], n_nodes == 1, bvh.tris.data(), bvh.self_box.data(), bvh.frame, bvh.frame_on, &bvh.self_box[6 * k], &bvh.self_box[6 * k + 3]);
+        if (mark[k]) bvh_math::refit_slots(bvh.nodes[k], n_nodes == 1, bvh.tris.data(), bvh.self_box.data(), bvh.frame, bvh.frame_on, bvh_math::frame_pad_of(bvh.frame_magnitude), &bvh.self_box[6 * k], &bvh.self_box[6 * k + 3]);
     // 4. the scene centre from the root's two slots
     float centre[3];
     bvh_math::centre_of_root(bvh.nodes[0], centre);

@@ -5,7 +5,9 @@
 // scene HAS a dominant orientation (a building, a street), is to give the hierarchy that orientation: the boxes are built around the triangles'
 // corners in a rotated frame R, and a walker rotates its ray once (18 FMAs) before the slab tests.  Only the boxes move: the leaf records stay
 // the world-space records, the triangle test stays raygen.rgen's arithmetic on the world-space ray, so what a ray hits, at which t and with
-// which barycentrics is untouched (boxes only cull; the padding of a box, 1e-3 + 1e-5 |x|, is two orders above the rotation's rounding).
+// which barycentrics is untouched (boxes only cull).  The rotation's rounding, ~1e-6 of the WORLD coordinates, is not covered by a padding
+// of 1e-3 + 1e-5 |frame coordinate|: a frame coordinate near 0 can be made of world coordinates of any size.  A tree in a frame therefore pads
+// by 2^-18 of its world magnitude on top (bvh_math.hpp, "the frame's padding"; tests/tree_truth.py judges the slots against exact geometry).
 //
 // The frame is found, not given: R = the rotation (Euler angles about Y, X, Z, coarse to fine) that minimises the sum over the triangles of the
 // half area of the triangle's box in the frame -- the quantity every level of a surface-area tree is made of.  The sum is taken in 64-bit

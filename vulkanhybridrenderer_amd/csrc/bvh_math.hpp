@@ -86,30 +86,77 @@ VHR_BM void leaf_box(int32_t link, const BvhTri *tris, const float frame[9], boo
     }
 }
 // A child box as its parent stores it, (lo.x, hi.x, lo.y, hi.y, lo.z, hi.z), with the conservative padding: box culling must never change
-// which triangles are accepted.
-VHR_BM void pad_slot(const float lo[3], const float hi[3], float slot[6]) {
+// which triangles are accepted.  frame_pad: frame_pad_of(the tree's world magnitude) in a frame, 0 on the world axes (x + 0 = x: the
+// world-axes slots keep their bits).
+VHR_BM void pad_slot(const float lo[3], const float hi[3], float frame_pad, float slot[6]) {
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        const float pad = 1e-3f + 1e-5f * fmaxf(fabsf(lo[a]), fabsf(hi[a]));
+        const float pad = (1e-3f + 1e-5f * fmaxf(fabsf(lo[a]), fabsf(hi[a]))) + frame_pad;
         slot[2 * a] = lo[a] - pad;
         slot[2 * a + 1] = hi[a] + pad;
     }
 }
+// ---- the frame's padding ----
+// In a frame a box coordinate near 0 can come from world coordinates of any size, and the roundings of bvh_frame::rotate() -- the builder's on
+// the corners, the walker's on the ray (box_ray) -- are relative to the WORLD magnitude W, not to the frame coordinate 1e-5 |x| pads by.  With
+// every |world coordinate| <= W: the builder's corner sum and rotation 6 sqrt(3) 2^-24 W, the walker's origin 5 sqrt(3) 2^-24 W, its direction
+// over t <= 2 sqrt(3) W inside the scene 30 * 2^-24 W, the slab products 3 * 2^-24 |face - origin| <= 6 sqrt(3) 2^-24 W: together below
+// 60 * 2^-24 W, which 2^-18 W covers.  W is fixed when the tree is built -- the power of two at or above twice the largest |coordinate| of the
+// records' corners -- so that a refit of either kind pads as the build did; a refit whose records leave W fails like one that meets a
+// non-finite coordinate (coordinates_beyond), and the caller rebuilds.
+constexpr float kFramePadFactor = 1.0f / 262144.0f;          // 2^-18
+VHR_BM float frame_pad_of(float magnitude) { return magnitude * kFramePadFactor; }
+// the largest |coordinate| of a record's three corners as record_box meets them (0 for a non-finite one: world_record has counted it)
+VHR_BM float record_magnitude(const BvhTri &t) {
+    float m = 0.0f;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float c[3] = { t.v0[a], t.v0[a] + t.e1[a], t.v0[a] + t.e2[a] };
+#pragma unroll
+        for (int k = 0; k < 3; ++k) if (__builtin_isfinite(c[k])) m = fmaxf(m, fabsf(c[k]));
+    }
+    return m;
+}
+// W from the largest |coordinate| of all records: the power of two >= 2 * largest (0 for an empty or all-zero scene; at most 2^127)
+VHR_BM float frame_magnitude_of(float largest) {
+    if (!(largest > 0.0f)) return 0.0f;
+    uint32_t bits;
+    memcpy(&bits, &largest, 4);
+    uint32_t e = (bits >> 23) + ((bits & 0x7fffffu) ? 2u : 1u);          // exponent field of the power of two >= 2 * largest
+    if (e < 1u) e = 1u;
+    if (e > 254u) e = 254u;
+    bits = e << 23;
+    float w;
+    memcpy(&w, &bits, 4);
+    return w;
+}
+// finite corner coordinates of a record beyond the tree's world magnitude (a tree on the world axes has none: its padding does not depend on W)
+VHR_BM uint32_t coordinates_beyond(const float v0[3], const float e1[3], const float e2[3], float magnitude, bool frame_on) {
+    if (!frame_on) return 0u;
+    uint32_t n = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float c[3] = { v0[a], v0[a] + e1[a], v0[a] + e2[a] };
+#pragma unroll
+        for (int k = 0; k < 3; ++k) n += uint32_t(__builtin_isfinite(c[k]) && fabsf(c[k]) > magnitude);
+    }
+    return n;
+}
 // One node of a refit: its children's unpadded boxes (a leaf's from its records, an inner child's from `self_box`, six floats per node, lo
-// then hi, filled for every node below this one) padded into its two slots; mine = its own unpadded box, for its parent.  Links are read,
-// never written.
-VHR_BM void refit_slots(BvhNode &nd, bool single, const BvhTri *tris, const float *self_box, const float frame[9], bool frame_on, float mine_lo[3], float mine_hi[3]) {
+// then hi, filled for every node below this one) padded into its two slots (frame_pad: pad_slot's); mine = its own unpadded box, for its
+// parent.  Links are read, never written.
+VHR_BM void refit_slots(BvhNode &nd, bool single, const BvhTri *tris, const float *self_box, const float frame[9], bool frame_on, float frame_pad, float mine_lo[3], float mine_hi[3]) {
     auto child_box = [&](int32_t link, float lo[3], float hi[3]) {
         if (link < 0) { leaf_box(link, tris, frame, frame_on, lo, hi); return; }
 #pragma unroll
         for (int a = 0; a < 3; ++a) { lo[a] = self_box[6 * size_t(link) + a]; hi[a] = self_box[6 * size_t(link) + 3 + a]; }
     };
     child_box(nd.child0, mine_lo, mine_hi);
-    pad_slot(mine_lo, mine_hi, nd.box0);
+    pad_slot(mine_lo, mine_hi, frame_pad, nd.box0);
     if (absent_child1(nd, single)) return;
     float lo[3], hi[3];
     child_box(nd.child1, lo, hi);
-    pad_slot(lo, hi, nd.box1);
+    pad_slot(lo, hi, frame_pad, nd.box1);
     grow(mine_lo, mine_hi, lo, hi);
 }
 

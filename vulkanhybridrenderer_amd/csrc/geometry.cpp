@@ -214,6 +214,7 @@ static int build_and_install_tree(vhr_context *ctx, const char *who, HostSceneAr
         ctx->bvh_presplit_level = bvh.presplit_level;
         for (int i = 0; i < 9; ++i) ctx->bvh_frame[i] = bvh.frame[i];
         ctx->bvh_frame_on = bvh.frame_on;
+        ctx->bvh_frame_magnitude = bvh.frame_magnitude;
     }
     if (uint64_t(device_built ? ctx->node_count : bvh.nodes48.size()) * sizeof(BvhNode48) >= (1ull << 31))     // an inner link of the 48-byte nodes is a non-negative 32-bit byte offset
         return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, std::string(who) + ": more than 44 million BVH nodes");
@@ -544,6 +545,7 @@ static int refit_geometry(vhr_context *ctx, const char *who, bool partial, bool 
         ctx->refit_stats[kRefitRecordsOutside] = counts[0];
         ctx->refit_stats[kRefitChildrenOutside] = counts[1];
         ctx->refit_stats[kRefitNonFinite] = counts[2];
+        ctx->refit_beyond = ctx->h_bvh.refit_beyond;
         ctx->refit_stats[kRefitHalfNodes] = ctx->nodes16_valid ? 1u : 0u;
         ctx->motion_refit_differing = ctx->h_bvh.prev_differing;
         for (int i = 1; i < 4; ++i) ctx->refit_times_ms[i] = 0.0;
@@ -564,9 +566,14 @@ static int refit_geometry(vhr_context *ctx, const char *who, bool partial, bool 
         ctx->partial_stats[kPartialVertexRanges] = ctx->refit_dirty.vertices.count;
         ctx->partial_stats[kPartialPrimitiveRanges] = ctx->refit_dirty.primitives.count;
     }
-    if (ctx->refit_stats[kRefitNonFinite])               // (updates stay pending: nothing may trace these arrays; not counted as a refit)
-        return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, std::string(who) + ": " + std::to_string(ctx->refit_stats[kRefitNonFinite]) +
-                         " non-finite coordinates in the triangle records: the tree's arrays are not valid; update the vertices / transforms and refit again, or rebuild");
+    if (ctx->refit_stats[kRefitNonFinite]) {             // (updates stay pending: nothing may trace these arrays; not counted as a refit)
+        const uint64_t beyond = ctx->refit_beyond, non_finite = ctx->refit_stats[kRefitNonFinite] - beyond;
+        std::string met;
+        if (non_finite) met = std::to_string(non_finite) + " non-finite coordinates in the triangle records (update the vertices / transforms and refit again, or rebuild)";
+        if (beyond) met += std::string(non_finite ? " and " : "") + std::to_string(beyond) + " coordinates beyond the world magnitude " + std::to_string(ctx->bvh_frame_magnitude) +
+                           " the padding of this \"bvh_frame\" tree was built with (the scene has moved too far for a refit: vhr_rebuild_geometry)";
+        return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, std::string(who) + ": " + met + ": the tree's arrays are not valid");
+    }
     ++ctx->refit_stats[kRefitCount];
     if (asked_partial && ran_as == kRanDirty) ++ctx->partial_stats[kPartialCount];
     if (ctx->motion_valid()) { ++ctx->motion_epoch; ctx->motion_differing = ctx->motion_refit_differing; }      // (a failed attempt leaves both: its retry has the same number)
@@ -739,6 +746,43 @@ int vhr_debug_triangle_records(vhr_context *ctx, int32_t previous, float *out, u
         float *o = out + size_t(t.flat) * 9;
         for (int c = 0; c < 3; ++c) { o[c] = t.v0[c]; o[3 + c] = t.e1[c]; o[6 + c] = t.e2[c]; }
     }
+    return VHR_OK;
+}
+
+// The tree as the walkers read it, for a judge outside the library (tests/tree_truth.py): bytes only, nothing derived or checked here.
+int vhr_debug_bvh_arrays(vhr_context *ctx, uint32_t header[24], void *nodes, void *nodes_ch, void *nodes48, void *nodes16, void *records, uint32_t capacity_nodes,
+                         uint32_t capacity_records, uint32_t counts[2]) {
+    static const char *who = "vhr_debug_bvh_arrays";
+    if (!ctx || !header || !counts) return ctx ? ctx->fail(VHR_ERROR_INVALID_ARGUMENT, std::string(who) + ": header and counts must not be NULL") : VHR_ERROR_INVALID_ARGUMENT;
+    const bool tree = ctx->has_geometry();
+    counts[0] = tree ? ctx->node_count : 0u;
+    counts[1] = tree ? ctx->tri_count : 0u;
+    if (capacity_nodes < counts[0] || capacity_records < counts[1] || (counts[0] && (!nodes || !nodes_ch || !nodes48 || !nodes16)) || (counts[1] && !records))
+        return ctx->fail(VHR_ERROR_INVALID_ARGUMENT, std::string(who) + ": room for " + std::to_string(capacity_nodes) + " nodes and " + std::to_string(capacity_records) +
+                         " records (or a NULL array), the tree has " + std::to_string(counts[0]) + " and " + std::to_string(counts[1]));
+    if (ctx->recording || ctx->cur_pass || ctx->in_execute) return ctx->fail(VHR_ERROR_GRAPH, std::string(who) + ": called from inside a pass");
+    if (!tree) return no_geometry(ctx, who);
+    HostBvh fetched;
+    if (!ctx->host_only) {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        VHR_TRY(ctx->sync_streams());
+        VHR_TRY(fetch_device_tree(ctx, fetched));
+    }
+    const HostBvh &bvh = ctx->host_only ? ctx->h_bvh : fetched;
+    std::memcpy(nodes, bvh.nodes.data(), sizeof(BvhNode) * counts[0]);
+    std::memcpy(nodes_ch, bvh.nodes_ch.data(), sizeof(BvhNodeCH) * counts[0]);
+    std::memcpy(nodes48, bvh.nodes48.data(), sizeof(BvhNode48) * counts[0]);
+    std::memcpy(nodes16, bvh.nodes16.data(), sizeof(BvhNode16) * counts[0]);
+    std::memcpy(records, bvh.tris.data(), sizeof(BvhTri) * counts[1]);
+    for (int i = 0; i < 24; ++i) header[i] = 0u;
+    std::memcpy(header, ctx->host_only ? ctx->h_bvh.centre : ctx->bvh_centre, 3 * sizeof(float));
+    std::memcpy(header + 3, ctx->bvh_frame, 9 * sizeof(float));
+    header[12] = ctx->bvh_frame_on ? 1u : 0u;
+    header[13] = ctx->nodes16_valid ? 1u : 0u;
+    header[14] = ctx->node_count;
+    header[15] = ctx->tri_count;
+    header[16] = ctx->bvh_depth;
+    std::memcpy(header + 17, &ctx->bvh_frame_magnitude, sizeof(float));
     return VHR_OK;
 }
 

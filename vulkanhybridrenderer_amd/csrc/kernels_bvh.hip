@@ -115,7 +115,7 @@ __device__ __forceinline__ uint32_t first_triangle(const int2 *node_children, co
 }
 __global__ __launch_bounds__(256) void k0_emit_kernel(const int2 *__restrict__ node_children, const Box6 *__restrict__ node_box, const uint32_t *__restrict__ node_size,
                                                       const uint32_t *__restrict__ kept_rank, const uint32_t *__restrict__ position, uint32_t n, uint32_t total_nodes,
-                                                      uint32_t leaf_tris, BvhNode *__restrict__ nodes) {
+                                                      uint32_t leaf_tris, float frame_pad, BvhNode *__restrict__ nodes) {
     const uint32_t node = n + blockIdx.x * 256u + threadIdx.x;
     if (node >= total_nodes || node_size[node] <= leaf_tris) return;
     const int2 ch = node_children[node];
@@ -126,8 +126,8 @@ __global__ __launch_bounds__(256) void k0_emit_kernel(const int2 *__restrict__ n
     };
     BvhNode out{};
     const Box6 b0 = node_box[uint32_t(ch.x)], b1 = node_box[uint32_t(ch.y)];
-    bvh_math::pad_slot(b0.lo, b0.hi, out.box0);
-    bvh_math::pad_slot(b1.lo, b1.hi, out.box1);
+    bvh_math::pad_slot(b0.lo, b0.hi, frame_pad, out.box0);
+    bvh_math::pad_slot(b1.lo, b1.hi, frame_pad, out.box1);
     out.child0 = link_of(uint32_t(ch.x));
     out.child1 = link_of(uint32_t(ch.y));
     nodes[kept_rank[node - n]] = out;
@@ -633,16 +633,23 @@ __global__ __launch_bounds__(256) void k0_frame_cost_kernel(const BvhTri *__rest
     }
 }
 struct FrameMatrix { float r[9]; };
+// ... and the largest |world coordinate| of the records' corners (bvh_math::record_magnitude: what the frame's padding is sized by), as the bits of
+// a non-negative float, which order like unsigned integers
 __global__ __launch_bounds__(256) void k0_frame_boxes_kernel(const BvhTri *__restrict__ tris, uint32_t n, FrameMatrix frame, Box6 *__restrict__ boxes,
-                                                             uint32_t *__restrict__ centre_bounds) {
+                                                             uint32_t *__restrict__ centre_bounds, uint32_t *__restrict__ largest) {
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
     float c[3] = { 0.0f, 0.0f, 0.0f };
+    float magnitude = 0.0f;
     if (t < n) {
+        const BvhTri tri = tris[t];
         Box6 b;
-        bvh_frame::box_in_frame(frame.r, tris[t], b.lo, b.hi);
+        bvh_frame::box_in_frame(frame.r, tri, b.lo, b.hi);
         for (int a = 0; a < 3; ++a) c[a] = 0.5f * (b.lo[a] + b.hi[a]);
         boxes[t] = b;
+        magnitude = bvh_math::record_magnitude(tri);
     }
+    for (int off = 32; off > 0; off >>= 1) magnitude = fmaxf(magnitude, __shfl_xor(magnitude, off));
+    if ((threadIdx.x & 63u) == 0u) atomic_max_checked(largest, __float_as_uint(magnitude));
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         float mn = t < n ? c[a] : 3.0e38f, mx = t < n ? c[a] : -3.0e38f;
@@ -764,7 +771,7 @@ struct DeviceBuild {
 // ---- the triangles (world space, their boxes, the bounds of the box centres) ----
 int DeviceBuild::triangles(vhr_context *ctx) {
     BVH_TRY("device K0", tmp.alloc(&d_prefix, tri_prefix.size()));
-    BVH_TRY("device K0", tmp.alloc(&d_bounds, 12));
+    BVH_TRY("device K0", tmp.alloc(&d_bounds, 13));      // [12]: the largest |world coordinate| (k0_frame_boxes_kernel)
     BVH_TRY("device K0", tmp.alloc(&d_counts, 4));
     BVH_TRY("device K0", tmp.alloc(&d_tris_flat, n)); BVH_TRY("device K0", tmp.alloc(&d_boxes, n));
     BVH_TRY("device K0", hipMemcpyAsync(d_prefix, tri_prefix.data(), tri_prefix.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
@@ -780,6 +787,7 @@ int DeviceBuild::triangles(vhr_context *ctx) {
 // ---- "bvh_frame" 1: the frame search (the host builder's, with a kernel as its pass over the triangles), then the boxes in that frame ----
 int DeviceBuild::find_frame(vhr_context *ctx) {
     ctx->bvh_frame_on = false;
+    ctx->bvh_frame_magnitude = 0.0f;
     { const float identity[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 }; std::memcpy(ctx->bvh_frame, identity, sizeof(identity)); }
     if (frame_mode == 1) {
         unsigned long long *d_sums;
@@ -800,10 +808,14 @@ int DeviceBuild::find_frame(vhr_context *ctx) {
             FrameMatrix fm;
             std::memcpy(fm.r, frame, sizeof(frame));
             BVH_TRY("device K0", hipMemcpyAsync(d_bounds, init_bounds, sizeof(init_bounds), hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(k0_frame_boxes_kernel, grid(n), block, 0, s, d_tris_flat, n, fm, d_boxes, d_bounds);
+            BVH_TRY("device K0", hipMemsetAsync(d_bounds + 12, 0, sizeof(uint32_t), s));
+            hipLaunchKernelGGL(k0_frame_boxes_kernel, grid(n), block, 0, s, d_tris_flat, n, fm, d_boxes, d_bounds, d_bounds + 12);
+            float largest = 0.0f;
             BVH_TRY("device K0", hipMemcpyAsync(h_bounds, d_bounds, sizeof(h_bounds), hipMemcpyDeviceToHost, s));
+            BVH_TRY("device K0", hipMemcpyAsync(&largest, d_bounds + 12, sizeof(float), hipMemcpyDeviceToHost, s));
             BVH_TRY("device K0", hipStreamSynchronize(s));
             BVH_TRY("device K0", hipGetLastError());
+            ctx->bvh_frame_magnitude = bvh_math::frame_magnitude_of(largest);
             std::memcpy(ctx->bvh_frame, frame, sizeof(frame));
             ctx->bvh_frame_on = true;
         }
@@ -988,7 +1000,7 @@ int DeviceBuild::layout(vhr_context *ctx) {
         BVH_TRY("device K0", hipcub::DeviceRadixSort::SortPairs(d_sort_work, sort_bytes, d_keys[0], d_keys[1], d_vals[0], d_vals[1], int(n_inner_all), 0, 40, s));
         hipLaunchKernelGGL(k0_bfs_rank_kernel, grid(n_inner), block, 0, s, d_vals[1], n_inner, d_kept_rank);
     }
-    hipLaunchKernelGGL(k0_emit_kernel, grid(n_inner_all), block, 0, s, d_children, d_node_box, d_size, d_kept_rank, d_position, n, total_nodes, leaf_tris, ctx->d_nodes);
+    hipLaunchKernelGGL(k0_emit_kernel, grid(n_inner_all), block, 0, s, d_children, d_node_box, d_size, d_kept_rank, d_position, n, total_nodes, leaf_tris, bvh_math::frame_pad_of(ctx->bvh_frame_magnitude), ctx->d_nodes);
     return VHR_OK;
 }
 

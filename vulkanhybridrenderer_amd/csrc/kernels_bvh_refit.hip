@@ -14,21 +14,28 @@ namespace vhr {
 namespace {
 
 // ---- refit (vhr_refit_geometry): the topology stays, the records and the boxes follow the vertices and the transforms ----
-struct RefitFrame { float r[9]; uint32_t on; };
-struct RefitCounters { unsigned long long non_finite, records_outside, children_outside, differing; };      // differing: "object_motion_vectors" only
+struct RefitFrame { float r[9]; uint32_t on; float magnitude; };      // magnitude: the world magnitude the tree's padding was built with (0 on the world axes)
+struct RefitCounters { unsigned long long non_finite, records_outside, children_outside, differing, beyond; };      // differing: "object_motion_vectors" only; beyond: the part of non_finite that is finite and beyond the frame's magnitude
 // the leaf pass: record k re-derived in its slot from (prim, tri) with bvh_math::world_record; three 16-byte loads' worth of gather per corner,
 // three 16-byte stores
 // one record from its primitive's transform and its three vertices (absolute indices `vi`): the one place a refit of either kind derives a
-// record; `now`: what it stored; returns the non-finite coordinates met
+// record; `now`: what it stored; returns the coordinates met that the tree cannot hold: non-finite ones in the low 16 bits and, in a frame, those
+// beyond f.magnitude in the high 16 (at most 9 each per record: a wave's sum keeps them apart)
 __device__ __forceinline__ uint32_t refit_write_record(float4 *slot, const float4 &q2, const vhr_primitive &pr, const vhr_vertex *__restrict__ vertices, const uint32_t vi[3],
-                                                       float4 now[3]) {
+                                                       const RefitFrame &f, float4 now[3]) {
     float v0[3], e1[3], e2[3];
-    const uint32_t bad = bvh_math::world_record(pr.transform, vertices[vi[0]].pos, vertices[vi[1]].pos, vertices[vi[2]].pos, v0, e1, e2);
+    const uint32_t bad = bvh_math::world_record(pr.transform, vertices[vi[0]].pos, vertices[vi[1]].pos, vertices[vi[2]].pos, v0, e1, e2) +
+                         (bvh_math::coordinates_beyond(v0, e1, e2, f.magnitude, f.on != 0u) << 16);
     now[0] = float4{ v0[0], v0[1], v0[2], e1[0] };
     now[1] = float4{ e1[1], e1[2], e2[0], e2[1] };
     now[2] = float4{ e2[2], q2.y, q2.z, q2.w };
     slot[0] = now[0]; slot[1] = now[1]; slot[2] = now[2];
     return bad;
+}
+// a wave's sum of refit_write_record's results into the two counters (non_finite counts both kinds: vhr_get_refit_statistics out[5])
+__device__ __forceinline__ void count_unholdable(RefitCounters *counters, uint32_t bad) {
+    atomicAdd(&counters->non_finite, (unsigned long long)((bad & 0xffffu) + (bad >> 16)));
+    if (bad >> 16) atomicAdd(&counters->beyond, (unsigned long long)(bad >> 16));
 }
 // "object_motion_vectors" (the MOTION instantiations; vhr_context::d_prev_saved has the rules): per record its state before the last successful
 // refit, the whole 48 bytes in the same slot, and the number of the refit that last saved it.  `epoch`: the number of the refit that is running.
@@ -56,7 +63,7 @@ __device__ __forceinline__ void motion_save(const RefitMotion &m, uint32_t k, co
 template <bool MOTION>
 __global__ __launch_bounds__(256) void k0_refit_records_kernel(const vhr_vertex *__restrict__ vertices, const uint32_t *__restrict__ indices,
                                                                const vhr_primitive *__restrict__ primitives, uint32_t primitive_count, uint32_t n,
-                                                               BvhTri *__restrict__ tris, RefitCounters *__restrict__ counters, const RefitMotion motion) {
+                                                               BvhTri *__restrict__ tris, RefitCounters *__restrict__ counters, const RefitMotion motion, const RefitFrame f) {
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
     uint32_t bad = 0, differs = 0;
     if (k < n) {
@@ -70,14 +77,14 @@ __global__ __launch_bounds__(256) void k0_refit_records_kernel(const vhr_vertex 
             for (int c = 0; c < 3; ++c) vi[c] = pr.vertex_offset + indices[pr.index_offset + 3u * local + uint32_t(c)];
             float4 was[3], now[3];
             if constexpr (MOTION) motion_save(motion, k, slot, q2, was);
-            bad = refit_write_record(slot, q2, pr, vertices, vi, now);
+            bad = refit_write_record(slot, q2, pr, vertices, vi, f, now);
             if constexpr (MOTION) differs = motion_differs(was, now);
         } else {
             bad = 1u;                                                // (not a record of this scene: cannot happen, never dereferenced)
         }
     }
     for (int off = 32; off > 0; off >>= 1) bad += uint32_t(__shfl_xor(int(bad), off));
-    if ((threadIdx.x & 63u) == 0u && bad) atomicAdd(&counters->non_finite, (unsigned long long)bad);
+    if ((threadIdx.x & 63u) == 0u && bad) count_unholdable(counters, bad);
     if constexpr (MOTION) {
         for (int off = 32; off > 0; off >>= 1) differs += uint32_t(__shfl_xor(int(differs), off));
         if ((threadIdx.x & 63u) == 0u && differs) atomicAdd(&counters->differing, (unsigned long long)differs);
@@ -98,7 +105,7 @@ __global__ __launch_bounds__(256) void k0_refit_mark_kernel(const vhr_vertex *__
                                                             const vhr_primitive *__restrict__ primitives, uint32_t primitive_count, uint32_t n,
                                                             BvhTri *__restrict__ tris, const uint32_t *__restrict__ owner, const uint32_t *__restrict__ parent,
                                                             uint32_t *__restrict__ dirty, RefitDirty ranges, RefitCounters *__restrict__ counters,
-                                                            PartialCounters *__restrict__ partial, const RefitMotion motion) {
+                                                            PartialCounters *__restrict__ partial, const RefitMotion motion, const RefitFrame f) {
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
     uint32_t bad = 0, records = 0, nodes = 0, differs = 0;
     if (k < n) {
@@ -113,7 +120,7 @@ __global__ __launch_bounds__(256) void k0_refit_mark_kernel(const vhr_vertex *__
             if (ranges.primitives.holds(p) || ranges.vertices.holds(vi[0]) || ranges.vertices.holds(vi[1]) || ranges.vertices.holds(vi[2])) {
                 float4 was[3], now[3];
                 if constexpr (MOTION) motion_save(motion, k, slot, q2, was);
-                bad = refit_write_record(slot, q2, pr, vertices, vi, now);
+                bad = refit_write_record(slot, q2, pr, vertices, vi, f, now);
                 if constexpr (MOTION) differs = motion_differs(was, now);
                 records = 1u;
                 for (uint32_t node = owner[k]; node != kNoParent; node = parent[node]) {
@@ -139,7 +146,7 @@ __global__ __launch_bounds__(256) void k0_refit_mark_kernel(const vhr_vertex *__
         bad += uint32_t(__shfl_xor(int(bad), off)); records += uint32_t(__shfl_xor(int(records), off)); nodes += uint32_t(__shfl_xor(int(nodes), off));
     }
     if ((threadIdx.x & 63u) == 0u) {
-        if (bad) atomicAdd(&counters->non_finite, (unsigned long long)bad);
+        if (bad) count_unholdable(counters, bad);
         if (records) atomicAdd(&partial->dirty_records, (unsigned long long)records);
         if (nodes) atomicAdd(&partial->dirty_nodes, (unsigned long long)nodes);
     }
@@ -217,7 +224,7 @@ __global__ __launch_bounds__(256) void k0_rebuild_scatter_kernel(const BvhTri *_
 __device__ __forceinline__ void refit_node(uint32_t k, BvhNode *nodes, const BvhTri *tris, Box6 *self_box, const RefitFrame &f, bool single) {
     BvhNode nd = nodes[k];
     Box6 mine;
-    bvh_math::refit_slots(nd, single, tris, reinterpret_cast<const float *>(self_box), f.r, f.on != 0u, mine.lo, mine.hi);
+    bvh_math::refit_slots(nd, single, tris, reinterpret_cast<const float *>(self_box), f.r, f.on != 0u, bvh_math::frame_pad_of(f.magnitude), mine.lo, mine.hi);
     nodes[k] = nd;
     self_box[k] = mine;
 }
@@ -391,6 +398,7 @@ static RefitFrame refit_frame(const vhr_context *ctx) {
     RefitFrame f;
     for (int i = 0; i < 9; ++i) f.r[i] = ctx->bvh_frame[i];
     f.on = ctx->bvh_frame_on ? 1u : 0u;
+    f.magnitude = ctx->bvh_frame_magnitude;
     return f;
 }
 // the upward pass: the boxes, level by level from the deepest; the levels at the top in one launch.  `dirty`: nullptr = every node
@@ -439,6 +447,7 @@ static void refit_publish(vhr_context *ctx, RefitPlan *p, const RefitReadback &g
     ctx->refit_stats[kRefitRecordsOutside] = p->totals[4];
     ctx->refit_stats[kRefitChildrenOutside] = p->totals[5];
     ctx->refit_stats[kRefitNonFinite] = got.c.non_finite;
+    ctx->refit_beyond = got.c.beyond;
     ctx->motion_refit_differing = got.c.differing;
     ctx->refit_stats[kRefitHalfNodes] = ctx->nodes16_valid ? 1u : 0u;
     ctx->refit_stats[7] = p->launches;
@@ -486,7 +495,7 @@ int device_refit_bvh(vhr_context *ctx) {
     // 1. the records
     const RefitMotion motion = refit_motion(ctx);
     hipLaunchKernelGGL(motion.prev ? k0_refit_records_kernel<true> : k0_refit_records_kernel<false>, refit_grid(n_tris), block, 0, s, ctx->d_vertices, ctx->d_indices,
-                       ctx->d_primitives, ctx->primitive_count, n_tris, ctx->d_tris, p->d_counters, motion);
+                       ctx->d_primitives, ctx->primitive_count, n_tris, ctx->d_tris, p->d_counters, motion, f);
     if (timed) BVH_TRY("refit", hipEventRecord(p->ev[1], s));
     // 2. + 3. the boxes
     refit_upward(ctx, p, f, nullptr);
@@ -538,7 +547,7 @@ int device_refit_bvh_partial(vhr_context *ctx, bool *ran_whole) {
     // 1. mark, and the dirty records
     const RefitMotion motion = refit_motion(ctx);
     hipLaunchKernelGGL(motion.prev ? k0_refit_mark_kernel<true> : k0_refit_mark_kernel<false>, refit_grid(n_tris), block, 0, s, ctx->d_vertices, ctx->d_indices, ctx->d_primitives,
-                       ctx->primitive_count, n_tris, ctx->d_tris, p->d_owner, p->d_parent, p->d_dirty, ctx->refit_dirty, &d->c, &d->partial, motion);
+                       ctx->primitive_count, n_tris, ctx->d_tris, p->d_owner, p->d_parent, p->d_dirty, ctx->refit_dirty, &d->c, &d->partial, motion, f);
     if (timed) BVH_TRY("refit", hipEventRecord(p->ev[1], s));
     // 2. + 3. the dirty nodes' boxes: the same launches, a one-bit test per node
     refit_upward(ctx, p, f, p->d_dirty);

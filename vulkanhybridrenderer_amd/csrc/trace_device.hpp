@@ -136,7 +136,8 @@ __device__ __forceinline__ bool box_test(float lox, float loy, float loz, float 
 
 // "bvh_frame": what the slab tests see of a ray.  The boxes of all node forms live in the frame DeviceScene::frame (row i = axis i in world
 // coordinates); a walker rotates origin and direction once per ray for them and intersects triangles in world space as ever (boxes only cull:
-// the rotation's rounding, ~1e-6 |x|, is two orders below the boxes' padding).  frame_on is uniform: a scalar branch around 18 FMAs.
+// the rotation's five roundings per coordinate, each 2^-24 of the WORLD magnitude, are what the frame's share of the boxes' padding -- 2^-18 of
+// the tree's world magnitude, bvh_math.hpp -- is sized for).  frame_on is uniform: a scalar branch around 18 FMAs.
 __device__ __forceinline__ f3 frame_rotate(const float *R, f3 p) {
     return f3{ (R[0] * p.x + R[1] * p.y) + R[2] * p.z, (R[3] * p.x + R[4] * p.y) + R[5] * p.z, (R[6] * p.x + R[7] * p.y) + R[8] * p.z };
 }

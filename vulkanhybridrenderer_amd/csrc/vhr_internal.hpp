@@ -157,6 +157,8 @@ struct HostBvh {
     bool nodes16_valid = false;        // false: some box does not fit the half range around `centre` (the walkers then stay on nodes48)
     float frame[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 };     // "bvh_frame": the frame the boxes are in (identity: the world axes)
     bool frame_on = false;
+    float frame_magnitude = 0.0f;      // a tree in a frame: the world magnitude its padding was built with (bvh_math::frame_magnitude_of), kept by refits; else 0
+    uint64_t refit_beyond = 0;         // of the coordinates the last refit counted as ones the tree cannot hold: the finite ones beyond frame_magnitude
     std::vector<BvhTri> tris;          // one per REFERENCE ("bvh_presplit": a fat triangle is in several leaves)
     uint32_t max_depth = 0;
     int presplit_level = -1;           // the grid level the references were split on, -1 = none were
@@ -562,6 +564,8 @@ struct vhr_context {
     int bvh_frame_mode = 1;                      // "bvh_frame": 1 (default) = the boxes in the frame that minimises the triangles' summed box area (csrc/bvh_frame.hpp; the world axes if none gains 5 %), 0 = world axes
     float bvh_frame[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 };      // the current tree's frame
     bool bvh_frame_on = false;
+    float bvh_frame_magnitude = 0.0f;      // HostBvh::frame_magnitude of the tree the context holds
+    uint64_t refit_beyond = 0;             // HostBvh::refit_beyond of the last refit (the rest of refit_stats[kRefitNonFinite] is non-finite)
     int bvh_presplit = 0;                        // "bvh_presplit": budget of extra triangle references in percent (csrc/presplit.hpp), 0 = off
     int bvh_presplit_level = -1;                 // the grid level the current tree's references were split on (-1: none)
     int bvh_builder = 1;                         // "bvh_builder": 1 = binned SAH on the device (csrc/kernels_bvh.hip, default), 0 = on the host (csrc/bvh_build.cpp)

@@ -42,7 +42,7 @@ EXPORTS = [
     "vhr_calibration_stream_read", "vhr_ray_query", "vhr_get_ray_query_statistics", "vhr_ray_query_struct_layout",
     "vhr_update_vertices", "vhr_update_primitive_transforms", "vhr_refit_geometry", "vhr_get_refit_statistics", "vhr_get_refit_times",
     "vhr_get_bvh_sah_cost", "vhr_refit_geometry_partial", "vhr_get_partial_refit_statistics",
-    "vhr_get_object_motion_statistics", "vhr_debug_triangle_records",
+    "vhr_get_object_motion_statistics", "vhr_debug_triangle_records", "vhr_debug_bvh_arrays",
     "vhr_set_primitive_masks", "vhr_get_primitive_masks", "vhr_ray_query_masked", "vhr_get_ray_mask_statistics",
     "vhr_closest_point_query", "vhr_get_point_query_statistics", "vhr_debug_point_triangle",
     "vhr_rebuild_geometry", "vhr_get_rebuild_statistics",
@@ -338,6 +338,7 @@ def load():
     L.vhr_rebuild_geometry.argtypes = [vp, u32]
     L.vhr_get_rebuild_statistics.argtypes = [vp, C.POINTER(u64)]
     L.vhr_debug_triangle_records.argtypes = [vp, i32, C.c_void_p, u32, C.POINTER(u32)]
+    L.vhr_debug_bvh_arrays.argtypes = [vp, C.POINTER(u32)] + [C.c_void_p] * 5 + [u32, u32, C.POINTER(u32)]
     L.vhr_set_kernel_timing.argtypes = [vp, i32]
     L.vhr_get_kernel_time.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(u64), i32]
     _lib = L
@@ -555,6 +556,23 @@ class Context:
             self.check(rc, "triangle_records")
         out = np.zeros((n.value, 9), np.float32)
         self.check(self.L.vhr_debug_triangle_records(self.handle, 1 if previous else 0, out.ctypes.data, n.value, C.byref(n)), "triangle_records")
+        return out
+
+    def bvh_arrays(self):
+        """vhr_debug_bvh_arrays: the tree as the walkers read it -- the raw bytes of the four node forms ((n, 64), (n, 64), (n, 48), (n, 32)
+        uint8) and of the leaf records in slot order ((m, 48) uint8), with the header's fields.  The library interprets none of it here."""
+        counts, header = (C.c_uint32 * 2)(), (C.c_uint32 * 24)()
+        rc = self.L.vhr_debug_bvh_arrays(self.handle, header, None, None, None, None, None, 0, 0, counts)      # the counts: "too small" while there is a tree
+        if rc != -1 or counts[0] == 0:
+            self.check(rc, "bvh_arrays")
+        n, m = int(counts[0]), int(counts[1])
+        out = {"nodes": np.zeros((n, 64), np.uint8), "nodes_ch": np.zeros((n, 64), np.uint8), "nodes48": np.zeros((n, 48), np.uint8),
+               "nodes16": np.zeros((n, 32), np.uint8), "records": np.zeros((m, 48), np.uint8)}
+        self.check(self.L.vhr_debug_bvh_arrays(self.handle, header, *[out[k].ctypes.data for k in ("nodes", "nodes_ch", "nodes48", "nodes16", "records")], n, m, counts),
+                   "bvh_arrays")
+        words = np.array(list(header), np.uint32)
+        out.update(centre=words[0:3].view(np.float32).copy(), frame=words[3:12].view(np.float32).copy(), frame_on=bool(words[12]), half_nodes=bool(words[13]),
+                   node_count=int(words[14]), record_count=int(words[15]), depth=int(words[16]), frame_magnitude=float(words[17:18].view(np.float32)[0]))
         return out
 
     def refit_statistics(self):
