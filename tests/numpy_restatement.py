@@ -338,8 +338,8 @@ def sample_linear_repeat(img, u, v):
 
 
 def _unproject(M, depth, u, v):
-    p = np.stack([u * 2.0 - 1.0, v * 2.0 - 1.0, depth, np.ones_like(depth)], -1) @ M.T
     with np.errstate(divide="ignore", invalid="ignore"):
+        p = np.stack([u * 2.0 - 1.0, v * 2.0 - 1.0, depth, np.ones_like(depth)], -1) @ M.T
         return p[..., :3] / p[..., 3:4]
 
 
@@ -347,31 +347,73 @@ def _fmax(a, b):          # IEEE maxNum: a NaN operand loses (oracle decision xi
     return np.fmax(a, b)
 
 
+def _ssao_centre(pfd, depth, radius):
+    """ssao.comp:15-29 of every pixel: (cu, cv, centre depth, P, the uv radius)."""
+    H, W = depth.shape
+    ys, xs = np.mgrid[0:H, 0:W]
+    inv = np.asarray(pfd["display_size_inverse"], np.float64)
+    cu, cv = xs * inv[0], ys * inv[1]                                   # :15, uv = pixel * display_size_inverse
+    cur = sample_linear_repeat(depth, cu, cv)
+    Pinv = _mat(pfd, "camera_proj_inverse")
+    P = _unproject(Pinv, cur, cu, cv)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        pr = radius / P[..., 2]
+    return cu, cv, cur, P, pr
+
+
+def _ssao_samples(pfd, cu, cv, pr):
+    """The 16 sample coordinates (su, sv) of every pixel, ssao.comp:32-39.  The seed is uint((y * uint(display_size.y) + x) * frame_index):
+    the product wraps at 2^32 (seed_thread_v masks it; the uint64 product of two numbers below 2^32 has not wrapped yet)."""
+    H, W = cu.shape
+    ys, xs = np.mgrid[0:H, 0:W]
+    rng = seed_thread_v((ys.astype(np.uint64) * np.uint64(int(pfd["display_size"][1])) + xs.astype(np.uint64)) * np.uint64(int(pfd["frame_index"])))
+    for _ in range(16):
+        rng, r1 = random01_v(rng)
+        rng, r2 = random01_v(rng)
+        with np.errstate(invalid="ignore", over="ignore"):
+            ang, dist = r1 * 2 * np.pi, r2 * pr
+            yield cu + np.cos(ang) * dist, cv + np.sin(ang) * dist
+
+
 def ssao(pfd, normals_bits, depth, radius=0.75):
     H, W = depth.shape
     depth = depth.astype(np.float64)
     nrm = h2f(normals_bits).astype(np.float64)
-    ys, xs = np.mgrid[0:H, 0:W]
-    inv = np.asarray(pfd["display_size_inverse"], np.float64)
-    cu, cv = xs * inv[0], ys * inv[1]
-    cur = sample_linear_repeat(depth, cu, cv)
+    cu, cv, cur, P, pr = _ssao_centre(pfd, depth, radius)
     Pinv = _mat(pfd, "camera_proj_inverse")
-    P = _unproject(Pinv, cur, cu, cv)
-    N = sample_linear_repeat(nrm, cu, cv)[..., :3] @ _mat(pfd, "camera_view")[:3, :3].T
-    with np.errstate(divide="ignore", invalid="ignore"):
-        pr = radius / P[..., 2]
-    rng = seed_thread_v((ys.astype(np.uint64) * np.uint64(int(pfd["display_size"][1])) + xs.astype(np.uint64)) * np.uint64(int(pfd["frame_index"])))
+    with np.errstate(invalid="ignore"):
+        N = sample_linear_repeat(nrm, cu, cv)[..., :3] @ _mat(pfd, "camera_view")[:3, :3].T
     total = np.zeros((H, W))
-    for _ in range(16):
-        rng, r1 = random01_v(rng)
-        rng, r2 = random01_v(rng)
-        ang, dist = r1 * 2 * np.pi, r2 * pr
-        su, sv = cu + np.cos(ang) * dist, cv + np.sin(ang) * dist
-        V = _unproject(Pinv, sample_linear_repeat(depth, su, sv), su, sv) - P
+    for su, sv in _ssao_samples(pfd, cu, cv, pr):
         with np.errstate(invalid="ignore", over="ignore"):
+            V = _unproject(Pinv, sample_linear_repeat(depth, su, sv), su, sv) - P
             total = total + _fmax((V * N).sum(-1) - 1e-4, 0.0) / ((V * V).sum(-1) + 1e-4)
-    ao = _fmax(1.0 - (2.0 / 16.0) * total, 0.0)
+    with np.errstate(invalid="ignore"):
+        ao = _fmax(1.0 - (2.0 / 16.0) * total, 0.0)
     return np.where(cur == 0.0, 0.0, ao)
+
+
+def ssao_sample_census(pfd, depth, radius=0.75):
+    """What the 16 x W x H sample coordinates of ssao.comp reach on these inputs (pixels that return early at :17-24 take no samples).  A
+    sample is counted once, by the worse of its two unnormalised coordinates t = u * W - 0.5 (v * H - 0.5):
+      wrapped    -- floor(t) is finite, converts to an int and lies more than two periods from the image (t < -2 W or t >= 3 W);
+      saturated  -- floor(t) is finite and at or beyond +-2^31: the float -> int conversion saturates (oracle decision xiii);
+      non_finite -- t is inf or NaN: the conversion gives INT_MAX, INT_MIN or 0 and the bilinear weights are NaN."""
+    H, W = depth.shape
+    cu, cv, cur, _, pr = _ssao_centre(pfd, depth.astype(np.float64), radius)
+    counts = dict(wrapped=0, saturated=0, non_finite=0, samples=0)
+    taken = cur != 0.0
+    for su, sv in _ssao_samples(pfd, cu, cv, pr):
+        with np.errstate(invalid="ignore", over="ignore"):
+            tx, ty = np.floor(su * W - 0.5), np.floor(sv * H - 0.5)
+            bad = ~(np.isfinite(tx) & np.isfinite(ty))
+            sat = ~bad & ((tx >= 2.0 ** 31) | (tx < -2.0 ** 31) | (ty >= 2.0 ** 31) | (ty < -2.0 ** 31))
+            far = ~bad & ~sat & ((tx < -2 * W) | (tx >= 3 * W) | (ty < -2 * H) | (ty >= 3 * H))
+        counts["wrapped"] += int((far & taken).sum())
+        counts["saturated"] += int((sat & taken).sum())
+        counts["non_finite"] += int((bad & taken).sum())
+        counts["samples"] += int(taken.sum())
+    return counts
 
 
 def ssao_blur_f32(raw_bits, display_w, display_h):
@@ -386,6 +428,23 @@ def ssao_blur_f32(raw_bits, display_w, display_h):
             mask &= ((xs + dx) < display_w) & ((ys + dy) < display_h)
             acc = np.where(mask, (acc + tap).astype(np.float32), acc)
     return (acc / np.float32(13.0 * 13.0)).astype(np.float32)
+
+
+def ssao_blur_exact(raw_bits, display_w, display_h):
+    """ssao_blur.comp:11-26 in float64: the sum of the taps inside the display (and the image), divided by 169.  The sum is EXACT whenever
+    its taps are finite -- an fp16 value is a multiple of 2^-24 below 2^16, and 169 of them need 48 of float64's 53 bits -- so the only
+    rounding is the division's; NaN and inf taps follow IEEE."""
+    H, W = raw_bits.shape[:2]
+    src = h2f(raw_bits[..., 0]).astype(np.float64)
+    ys, xs = np.mgrid[0:H, 0:W]
+    acc = np.zeros((H, W))
+    for dy in range(-6, 7):
+        for dx in range(-6, 7):
+            tap, mask = _shift(src, dx, dy)
+            mask &= ((xs + dx).astype(np.float32) < np.float32(display_w)) & ((ys + dy).astype(np.float32) < np.float32(display_h))
+            with np.errstate(invalid="ignore"):
+                acc = np.where(mask, acc + tap, acc)
+    return acc / 169.0
 
 
 def ssr(pfd, albedo_bgra8, normals_bits, motion_bits, depth, ray_distance=25.0, step_size=0.1, thickness=0.5, bsearch_steps=10):

@@ -4,7 +4,13 @@ ssao_blur.comp, ssr.comp (hybrid_render_path.cpp:138-243) and their use by compo
 CPU: the oracle against hand-derived values and against the independent float64 numpy restatement; the host graph.
 GPU (-m gpu): the HIP kernels through the C ABI against the oracle.  Bar: the kernels use the oracle's operation order
 with contraction off, so every RGBA16F texel is expected to be bit-identical; the tests allow ssao / ssr a last-place
-disagreement on < 0.1 % of the texels (none observed) and demand exact equality for the blur."""
+disagreement on < 0.1 % of the texels (none observed) and demand exact equality for the blur.
+
+The G-buffers here are rendered ones: images of 64x40 and more, display_size equal to the image, dispatches that cover it, an SSAO radius below
+0.27 uv.  The corners those inputs do not reach -- samples several periods out, the saturating float -> int conversion, NaN / inf texels, a
+display smaller than the image, images smaller than a block or the blur's window, partial dispatches, frame 0 -- are tests/screen_cases.py
+(the case families), tests/test_screen_cases.py (oracle against float64, no GPU) and tests/test_gpu_screen_cases.py (the kernels against
+float64 and the oracle)."""
 import numpy as np
 import pytest
 
