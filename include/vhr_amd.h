@@ -1015,6 +1015,30 @@ int vhr_get_point_query_statistics(vhr_context *ctx, uint64_t out[4]);
  * testable without a GPU, and the two are comparable, bit for bit, on one. */
 int vhr_debug_point_triangle(vhr_context *ctx, const float *pairs, uint32_t count, float *out);
 
+/* ---- Batched k-nearest queries on the scene's BVH: the k nearest triangles to a point, in order ----
+ * The CANDIDATES of a query are exactly those of vhr_closest_point_query (above): d2_i <= fl(max_distance * max_distance) by the same fp32
+ * point / triangle function, and (masks[primitive of i] & cull_mask) != 0; +inf bounds nothing, a negative or NaN max_distance and a non-finite
+ * point find nothing.  They are ORDERED by (d2, flat triangle index) ascending -- a total order, so the answer does not depend on the tree --
+ * and every triangle appears at most once, also on a "bvh_presplit" tree that holds several references to it.
+ *   - results = vhr_ray_hit[count * k], 1 <= k <= VHR_NEAREST_MAX_K; query q owns entries [q * k, q * k + k).  Entry j is the j-th candidate in
+ *     that order: t = the correctly rounded sqrtf(d2), (u, v) = the barycentrics the function settled on, geometry_index / primitive_index as in
+ *     a ray hit, reserved = 0.  Once the candidates run out every remaining entry is the miss record: both indices 0xFFFFFFFF, t = u = v = 0.
+ *   - k == 1 is vhr_closest_point_query without VHR_POINT_QUERY_ANY_WITHIN, bit for bit.
+ *   - Results equal, bit for bit, the brute force over all triangles in flat order: on either builder's tree, with "bvh_frame", "bvh_presplit",
+ *     any leaf size, after refits and a rebuild.  No alpha rule.  No frame state is read or written.
+ *   - Device pointers, streams and staging as vhr_closest_point_query's.  VHR_POINT_QUERY_HOST_MEMORY is the only flag
+ *     (VHR_POINT_QUERY_ANY_WITHIN is an unknown flag here).  count == 0 returns VHR_OK and launches nothing; a context without geometry
+ *     returns only miss records.
+ *   - VHR_ERROR_INVALID_ARGUMENT (message in vhr_last_error, with the entry point's name) for a NULL pointer with count > 0, an unknown flag
+ *     bit, `points` not 16-byte aligned, `results` not 4-byte aligned, cull_mask > 0xFF, k == 0 or k > VHR_NEAREST_MAX_K -- checked first, in that
+ *     order, on every context.  Then VHR_ERROR_NO_DEVICE on a host-only context, and VHR_ERROR_GRAPH while geometry updates are pending. */
+int vhr_nearest_points_query(vhr_context *ctx, const vhr_point_query *points, uint32_t count, uint32_t k, uint32_t flags, uint32_t cull_mask,
+                             vhr_ray_hit *results);
+/* The last vhr_nearest_points_query (waits for the device): out[0] = queries, out[1] = entries returned over all queries, out[2] = point /
+ * triangle evaluations of the walks (the one more per returned entry that recovers its (u, v) is not counted), out[3] = waves whose traversal
+ * stack overflowed (must be 0).  All 0 before the first call. */
+int vhr_get_nearest_query_statistics(vhr_context *ctx, uint64_t out[4]);
+
 /* ---- Ray face culling and the hit kind of ray queries (gl_RayFlagsCullBackFacingTrianglesEXT / gl_RayFlagsCullFrontFacingTrianglesEXT of
  *      rayQueryInitializeEXT; rayQueryGetIntersectionFrontFaceEXT, gl_HitKindFrontFacingTriangleEXT) ----
  * A triangle (v0, v1, v2) of primitive p is FRONT-FACING for a ray of direction d iff (det > 0) != flip[p], where det = e1 . (d x e2),

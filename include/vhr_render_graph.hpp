@@ -178,6 +178,12 @@ public:
     void QueryClosestPoints(const vhr_point_query *points, uint32_t count, uint32_t flags, void *results, uint32_t cull_mask = 0xFFu) {
         check(context.handle, vhr_closest_point_query(context.handle, points, count, flags, cull_mask, results), "QueryClosestPoints");
     }
+    // Extension: the k nearest triangles to each point, within its max_distance, ordered by (distance, flat triangle index), on the TLAS this
+    // manager owns (vhr_nearest_points_query).  1 <= k <= VHR_NEAREST_MAX_K; `flags` = 0 or VHR_POINT_QUERY_HOST_MEMORY; results =
+    // vhr_ray_hit[count * k], query q's entries at [q * k, q * k + k), miss records once its candidates run out; cull_mask as in QueryRays.
+    void QueryNearestPoints(const vhr_point_query *points, uint32_t count, uint32_t k, uint32_t flags, vhr_ray_hit *results, uint32_t cull_mask = 0xFFu) {
+        check(context.handle, vhr_nearest_points_query(context.handle, points, count, k, flags, cull_mask, results), "QueryNearestPoints");
+    }
     // Extension: the surface points of hits (vhr_resolve_hits) -- position, geometric and shading normal, uv and, with VHR_SURFACE_MATERIAL, what
     // gbuf.frag writes there -- from the scene arrays this manager owns.  `hits` as QueryRays and QueryClosestPoints return them; `flags` =
     // VHR_SURFACE_MATERIAL and / or VHR_SURFACE_HOST_MEMORY; `out` starts at a 16-byte boundary.  Device pointers: enqueued on the context's

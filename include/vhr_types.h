@@ -142,6 +142,7 @@ typedef struct vhr_point_query {
 } vhr_point_query;
 #define VHR_POINT_QUERY_ANY_WITHIN   1u   /* results: uint8_t[count], 1 = some surface lies within max_distance */
 #define VHR_POINT_QUERY_HOST_MEMORY  2u   /* host pointers, staged; returns with results in place */
+#define VHR_NEAREST_MAX_K 16u             /* vhr_nearest_points_query: the most entries a query returns (its list lives in LDS beside the stack) */
 
 /* The surface point of one hit (vhr_resolve_hits, include/vhr_amd.h).  80 bytes; an array of them must start at a 16-byte boundary (the kernel
  * writes a record as five 16-byte stores). */

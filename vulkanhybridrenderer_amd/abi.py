@@ -61,6 +61,7 @@ RAY_MISS = 0xFFFFFFFF              # vhr_ray_hit.geometry_index / primitive_inde
 # vhr_closest_point_query (include/vhr_types.h: vhr_point_query; its results are ray_hit_dtype with t = the distance, RAY_MISS = nothing found)
 point_query_dtype = np.dtype([("point", "<f4", 3), ("max_distance", "<f4")])
 POINT_QUERY_ANY_WITHIN, POINT_QUERY_HOST_MEMORY = 1, 2
+NEAREST_MAX_K = 16      # VHR_NEAREST_MAX_K: the largest k of vhr_nearest_points_query
 # vhr_ray_query_faces (include/vhr_types.h): its face_cull, and the hit kind it reports in vhr_ray_hit.reserved
 FACE_CULL_NONE, FACE_CULL_BACK, FACE_CULL_FRONT = 0, 1, 2
 HIT_KIND_FRONT_FACING, HIT_KIND_BACK_FACING = 0xFE, 0xFF

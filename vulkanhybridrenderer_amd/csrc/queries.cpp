@@ -1,4 +1,4 @@
-// Query half of the C ABI (include/vhr_amd.h): batched ray queries and closest-point queries on the scene's tree, the surface points of their
+// Query half of the C ABI (include/vhr_amd.h): batched ray queries, closest-point and k-nearest queries on the scene's tree, the surface points of their
 // hits (vhr_resolve_hits), their host-memory staging and statistics, and the pair entry points that run one shared function (ray / triangle, facing, point / triangle) on a list of inputs.
 #include <cstring>
 #include <string>
@@ -11,7 +11,7 @@
 using namespace vhr;
 
 void vhr::free_query_scratch(vhr_context *ctx) {
-    for (auto *all : { &ctx->rq_scratch, &ctx->pq_scratch, &ctx->sp_scratch })
+    for (auto *all : { &ctx->rq_scratch, &ctx->pq_scratch, &ctx->nq_scratch, &ctx->sp_scratch })
         for (QueryScratch &q : *all) { hipFree(q.counters); hipFree(q.list); }
     hipFree(ctx->d_rq_staging);
 }
@@ -157,6 +157,38 @@ int vhr_get_point_query_statistics(vhr_context *ctx, uint64_t out[4]) {
     PointQueryCounters c;
     VHR_TRY(read_last_counters(ctx, &c, ctx->pq_last_counters, sizeof(c)));
     out[0] = ctx->pq_queries; out[1] = c.found; out[2] = c.evaluations; out[3] = c.overflows;
+    return VHR_OK;
+}
+
+// vhr_nearest_points_query: the closest-point query's checks in its order, then k; staged the same way, k records per query out
+int vhr_nearest_points_query(vhr_context *ctx, const vhr_point_query *points, uint32_t count, uint32_t k, uint32_t flags, uint32_t cull_mask, vhr_ray_hit *results) {
+    if (!ctx) return VHR_ERROR_INVALID_ARGUMENT;
+    const std::string who("vhr_nearest_points_query");
+    if (count > 0 && (!points || !results)) return invalid(ctx, who + ": points and results must not be NULL when count > 0");
+    if (flags & ~uint32_t(VHR_POINT_QUERY_HOST_MEMORY)) return invalid(ctx, who + ": unknown flag bits " + std::to_string(flags));
+    if (misaligned(points, count, 16u)) return invalid(ctx, who + ": points must be 16-byte aligned");
+    if (misaligned(results, count, 4u)) return invalid(ctx, who + ": results must be 4-byte aligned");
+    if (cull_mask > 0xFFu) return invalid(ctx, who + ": cull_mask " + std::to_string(cull_mask) + " exceeds 0xFF");
+    if (k == 0 || k > VHR_NEAREST_MAX_K) return invalid(ctx, who + ": k " + std::to_string(k) + " is not in 1 .. VHR_NEAREST_MAX_K (" + std::to_string(VHR_NEAREST_MAX_K) + ")");
+    if (ctx->host_only) return ctx->fail(VHR_ERROR_NO_DEVICE, who + ": host-only context: no device work");
+    VHR_TRY(ctx->refuse_if_stale("vhr_nearest_points_query"));
+    if (count == 0) return VHR_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->nq_queries = count;
+    const auto enqueue = [&](const void *p, void *out, const void *) {
+        return vhr::launch_nearest_query(ctx, static_cast<const vhr_point_query *>(p), count, k, cull_mask, static_cast<vhr_ray_hit *>(out));
+    };
+    if (!(flags & VHR_POINT_QUERY_HOST_MEMORY)) return enqueue(points, results, nullptr);
+    return staged_call(ctx, points, uint64_t(count) * sizeof(vhr_point_query), nullptr, 0, results, uint64_t(count) * k * sizeof(vhr_ray_hit), enqueue);
+}
+
+int vhr_get_nearest_query_statistics(vhr_context *ctx, uint64_t out[4]) {
+    if (!ctx || !out) return VHR_ERROR_INVALID_ARGUMENT;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (ctx->host_only || ctx->nq_queries == 0 || !ctx->nq_last_counters) return VHR_OK;
+    NearestQueryCounters c;
+    VHR_TRY(read_last_counters(ctx, &c, ctx->nq_last_counters, sizeof(c)));
+    out[0] = ctx->nq_queries; out[1] = c.entries; out[2] = c.evaluations; out[3] = c.overflows;
     return VHR_OK;
 }
 

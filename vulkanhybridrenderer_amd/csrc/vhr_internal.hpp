@@ -383,6 +383,9 @@ struct QueryScratch { hipStream_t stream; void *counters; uint32_t *list; uint64
 // vhr_closest_point_query's counters (csrc/kernels_point_query.hip): queries that found something, point_triangle evaluations, waves whose stack
 // overflowed
 struct PointQueryCounters { unsigned long long found, evaluations; uint32_t overflows, pad; };
+// vhr_nearest_points_query's counters (csrc/kernels_point_query.hip): entries returned over all queries, point_triangle evaluations of the walks
+// (the one more per returned entry that recovers its (u, v) is not counted: it is `entries`), waves whose stack overflowed
+struct NearestQueryCounters { unsigned long long entries, evaluations; uint32_t overflows, pad; };
 // vhr_resolve_hits' counters (csrc/kernels_surface.hip): records with VHR_SURFACE_VALID, records with VHR_SURFACE_DISCARDED.  A set is
 // kSurfaceCounterSlots slots of one 64-byte line each, a wave adds to the slot of its block's index and vhr_get_surface_statistics sums them: a resolve is one wave per 64 hits and little work per hit, and that many adds to ONE address
 // queue up behind each other (measured: 16 384 waves' adds to one counter took 0.2 ms of a 2^20-hit call, whatever else the kernel did)
@@ -664,6 +667,10 @@ struct vhr_context {
     std::vector<vhr::QueryScratch> pq_scratch;
     const vhr::PointQueryCounters *pq_last_counters = nullptr;  // the last query's (vhr_get_point_query_statistics)
     uint64_t pq_queries = 0;            // queries of the last call (0: none yet)
+    // vhr_nearest_points_query: the same arrangement, its own counters
+    std::vector<vhr::QueryScratch> nq_scratch;
+    const vhr::NearestQueryCounters *nq_last_counters = nullptr;  // the last query's (vhr_get_nearest_query_statistics)
+    uint64_t nq_queries = 0;            // queries of the last call (0: none yet)
     // vhr_resolve_hits: counters per stream; VHR_SURFACE_HOST_MEMORY stages through d_rq_staging as the queries' host-memory paths do.  A host-only
     // context counts on the host (sp_host_counters)
     std::vector<vhr::QueryScratch> sp_scratch;
@@ -845,6 +852,9 @@ int launch_ray_facing_pairs(vhr_context *ctx, const float *pairs, const uint8_t 
 // query) are device memory; enqueued on ctx->stream.  vhr_debug_point_triangle on a device context: host arrays, 12 floats in and 3 out per pair
 int launch_point_query(vhr_context *ctx, const vhr_point_query *points, uint32_t count, bool any_within, uint32_t cull_mask, void *results);
 int launch_point_triangle_pairs(vhr_context *ctx, const float *pairs, uint32_t n, float *out);
+// vhr_nearest_points_query's device path (the same unit): `points` (count x vhr_point_query) and `results` (count * k x vhr_ray_hit) are device
+// memory, 1 <= k <= VHR_NEAREST_MAX_K; enqueued on ctx->stream
+int launch_nearest_query(vhr_context *ctx, const vhr_point_query *points, uint32_t count, uint32_t k, uint32_t cull_mask, vhr_ray_hit *results);
 // vhr_resolve_hits' device path (csrc/kernels_surface.hip): `hits` (count x vhr_ray_hit) and `out` (count x vhr_surface_point) are device memory;
 // enqueued on ctx->stream
 int launch_resolve_hits(vhr_context *ctx, const vhr_ray_hit *hits, uint32_t count, bool material, vhr_surface_point *out);

@@ -45,6 +45,7 @@ EXPORTS = [
     "vhr_get_object_motion_statistics", "vhr_debug_triangle_records", "vhr_debug_bvh_arrays",
     "vhr_set_primitive_masks", "vhr_get_primitive_masks", "vhr_ray_query_masked", "vhr_get_ray_mask_statistics",
     "vhr_closest_point_query", "vhr_get_point_query_statistics", "vhr_debug_point_triangle",
+    "vhr_nearest_points_query", "vhr_get_nearest_query_statistics",
     "vhr_rebuild_geometry", "vhr_get_rebuild_statistics",
     "vhr_ray_query_faces", "vhr_get_primitive_facing_flips", "vhr_get_face_cull_statistics", "vhr_debug_ray_facing",
     "vhr_resolve_hits", "vhr_get_surface_statistics", "vhr_surface_point_layout",
@@ -322,6 +323,8 @@ def load():
     L.vhr_ray_query_struct_layout.argtypes = [C.POINTER(u32)]
     L.vhr_closest_point_query.argtypes = [vp, vp, u32, u32, u32, vp]
     L.vhr_get_point_query_statistics.argtypes = [vp, C.POINTER(u64)]
+    L.vhr_nearest_points_query.argtypes = [vp, vp, u32, u32, u32, u32, vp]
+    L.vhr_get_nearest_query_statistics.argtypes = [vp, C.POINTER(u64)]
     L.vhr_debug_point_triangle.argtypes = [vp, C.c_void_p, u32, C.c_void_p]
     L.vhr_resolve_hits.argtypes = [vp, vp, u32, u32, vp]
     L.vhr_get_surface_statistics.argtypes = [vp, C.POINTER(u64)]
@@ -1001,6 +1004,28 @@ class Context:
     def point_query_statistics(self):
         """The last closest-point query: [queries, queries that found something, point / triangle evaluations, waves whose stack overflowed (must be 0)]."""
         return self._read("point_query_statistics", 4)
+
+    def nearest_points_query(self, points, k, cull_mask=None):
+        """vhr_nearest_points_query on host arrays: points as in closest_point_query(), 1 <= k <= abi.NEAREST_MAX_K.  Returns abi.ray_hit_dtype of
+        shape (n, k): row q holds query q's candidates ordered by (distance, flat triangle index), every triangle at most once, then records with
+        geometry_index = primitive_index = abi.RAY_MISS.  k == 1 is closest_point_query(), bit for bit."""
+        p = self._points_array(points)
+        n, k = len(p), int(k)
+        out = np.zeros((n, max(k, 0)), abi.ray_hit_dtype)
+        self.check(self.L.vhr_nearest_points_query(self.handle, p.ctypes.data if n else None, n, k, abi.POINT_QUERY_HOST_MEMORY, 0xFF if cull_mask is None else int(cull_mask),
+                                                   out.ctypes.data if n else None), "nearest_points_query")
+        return out
+
+    def nearest_points_query_device(self, points_ptr, count, k, results_ptr, cull_mask=None):
+        """vhr_nearest_points_query on device memory (e.g. torch tensors' data_ptr()): `count` vhr_point_query records at points_ptr (16-byte
+        aligned), count * k vhr_ray_hit records at results_ptr.  Enqueued on current_stream(); returns without synchronising."""
+        self.check(self.L.vhr_nearest_points_query(self.handle, points_ptr or None, int(count), int(k), 0, 0xFF if cull_mask is None else int(cull_mask),
+                                                   results_ptr or None), "nearest_points_query_device")
+
+    def nearest_query_statistics(self):
+        """The last nearest-points query: [queries, entries returned over all queries, point / triangle evaluations of the walks, waves whose stack
+        overflowed (must be 0)]."""
+        return self._read("nearest_query_statistics", 4)
 
     def resolve_hits(self, hits, material=False):
         """vhr_resolve_hits on host arrays: hits = abi.ray_hit_dtype[n], as ray_query() and closest_point_query() return them (only u, v,
