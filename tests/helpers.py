@@ -122,14 +122,18 @@ def ulp16_diff(a_bits, b_bits):
 class GpuSvgfHarness:
     """A graph of [producer] -> [SVGF compute pass with a caller-supplied body] -> [sink], for kernel-level tests."""
 
-    def __init__(self, W, H, body):
+    def __init__(self, W, H, body, options=None):
         self.W, self.H = W, H
         self.ctx = lib.Context(W, H)
         c = self.ctx
+        for key, value in (options or {}).items():          # (before build(): "frames_in_flight" is read there)
+            c.set_option(key, value)
         self.inputs = None
         F4, F2, D = abi.FORMAT_R16G16B16A16_SFLOAT, abi.FORMAT_R16G16_SFLOAT, abi.FORMAT_D32_SFLOAT
 
         def produce(ctx):
+            if self.inputs is None:          # the G-buffer of the frame before stays (an upload would wait for every stream)
+                return
             n, m, rt = self.inputs
             ctx.upload(lib.NORMALS, n)
             ctx.upload(lib.MOTION, m)
@@ -159,11 +163,19 @@ class GpuSvgfHarness:
         pc["atrous_step"] = step
         return pc
 
-    def run(self, pfd, inputs):
+    def alloc_images(self, **formats):
+        """More storage images of the context's extent, by name: alloc_images(c=FORMAT_..., m2=FORMAT_...)."""
+        for name, fmt in formats.items():
+            assert name not in self.images
+            self.images[name] = self.ctx.upload_new_storage_image(self.W, self.H, fmt)
+
+    def run(self, pfd, inputs, sync=True):
+        """One frame.  inputs None: the producer uploads nothing; sync False: the host does not wait for the frame."""
         self.inputs = inputs
         self.ctx.update_per_frame_ubo(0, pfd)
         self.ctx.execute(0, 0)
-        self.ctx.synchronize()
+        if sync:
+            self.ctx.synchronize()
 
     def close(self):
         self.ctx.close()

@@ -851,22 +851,43 @@ static bool async_candidate(vhr_context *ctx, const std::vector<SvgfCmd> &rec, s
     // first a-trous dispatch (which overwrites this dispatch's output).  The same for the normals: an earlier dispatch's `normals_out`.
     input_copy = nullptr;
     const void *fused_normals = nullptr;
+    // the normals are an input like `in`: a blit into the G-buffer image (the only command that can write a transient) ends every copy
+    // made before it, and behind the dispatch it keeps the dispatch in place (H19, H20)
+    auto writes_normals = [&](const SvgfCmd &c) {
+        const void *n = w.a.normals;
+        switch (c.kind) {
+            case SvgfCmd::Temporal: return c.t.integrated_out == n || static_cast<const void *>(c.t.moments_out) == n;
+            case SvgfCmd::Atrous: return c.a.out == n || c.a.out2 == n || c.a.normals_out == n;
+            default: return c.dst_base == n;
+        }
+    };
     for (size_t j = 0; j < k; ++j) {
         const SvgfCmd &c = rec[j];
-        if (c.kind == SvgfCmd::Atrous && c.a.normals == w.a.normals && c.a.normals_out && covers(rect_of(c.a), need_n)) fused_normals = c.a.normals_out;
+        if (writes_normals(c)) fused_normals = nullptr;
+        else if (c.kind == SvgfCmd::Atrous && c.a.normals == w.a.normals && c.a.normals_out && covers(rect_of(c.a), need_n)) fused_normals = c.a.normals_out;
         else if ((c.kind == SvgfCmd::Atrous && (c.a.out == fused_normals || c.a.out2 == fused_normals)) || (c.kind == SvgfCmd::Copy && c.dst_base == fused_normals) ||
                  (c.kind == SvgfCmd::Temporal && c.t.integrated_out == fused_normals)) fused_normals = nullptr;
-        if (c.kind == SvgfCmd::Atrous && c.a.out == w.a.in && c.a.out2 && covers(rect_of(c.a), need_in)) input_copy = c.a.out2;
-        else if (c.kind == SvgfCmd::Atrous && (c.a.out == input_copy || c.a.out2 == input_copy)) input_copy = nullptr;
-        else if (c.kind == SvgfCmd::Copy && c.dst_base == input_copy) input_copy = nullptr;
-        else if (c.kind == SvgfCmd::Temporal && c.t.integrated_out == input_copy) input_copy = nullptr;
+        // `input_copy` holds what `in` holds only while neither is written again: a command that writes `in` ends the copy (unless it is
+        // the a-trous dispatch that makes a new one), and so does every store into the copy itself -- a fused normals store included
+        // (tests/test_gpu_svgf_schedule.py: H10, H15)
+        if (c.kind == SvgfCmd::Atrous && c.a.out == w.a.in) input_copy = (c.a.out2 && covers(rect_of(c.a), need_in)) ? c.a.out2 : nullptr;
+        else if (c.kind == SvgfCmd::Atrous && (c.a.out2 == w.a.in || c.a.normals_out == w.a.in)) input_copy = nullptr;
+        else if (c.kind == SvgfCmd::Atrous && (c.a.out == input_copy || c.a.out2 == input_copy || c.a.normals_out == input_copy)) input_copy = nullptr;
+        else if (c.kind == SvgfCmd::Copy && (c.dst_base == input_copy || c.dst_base == w.a.in)) input_copy = nullptr;
+        else if (c.kind == SvgfCmd::Temporal && (c.t.integrated_out == input_copy || c.t.integrated_out == w.a.in)) input_copy = nullptr;
     }
+    // the dispatch itself writes `out`: a copy that lives there would be filtered in place, taps reading texels already stored (H17, H18)
+    if (fused_normals == w.a.out) fused_normals = nullptr;
+    if (input_copy == w.a.out) input_copy = nullptr;
     normals_copy = fused_normals;
     for (size_t j = k + 1; j < rec.size(); ++j) {
         const SvgfCmd &c = rec[j];
+        if (writes_normals(c)) return false;
         switch (c.kind) {
             case SvgfCmd::Temporal:
                 if (c.t.integrated_out == w.a.in || c.t.integrated_out == w.a.out || c.t.moments_out == static_cast<const void *>(w.a.in)) return false;
+                if (c.t.integrated_out == input_copy) input_copy = nullptr;                // svgf.comp overwrites a copy like any other command (H16)
+                if (c.t.integrated_out == normals_copy) normals_copy = nullptr;
                 break;
             case SvgfCmd::Atrous:
                 if (c.a.out == w.a.in || c.a.out == w.a.out || c.a.out2 == w.a.in || c.a.out2 == w.a.out) return false;
