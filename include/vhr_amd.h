@@ -1121,6 +1121,43 @@ int vhr_get_surface_statistics(vhr_context *ctx, uint64_t out[4]);
  * metallic, shading_normal, roughness, base_color and uv0.  Returns 8. */
 int vhr_surface_point_layout(uint32_t out[8]);
 
+/* ---- Hemisphere occlusion masks at surface points: raygen.rgen:44-55's AO rays at arbitrary points, `samples` of them, one bit each ----
+ * A QUERY POINT is a vhr_ray read differently: `origin` is where the rays start (the caller applies any normal bias), `direction` is the axis N
+ * of the hemisphere -- used as given and never normalised, exactly as raygen.rgen uses the rounded G-buffer normal -- and [tmin, tmax] is the
+ * interval of every ray of the point.  The array must be 16-byte aligned, as rays are.
+ * RAY (i, j) of point i, sample j < samples, 1 <= samples <= VHR_OCCLUSION_MAX_SAMPLES (64):
+ *     g     = i * samples + j                      (uint32_t arithmetic)
+ *     state = seed_thread(g ^ seed_thread(seed))   (common.glsl:47-55); a state of 0 is replaced by 0x9E3779B9 -- xorshift would stay at 0 for
+ *                                                  ever, and seed_thread is a bijection, so exactly one g per seed meets this
+ *     rnd1  = random01(state), rnd2 = random01(state)                (common.glsl:57-76)
+ *     d     = onb_transform(N, cosine_hemisphere(rnd1, rnd2))        (common.glsl:37-42, 80-93; the library's fixed-polynomial sin / cos)
+ *     ray   = { origin, tmin, d, tmax }
+ * every operation the render paths' own, individually rounded fp32.  Samples are keyed independently: ray (i, j) depends on (g, seed) only.
+ * THE ANSWER: bit j of occluded[i] is 1 iff vhr_ray_query_masked(..., VHR_RAY_QUERY_TERMINATE_ON_FIRST_HIT, cull_mask, NULL, ...) answers 1 for
+ * ray (i, j); bits `samples` and above are 0.  That sentence is the whole definition: decision (vi) with its binary64 re-decision, the mask rule
+ * and every degenerate case (a zero or NaN axis, tmin >= tmax, an infinite tmax) follow from it.  AO is 1 - popcount / samples; a bent normal is
+ * the caller's sum, over the clear bits, of the directions vhr_debug_occlusion_rays reports.  Results never depend on the tree.
+ *   - `flags`: VHR_OCCLUSION_HOST_MEMORY (2) is the only one -- host pointers, staged; the call returns with the masks in place.  Without it
+ *     `points` and `occluded` are device pointers and the work is enqueued on the stream vhr_get_current_stream reports, with no
+ *     synchronisation, between frames or inside a pass callback.  No frame state is read or written; scratch and counters are per stream.
+ *   - VHR_ERROR_INVALID_ARGUMENT (message in vhr_last_error, with the entry point's name) for, in this order: a NULL context; a NULL pointer
+ *     with count > 0; an unknown flag bit; `points` not 16-byte aligned; `occluded` not 8-byte aligned; cull_mask > 0xFF; samples == 0 or
+ *     samples > VHR_OCCLUSION_MAX_SAMPLES -- on every context.  Then VHR_ERROR_NO_DEVICE on a host-only context and VHR_ERROR_GRAPH while
+ *     geometry updates are pending.  count == 0 returns VHR_OK and launches nothing; a context without geometry returns all-zero masks.
+ *   - OUT OF SCOPE: the alpha rule (VHR_RAY_QUERY_ALPHA_TEST's bit is an unknown flag here); per-point masks and face culling; stratified or
+ *     caller-supplied sample sets; floating-point outputs -- a sum over rays that finish in any order is not reproducible, the mask is. */
+int vhr_occlusion_query(vhr_context *ctx, const vhr_ray *points, uint32_t count, uint32_t samples, uint32_t seed, uint32_t flags, uint32_t cull_mask,
+                        uint64_t *occluded);
+/* The last vhr_occlusion_query (waits for the device): out[0] = points, out[1] = occluded rays over all points, out[2] = points computed again
+ * in binary64 (decision (vi): all rays of a point with one self-contradicting candidate), out[3] = waves whose traversal stack overflowed (must
+ * be 0).  All 0 before the first call. */
+int vhr_get_occlusion_statistics(vhr_context *ctx, uint64_t out[4]);
+/* The rays themselves (host memory): the count * samples rays of `points`, point-major, ray (i, j) at out[i * samples + j].  A device context
+ * runs the device's copy of the generator, one ray per thread; a HOST-ONLY context runs the host's copy of the same source (as
+ * vhr_debug_point_triangle does): the generator is testable without a GPU, and the two are comparable, bit for bit, on one.
+ * VHR_ERROR_INVALID_ARGUMENT for a NULL pointer with count > 0 and for samples outside 1 .. VHR_OCCLUSION_MAX_SAMPLES. */
+int vhr_debug_occlusion_rays(vhr_context *ctx, const vhr_ray *points, uint32_t count, uint32_t samples, uint32_t seed, vhr_ray *out);
+
 #ifdef __cplusplus
 }
 #endif

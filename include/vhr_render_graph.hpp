@@ -191,6 +191,12 @@ public:
     void ResolveHits(const vhr_ray_hit *hits, uint32_t count, uint32_t flags, vhr_surface_point *out) {
         check(context.handle, vhr_resolve_hits(context.handle, hits, count, flags, out), "ResolveHits");
     }
+    // Extension: how open the hemisphere above each point is (vhr_occlusion_query): `points` are vhr_ray records read as (origin, tmin, axis, tmax),
+    // 1 <= samples <= VHR_OCCLUSION_MAX_SAMPLES cosine-distributed any-hit rays each, bit j of occluded[i] = ray (i, j) is occluded; `flags` = 0
+    // or VHR_OCCLUSION_HOST_MEMORY; cull_mask as in QueryRays.  ResolveHits' records make the points: origin = position + bias * geometric_normal.
+    void QueryOcclusion(const vhr_ray *points, uint32_t count, uint32_t samples, uint32_t seed, uint32_t flags, uint64_t *occluded, uint32_t cull_mask = 0xFFu) {
+        check(context.handle, vhr_occlusion_query(context.handle, points, count, samples, seed, flags, cull_mask, occluded), "QueryOcclusion");
+    }
     // Extension: per-primitive ray cull masks (VkAccelerationStructureInstanceKHR::mask, per geometry; 0xFF after UpdateGeometry).  No refit needed.
     void SetPrimitiveMasks(uint32_t first_primitive, const std::vector<uint8_t> &masks) {
         check(context.handle, vhr_set_primitive_masks(context.handle, first_primitive, uint32_t(masks.size()), masks.data()), "SetPrimitiveMasks");

@@ -144,6 +144,10 @@ typedef struct vhr_point_query {
 #define VHR_POINT_QUERY_HOST_MEMORY  2u   /* host pointers, staged; returns with results in place */
 #define VHR_NEAREST_MAX_K 16u             /* vhr_nearest_points_query: the most entries a query returns (its list lives in LDS beside the stack) */
 
+/* vhr_occlusion_query (include/vhr_amd.h): its one flag, and the most rays per point (a point's answer is one 64-bit mask) */
+#define VHR_OCCLUSION_HOST_MEMORY  2u    /* host pointers, staged; returns with the masks in place */
+#define VHR_OCCLUSION_MAX_SAMPLES 64u
+
 /* The surface point of one hit (vhr_resolve_hits, include/vhr_amd.h).  80 bytes; an array of them must start at a 16-byte boundary (the kernel
  * writes a record as five 16-byte stores). */
 typedef struct vhr_surface_point {

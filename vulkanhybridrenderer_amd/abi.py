@@ -62,6 +62,9 @@ RAY_MISS = 0xFFFFFFFF              # vhr_ray_hit.geometry_index / primitive_inde
 point_query_dtype = np.dtype([("point", "<f4", 3), ("max_distance", "<f4")])
 POINT_QUERY_ANY_WITHIN, POINT_QUERY_HOST_MEMORY = 1, 2
 NEAREST_MAX_K = 16      # VHR_NEAREST_MAX_K: the largest k of vhr_nearest_points_query
+# vhr_occlusion_query (include/vhr_types.h): its one flag and the most rays per point; query points are ray_dtype (origin, tmin, axis, tmax)
+OCCLUSION_HOST_MEMORY = 2
+OCCLUSION_MAX_SAMPLES = 64      # VHR_OCCLUSION_MAX_SAMPLES
 # vhr_ray_query_faces (include/vhr_types.h): its face_cull, and the hit kind it reports in vhr_ray_hit.reserved
 FACE_CULL_NONE, FACE_CULL_BACK, FACE_CULL_FRONT = 0, 1, 2
 HIT_KIND_FRONT_FACING, HIT_KIND_BACK_FACING = 0xFE, 0xFF

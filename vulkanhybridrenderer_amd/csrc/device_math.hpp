@@ -11,6 +11,7 @@
 #include <hip/hip_fp16.h>
 
 #include <cstdint>
+#include <cstring>
 
 namespace vhr {
 
@@ -55,7 +56,8 @@ __device__ __forceinline__ float half_bits_to_float(uint16_t h) { return __half2
 __device__ __forceinline__ uint16_t float_to_half_bits(float f) { asm("" : "+v"(f)); return __half_as_ushort(__float2half_rn(f)); }
 
 // ---- data/shaders/common.glsl:47-76 RNG (integer exact) ----
-__device__ __forceinline__ uint32_t seed_thread(uint32_t seed) {
+// (these three, exact_sincos, cosine_hemisphere and onb_transform are qualified for the host too: occlusion_rays.hpp runs them in queries.cpp)
+__host__ __device__ __forceinline__ uint32_t seed_thread(uint32_t seed) {
     seed = (seed ^ 61u) ^ (seed >> 16);
     seed *= 9u;
     seed = seed ^ (seed >> 4);
@@ -63,19 +65,26 @@ __device__ __forceinline__ uint32_t seed_thread(uint32_t seed) {
     seed = seed ^ (seed >> 15);
     return seed;
 }
-__device__ __forceinline__ uint32_t xorshift(uint32_t &state) {
+__host__ __device__ __forceinline__ uint32_t xorshift(uint32_t &state) {
     state ^= (state << 13);
     state ^= (state >> 17);
     state ^= (state << 5);
     return state;
 }
-__device__ __forceinline__ float random01(uint32_t &state) {
-    return __uint_as_float(0x3f800000u | (xorshift(state) >> 9)) - 1.0f;
+__host__ __device__ __forceinline__ float random01(uint32_t &state) {
+    const uint32_t bits = 0x3f800000u | (xorshift(state) >> 9);
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __uint_as_float(bits) - 1.0f;
+#else
+    float f;                               // (the host's copy: occlusion_rays.hpp)
+    std::memcpy(&f, &bits, sizeof(f));
+    return f - 1.0f;
+#endif
 }
 
 // ---- sin/cos on [0, 2*pi]: quadrant reduction (3-term Cody-Waite split of pi/2) + Cephes minimax
 //      polynomials on [-pi/4, pi/4]; every operation individually rounded ----
-__device__ __forceinline__ void exact_sincos(float phi, float &s_out, float &c_out) {
+__host__ __device__ __forceinline__ void exact_sincos(float phi, float &s_out, float &c_out) {
     float k = rintf(phi * 0.636619772367581343f);
     float r = ((phi - k * 1.5703125f) - k * 4.837512969970703125e-4f) - k * 7.54978995489188e-8f;
     float z = r * r;
@@ -104,14 +113,14 @@ __device__ __forceinline__ f3 uniform_sample_cone(float ux, float uy, float cos_
     return f3{ c * sin_theta, s * sin_theta, cos_theta };
 }
 // common.glsl:37-42
-__device__ __forceinline__ f3 cosine_hemisphere(float ux, float uy) {
+__host__ __device__ __forceinline__ f3 cosine_hemisphere(float ux, float uy) {
     float s, c;
     exact_sincos(VHR_TWO_PI * uy, s, c);
     float sq = sqrtf(ux);
     return f3{ sq * c, sq * s, sqrtf(1.0f - ux) };
 }
 // common.glsl:80-93 Frisvad basis; returns R * v for R = onb_from_unit_vector(n)
-__device__ __forceinline__ f3 onb_transform(f3 n, f3 v) {
+__host__ __device__ __forceinline__ f3 onb_transform(f3 n, f3 v) {
     f3 c0, c1;
     if (n.z < -0.9999999f) {
         c0 = f3{ 0.0f, -1.0f, 0.0f };

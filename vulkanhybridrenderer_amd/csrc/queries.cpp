@@ -1,17 +1,18 @@
 // Query half of the C ABI (include/vhr_amd.h): batched ray queries, closest-point and k-nearest queries on the scene's tree, the surface points of their
-// hits (vhr_resolve_hits), their host-memory staging and statistics, and the pair entry points that run one shared function (ray / triangle, facing, point / triangle) on a list of inputs.
+// hits (vhr_resolve_hits), hemisphere occlusion masks at such points (vhr_occlusion_query), their host-memory staging and statistics, and the pair entry points that run one shared function (ray / triangle, facing, point / triangle) on a list of inputs.
 #include <cstring>
 #include <string>
 
 #include "vhr_internal.hpp"
 #include "closest_point.hpp"  // point_triangle's host copy (vhr_debug_point_triangle on a host-only context)
+#include "occlusion_rays.hpp" // occlusion_ray's host copy (vhr_debug_occlusion_rays on a host-only context)
 #include "ray_facing.hpp"     // ray_hit_kind's host copy (vhr_debug_ray_facing on a host-only context)
 #include "surface_point.hpp"  // surface_geometry's host copy (vhr_resolve_hits on a host-only context)
 
 using namespace vhr;
 
 void vhr::free_query_scratch(vhr_context *ctx) {
-    for (auto *all : { &ctx->rq_scratch, &ctx->pq_scratch, &ctx->nq_scratch, &ctx->sp_scratch })
+    for (auto *all : { &ctx->rq_scratch, &ctx->pq_scratch, &ctx->nq_scratch, &ctx->sp_scratch, &ctx->oq_scratch })
         for (QueryScratch &q : *all) { hipFree(q.counters); hipFree(q.list); }
     hipFree(ctx->d_rq_staging);
 }
@@ -263,6 +264,59 @@ int vhr_get_surface_statistics(vhr_context *ctx, uint64_t out[4]) {
         for (const SurfaceCounters &slot : slots) { c.valid += slot.valid; c.discarded += slot.discarded; }
     }
     out[0] = ctx->sp_hits; out[1] = c.valid; out[2] = c.discarded; out[3] = ctx->sp_material ? 1u : 0u;
+    return VHR_OK;
+}
+
+// vhr_occlusion_query: the arguments first, in the contract's order (the same answer on every context), then the device; staged like the queries' host paths
+int vhr_occlusion_query(vhr_context *ctx, const vhr_ray *points, uint32_t count, uint32_t samples, uint32_t seed, uint32_t flags, uint32_t cull_mask, uint64_t *occluded) {
+    if (!ctx) return VHR_ERROR_INVALID_ARGUMENT;
+    const std::string who("vhr_occlusion_query");
+    if (count > 0 && (!points || !occluded)) return invalid(ctx, who + ": points and occluded must not be NULL when count > 0");
+    if (flags & ~uint32_t(VHR_OCCLUSION_HOST_MEMORY)) return invalid(ctx, who + ": unknown flag bits " + std::to_string(flags));
+    if (misaligned(points, count, 16u)) return invalid(ctx, who + ": points must be 16-byte aligned");
+    if (misaligned(occluded, count, 8u)) return invalid(ctx, who + ": occluded must be 8-byte aligned");
+    if (cull_mask > 0xFFu) return invalid(ctx, who + ": cull_mask " + std::to_string(cull_mask) + " exceeds 0xFF");
+    if (samples == 0 || samples > VHR_OCCLUSION_MAX_SAMPLES)
+        return invalid(ctx, who + ": samples " + std::to_string(samples) + " is not in 1 .. VHR_OCCLUSION_MAX_SAMPLES (" + std::to_string(VHR_OCCLUSION_MAX_SAMPLES) + ")");
+    if (ctx->host_only) return ctx->fail(VHR_ERROR_NO_DEVICE, who + ": host-only context: no device work");
+    VHR_TRY(ctx->refuse_if_stale("vhr_occlusion_query"));
+    if (count == 0) return VHR_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->oq_points = count;
+    const auto enqueue = [&](const void *p, void *out, const void *) {
+        return vhr::launch_occlusion_query(ctx, static_cast<const vhr_ray *>(p), count, samples, seed, cull_mask, static_cast<uint64_t *>(out));
+    };
+    if (!(flags & VHR_OCCLUSION_HOST_MEMORY)) return enqueue(points, occluded, nullptr);
+    return staged_call(ctx, points, uint64_t(count) * sizeof(vhr_ray), nullptr, 0, occluded, uint64_t(count) * sizeof(uint64_t), enqueue);
+}
+
+int vhr_get_occlusion_statistics(vhr_context *ctx, uint64_t out[4]) {
+    if (!ctx || !out) return VHR_ERROR_INVALID_ARGUMENT;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (ctx->host_only || ctx->oq_points == 0 || !ctx->oq_last_counters) return VHR_OK;
+    OcclusionCounters c;
+    VHR_TRY(read_last_counters(ctx, &c, ctx->oq_last_counters, sizeof(c)));
+    out[0] = ctx->oq_points; out[1] = c.occluded; out[2] = c.redo_count; out[3] = c.overflows;
+    return VHR_OK;
+}
+
+// a device context runs the device's copy of occlusion_ray, a host-only context the host's: one source (occlusion_rays.hpp)
+int vhr_debug_occlusion_rays(vhr_context *ctx, const vhr_ray *points, uint32_t count, uint32_t samples, uint32_t seed, vhr_ray *out) {
+    if (!ctx) return VHR_ERROR_INVALID_ARGUMENT;
+    if (count && (!points || !out)) return invalid(ctx, "vhr_debug_occlusion_rays: null argument");
+    if (samples == 0 || samples > VHR_OCCLUSION_MAX_SAMPLES)
+        return invalid(ctx, "vhr_debug_occlusion_rays: samples " + std::to_string(samples) + " is not in 1 .. VHR_OCCLUSION_MAX_SAMPLES (" + std::to_string(VHR_OCCLUSION_MAX_SAMPLES) + ")");
+    if (!ctx->host_only) return launch_occlusion_rays(ctx, points, count, samples, seed, out);
+    for (uint32_t i = 0; i < count; ++i) {
+        const vhr_ray &p = points[i];
+        const OcclusionRay point{ f3{ p.origin[0], p.origin[1], p.origin[2] }, p.tmin, f3{ p.direction[0], p.direction[1], p.direction[2] }, p.tmax };
+        for (uint32_t j = 0; j < samples; ++j) {
+            const OcclusionRay r = occlusion_ray(point, i, j, samples, seed);
+            vhr_ray &o = out[size_t(i) * samples + j];
+            o.origin[0] = r.o.x; o.origin[1] = r.o.y; o.origin[2] = r.o.z; o.tmin = r.tmin;
+            o.direction[0] = r.d.x; o.direction[1] = r.d.y; o.direction[2] = r.d.z; o.tmax = r.tmax;
+        }
+    }
     return VHR_OK;
 }
 

@@ -386,6 +386,9 @@ struct PointQueryCounters { unsigned long long found, evaluations; uint32_t over
 // vhr_nearest_points_query's counters (csrc/kernels_point_query.hip): entries returned over all queries, point_triangle evaluations of the walks
 // (the one more per returned entry that recovers its (u, v) is not counted: it is `entries`), waves whose stack overflowed
 struct NearestQueryCounters { unsigned long long entries, evaluations; uint32_t overflows, pad; };
+// vhr_occlusion_query's counters (csrc/kernels_occlusion.hip): points the binary64 launch computed again (= entries of the redo list, which holds
+// points there), waves whose stack overflowed, occluded rays over all points
+struct OcclusionCounters { uint32_t redo_count, overflows; unsigned long long occluded; };
 // vhr_resolve_hits' counters (csrc/kernels_surface.hip): records with VHR_SURFACE_VALID, records with VHR_SURFACE_DISCARDED.  A set is
 // kSurfaceCounterSlots slots of one 64-byte line each, a wave adds to the slot of its block's index and vhr_get_surface_statistics sums them: a resolve is one wave per 64 hits and little work per hit, and that many adds to ONE address
 // queue up behind each other (measured: 16 384 waves' adds to one counter took 0.2 ms of a 2^20-hit call, whatever else the kernel did)
@@ -671,6 +674,11 @@ struct vhr_context {
     std::vector<vhr::QueryScratch> nq_scratch;
     const vhr::NearestQueryCounters *nq_last_counters = nullptr;  // the last query's (vhr_get_nearest_query_statistics)
     uint64_t nq_queries = 0;            // queries of the last call (0: none yet)
+    // vhr_occlusion_query: counters and the list of points for the binary64 launch per stream, as the ray query's
+    std::vector<vhr::QueryScratch> oq_scratch;
+    const vhr::OcclusionCounters *oq_last_counters = nullptr;     // the last call's (vhr_get_occlusion_statistics)
+    uint64_t oq_points = 0;             // points of the last call (0: none yet)
+    uint32_t oq_mask_ran = 0;           // ... and whether it launched the filtering kernels
     // vhr_resolve_hits: counters per stream; VHR_SURFACE_HOST_MEMORY stages through d_rq_staging as the queries' host-memory paths do.  A host-only
     // context counts on the host (sp_host_counters)
     std::vector<vhr::QueryScratch> sp_scratch;
@@ -858,6 +866,11 @@ int launch_nearest_query(vhr_context *ctx, const vhr_point_query *points, uint32
 // vhr_resolve_hits' device path (csrc/kernels_surface.hip): `hits` (count x vhr_ray_hit) and `out` (count x vhr_surface_point) are device memory;
 // enqueued on ctx->stream
 int launch_resolve_hits(vhr_context *ctx, const vhr_ray_hit *hits, uint32_t count, bool material, vhr_surface_point *out);
+// vhr_occlusion_query's device path (csrc/kernels_occlusion.hip): `points` (count x vhr_ray, read as query points) and `occluded` (count x
+// uint64_t) are device memory, 1 <= samples <= VHR_OCCLUSION_MAX_SAMPLES; enqueued on ctx->stream.  vhr_debug_occlusion_rays on a device
+// context: host arrays, count points in and count * samples rays out
+int launch_occlusion_query(vhr_context *ctx, const vhr_ray *points, uint32_t count, uint32_t samples, uint32_t seed, uint32_t cull_mask, uint64_t *occluded);
+int launch_occlusion_rays(vhr_context *ctx, const vhr_ray *points, uint32_t count, uint32_t samples, uint32_t seed, vhr_ray *out);
 // the primitives' mask bytes on the device (made, from h_prim_masks or as all-0xFF, if no call has made them yet): before a launch that filters
 int ensure_device_prim_masks(vhr_context *ctx);
 // the primitives' facing-flip bytes on the device (made from h_prim_flips if no launch has made them yet): before a launch of the face instantiation

@@ -49,6 +49,7 @@ EXPORTS = [
     "vhr_rebuild_geometry", "vhr_get_rebuild_statistics",
     "vhr_ray_query_faces", "vhr_get_primitive_facing_flips", "vhr_get_face_cull_statistics", "vhr_debug_ray_facing",
     "vhr_resolve_hits", "vhr_get_surface_statistics", "vhr_surface_point_layout",
+    "vhr_occlusion_query", "vhr_get_occlusion_statistics", "vhr_debug_occlusion_rays",
 ]
 
 PATH_PREFIXES = ("hybrid", "raytraced", "rayquery", "forward_raster")      # vhr_<prefix>_{create,destroy,build,rebuild,last_error}
@@ -328,6 +329,9 @@ def load():
     L.vhr_debug_point_triangle.argtypes = [vp, C.c_void_p, u32, C.c_void_p]
     L.vhr_resolve_hits.argtypes = [vp, vp, u32, u32, vp]
     L.vhr_get_surface_statistics.argtypes = [vp, C.POINTER(u64)]
+    L.vhr_occlusion_query.argtypes = [vp, vp, u32, u32, u32, u32, u32, vp]
+    L.vhr_get_occlusion_statistics.argtypes = [vp, C.POINTER(u64)]
+    L.vhr_debug_occlusion_rays.argtypes = [vp, vp, u32, u32, u32, vp]
     L.vhr_surface_point_layout.argtypes = [C.POINTER(u32)]
     L.vhr_update_vertices.argtypes = [vp, u32, u32, vp, u32]
     L.vhr_update_primitive_transforms.argtypes = [vp, u32, u32, vp]
@@ -1048,6 +1052,42 @@ class Context:
     def surface_statistics(self):
         """The last resolve_hits: [hits, records with SURFACE_VALID, records with SURFACE_DISCARDED, 1 if the material instantiation ran]."""
         return self._read("surface_statistics", 4)
+
+    @staticmethod
+    def _occlusion_points_array(points):
+        """(n, 8) float32 (origin, tmin, axis, tmax) or abi.ray_dtype -> a C-contiguous, 16-byte-aligned ray_dtype array."""
+        return Context._records_array(points, abi.ray_dtype, 8, ("occlusion_query", "points", "ray_dtype"))
+
+    def occlusion_query(self, points, samples, seed=0, cull_mask=None):
+        """vhr_occlusion_query on host arrays: points (n, 8) float32 or abi.ray_dtype, read as (origin, tmin, axis, tmax); 1 <= samples <=
+        abi.OCCLUSION_MAX_SAMPLES cosine-distributed any-hit rays around each axis.  Returns uint64[n]: bit j of entry i = ray (i, j) is
+        occluded, bits from `samples` up are 0 (AO = 1 - popcount / samples).  cull_mask (0..255, default 0xFF) as in ray_query()."""
+        p = self._occlusion_points_array(points)
+        n = len(p)
+        out = np.zeros(n, np.uint64)
+        self.check(self.L.vhr_occlusion_query(self.handle, p.ctypes.data if n else None, n, int(samples), int(seed) & 0xFFFFFFFF, abi.OCCLUSION_HOST_MEMORY,
+                                              0xFF if cull_mask is None else int(cull_mask), out.ctypes.data if n else None), "occlusion_query")
+        return out
+
+    def occlusion_query_device(self, points_ptr, count, samples, occluded_ptr, seed=0, cull_mask=None):
+        """vhr_occlusion_query on device memory (e.g. torch tensors' data_ptr()): `count` query points at points_ptr (16-byte aligned), one
+        uint64 mask per point at occluded_ptr (8-byte aligned).  Enqueued on current_stream(); returns without synchronising."""
+        self.check(self.L.vhr_occlusion_query(self.handle, points_ptr or None, int(count), int(samples), int(seed) & 0xFFFFFFFF, 0,
+                                              0xFF if cull_mask is None else int(cull_mask), occluded_ptr or None), "occlusion_query_device")
+
+    def occlusion_statistics(self):
+        """The last occlusion query: [points, occluded rays over all points, points computed again in binary64, waves whose stack overflowed
+        (must be 0)]."""
+        return self._read("occlusion_statistics", 4)
+
+    def debug_occlusion_rays(self, points, samples, seed=0):
+        """The rays occlusion_query() walks: points as there -> (n, samples, 8) float32 (origin, tmin, direction, tmax), ray (i, j) at [i, j].  A
+        device context runs the device's copy of the generator, a host-only context the host's."""
+        p = self._occlusion_points_array(points)
+        n, samples = len(p), int(samples)
+        out = self._aligned_zeros(n * max(samples, 0), abi.ray_dtype)
+        self.check(self.L.vhr_debug_occlusion_rays(self.handle, p.ctypes.data if n else None, n, samples, int(seed) & 0xFFFFFFFF, out.ctypes.data if n else None), "debug_occlusion_rays")
+        return out.view(np.float32).reshape(n, max(samples, 0), 8)
 
     def debug_point_triangle(self, pairs):
         """The query's point / triangle function on explicit pairs: pairs = (n, 12) float32 (p, v0, e1, e2) -> (n, 3) float32 (d2, u, v).  A device

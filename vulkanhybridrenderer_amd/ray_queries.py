@@ -67,3 +67,18 @@ def random_rays(rng, n, lo, hi, margin=0.25, tmins=(0.0,), tmaxs=(np.inf,)):
     rays[:, 3] = rng.choice(np.asarray(tmins, np.float32), n)
     rays[:, 7] = rng.choice(np.asarray(tmaxs, np.float32), n)
     return rays
+
+
+def occlusion_points(surface_points, bias=0.1, tmin=0.01, tmax=5.0):
+    """Query points for Context.occlusion_query from abi.surface_point_dtype records (Context.resolve_hits): origin = position + bias *
+    geometric normal (fp32, the product rounded before the sum), axis = the geometric normal, [tmin, tmax] for every ray of the point.  The
+    defaults are abi.default_trace_params()' normal_bias, tmin and ao_tmax.  Records that were not resolved (flags == 0) give points whose rays
+    can hit nothing (tmax = -1).  Returns (n, 8) float32."""
+    sp = np.asarray(surface_points)
+    n = np.asarray(sp["geometric_normal"], np.float32)
+    pts = np.empty((len(sp), 8), np.float32)
+    pts[:, 0:3] = np.asarray(sp["position"], np.float32) + np.float32(bias) * n
+    pts[:, 3] = tmin
+    pts[:, 4:7] = n
+    pts[:, 7] = np.where(sp["flags"] & abi.SURFACE_VALID, np.float32(tmax), np.float32(-1.0))
+    return pts
