@@ -345,12 +345,17 @@ int vhr_standin_shadow_map(vhr_context *ctx, uint32_t resource_idx, const char *
  * composition.frag:60-161: shadows ray traced (0), from the shadow map with the shader's 16-tap PCF (1, :81-107) or off (2);
  * ambient occlusion and reflections ray traced (0), screen space (1: ssao.comp + ssao_blur.comp / ssr.comp, row f4) or
  * off (2).  Reads the named transient images, writes swapchain-format texels (B8G8R8A8_SRGB, bytes
- * b g r a, presentation orientation: row 0 = top) into a storage image of 4-byte texels. */
+ * b g r a, presentation orientation: row 0 = top) into a storage image of 4-byte texels.
+ * Refused with VHR_ERROR_INVALID_ARGUMENT, nothing launched: image extents that differ from the depth image's, formats other than
+ * 4-byte texels (albedo, output), R16G16B16A16_SFLOAT (normals, motion, ssao), D32_SFLOAT (depth, shadow map) and R16G16_SFLOAT or
+ * R16G16B16A16_SFLOAT (shadow_ao), a mode outside 0 .. 2, shadow_mode 1 without a square D32 shadow map, ambient_occlusion_mode 1 without
+ * ssao, and reflection_mode 0 or 1 without a reflections image: the blend of composition.frag:139-156 is never skipped silently (the
+ * kernel itself would skip it).  These checks follow the host-only refusal (VHR_ERROR_NO_DEVICE) and the image look-up (VHR_ERROR_NOT_FOUND). */
 typedef struct vhr_composition_desc {
     int32_t shadow_mode, ambient_occlusion_mode, reflection_mode;      /* the three specialization constants, :6-8 */
     const char *albedo_image, *normals_image, *motion_image, *depth_image;
     const char *shadow_ao_image;      /* "Denoised Raytraced Shadows and Ambient Occlusion" or the raw RG16F image (:353-355) */
-    const char *reflections_image;    /* "Raytraced Reflections" (mode 0) / "Screen Space Reflections" (mode 1); may be NULL for mode 2 */
+    const char *reflections_image;    /* "Raytraced Reflections" (mode 0) / "Screen Space Reflections" (mode 1); may be NULL for mode 2 only */
     int32_t output_storage_image;
     const char *ssao_image;           /* "Screen Space Ambient Occlusion" for ambient_occlusion_mode 1, else may be NULL */
     const char *shadow_map_image;     /* "Shadow Map" (square D32_SFLOAT) for shadow_mode 1, else may be NULL */

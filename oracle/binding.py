@@ -73,6 +73,7 @@ def lib():
         L.orc_gbuffer.argtypes = [vp, vp, u32, u32, vp, vp, vp]
         L.orc_gbuffer_albedo.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
         L.orc_composition.argtypes = [vp, u32, u32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, u32, vp]
+        L.orc_composition_lit.argtypes = L.orc_composition.argtypes + [vp]
         L.orc_shadow_map.argtypes = [vp, vp, u32, u32, u32, vp, i32]
         L.orc_raygen.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp, i32]
         L.orc_raytraced.argtypes = [vp, vp, u32, u32, u32, u32, i32, vp, vp, i32]
@@ -229,18 +230,24 @@ def raytraced_composition(raytraced_bgra8):
     return out
 
 
-def composition(pfd, modes, albedo, normals, motion, depth, shadow_ao, reflections, ssao=None, shadow_map=None):
-    """composition.frag with (shadow_mode, ao_mode, reflection_mode); returns B8G8R8A8_SRGB texels (H, W, 4)."""
+def composition(pfd, modes, albedo, normals, motion, depth, shadow_ao, reflections, ssao=None, shadow_map=None, with_lighting=False):
+    """composition.frag with (shadow_mode, ao_mode, reflection_mode); returns B8G8R8A8_SRGB texels (H, W, 4) -- with_lighting: and the fp32
+    lighting before the store, (H, W, 3) r g b in the same orientation.  reflection_mode 0 / 1 without a reflections image is refused, as
+    vhr_standin_composition refuses it (VHR_ERROR_INVALID_ARGUMENT); under reflection_mode 2 the image is never read and may be None."""
     H, W = depth.shape
+    if reflections is None and modes[2] in (0, 1):
+        raise ValueError("composition: reflection_mode 0 / 1 needs a reflections image")
     out = np.zeros((H, W, 4), np.uint8)
+    lighting = np.zeros((H, W, 3), np.float32) if with_lighting else None
     pfd = _c(pfd)
     albedo, normals, motion = _c(albedo, np.uint8), _c(normals, np.uint16), _c(motion, np.uint16)
     depth, shadow_ao = _c(depth, np.float32), _c(shadow_ao, np.uint16)
-    reflections = _c(reflections, np.uint16) if reflections is not None else np.zeros((H, W, 4), np.uint16)
-    lib().orc_composition(_p(pfd), W, H, modes[0], modes[1], modes[2], _p(albedo), _p(normals), _p(motion), _p(depth), _p(shadow_ao),
-                          shadow_ao.shape[-1], _p(reflections), _p(_c(ssao, np.uint16)) if ssao is not None else None,
-                          _p(_c(shadow_map, np.float32)) if shadow_map is not None else None, 0 if shadow_map is None else shadow_map.shape[0], _p(out))
-    return out
+    reflections = _c(reflections, np.uint16) if reflections is not None else None
+    lib().orc_composition_lit(_p(pfd), W, H, modes[0], modes[1], modes[2], _p(albedo), _p(normals), _p(motion), _p(depth), _p(shadow_ao),
+                              shadow_ao.shape[-1], _p(reflections), _p(_c(ssao, np.uint16)) if ssao is not None else None,
+                              _p(_c(shadow_map, np.float32)) if shadow_map is not None else None, 0 if shadow_map is None else shadow_map.shape[0],
+                              _p(out), _p(lighting))
+    return (out, lighting) if with_lighting else out
 
 
 def sample_linear_repeat(img, u, v):

@@ -1444,10 +1444,12 @@ void orc_shadow_map(const orc_scene *s, const orc_per_frame_data *pfd, uint32_t 
     }
 }
 
-void orc_composition(const orc_per_frame_data *pfd, uint32_t W, uint32_t H, int shadow_mode, int ao_mode, int reflection_mode,
-                     const uint8_t *albedo_img, const uint16_t *normals_ids, const uint16_t *motion_mr, const float *depth,
-                     const uint16_t *shadow_ao, int shadow_ao_channels, const uint16_t *reflections, const uint16_t *ssao,
-                     const float *shadow_map, uint32_t shadow_map_size, uint8_t *out) {
+/* orc_composition with the lighting before the B8G8R8A8_SRGB store as a second output (tests/composition_cases.py judges a device texel by it):
+ * `lighting`, when not NULL, receives r, g, b of composition.frag:158 per texel, in the presented orientation of `out`. */
+void orc_composition_lit(const orc_per_frame_data *pfd, uint32_t W, uint32_t H, int shadow_mode, int ao_mode, int reflection_mode,
+                         const uint8_t *albedo_img, const uint16_t *normals_ids, const uint16_t *motion_mr, const float *depth,
+                         const uint16_t *shadow_ao, int shadow_ao_channels, const uint16_t *reflections, const uint16_t *ssao,
+                         const float *shadow_map, uint32_t shadow_map_size, uint8_t *out, float *lighting_out) {
     /* composition.frag:82 `SHADOW_BIAS_MATRIX * pfd.directional_light.projview * vec4(P, 1)`: the matrix product first */
     static const float bias[16] = { 0.5f, 0.0f, 0.0f, 0.0f, 0.0f, 0.5f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.5f, 0.5f, 0.0f, 1.0f };   /* common.glsl:6-11 */
     float bias_projview[16];
@@ -1509,8 +1511,20 @@ void orc_composition(const orc_per_frame_data *pfd, uint32_t W, uint32_t H, int 
             v3 lighting = v3add(v3add(ambient, diff), spec);                                   /* :160-162 */
             uint8_t *o = out + ((size_t)j * W + x) * 4;
             o[0] = srgb8(lighting.z); o[1] = srgb8(lighting.y); o[2] = srgb8(lighting.x); o[3] = 255;
+            if (lighting_out) {
+                float *lo = lighting_out + ((size_t)j * W + x) * 3;
+                lo[0] = lighting.x; lo[1] = lighting.y; lo[2] = lighting.z;
+            }
         }
     }
+}
+
+void orc_composition(const orc_per_frame_data *pfd, uint32_t W, uint32_t H, int shadow_mode, int ao_mode, int reflection_mode,
+                     const uint8_t *albedo_img, const uint16_t *normals_ids, const uint16_t *motion_mr, const float *depth,
+                     const uint16_t *shadow_ao, int shadow_ao_channels, const uint16_t *reflections, const uint16_t *ssao,
+                     const float *shadow_map, uint32_t shadow_map_size, uint8_t *out) {
+    orc_composition_lit(pfd, W, H, shadow_mode, ao_mode, reflection_mode, albedo_img, normals_ids, motion_mr, depth, shadow_ao, shadow_ao_channels,
+                        reflections, ssao, shadow_map, shadow_map_size, out, NULL);
 }
 
 /* ------------------------------------------------------------------------------------------

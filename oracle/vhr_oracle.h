@@ -118,6 +118,12 @@ void orc_composition(const orc_per_frame_data *pfd, uint32_t W, uint32_t H, int 
                      const uint16_t *ssao /* "Screen Space Ambient Occlusion" for ao_mode 1, else may be NULL */,
                      const float *shadow_map /* D32F, shadow_map_size^2, for shadow_mode 1, else may be NULL */, uint32_t shadow_map_size,
                      uint8_t *out_bgra8_srgb);
+/* The same, and the fp32 lighting before the sRGB store (composition.frag:158; r, g, b per texel, the orientation of out_bgra8_srgb) into
+ * `lighting` when it is not NULL.  reflection_mode 0 / 1 needs `reflections`, as vhr_standin_composition does (oracle/binding.py refuses None). */
+void orc_composition_lit(const orc_per_frame_data *pfd, uint32_t W, uint32_t H, int shadow_mode, int ao_mode, int reflection_mode,
+                         const uint8_t *albedo_bgra8, const uint16_t *normals_ids, const uint16_t *motion_mr, const float *depth,
+                         const uint16_t *shadow_ao, int shadow_ao_channels, const uint16_t *reflections, const uint16_t *ssao,
+                         const float *shadow_map, uint32_t shadow_map_size, uint8_t *out_bgra8_srgb, float *lighting);
 /* Stand-in for the rasterised "Shadow Map Pass" (hybrid_render_path.cpp:58-99): decision (xiv), orthographic closest-hit rays
  * through the texel centres of directional_light.projview's frustum, depth = 1 - t (reverse Z), clear value 0. */
 void orc_shadow_map(const orc_scene *s, const orc_per_frame_data *pfd, uint32_t size, uint32_t row_begin, uint32_t row_end,

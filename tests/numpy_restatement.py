@@ -522,3 +522,203 @@ def ssr(pfd, albedo_bgra8, normals_bits, motion_bits, depth, ray_distance=25.0, 
         diff = (1.0 - F) * (1.0 - metallic) * albedo / np.pi
         lit = albedo * (0.2 / np.pi) + (diff + spec) * nl * np.asarray(light["intensity"], np.float64)[:3] * np.asarray(light["color"], np.float64)[:3]
     return found, np.where(found[..., None], lit, 0.0), np.where(found, final, -1.0)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# composition.frag:60-161 in float64, written from the GLSL (and common.glsl:116-150, glsl_common.h:118-122), the presentation flip
+# (pipeline.cpp:175-178) and the B8G8R8A8_SRGB store.  min / max / clamp drop a NaN operand (decision xii), the sampler is decision x / xiii.
+# ---------------------------------------------------------------------------------------------------------
+COMPOSITION_MUTANTS = ("ambient_times_shadow", "reflections_without_shadow", "metallic_branch_at_0.999", "roughness_floor_0", "metallic_unclamped",
+                       "red_blue_swapped", "no_flip", "pcf_bias_plus", "pcf_scale_2048", "pcf_clamp", "linear_segment_to_0.04045",
+                       "rg16f_read_with_rgba_stride")
+SHADOW_BIAS = np.array([[0.5, 0, 0, 0.5], [0, 0.5, 0, 0.5], [0, 0, 1, 0], [0, 0, 0, 1.0]])      # common.glsl:6-11 as a math matrix
+U24 = 2.0 ** -24
+
+
+def srgb_code(c, slack=0.0, linear_up_to=0.0031308):
+    """The B8G8R8A8_SRGB store of a float64 channel: NaN and negatives store 0, >= 1 stores 255, else the encode, * 255 + 0.5 (+ slack, in
+    code units), truncated."""
+    c = np.asarray(c, np.float64)
+    with np.errstate(invalid="ignore"):
+        inside = (c > 0.0) & (c < 1.0)
+        x = np.where(inside, c, 0.5)
+        e = np.where(x <= linear_up_to, 12.92 * x, 1.055 * np.power(x, 1.0 / 2.4) - 0.055)
+        code = np.clip(np.floor(e * 255.0 + 0.5 + slack), 0, 255)
+        return np.where(inside, code, np.where(c >= 1.0, 255, 0)).astype(np.uint8)
+
+
+def _sample_linear_clamp(img, u, v):
+    """CLAMP_TO_EDGE instead of REPEAT (the `pcf_clamp` mutant alone)."""
+    H, W = img.shape[:2]
+    with np.errstate(invalid="ignore"):
+        fx, fy = u * W - 0.5, v * H - 0.5
+        x0f, y0f = np.floor(fx), np.floor(fy)
+        ax, ay = fx - x0f, fy - y0f
+        bad = ~(np.isfinite(x0f) & np.isfinite(y0f))
+        x0 = np.where(bad, 0, np.clip(x0f, -2**31, 2**31 - 1)).astype(np.int64)
+        y0 = np.where(bad, 0, np.clip(y0f, -2**31, 2**31 - 1)).astype(np.int64)
+    cx, cy = lambda i: np.clip(i, 0, W - 1), lambda i: np.clip(i, 0, H - 1)      # noqa: E731
+    return (img[cy(y0), cx(x0)] * (1 - ax) + img[cy(y0), cx(x0 + 1)] * ax) * (1 - ay) + (img[cy(y0 + 1), cx(x0)] * (1 - ax) + img[cy(y0 + 1), cx(x0 + 1)] * ax) * ay
+
+
+def _pcf(pfd, P, dist, shadow_map, mutant):
+    """composition.frag:81-107.  Returns (lit taps, undecided taps, census): per pixel the number of the 16 taps that pass
+    `!(sz < ds - 1e-4)` in float64, and the number whose margin |sz - (ds - 1e-4)| lies under the bound on what an fp32 evaluation of the same
+    expressions may move it by ("composition cases"): such a tap may fall either way on the device."""
+    sm = np.asarray(shadow_map, np.float64)
+    S = sm.shape[0]
+    M = SHADOW_BIAS @ _mat(pfd["directional_light"], "projview")
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        pl = np.concatenate([P, np.ones(P.shape[:2] + (1,))], -1) @ M.T
+        s = pl[..., :3] / pl[..., 3:4]
+        # fp32 error of P (|P| <= 8 m, dist >= 2 m: (16 dist + 24) u), through the matrix (4 roundings per row) and the division
+        err_p = (16.0 * dist + 24.0) * U24
+        mag = np.concatenate([np.abs(P), np.ones(P.shape[:2] + (1,))], -1) @ np.abs(M).T
+        err_pl = np.abs(M[:, :3]).sum(1) * err_p[..., None] + 4.0 * U24 * mag
+        err_s = (err_pl[..., :3] + np.abs(s) * err_pl[..., 3:4]) / np.abs(pl[..., 3:4]) + U24 * np.abs(s)
+    sx, sy, sz = s[..., 0], s[..., 1], s[..., 2]
+    scale = 1.0 / 2048.0 if mutant == "pcf_scale_2048" else 1.0 / 4096.0
+    bias = -1e-4 if mutant == "pcf_bias_plus" else 1e-4
+    sample = _sample_linear_clamp if mutant == "pcf_clamp" else sample_linear_repeat
+    whole_range = float(np.nanmax(sm) - np.nanmin(sm)) if np.isfinite(sm).all() else np.inf
+    lit = np.zeros(sx.shape, np.int64)
+    undecided = np.zeros(sx.shape, np.int64)
+    census = dict(wrapped=0, saturated=0, non_finite=0, taps=0, cleared_texel_taps=0)
+    for i in range(16):
+        ox, oy = ((i >> 2) - 1.5) * scale, ((i & 3) - 1.5) * scale                        # offsets[i], :89-94
+        u, v = sx + ox, sy + oy
+        with np.errstate(invalid="ignore", over="ignore"):
+            ds = sample(sm, u, v)
+            margin = sz - (ds - bias)
+            lit += ~(margin < 0)
+            tx, ty = np.floor(u * S - 0.5), np.floor(v * S - 0.5)
+            du = S * (err_s[..., 0] + 2 * U24 * np.abs(u)) + U24 * np.abs(u * S)
+            dv = S * (err_s[..., 1] + 2 * U24 * np.abs(v)) + U24 * np.abs(v * S)
+            bad = ~(np.isfinite(tx) & np.isfinite(ty))
+            sat = ~bad & ((np.abs(tx) >= 2.0 ** 31) | (np.abs(ty) >= 2.0 ** 31))
+            far = ~bad & ~sat & ((tx < -S) | (tx >= 2 * S) | (ty < -S) | (ty >= 2 * S))
+            x0 = np.mod(np.where(bad, 0, np.clip(tx, -2**31, 2**31 - 1)).astype(np.int64), S)
+            y0 = np.mod(np.where(bad, 0, np.clip(ty, -2**31, 2**31 - 1)).astype(np.int64), S)
+            near = np.stack([sm[(y0 + b) % S, (x0 + a) % S] for a in (-1, 0, 1, 2) for b in (-1, 0, 1, 2)], -1)
+            local = near.max(-1) - near.min(-1)
+            spread = np.where((du + dv) < 0.5, local, whole_range)
+            err_ds = np.where(spread > 0, (du + dv) * spread, 0.0) + 8 * U24 * np.abs(near).max(-1)
+            bound = err_s[..., 2] + err_ds + 2 * U24
+            undecided += np.abs(margin) < bound
+        census["wrapped"] += int(far.sum())
+        census["saturated"] += int(sat.sum())
+        census["non_finite"] += int(bad.sum())
+        census["taps"] += int(bad.size)
+        census["cleared_texel_taps"] += int((~bad & (near[..., 5] == 0.0)).sum())       # near[..., 5] is the texel (x0, y0)
+    return lit, undecided, census
+
+
+def composition(pfd, modes, albedo, normals, motion, depth, shadow_ao, reflections=None, ssao=None, shadow_map=None, mutant=None, delta=None,
+                eps=0.0, code_slack=1e-3):
+    """composition.frag with (shadow_mode, ambient_occlusion_mode, reflection_mode) on B8G8R8A8 albedo, RGBA16F normals / motion, D32 depth,
+    RG16F or RGBA16F shadow_ao and the optional RGBA16F reflections and ssao and square D32 shadow map.  Everything returned is in the
+    presented orientation (row 0 = top: G-buffer row H - 1):
+      lighting   (H, W, 3) float64 r g b, before the store;      codes   (H, W, 4) uint8 b g r a, the B8G8R8A8_SRGB texels;
+      pcf        under shadow_mode 1: dict(lit, undecided: (H, W) tap counts; census);
+    and with `delta` (not None), the envelope an fp32 evaluation must fall into: lo, hi -- the least and the greatest lighting over the 16 sign
+    combinations of moving H.V, N.L, N.H, N.V by +-delta (before their max with 0) and over the undecided PCF taps counted as dark / as lit,
+    widened by the relative eps -- and code_lo, code_hi (H, W, 3) b g r: the codes of lo and hi with `code_slack` code units taken off / added.
+    mutant: one of COMPOSITION_MUTANTS, a planted error."""
+    assert mutant is None or mutant in COMPOSITION_MUTANTS, mutant
+    H, W = depth.shape
+    depth = np.asarray(depth, np.float64)
+    alb = np.asarray(albedo)[..., [2, 1, 0]].astype(np.float64) / 255.0                    # :61
+    ys, xs = np.mgrid[0:H, 0:W]
+    cam = _mat(pfd, "camera_view_inverse")[:3, 3]
+    P = _unproject(_mat(pfd, "camera_viewproj_inverse"), depth, (xs + 0.5) / W, (ys + 0.5) / H)      # :63, in_uv is the texel centre
+    N = h2f(normals).astype(np.float64)[..., :3]                                           # :64
+    mr = h2f(motion).astype(np.float64)[..., 2:4]                                          # :65
+    sa_bits = np.asarray(shadow_ao, np.uint16)
+    if mutant == "rg16f_read_with_rgba_stride" and sa_bits.shape[-1] == 2:                 # texel (x, y) read at 8 bytes a texel, wrapped into the buffer
+        flat = sa_bits.reshape(-1)
+        at = ((ys * W + xs) * 4) % flat.size
+        sa_bits = np.stack([flat[at], flat[at + 1]], -1)
+    sa = h2f(sa_bits).astype(np.float64)
+    light = pfd["directional_light"]
+    L = -np.asarray(light["direction"], np.float64)[:3]                                    # :74
+    li, lc = np.asarray(light["intensity"], np.float64)[:3], np.asarray(light["color"], np.float64)[:3]
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        dist = np.linalg.norm(cam - P, axis=-1)
+        V = (cam - P) / dist[..., None]                                                    # :73
+        Hh = (L + V) / np.linalg.norm(L + V, axis=-1, keepdims=True)                       # :75
+        dots = np.stack([(Hh * V).sum(-1), (N * L).sum(-1), (N * Hh).sum(-1), (N * V).sum(-1)])
+    pcf = None
+    shadows = [np.ones((H, W))] * 2                                                        # (dark end, lit end)
+    if modes[0] == 0:
+        shadows = [sa[..., 0]] * 2
+    elif modes[0] == 1:
+        lit, undecided, census = _pcf(pfd, P, dist, shadow_map, mutant)
+        pcf = dict(lit=lit[::-1], undecided=undecided[::-1], census=census)
+        # an undecided tap that float64 saw lit may be dark on the device, and the other way round: at most `undecided` taps either way
+        shadows = [np.clip(lit - undecided, 0, 16) / 16.0, np.clip(lit + undecided, 0, 16) / 16.0, lit / 16.0]
+    ao = np.ones((H, W))                                                                   # :113-119
+    if modes[1] == 0:
+        ao = sa[..., 1]
+    elif modes[1] == 1:
+        ao = h2f(ssao).astype(np.float64)[..., 0]
+    metallic = mr[..., 0] if mutant == "metallic_unclamped" else np.fmin(np.fmax(mr[..., 0], 0.0), 1.0)      # :122-123
+    rough = np.fmin(np.fmax(mr[..., 1], 0.0 if mutant == "roughness_floor_0" else 0.04), 1.0)
+    refl = h2f(reflections).astype(np.float64)[..., :3] if (modes[2] in (0, 1)) else None
+    m3, r3 = metallic[..., None], rough[..., None]
+
+    def shade(hv, nl, nh, nv, shadow):
+        with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+            hv, nl, nh, nv = (np.fmax(d, 0.0) for d in (hv, nl, nh, nv))
+            f0 = 0.04 * (1.0 - m3) + alb * m3                                              # :129-130
+            F = f0 + (1.0 - f0) * ((1.0 - hv) ** 5)[..., None]                             # common.glsl:116-119
+            a2 = rough * rough
+            f = nh * nh * (a2 - 1.0) + 1.0
+            D = a2 / (np.pi * f * f)                                                       # :122-127
+            k = (rough + 1.0) * (rough + 1.0) * 0.125
+            G = (nv / (nv * (1.0 - k) + k)) * (nl / (nl * (1.0 - k) + k))                  # :130-138
+            spec_brdf = (D * G)[..., None] * F / np.fmax(4.0 * nv * nl, 1e-6)[..., None]   # :140-144
+            diff_brdf = (1.0 - F) * (1.0 - m3) * alb / np.pi                               # :146-150
+            sh = shadow[..., None]
+            ambient = ao[..., None] * alb * (1.0 / np.pi)                                  # :135
+            if mutant == "ambient_times_shadow":
+                ambient = ambient * sh
+            diffuse = diff_brdf * nl[..., None] * li * lc * sh                             # :136
+            spec = spec_brdf * nl[..., None] * li * lc * sh                                # :137
+            if refl is not None:                                                           # :139-156
+                r = refl if mutant == "reflections_without_shadow" else refl * sh
+                mirror = (m3 >= 0.999) if mutant == "metallic_branch_at_0.999" else (m3 == 1.0)
+                spec = np.where(mirror, r, spec * (1.0 - r3) + r * r3)
+            return ambient + diffuse + spec                                                # :158
+
+    encode = (lambda c, slack=0.0: srgb_code(c, slack, 0.04045)) if mutant == "linear_segment_to_0.04045" else srgb_code      # noqa: E731
+    flip = (lambda a: a) if mutant == "no_flip" else (lambda a: a[::-1])                   # noqa: E731
+    lighting = shade(*dots, shadows[-1])
+    order = [0, 1, 2] if mutant == "red_blue_swapped" else [2, 1, 0]
+    codes = np.concatenate([encode(lighting)[..., order], np.full((H, W, 1), 255, np.uint8)], -1)
+    out = dict(lighting=flip(lighting), codes=flip(codes), pcf=pcf)
+    if delta is not None:
+        lo, hi = lighting.copy(), lighting.copy()
+        nan = np.isnan(lighting)
+        for bits in range(16):
+            moved = [dots[i] + (delta if bits >> i & 1 else -delta) for i in range(4)]
+            for sh in shadows[:2]:
+                with np.errstate(invalid="ignore"):
+                    l = shade(*moved, sh)
+                    lo, hi = np.fmin(lo, l), np.fmax(hi, l)
+                    nan |= np.isnan(l)
+        with np.errstate(invalid="ignore", over="ignore"):
+            lo = np.where(lo > 0, lo * (1.0 - eps), lo * (1.0 + eps))
+            hi = np.where(hi > 0, hi * (1.0 + eps), hi * (1.0 - eps))
+        code_lo, code_hi = encode(lo, -code_slack)[..., ::-1], encode(hi, code_slack)[..., ::-1]
+        code_lo = np.where(nan[..., ::-1], 0, code_lo)          # a NaN anywhere in the envelope: the store of a NaN (0) is admitted too
+        out.update(lo=flip(lo), hi=flip(hi), code_lo=flip(code_lo), code_hi=flip(code_hi))
+    return out
+
+
+def raytraced_composition(raytraced_bgra8):
+    """raytraced_render_path/composition.frag:11-13 with the flipped presentation and the B8G8R8A8_SRGB store: colour bytes / 255 encoded,
+    alpha passed through.  Returns (codes (H, W, 4) uint8, code_lo, code_hi (H, W, 3)): the float64 encode and its +-1e-3 code-unit ends."""
+    src = np.asarray(raytraced_bgra8, np.uint8)[::-1]
+    c = src[..., :3].astype(np.float64) / 255.0
+    codes = np.concatenate([srgb_code(c), src[..., 3:]], -1)
+    return codes, srgb_code(c * (1 - 4 * U24), -1e-3), srgb_code(c * (1 + 4 * U24), 1e-3)
